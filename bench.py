@@ -18,9 +18,14 @@ RCCL once per item half-sweep -- inside libpmf_hip.so (pmf_comm_init).  `--scali
 weak` gives every rank its own 1M-user / 50M-rating shard instead.  This program
 never imports torch (`config.torch_imported`).
 
-Rank 0 prints ONE JSON line (see the driver contract) with two extra objects:
-`roofline` (dominant kernel: algorithmic bytes / live hipEvent time vs its bound)
-and `cpu_baseline` (the CPU oracle timed on a bounded sample).
+Rank 0 prints ONE JSON line (see the driver contract).  A plain run sets up, warms up, times
+the steps and prints the line; `roofline` and `kernels_ms_per_step` come from the hipEvents of
+those timed steps.  `--full` adds what takes runs or checks of its own: the secondary
+measurements of the default workload (HPF-CAVI, f64, top-k), the live gather ceiling of the
+HPF roofline, the top-k agreement with NumPy and `cpu_baseline` (the CPU oracle timed on a
+bounded sample).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (a seeded sample of rows of every state array a caller reads back, at most
+64 MB; the same arguments give the same inputs on every run).
 """
 from __future__ import annotations
 
@@ -60,9 +65,46 @@ WORKLOADS = {
 }
 SMALL = dict(U=100_000, I=10_000, N=5_000_000)  # --small: quick functional run
 MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 at 64 FLOP/clk/SIMD (= the fp32 vector peak)
+DUMP_BYTES = 64 << 20         # --dump-outputs: the most it writes
 
 
-def topk_measure(args, local_rank, steps=None):
+def dump_outputs(dirname, arrays, dtype):
+    """`arrays` (name -> array) as dirname/<name>.npy in the run's precision (float32 for f32, float64 for f64)."""
+    np_dtype = np.float32 if dtype == "f32" else np.float64
+    arrays = {k: np.ascontiguousarray(v, dtype=np_dtype) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_BYTES})")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def sample_rows(n_rows, n_max):
+    """A fixed, seeded, sorted sample of at most n_max of n_rows row ids."""
+    if n_rows <= n_max:
+        return np.arange(n_rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(1234).choice(n_rows, n_max, replace=False)).astype(np.int64)
+
+
+def state_outputs(ctx, arrays, K, elem):
+    """The state a caller of the timed path reads back (`arrays`: (name, side, array id, per-row width) per array),
+    on a seeded sample of each side's rows sized to stay within DUMP_BYTES: K-wide arrays and row scalars share ~40 MB,
+    K x K covariances ~16 MB."""
+    from pmf_hip import ARR_COV, ITEM, USER
+    out = {}
+    for side, tag in ((USER, "user"), (ITEM, "item")):
+        mine = [a for a in arrays if a[1] == side]
+        row_bytes = elem * sum(w for _, _, aid, w in mine if aid != ARR_COV)
+        rows = sample_rows(ctx.rows(side), max(1, int(20e6 // max(row_bytes, 1))))
+        cov_rows = rows[:max(1, int(8e6 // (elem * K * K)))]
+        out[f"{tag}_rows"] = rows.astype(np.float64)
+        for name, _, aid, _ in mine:
+            out[name] = ctx.get_array_rows(side, aid, cov_rows if aid == ARR_COV else rows)
+    return out
+
+
+def topk_measure(args, local_rank, steps=None, dump=None):
     """`--workload topk`: top-10 items of 100k for a batch of query users at K = 64 from
     the dense reconstruction Theta . Beta^T -- the one MFMA-bound kernel of the product.  A step = one
     pmf_topk_items call over the batch (ids in, ranked lists out: the host legs are inside the call, the roofline
@@ -90,10 +132,14 @@ def topk_measure(args, local_rank, steps=None):
     ms, launches = ctx.prof_get()["topk"]
     flops = 2.0 * Q * I * K * steps
     ach = flops / (ms * 1e-3) / 1e12
-    # spot check against a NumPy ranking (exact fp32 tables, fp64 products)
-    A, B = ctx.get_array(USER, ARR_FACTOR)[users[:64]], ctx.get_array(ITEM, ARR_FACTOR)
-    want = np.argsort(-(A @ B.T), axis=1, kind="stable")[:, :k]
-    agree = float(np.mean(items[:64] == want))
+    if dump:
+        dump_outputs(dump, {"topk_items": items, "topk_scores": scores}, "f32")
+    agree = None
+    if args.full:
+        # spot check against a NumPy ranking (exact fp32 tables, fp64 products)
+        A, B = ctx.get_array(USER, ARR_FACTOR)[users[:64]], ctx.get_array(ITEM, ARR_FACTOR)
+        want = np.argsort(-(A @ B.T), axis=1, kind="stable")[:, :k]
+        agree = float(np.mean(items[:64] == want))
     ctx.close()
     return {
         "metric": f"query users/sec, top-{k} of {I} items from Theta.Beta^T, K={K}", "value": Q * steps / elapsed,
@@ -108,7 +154,7 @@ def topk_measure(args, local_rank, steps=None):
 
 
 def topk_bench(args, local_rank):
-    print(json.dumps(topk_measure(args, local_rank)), flush=True)
+    print(json.dumps(topk_measure(args, local_rank, dump=args.dump_outputs)), flush=True)
 
 
 def algorithmic_bytes(workload, U, I, N, K, elem=4):
@@ -314,8 +360,8 @@ def main():
                     help="N > 1: strong = shard the one fixed matrix by user range (default, the north star's "
                          "problem); weak = every rank its own full-size shard")
     ap.add_argument("--small", action="store_true", help="1/10 size functional run (not a valid bench)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--only", action="store_true", help="skip the secondary measurements (HPF-CAVI, f64) of the default run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--only", action="store_true", help="with --full: skip the secondary measurements (HPF-CAVI, f64, top-k) of the default workload")
     ap.add_argument("--transport", choices=["rccl", "hostshm"], default=os.environ.get("PMF_COMM_TRANSPORT", "rccl"),
                     help="rccl = one rank per GPU over xGMI; hostshm = rehearsal transport for ranks sharing one GPU")
     ap.add_argument("--chunks", type=int, default=None, help="item row chunks of the pipelined item half-sweep at "
@@ -327,11 +373,20 @@ def main():
     ap.add_argument("--factors", type=int, default=None, help="exploration: override the workload's K")
     ap.add_argument("--cpu-full", action="store_true",
                     help="time the HPF cpu_baseline on the FULL C3 matrix (1M x 100k, 50M ratings, one iteration of the oracle's "
-                         "per-row loop: about a minute of CPU) instead of the default 300k x 30k x 16.5M sample")
+                         "per-row loop: about a minute of CPU) instead of the default 300k x 30k x 16.5M sample (implies --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: HPF-CAVI, f64 and top-k beside the default workload "
+                         "(unless --only), the live gather ceiling of the HPF roofline, the top-k agreement with NumPy, "
+                         "the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, a seeded sample of "
+                         "rows, at most 64 MB)")
     args = ap.parse_args()
+    args.full = args.full or args.cpu_full
 
     import pmf_hip
-    from pmf_hip import ARR_BIAS, ARR_FACTOR, ARR_PRIOR_RATE, ITEM, USER, dist as pdist
+    from pmf_hip import (ARR_BIAS, ARR_COV, ARR_FACTOR, ARR_HYPER_RATE, ARR_PRIOR_RATE, ARR_RATE, ARR_SHAPE, ITEM, USER,
+                         dist as pdist)
     from pmf_hip.synth import BASE_SEED, synth_ratings
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -382,7 +437,7 @@ def main():
     else:
         ratings_total, users_total, centre = N_loc, U_loc, float(r.mean())
 
-    def run(workload, hp, steps, warmup, dtype):
+    def run(workload, hp, steps, warmup, dtype, dump=None):
         """Build the device state of `workload` on the shared ratings, run warmup + timed steps
         (device sync + barrier on both sides, max over ranks) and return the measurements."""
         elem = 4 if dtype == "f32" else 8
@@ -463,11 +518,25 @@ def main():
         ctx.prof_enable(False)
         if comm is not None:
             elapsed = float(comm.all_reduce_host([elapsed], op="max")[0])
-        t0 = time.time()
-        ctx.get_array(USER, ARR_FACTOR)
-        item_factors = ctx.get_array(ITEM, ARR_FACTOR)
-        t_pull = time.time() - t0
-        consistent = None
+        if dump and rank == 0:
+            if gauss:
+                arrays = [("user_mean", USER, ARR_FACTOR, K), ("item_mean", ITEM, ARR_FACTOR, K),
+                          ("user_cov", USER, ARR_COV, 0), ("item_cov", ITEM, ARR_COV, 0),
+                          ("user_bias", USER, ARR_BIAS, 1), ("item_bias", ITEM, ARR_BIAS, 1)]
+            elif sgd:
+                arrays = [("user_mean", USER, ARR_FACTOR, K), ("item_mean", ITEM, ARR_FACTOR, K),
+                          ("user_bias", USER, ARR_BIAS, 1), ("item_bias", ITEM, ARR_BIAS, 1)]
+            else:
+                arrays = [(f"{tag}_{name}", side, aid, w) for side, tag in ((USER, "user"), (ITEM, "item"))
+                          for name, aid, w in (("mean", ARR_FACTOR, K), ("shape", ARR_SHAPE, K), ("rate", ARR_RATE, K),
+                                               ("prior_rate", ARR_PRIOR_RATE, 1), ("hyper_rate", ARR_HYPER_RATE, 1))]
+            dump_outputs(dump, state_outputs(ctx, arrays, K, elem), dtype)
+        t_pull, consistent = None, None
+        if args.full or comm is not None:
+            t0 = time.time()
+            ctx.get_array(USER, ARR_FACTOR)
+            item_factors = ctx.get_array(ITEM, ARR_FACTOR)
+            t_pull = time.time() - t0
         if comm is not None:
             # outside the timed region: the replicated item state must be bit-identical on all ranks
             digest = np.frombuffer(hashlib.sha256(item_factors.tobytes()).digest()[:8], dtype=np.uint8).astype(np.float64)
@@ -477,7 +546,6 @@ def main():
                 # reported, not raised: the line still carries the diagnostics, flagged invalid below
                 print(f"bench.py: {workload}: the replicated item state differs between ranks -- the item half-sweep "
                       "and its collective are not ordered; the rate is not valid", file=sys.stderr, flush=True)
-        del item_factors
         # roofline of the dominant kernel: this rank's launches against this rank's algorithmic bytes
         total_bytes, dom_bytes = algorithmic_bytes(workload, U_loc, I, N_loc, K, elem)
         whole_bytes, _ = algorithmic_bytes(workload, users_total if strong or comm is None else U_loc * world, I,
@@ -494,7 +562,7 @@ def main():
                 roofline["traffic_source"] = "profiles/traffic.json (rocprofv3 --pmc passes of this workload; static)"
             except Exception:
                 pass
-        if dominant == "gamma_sweep":
+        if dominant == "gamma_sweep" and args.full:
             # The gathered tables live in L2 / Infinity Cache (25.6 MB of item rows, 256 MB of user rows), so HBM
             # does not bound this kernel: its roofline is what the cache hierarchy delivers for this gather
             # pattern, measured live by the kernel's gather-only twin on the same ratings and tables.
@@ -542,9 +610,9 @@ def main():
         return res
 
     gauss = args.workload.startswith("gaussian_mf")
-    main_res = run(args.workload, hp, args.steps, args.warmup, args.dtype)
+    main_res = run(args.workload, hp, args.steps, args.warmup, args.dtype, dump=args.dump_outputs)
     also = {}
-    if args.workload == "gaussian_mf" and not args.only:
+    if args.workload == "gaussian_mf" and args.full and not args.only:
         # the north star names both models: HPF-CAVI on the same ratings (+1), same protocol
         also["hpf_cavi"] = run("hpf_cavi", WORKLOADS["hpf_cavi"]["hp"], max(args.steps, 10), max(args.warmup, 2), args.dtype)
         if comm is None and args.dtype == "f32":
@@ -616,7 +684,7 @@ def main():
         if "f64" in also:
             out["also"]["f64"] = {"gaussian_mf": brief(also["f64"]["gaussian_mf"], f"ratings/sec (epoch) Gaussian-MF K={K}", "f64"),
                                   "hpf_cavi": brief(also["f64"]["hpf_cavi"], f"ratings/sec (epoch) HPF-CAVI K={K}", "f64")}
-    if not args.no_cpu_baseline and world == 1 and args.workload != "gaussian_mf_sgd":
+    if args.full and not args.no_cpu_baseline and world == 1 and args.workload != "gaussian_mf_sgd":
         out["cpu_baseline"] = cpu_baseline(args.workload, K, hp, local_rank, full=args.cpu_full)
         if "hpf_cavi" in also:
             out["also"]["hpf_cavi"]["cpu_baseline"] = cpu_baseline("hpf_cavi", K, WORKLOADS["hpf_cavi"]["hp"], local_rank,

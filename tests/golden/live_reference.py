@@ -12,12 +12,13 @@ of `fit` (verbose=True) per trial.  Data only -- no code travels."""
 import contextlib
 import io
 import json
+import os
 import sys
 
 import numpy as np
 import pandas as pd
 
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ["PMF_REFERENCE_DIR"])     # the reference checkout (tests/test_live_reference_cpu.py)
 from src.models.gaussian_mf_cavi import GaussianMFCAVI as Gauss, GaussianMFCAVIConfig as GaussCfg  # noqa: E402
 from src.models.gaussian_mf_cavi_bias import GaussianMFCAVI as GaussBias, GaussianMFCAVIConfig as GaussBiasCfg  # noqa: E402
 from src.models.hpf_cavi import HPF_CAVI, HPF_CAVI_Config  # noqa: E402

@@ -13,7 +13,7 @@ import os
 import sys
 
 os.environ.setdefault("MPLBACKEND", "Agg")
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ["PMF_REFERENCE_DIR"])     # the reference checkout (tests/test_live_reference_cpu.py)
 from src.experiments.train_gaussian_full import train_full_gaussian  # noqa: E402
 from src.experiments.train_hpf_cavi_full import train_full_hpf_cavi  # noqa: E402
 from src.experiments.train_hpf_pytorch_full import train_full_hpf_pytorch  # noqa: E402

@@ -9,7 +9,7 @@ import os
 import sys
 
 os.environ.setdefault("MPLBACKEND", "Agg")
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ["PMF_REFERENCE_DIR"])     # the reference checkout (tests/test_live_reference_cpu.py)
 from src.experiments import compare_models, train_all_models  # noqa: E402
 
 for name, fn, argv in (("train_all", train_all_models.main, ["train_all_models", "--dataset_mode", "train"]),

@@ -3,9 +3,10 @@
 tests/test_live_reference_cpu.py).  Leaves stdout_tune_torch.txt."""
 import contextlib
 import io
+import os
 import sys
 
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ["PMF_REFERENCE_DIR"])     # the reference checkout (tests/test_live_reference_cpu.py)
 from src.experiments import tune_hpf_pytorch  # noqa: E402
 
 buf = io.StringIO()

@@ -7,7 +7,7 @@ import os
 import sys
 
 os.environ.setdefault("MPLBACKEND", "Agg")
-sys.path.insert(0, "/root/reference")
+sys.path.insert(0, os.environ["PMF_REFERENCE_DIR"])     # the reference checkout (tests/test_live_reference_cpu.py)
 from src.experiments import tune_all_models  # noqa: E402
 
 sys.argv = ["tune_all_models", "--n_trials", "1"]

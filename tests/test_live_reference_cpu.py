@@ -1,13 +1,15 @@
-"""Random problems through the model classes' HOST logic against the reference itself, run live.
+"""Random problems through the model classes' HOST logic against what the reference itself computes on them.
 
-Only in the build container: `/root/reference` does not exist on the GPU box, and nothing of it travels --
-`tests/golden/live_reference.py` runs the reference's classes in a subprocess (its `src` package and this repo's
-never share an interpreter) and hands back arrays and the captured stdout.  This side runs the SAME model classes
-the GPU uses, over the CPU stand-in of the engine (`tests/oracle_engine.py:OracleContext`), so what is compared is
-everything above the kernels: dimension inference, the RNG draw order of the initial state, the iteration order,
-the validation monitor, the early-stop rules, `predict` / `evaluate_*` semantics, and the verbose output --
-character for character."""
+The reference's outputs on these exact inputs are stored under `tests/golden/live_reference/` (data only: arrays, the
+captured stdout, the files its drivers write); each test regenerates its inputs, checks that they are the ones the
+stored outputs were computed on (SHA-256), and compares.  With PMF_REFERENCE_DIR pointing at a checkout of the
+reference, the `tests/golden/live_reference*.py` helpers run it live in a subprocess (its `src` package and this repo's
+never share an interpreter) and the stored outputs are re-recorded.  This side runs the SAME model classes the GPU uses,
+over the CPU stand-in of the engine (`tests/oracle_engine.py:OracleContext`), so what is compared is everything above
+the kernels: dimension inference, the RNG draw order of the initial state, the iteration order, the validation monitor,
+the early-stop rules, `predict` / `evaluate_*` semantics, and the verbose output -- character for character."""
 import contextlib
+import hashlib
 import io
 import json
 import os
@@ -18,10 +20,81 @@ import numpy as np
 import pandas as pd
 import pytest
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src", "models")),
-                                reason="the reference exists in the build container only")
+STORE = os.path.join(ROOT, "tests", "golden", "live_reference")
+LIVE = os.environ.get("PMF_REFERENCE_DIR")       # set: run the reference live and re-record STORE
+
+
+def _digest(items):
+    h = hashlib.sha256()
+    for k in sorted(items):
+        a = np.asarray(items[k])
+        h.update(f"{k}|{a.dtype.str}|{a.shape}|".encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def _live(helper, args, cwd, timeout=900):
+    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
+    done = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", helper)] + args, env=env,
+                          capture_output=True, text=True, timeout=timeout, cwd=cwd)
+    assert done.returncode == 0, done.stderr[-2000:]
+
+
+def _stored(name, digest):
+    ref = np.load(os.path.join(STORE, name + ".npz"), allow_pickle=False)
+    assert str(ref["inputs_sha256"]) == digest, f"{name}: the inputs are not those the stored reference outputs belong to"
+    return ref
+
+
+def _reference_arrays(name, inputs, tmp_path, part_of=None):
+    """What tests/golden/live_reference.py returns for `inputs` (a dict of arrays): stored, or run live and recorded.
+    `part_of` (trial prefix such as "t12" -> part) keeps the outputs in one file per part, `<name>_<part>.npz`, so
+    that no fixture grows large; the parts are read back as one dict."""
+    digest = _digest(inputs)
+    files = sorted({f"{name}_{p}" for p in part_of.values()}) if part_of else [name]
+    if LIVE:
+        src, dst = str(tmp_path / f"{name}_inputs.npz"), str(tmp_path / f"{name}_reference_out.npz")
+        np.savez(src, **inputs)
+        _live("live_reference.py", [src, dst], str(tmp_path))
+        parts = {f: {} for f in files}
+        with np.load(dst, allow_pickle=False) as d:
+            for k in d.files:
+                parts[f"{name}_{part_of[k.split('_', 1)[0]]}" if part_of else name][k] = d[k]
+        os.makedirs(STORE, exist_ok=True)
+        for f, out in parts.items():
+            np.savez_compressed(os.path.join(STORE, f + ".npz"), inputs_sha256=np.asarray(digest), **out)
+    ref = {}
+    for f in files:
+        stored = _stored(f, digest)
+        ref.update({k: stored[k] for k in stored.files if k != "inputs_sha256"})
+    return ref
+
+
+def _files(root):
+    return {os.path.relpath(os.path.join(d, f), root): open(os.path.join(d, f), "rb").read()
+            for d, _, fs in os.walk(root) for f in fs}
+
+
+def _reference_tree(name, helper, args, root):
+    """Leaves in `root` the text files the reference's drivers write there (`helper` runs them in `root`, which
+    holds their inputs): stored, or run live and recorded.  Plots are not kept."""
+    before = _files(root)
+    digest = _digest({k: np.frombuffer(v, dtype=np.uint8) for k, v in before.items()})
+    if LIVE:
+        _live(helper, args, root)
+        made = {k: v for k, v in _files(root).items() if k not in before and not k.endswith(".png")}
+        os.makedirs(STORE, exist_ok=True)
+        np.savez_compressed(os.path.join(STORE, name + ".npz"), inputs_sha256=np.asarray(digest),
+                            **{"file:" + k.replace(os.sep, "|"): np.frombuffer(v, dtype=np.uint8) for k, v in made.items()})
+    ref = _stored(name, digest)
+    for key in ref.files:
+        if key.startswith("file:"):
+            path = os.path.join(root, *key[len("file:"):].split("|"))
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path, "wb") as fh:
+                fh.write(ref[key].tobytes())
+
 
 KEYS = {"hpf": ["gamma_a_theta", "gamma_b_theta", "gamma_a_beta", "gamma_b_beta", "E_theta", "E_beta", "E_xi", "E_eta"],
         "poisson": ["a_theta", "b_theta", "a_beta", "b_beta", "E_theta", "E_beta"],
@@ -82,13 +155,7 @@ def test_random_problems_host_logic_equals_the_live_reference(tmp_path, monkeypa
         inputs.update({f"t{t}_u": u, f"t{t}_i": i, f"t{t}_x": x + shift, f"t{t}_vu": vu, f"t{t}_vi": vi, f"t{t}_vx": vx + shift,
                        f"t{t}_qu": rng.integers(0, U + 2, 20), f"t{t}_qi": rng.integers(0, I + 2, 20),
                        f"t{t}_cfg": np.asarray(json.dumps(meta))})
-    src, dst = str(tmp_path / "problems.npz"), str(tmp_path / "reference_out.npz")
-    np.savez(src, **inputs)
-    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    done = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "live_reference.py"), src, dst], env=env,
-                          capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
-    assert done.returncode == 0, done.stderr[-2000:]
-    ref = np.load(dst, allow_pickle=False)
+    ref = _reference_arrays("model_fits", inputs, tmp_path, part_of={f"t{t}": meta["kind"] for t, (meta, _) in enumerate(metas)})
 
     monkeypatch.setattr(pmf_hip, "Context", OracleContext)      # the model classes look the context class up at run time
     seen = {"validated": 0, "stopped_early": 0, "warned": 0, "kinds": set()}
@@ -151,13 +218,7 @@ def test_random_hpf_pytorch_cases_equal_the_live_reference(tmp_path):
                        f"t{t}_bu": u, f"t{t}_bi": i, f"t{t}_br": (rng.integers(0, 6, n) + 1).astype(np.float32),
                        f"t{t}_qu": rng.integers(0, U, 15), f"t{t}_qi": rng.integers(0, I, 15),
                        f"t{t}_cfg": np.asarray(json.dumps(meta))})
-    src, dst = str(tmp_path / "torch_problems.npz"), str(tmp_path / "torch_reference_out.npz")
-    np.savez(src, **inputs)
-    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    done = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "live_reference.py"), src, dst], env=env,
-                          capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
-    assert done.returncode == 0, done.stderr[-2000:]
-    ref = np.load(dst, allow_pickle=False)
+    ref = _reference_arrays("hpf_pytorch", inputs, tmp_path)
     names = ("theta_uncons", "beta_uncons", "xi_uncons", "eta_uncons")
     for t, meta in enumerate(metas):
         tag = f"trial {t}: {meta}"
@@ -199,13 +260,7 @@ def test_random_metric_inputs_equal_the_live_reference(tmp_path):
                        f"t{t}_i": rng.integers(0, I, n), f"t{t}_x": rng.integers(0, 6, n).astype(np.float64),
                        f"t{t}_theta": rng.normal(size=(U, K)), f"t{t}_beta": rng.normal(size=(I, K)),
                        f"t{t}_cfg": np.asarray(json.dumps(meta)), f"t{t}_sigma": np.asarray(meta["sigma"])})
-    src, dst = str(tmp_path / "metric_inputs.npz"), str(tmp_path / "metric_reference_out.npz")
-    np.savez(src, **inputs)
-    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    done = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "live_reference.py"), src, dst], env=env,
-                          capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
-    assert done.returncode == 0, done.stderr[-2000:]
-    ref = np.load(dst, allow_pickle=False)
+    ref = _reference_arrays("metrics", inputs, tmp_path)
     for t in range(n_trials):
         y, p = inputs[f"t{t}_y"], inputs[f"t{t}_p"]
         frame = pd.DataFrame({"u": inputs[f"t{t}_u"], "i": inputs[f"t{t}_i"], "rating": inputs[f"t{t}_x"]})
@@ -261,10 +316,7 @@ def test_driver_outputs_on_disk_equal_the_live_reference(mode, tmp_path, monkeyp
             pd.DataFrame({"i_new": np.arange(25), "i": raw_ids}).to_csv(d / "dict_i.csv", index=False)
             pd.DataFrame({"id": 5000 + raw_ids[:-1], "i": raw_ids[:-1], "other": 0}).to_csv(root / "data" / "raw" / "PP_recipes.csv", index=False)
         roots[who] = str(root)
-    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    done = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "live_reference_drivers.py"), mode], env=env,
-                          capture_output=True, text=True, timeout=900, cwd=roots["reference"])
-    assert done.returncode == 0, done.stderr[-2000:]
+    _reference_tree(f"drivers_{mode.replace('+', '_')}", "live_reference_drivers.py", [mode], roots["reference"])
 
     monkeypatch.setattr(pmf_hip, "Context", OracleContext)
     monkeypatch.chdir(roots["ours"])
@@ -342,10 +394,7 @@ def test_named_drivers_print_what_the_reference_prints(tmp_path, monkeypatch):
             pd.DataFrame({"u": u[part == k], "i": i[part == k], "rating": r[part == k]}).to_csv(d / f"interactions_{name}.csv", index=False)
         (root / "best_hyperparams.txt").write_text(DRIVER_HYPER)
         roots[who] = str(root)
-    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    done = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "live_reference_mains.py")], env=env,
-                          capture_output=True, text=True, timeout=900, cwd=roots["reference"])
-    assert done.returncode == 0, done.stderr[-2000:]
+    _reference_tree("mains", "live_reference_mains.py", [], roots["reference"])
 
     monkeypatch.setattr(pmf_hip, "Context", OracleContext)
     monkeypatch.chdir(roots["ours"])
@@ -403,10 +452,7 @@ def test_tuner_writes_the_file_the_reference_writes(tmp_path, monkeypatch):
         for k, name in enumerate(("train", "validation", "test")):
             pd.DataFrame({"u": u[part == k], "i": i[part == k], "rating": r[part == k]}).to_csv(d / f"interactions_{name}.csv", index=False)
         roots[who] = str(tmp_path / who)
-    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    done = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "live_reference_tuner.py")], env=env,
-                          capture_output=True, text=True, timeout=900, cwd=roots["reference"])
-    assert done.returncode == 0, done.stderr[-2000:]
+    _reference_tree("tuner", "live_reference_tuner.py", [], roots["reference"])
     monkeypatch.setattr(pmf_hip, "Context", OracleContext)
     monkeypatch.chdir(roots["ours"])
     monkeypatch.setattr(sys, "argv", ["tune_all_models", "--n_trials", "1"])
@@ -450,10 +496,7 @@ def test_torch_grid_search_prints_the_reference_protocol(tmp_path, monkeypatch):
         for k, name in enumerate(("train", "validation", "test")):
             pd.DataFrame({"u": u[part == k], "i": i[part == k], "rating": r[part == k]}).to_csv(d / f"interactions_{name}.csv", index=False)
         roots[who] = str(tmp_path / who)
-    env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    done = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "live_reference_tune_torch.py")], env=env,
-                          capture_output=True, text=True, timeout=900, cwd=roots["reference"])
-    assert done.returncode == 0, done.stderr[-2000:]
+    _reference_tree("tune_torch", "live_reference_tune_torch.py", [], roots["reference"])
     monkeypatch.chdir(roots["ours"])
     from src.experiments import tune_hpf_pytorch
     buf = io.StringIO()

@@ -1,8 +1,9 @@
 """Sanitizer job: the HOST half of every translation unit of libpmf_hip.so under
 AddressSanitizer + UndefinedBehaviorSanitizer, driven through the entry points that run without a GPU.
 
-CPU-only by construction (device code is compiled as usual; GPU sanitizers are not available on the GPU
-pool): this file is listed in .gpurunignore and never travels to the GPU box."""
+Host-only by construction: the sanitizers reach the host compilation only (each one behind -Xarch_host when
+compiling; the GPU sanitizer switched off when linking), device code is compiled as usual, and the driver runs with no
+GPU visible, so the test means the same on a machine with a GPU."""
 import os
 import subprocess
 import sys
@@ -62,7 +63,7 @@ print("sanitized entry points exercised:", called)
 
 
 def test_host_side_under_address_and_ub_sanitizers(tmp_path):
-    """Builds the host half of libpmf_hip.so with -fsanitize=address,undefined (device code is compiled as
+    """Builds the host half of libpmf_hip.so under ASan + UBSan (device code is compiled as
     usual; GPU sanitizers are not available) and drives what can run without a GPU: the failing
     pmf_ctx_create, null arguments on every entry point, destroy of a null context."""
     import glob
@@ -87,14 +88,18 @@ def test_host_side_under_address_and_ub_sanitizers(tmp_path):
         out, _ = p.communicate()
         assert p.returncode == 0, out.decode(errors="replace")[-3000:]
     lib = str(tmp_path / "libpmf_hip_san.so")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-fsanitize=address", "-fsanitize=undefined",
-                        "-shared-libsan", "-o", lib] + objs + ["-L/opt/rocm/lib", "-lrccl"], capture_output=True, text=True)
+    host_san = ["-fno-gpu-sanitize", "-fsanitize=address", "-fsanitize=undefined", "-shared-libsan"]   # host objects only
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + host_san + ["-o", lib] + objs + ["-L/opt/rocm/lib", "-lrccl"],
+                       capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     assert "__asan_init" in subprocess.run(["nm", "-D", lib], capture_output=True, text=True).stdout
     drv = tmp_path / "drive.py"
     drv.write_text(SAN_DRIVER)
-    env = dict(os.environ, LD_PRELOAD=rt[0], ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:halt_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    # the ASan runtime goes first in the preload list (libraries already preloaded stay); no GPU is visible to the
+    # driver, whether or not the machine has one
+    preload = " ".join(p for p in (rt[0], os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:halt_on_error=1",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
     out = subprocess.run([sys.executable, str(drv), lib, os.path.join(ROOT, "include", "pmf_hip.h")], env=env,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])

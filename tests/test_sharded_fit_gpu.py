@@ -235,7 +235,7 @@ def test_bench_two_rank_rehearsal_weak_scaling_flag():
 def test_single_gpu_bench_line_is_complete_and_torch_free():
     env = dict(os.environ)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--small", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert res["n_gpus"] == 1 and res["config"]["torch_imported"] is False

@@ -19,13 +19,13 @@ run() {  # name, program args...
 }
 STAGE="${1:-all}"    # trace | pmc | all | topk (a gpurun call is limited to 20 minutes: run the stages in separate calls)
 if [ "$STAGE" = "topk" ]; then
-run topk          "$R/bench.py" --workload topk --steps 3 --warmup 1
+run topk          "$R/bench.py" --workload topk --steps 3 --warmup 1 --full
 exit $?
 fi
 if [ "$STAGE" != "pmc" ]; then
 run gaussian_mf   "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline --only &&
-run hpf_cavi      "$R/bench.py" --workload hpf_cavi --steps 10 --warmup 2 --no-cpu-baseline &&
-run topk          "$R/bench.py" --workload topk --steps 2 --warmup 1 &&
+run hpf_cavi      "$R/bench.py" --workload hpf_cavi --steps 10 --warmup 2 --full --no-cpu-baseline &&
+run topk          "$R/bench.py" --workload topk --steps 2 --warmup 1 --full &&
 run gaussian_k128 "$R/bench.py" --workload gaussian_mf_k128 --steps 3 --warmup 1 --no-cpu-baseline &&
 run ksweep_gauss  "$R/tools/k_sweep.py" gauss 16 30 40 50 72 80 96 100 112 &&
 run ksweep_hpf    "$R/tools/k_sweep.py" hpf 16 20 32 40 || exit 1
