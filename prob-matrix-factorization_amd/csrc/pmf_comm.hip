@@ -506,7 +506,7 @@ void pmf_comm_release(pmf_ctx *ctx) {
     if (cm && --cm->refs == 0) comm_free(cm);
 }
 
-int pmf_comm_stats(pmf_ctx *ctx, int which, size_t bytes, void **out) {
+static int comm_stats(pmf_ctx *ctx, int which, size_t bytes, void **out) {
     *out = nullptr;
     if (ctx->stats_bytes[which] < bytes) {
         if (ctx->d_stats[which]) {
@@ -525,8 +525,8 @@ int pmf_comm_stats(pmf_ctx *ctx, int which, size_t bytes, void **out) {
     return PMF_OK;
 }
 
-// accumulate(c) -> exchange(c) -> finalize(c), pipelined over the row chunks of `side` (`chunked` = false: one
-// message for all rows).  `width` = statistics elements per row.  Three streams, ordered by events only:
+// accumulate(c) -> exchange(c) -> finalize(c) on statistics buffer `which`, pipelined over the row chunks of `side`
+// (`chunked` = false: one message for all rows).  Three streams, ordered by events only:
 //   compute stream      accumulate(0), accumulate(1), ...                       (HBM-bound gathers)
 //   collective stream   the collectives of chunk c as soon as accumulate(c) has finished      (xGMI)
 //   finalize stream     finalize(c) as soon as chunk c's statistics have landed  (row solves: VALU / LDS-bound)
@@ -541,12 +541,13 @@ int pmf_comm_stats(pmf_ctx *ctx, int which, size_t bytes, void **out) {
 // ncclAllGather per state array hands the finalised rows to everybody -- each rank solves 1/N of the rows and all
 // ranks hold the same finalised bytes.  Collective stream order (the same on every rank): RS(0), RS(1), AG(0),
 // RS(2), AG(1), ... so the reduce-scatter of chunk c + 1 never queues behind the finalisation of chunk c.
-int pmf_comm_half_sweep(pmf_ctx *ctx, int side, size_t width, void *stats, bool chunked,
-                        const std::function<int()> &accumulate, const std::function<int()> &finalize,
-                        const PmfExchange &ex) {
+int pmf_comm_half_sweep(pmf_ctx *ctx, int side, int which, size_t width, bool chunked, const PmfExchange &ex,
+                        const std::function<int(void *)> &accumulate, const std::function<int(void *)> &finalize) {
     PmfComm *cm = ctx->comm;
     const int n = chunked ? ctx->n_chunks[side] : 1;
-    int rc = ensure_events(cm, (size_t)n);
+    void *stats = nullptr;
+    int rc = comm_stats(ctx, which, (size_t)ctx->rows[side] * width * ctx->elem, &stats);
+    if (!rc) rc = ensure_events(cm, (size_t)n);
     if (rc) return rc;
     const bool sg = ex.n_arrays > 0 && (ctx->exchange == PMF_EXCHANGE_SCATTER_GATHER ||
                                         (ctx->exchange == PMF_EXCHANGE_AUTO && ex.prefer_scatter && cm->nranks > 1));
@@ -567,7 +568,7 @@ int pmf_comm_half_sweep(pmf_ctx *ctx, int side, size_t width, void *stats, bool 
         ctx->fin_row0 = a;
         ctx->fin_row1 = b;
         ctx->stream = cm->fin_stream;
-        const int r = finalize();
+        const int r = finalize(stats);
         ctx->stream = compute;
         ctx->fin_row0 = ctx->fin_row1 = -1;
         return r;
@@ -596,7 +597,7 @@ int pmf_comm_half_sweep(pmf_ctx *ctx, int side, size_t width, void *stats, bool 
     int gathered = 0;   // chunks whose all-gather has been queued
     for (int c = 0; c < n && !rc; ++c) {
         ctx->cur_chunk[side] = chunked ? c : -1;
-        if ((rc = accumulate())) break;
+        if ((rc = accumulate(stats))) break;
         int64_t r0, r1;
         chunk_rows(c, r0, r1);
         hipError_t e = hipEventRecord(cm->ev_ready[(size_t)c], compute);

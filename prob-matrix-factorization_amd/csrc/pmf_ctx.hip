@@ -490,21 +490,14 @@ static int fill_side_host(pmf_ctx *ctx, int side, int64_t nnz, const int32_t *ke
     for (int64_t n = 0; n < nnz; ++n) ix.h_ptr[(size_t)key[n] + 1]++;
     for (int64_t r = 0; r < rows; ++r) ix.h_ptr[(size_t)r + 1] += ix.h_ptr[(size_t)r];
     std::vector<int64_t> cursor(ix.h_ptr.begin(), ix.h_ptr.end() - 1);
-    if (ctx->dtype == PMF_F64) {
-        double *v = (double *)val.data();
+    pmf_with_dtype(ctx, [&](auto t) {
+        auto *v = (decltype(t) *)val.data();
         for (int64_t n = 0; n < nnz; ++n) {
             int64_t d = cursor[(size_t)key[n]]++;
             other[(size_t)d] = oth[n];
-            v[d] = ratings[n];
+            v[d] = (decltype(t))ratings[n];
         }
-    } else {
-        float *v = (float *)val.data();
-        for (int64_t n = 0; n < nnz; ++n) {
-            int64_t d = cursor[(size_t)key[n]]++;
-            other[(size_t)d] = oth[n];
-            v[d] = (float)ratings[n];
-        }
-    }
+    });
     PMF_HIP_CHECK(hipMemcpy(ix.d_ptr, ix.h_ptr.data(), (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (nnz) {
         PMF_HIP_CHECK(hipMemcpy(ix.d_other, other.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -699,13 +692,10 @@ void pmf_array_shape(const pmf_ctx *ctx, int array, int *host_width, int *dev_st
 void pmf_unpack_rows(const pmf_ctx *ctx, int array, const void *src, double *dst, int64_t rows) {
     int width, stride;
     pmf_array_shape(ctx, array, &width, &stride);
-    if (array == PMF_ARR_COV) {
-        if (ctx->dtype == PMF_F64) unpack_cov((const double *)src, dst, rows, ctx->K, stride);
-        else unpack_cov((const float *)src, dst, rows, ctx->K, stride);
-    } else {
-        if (ctx->dtype == PMF_F64) unpack_rows((const double *)src, dst, rows, width, stride);
-        else unpack_rows((const float *)src, dst, rows, width, stride);
-    }
+    pmf_with_dtype(ctx, [&](auto t) {
+        if (array == PMF_ARR_COV) unpack_cov((const decltype(t) *)src, dst, rows, ctx->K, stride);
+        else unpack_rows((const decltype(t) *)src, dst, rows, width, stride);
+    });
 }
 
 static const int64_t kStageBytes = 64ll << 20;
@@ -727,13 +717,10 @@ extern "C" int pmf_set_array(pmf_ctx *ctx, int side, int array, const double *ho
     for (int64_t r0 = 0; r0 < rows; r0 += step) {
         int64_t nr = std::min(step, rows - r0);
         const double *src = host + r0 * width;
-        if (array == PMF_ARR_COV) {
-            if (ctx->dtype == PMF_F64) pack_cov(src, (double *)ctx->h_pinned, nr, ctx->K, stride);
-            else pack_cov(src, (float *)ctx->h_pinned, nr, ctx->K, stride);
-        } else {
-            if (ctx->dtype == PMF_F64) pack_rows(src, (double *)ctx->h_pinned, nr, width, stride);
-            else pack_rows(src, (float *)ctx->h_pinned, nr, width, stride);
-        }
+        pmf_with_dtype(ctx, [&](auto t) {
+            if (array == PMF_ARR_COV) pack_cov(src, (decltype(t) *)ctx->h_pinned, nr, ctx->K, stride);
+            else pack_rows(src, (decltype(t) *)ctx->h_pinned, nr, width, stride);
+        });
         char *dst = (char *)ctx->arr[side][array] + r0 * row_bytes;
         PMF_HIP_CHECK(hipMemcpyAsync(dst, ctx->h_pinned, (size_t)(nr * row_bytes), hipMemcpyHostToDevice, ctx->stream));
         PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -830,13 +817,10 @@ static int array_rows_impl(pmf_ctx *ctx, int side, int array, int64_t n, const i
         PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // the pinned buffer is reused below
         if (host_in) {
             const double *src = host_in + r0 * width;
-            if (array == PMF_ARR_COV) {
-                if (ctx->dtype == PMF_F64) pack_cov(src, (double *)ctx->h_pinned, nr, ctx->K, stride);
-                else pack_cov(src, (float *)ctx->h_pinned, nr, ctx->K, stride);
-            } else {
-                if (ctx->dtype == PMF_F64) pack_rows(src, (double *)ctx->h_pinned, nr, width, stride);
-                else pack_rows(src, (float *)ctx->h_pinned, nr, width, stride);
-            }
+            pmf_with_dtype(ctx, [&](auto t) {
+                if (array == PMF_ARR_COV) pack_cov(src, (decltype(t) *)ctx->h_pinned, nr, ctx->K, stride);
+                else pack_rows(src, (decltype(t) *)ctx->h_pinned, nr, width, stride);
+            });
             PMF_HIP_CHECK(hipMemcpyAsync(d_data, ctx->h_pinned, (size_t)(nr * row_bytes), hipMemcpyHostToDevice, ctx->stream));
             launch_rows_copy<true>(ctx, ctx->arr[side][array], d_data, d_rows, nr, row_bytes);
             PMF_HIP_CHECK(hipGetLastError());
@@ -876,19 +860,16 @@ __global__ void cov_identity_kernel(T *cov, int64_t rows, int K, int stride, T s
 }
 
 extern "C" int pmf_set_cov_identity(pmf_ctx *ctx, int side, double scale) {
-    CHECK_CTX(ctx, "pmf_set_cov_identity");
-    CHECK_SIDE(side, "pmf_set_cov_identity");
-    PMF_HIP_CHECK(hipSetDevice(ctx->device));
+    PMF_SIDE_ENTRY("pmf_set_cov_identity");
     int rc = pmf_alloc_array(ctx, side, PMF_ARR_COV);
     if (rc) return rc;
     int64_t total = ctx->rows[side] * ctx->cov_stride;
     int grid = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    if (ctx->dtype == PMF_F64)
-        hipLaunchKernelGGL(cov_identity_kernel<double>, dim3(grid), dim3(256), 0, ctx->stream,
-                           (double *)ctx->arr[side][PMF_ARR_COV], ctx->rows[side], ctx->K, ctx->cov_stride, scale);
-    else
-        hipLaunchKernelGGL(cov_identity_kernel<float>, dim3(grid), dim3(256), 0, ctx->stream,
-                           (float *)ctx->arr[side][PMF_ARR_COV], ctx->rows[side], ctx->K, ctx->cov_stride, (float)scale);
+    pmf_with_dtype(ctx, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(cov_identity_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, (T *)ctx->arr[side][PMF_ARR_COV],
+                           ctx->rows[side], ctx->K, ctx->cov_stride, (T)scale);
+    });
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
 }

@@ -142,15 +142,6 @@ static int fill_params(pmf_ctx *ctx, int use_bias, double offset, PredictParams<
     return PMF_OK;
 }
 
-static inline int eval_lpr(const pmf_ctx *ctx) { return std::max(4, pmf_lanes_per_row(ctx->kpad)); }
-
-template <typename T, int LPR>
-static void launch_predict(pmf_ctx *ctx, const PredictParams<T> &p, double *out) {
-    constexpr int G = 256 / LPR;
-    int grid = (int)std::min<int64_t>((p.n + G - 1) / G, 8192);
-    hipLaunchKernelGGL((predict_kernel<T, LPR>), dim3(grid), dim3(256), 0, ctx->stream, p, out);
-}
-
 template <typename T>
 static int run_predict(pmf_ctx *ctx, int64_t n, const int32_t *u, const int32_t *i, int use_bias,
                        double offset, double *out) {
@@ -172,13 +163,10 @@ static int run_predict(pmf_ctx *ctx, int64_t n, const int32_t *u, const int32_t 
         p.n = cnt;
         {
             PmfProfScope prof(ctx, PMF_KERNEL_PREDICT);
-            switch (eval_lpr(ctx)) {
-                case 4: launch_predict<T, 4>(ctx, p, d_out); break;
-                case 8: launch_predict<T, 8>(ctx, p, d_out); break;
-                case 16: launch_predict<T, 16>(ctx, p, d_out); break;
-                case 32: launch_predict<T, 32>(ctx, p, d_out); break;
-                default: launch_predict<T, 64>(ctx, p, d_out); break;
-            }
+            pmf_with_pow2<4>(pmf_lanes_per_row(ctx->kpad), [&](auto L) {
+                const int grid = (int)std::min<int64_t>((p.n + 256 / L - 1) / (256 / L), 8192);
+                hipLaunchKernelGGL((predict_kernel<T, L>), dim3(grid), dim3(256), 0, ctx->stream, p, d_out);
+            });
         }
         PMF_HIP_CHECK(hipGetLastError());
         PMF_HIP_CHECK(hipMemcpyAsync(out + at, d_out, (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -194,8 +182,7 @@ extern "C" int pmf_predict(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, con
     if (n == 0) return PMF_OK;
     PMF_REQUIRE(user_ids && item_ids && out, PMF_EINVAL, "pmf_predict: null argument");
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
-    if (ctx->dtype == PMF_F64) return run_predict<double>(ctx, n, user_ids, item_ids, use_bias, offset, out);
-    return run_predict<float>(ctx, n, user_ids, item_ids, use_bias, offset, out);
+    return pmf_with_dtype(ctx, [&](auto t) { return run_predict<decltype(t)>(ctx, n, user_ids, item_ids, use_bias, offset, out); });
 }
 
 extern "C" int pmf_eval_set(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, const int32_t *item_ids,
@@ -231,12 +218,6 @@ extern "C" int pmf_eval_set(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, co
     return PMF_OK;
 }
 
-template <typename T, int LPR>
-static void launch_eval(pmf_ctx *ctx, const PredictParams<T> &p, int grid, double *block_out) {
-    hipLaunchKernelGGL((eval_kernel<T, LPR>), dim3(grid), dim3(256), 0, ctx->stream, p, ctx->eval.d_y,
-                       ctx->eval.d_label, ctx->eval.n_labels, block_out);
-}
-
 template <typename T>
 static int run_eval(pmf_ctx *ctx, int use_bias, double offset, double *sse, double *abs_l, int64_t *cnt_l) {
     PredictParams<T> p;
@@ -246,7 +227,7 @@ static int run_eval(pmf_ctx *ctx, int use_bias, double offset, double *sse, doub
     p.u = ev.d_u;
     p.i = ev.d_i;
     p.n = ev.n;
-    const int lpr = eval_lpr(ctx);
+    const int lpr = std::max(4, pmf_lanes_per_row(ctx->kpad));
     const int G = 256 / lpr;
     const int grid = (int)std::min<int64_t>((ev.n + G - 1) / G, 1024);
     const size_t rec = 1 + 2 * PMF_MAX_LABELS;
@@ -256,13 +237,10 @@ static int run_eval(pmf_ctx *ctx, int use_bias, double offset, double *sse, doub
     double *block_out = (double *)ctx->d_scratch;
     {
         PmfProfScope prof(ctx, PMF_KERNEL_EVAL);
-        switch (lpr) {
-            case 4: launch_eval<T, 4>(ctx, p, grid, block_out); break;
-            case 8: launch_eval<T, 8>(ctx, p, grid, block_out); break;
-            case 16: launch_eval<T, 16>(ctx, p, grid, block_out); break;
-            case 32: launch_eval<T, 32>(ctx, p, grid, block_out); break;
-            default: launch_eval<T, 64>(ctx, p, grid, block_out); break;
-        }
+        pmf_with_pow2<4>(lpr, [&](auto L) {
+            hipLaunchKernelGGL((eval_kernel<T, L>), dim3(grid), dim3(256), 0, ctx->stream, p, ev.d_y, ev.d_label, ev.n_labels,
+                               block_out);
+        });
     }
     PMF_HIP_CHECK(hipGetLastError());
     PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned, block_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -291,6 +269,7 @@ extern "C" int pmf_eval_run(pmf_ctx *ctx, int use_bias, double offset, double *s
     PMF_REQUIRE(sum_sq_err && abs_err_per_label && count_per_label, PMF_EINVAL, "pmf_eval_run: null argument");
     PMF_REQUIRE(ctx->eval.n > 0, PMF_EINVAL, "pmf_eval_run: no validation set (call pmf_eval_set)");
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
-    if (ctx->dtype == PMF_F64) return run_eval<double>(ctx, use_bias, offset, sum_sq_err, abs_err_per_label, count_per_label);
-    return run_eval<float>(ctx, use_bias, offset, sum_sq_err, abs_err_per_label, count_per_label);
+    return pmf_with_dtype(ctx, [&](auto t) {
+        return run_eval<decltype(t)>(ctx, use_bias, offset, sum_sq_err, abs_err_per_label, count_per_label);
+    });
 }

@@ -292,79 +292,46 @@ __global__ __launch_bounds__(256) void gamma_finalize_all_kernel(GammaParams<T> 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-template <typename T, int LPR>
-static int launch_gamma(pmf_ctx *ctx, int side, GammaParams<T> &p, const PmfTaskView &tl,
-                        int mode /*0 fused, 1 accumulate, 2 finalize, 3 extended, 4 gather probe*/) {
+struct GammaPriors { double shape = 0, rate = 0; int hierarchical = 0; double hyper_shape = 0, hyper_rate = 0; };
+
+// the sweep kernel over the tasks, then the split kernel over the rows cut into several tasks
+template <typename T, int LPR, bool STATS, bool EXT>
+static void launch_gamma(pmf_ctx *ctx, const GammaParams<T> &p, const PmfTaskView &tl) {
     constexpr int G = 256 / LPR;
-    if (mode == 4) {
-        if (tl.n_tasks > 0)
-            hipLaunchKernelGGL((gamma_gather_probe_kernel<T, LPR>), dim3((unsigned)((tl.n_tasks + G - 1) / G)), dim3(256), 0,
-                               ctx->stream, p, (T *)ctx->d_scratch);
-        PMF_HIP_CHECK(hipGetLastError());
-        return PMF_OK;
+    if (tl.n_tasks > 0) {
+        PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
+        hipLaunchKernelGGL((gamma_sweep_kernel<T, LPR, STATS, EXT>), dim3((unsigned)((tl.n_tasks + G - 1) / G)), dim3(256), 0, ctx->stream, p);
     }
-    if (mode != 2) {
-        if (tl.n_tasks > 0) {
-            PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
-            dim3 grid((unsigned)((tl.n_tasks + G - 1) / G));
-            if (mode == 0)
-                hipLaunchKernelGGL((gamma_sweep_kernel<T, LPR, false, false>), grid, dim3(256), 0, ctx->stream, p);
-            else if (mode == 3)
-                hipLaunchKernelGGL((gamma_sweep_kernel<T, LPR, false, true>), grid, dim3(256), 0, ctx->stream, p);
-            else
-                hipLaunchKernelGGL((gamma_sweep_kernel<T, LPR, true, false>), grid, dim3(256), 0, ctx->stream, p);
-        }
-        if (tl.n_split > 0) {
-            PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
-            size_t smem = (size_t)G * 2 * ctx->kpad * sizeof(T);
-            if (mode == 0)
-                hipLaunchKernelGGL((gamma_split_kernel<T, LPR, false, false>), dim3((unsigned)tl.n_split), dim3(256), smem, ctx->stream, p);
-            else if (mode == 3)
-                hipLaunchKernelGGL((gamma_split_kernel<T, LPR, false, true>), dim3((unsigned)tl.n_split), dim3(256), smem, ctx->stream, p);
-            else
-                hipLaunchKernelGGL((gamma_split_kernel<T, LPR, true, false>), dim3((unsigned)tl.n_split), dim3(256), smem, ctx->stream, p);
-        }
-    } else {
+    if (tl.n_split > 0) {
         PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
-        if (p.rows > p.row0) {
-            dim3 grid((unsigned)((p.rows - p.row0 + G - 1) / G));
-            hipLaunchKernelGGL((gamma_finalize_all_kernel<T, LPR>), grid, dim3(256), 0, ctx->stream, p);
-        }
+        size_t smem = (size_t)G * 2 * ctx->kpad * sizeof(T);
+        hipLaunchKernelGGL((gamma_split_kernel<T, LPR, STATS, EXT>), dim3((unsigned)tl.n_split), dim3(256), smem, ctx->stream, p);
     }
+}
+
+// f(std::integral_constant<int, LPR>()) for the context's lanes per row, then the launch error check
+template <typename F>
+static int gamma_launch(pmf_ctx *ctx, F &&f) {
+    const int lpr = pmf_lanes_per_row(ctx->kpad);
+    PMF_REQUIRE(lpr <= 64, PMF_ERANGE, "pmf_gamma_sweep: unsupported n_factors %d", ctx->K);
+    pmf_with_pow2<1>(lpr, f);
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
 }
 
-template <typename T>
-static int run_gamma(pmf_ctx *ctx, int side, int mode, void *stats, double shape_prior, double rate_prior,
-                     int hierarchical, double hyper_shape, double hyper_rate_prior) {
-    const int other = 1 - side;
-    const PmfSideIndex &ix = ctx->index[side];
-    const PmfTaskView tl = pmf_task_view(ctx, side, ix.gamma_tasks, mode == 1 || mode == 2);
+// the arrays and ratings every gamma launch reads
+static int check_gamma_inputs(pmf_ctx *ctx, int side) {
     int rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gamma_sweep"))) return rc;
-    if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gamma_sweep"))) return rc;
-    PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_gamma_sweep: ratings have not been set");
-    if (mode == 4) {
-        if ((rc = pmf_ensure_scratch(ctx, 64))) return rc;
-    } else if (mode != 1) {
-        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SHAPE))) return rc;
-        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_RATE))) return rc;
-        if (hierarchical) {
-            if ((rc = pmf_require_array(ctx, side, PMF_ARR_PRIOR_RATE, "pmf_gamma_sweep (hierarchical)"))) return rc;
-            if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_HYPER_RATE))) return rc;
-        }
-    }
-    const int pw = 2 * ctx->kpad + (mode == 3 ? PMF_VEC : 0);
-    if (mode != 2 && mode != 4 && tl.n_slots > 0)
-        if ((rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * pw * sizeof(T)))) return rc;
-    if (mode == 3) {
-        if ((rc = pmf_require_array(ctx, side, PMF_ARR_SCALE, "pmf_gamma_ext_sweep"))) return rc;
-        if ((rc = pmf_require_array(ctx, other, PMF_ARR_SCALE, "pmf_gamma_ext_sweep"))) return rc;
-        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SCALE_SHAPE))) return rc;
-        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SCALE_RATE))) return rc;
-    }
+    if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_FACTOR, "pmf_gamma_sweep"))) return rc;
+    PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gamma_sweep: ratings have not been set");
+    return PMF_OK;
+}
 
+template <typename T>
+static GammaParams<T> gamma_params(const pmf_ctx *ctx, int side, const PmfTaskView &tl, void *stats, const GammaPriors &pr, int pw) {
+    const int other = 1 - side;
+    const PmfSideIndex &ix = ctx->index[side];
     GammaParams<T> p;
     p.tasks = tl.d_tasks;
     p.n_tasks = tl.n_tasks;
@@ -384,103 +351,121 @@ static int run_gamma(pmf_ctx *ctx, int side, int mode, void *stats, double shape
     p.pw = pw;
     p.partial = (T *)ctx->d_partial;
     p.stats = (T *)stats;
-    p.shape_prior = (T)shape_prior;
-    p.rate_prior = (T)rate_prior;
-    p.hyper_shape = (T)hyper_shape;
-    p.hyper_rate_prior = (T)hyper_rate_prior;
-    p.hierarchical = hierarchical;
+    p.shape_prior = (T)pr.shape;
+    p.rate_prior = (T)pr.rate;
+    p.hyper_shape = (T)pr.hyper_shape;
+    p.hyper_rate_prior = (T)pr.hyper_rate;
+    p.hierarchical = pr.hierarchical;
     p.K = ctx->K;
     p.kpad = ctx->kpad;
     p.row0 = tl.row0;   // finalize-from-stats covers rows [row0, rows)
     p.rows = tl.row1;
-
-    switch (pmf_lanes_per_row(ctx->kpad)) {
-        case 1: return launch_gamma<T, 1>(ctx, side, p, tl, mode);
-        case 2: return launch_gamma<T, 2>(ctx, side, p, tl, mode);
-        case 4: return launch_gamma<T, 4>(ctx, side, p, tl, mode);
-        case 8: return launch_gamma<T, 8>(ctx, side, p, tl, mode);
-        case 16: return launch_gamma<T, 16>(ctx, side, p, tl, mode);
-        case 32: return launch_gamma<T, 32>(ctx, side, p, tl, mode);
-        case 64: return launch_gamma<T, 64>(ctx, side, p, tl, mode);
-    }
-    pmf_set_error("pmf_gamma_sweep: unsupported n_factors %d", ctx->K);
-    return PMF_ERANGE;
+    return p;
 }
 
-#define GAMMA_PROLOGUE(fn)                                                                              \
-    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, fn ": null context");                                       \
-    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, fn ": bad side %d", side);  \
-    PMF_HIP_CHECK(hipSetDevice(ctx->device));
-
-// several ranks: accumulate -> all-reduce -> finalize on the library's statistics buffer (pmf_comm.hip)
+// `ext`: the extended model (per-row scalar factors phi / psi), fused pass only
 template <typename T>
-static int run_gamma_dist(pmf_ctx *ctx, int side, double shape_prior, double rate_prior, int hierarchical,
-                          double hyper_shape, double hyper_rate_prior) {
-    const size_t width = (size_t)2 * ctx->kpad;
-    void *stats = nullptr;
-    int rc = pmf_comm_stats(ctx, 0, (size_t)ctx->rows[side] * width * sizeof(T), &stats);
-    if (rc) return rc;
-    // finalize is element-wise (cheap) and writes 3 Kpad + 2 values per row for 2 Kpad of statistics: the plain
-    // all-reduce is the default exchange here
-    PmfExchange ex;
-    ex.arrays[ex.n_arrays++] = PMF_ARR_FACTOR;
-    ex.arrays[ex.n_arrays++] = PMF_ARR_SHAPE;
-    ex.arrays[ex.n_arrays++] = PMF_ARR_RATE;
-    if (hierarchical) {
-        ex.arrays[ex.n_arrays++] = PMF_ARR_PRIOR_RATE;
-        ex.arrays[ex.n_arrays++] = PMF_ARR_HYPER_RATE;
+static int run_gamma(pmf_ctx *ctx, int side, PmfPass pass, bool ext, void *stats, const GammaPriors &pr) {
+    const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gamma_tasks, pass != PMF_PASS_FUSED);
+    int rc;
+    if ((rc = check_gamma_inputs(ctx, side))) return rc;
+    if (pass != PMF_PASS_ACCUMULATE) {
+        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SHAPE))) return rc;
+        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_RATE))) return rc;
+        if (pr.hierarchical) {
+            if ((rc = pmf_require_array(ctx, side, PMF_ARR_PRIOR_RATE, "pmf_gamma_sweep (hierarchical)"))) return rc;
+            if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_HYPER_RATE))) return rc;
+        }
     }
-    if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SHAPE))) return rc;   // (the gathers address them before finalize runs)
-    if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_RATE))) return rc;
-    if (hierarchical && (rc = pmf_alloc_array(ctx, side, PMF_ARR_HYPER_RATE))) return rc;
-    return pmf_comm_half_sweep(
-        ctx, side, width, stats, true, [&] { return run_gamma<T>(ctx, side, 1, stats, 0, 0, 0, 0, 0); },
-        [&] { return run_gamma<T>(ctx, side, 2, stats, shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior); },
-        ex);
+    const int pw = 2 * ctx->kpad + (ext ? PMF_VEC : 0);
+    if (pass != PMF_PASS_FINALIZE && tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * pw * sizeof(T)))) return rc;
+    if (ext) {
+        if ((rc = pmf_require_array(ctx, side, PMF_ARR_SCALE, "pmf_gamma_ext_sweep"))) return rc;
+        if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_SCALE, "pmf_gamma_ext_sweep"))) return rc;
+        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SCALE_SHAPE))) return rc;
+        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SCALE_RATE))) return rc;
+    }
+    const GammaParams<T> p = gamma_params<T>(ctx, side, tl, stats, pr, pw);
+    return gamma_launch(ctx, [&](auto L) {
+        constexpr int G = 256 / L;
+        if (pass == PMF_PASS_FINALIZE) {
+            PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
+            if (p.rows > p.row0)
+                hipLaunchKernelGGL((gamma_finalize_all_kernel<T, L>), dim3((unsigned)((p.rows - p.row0 + G - 1) / G)), dim3(256), 0,
+                                   ctx->stream, p);
+        } else if (pass == PMF_PASS_ACCUMULATE) {
+            launch_gamma<T, L, true, false>(ctx, p, tl);
+        } else if (ext) {
+            launch_gamma<T, L, false, true>(ctx, p, tl);
+        } else {
+            launch_gamma<T, L, false, false>(ctx, p, tl);
+        }
+    });
+}
+
+// one launch of the gather-only twin of the fused sweep (pmf_prof_gather_ceiling)
+template <typename T>
+static int run_gather_probe(pmf_ctx *ctx, int side) {
+    const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gamma_tasks, false);
+    int rc;
+    if ((rc = check_gamma_inputs(ctx, side)) || (rc = pmf_ensure_scratch(ctx, 64))) return rc;
+    const GammaParams<T> p = gamma_params<T>(ctx, side, tl, nullptr, GammaPriors(), 2 * ctx->kpad);
+    return gamma_launch(ctx, [&](auto L) {
+        constexpr int G = 256 / L;
+        if (tl.n_tasks > 0)
+            hipLaunchKernelGGL((gamma_gather_probe_kernel<T, L>), dim3((unsigned)((tl.n_tasks + G - 1) / G)), dim3(256), 0,
+                               ctx->stream, p, (T *)ctx->d_scratch);
+    });
 }
 
 extern "C" int pmf_gamma_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior,
                                int hierarchical, double hyper_shape, double hyper_rate_prior) {
-    GAMMA_PROLOGUE("pmf_gamma_sweep");
-    if (side == PMF_SIDE_ITEM && pmf_comm_active(ctx)) {
-        if (ctx->dtype == PMF_F64)
-            return run_gamma_dist<double>(ctx, side, shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior);
-        return run_gamma_dist<float>(ctx, side, shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior);
-    }
-    if (ctx->dtype == PMF_F64)
-        return run_gamma<double>(ctx, side, 0, nullptr, shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior);
-    return run_gamma<float>(ctx, side, 0, nullptr, shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior);
+    PMF_SIDE_ENTRY("pmf_gamma_sweep");
+    const GammaPriors pr = {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior};
+    return pmf_with_dtype(ctx, [&](auto t) {
+        using T = decltype(t);
+        if (side != PMF_SIDE_ITEM || !pmf_comm_active(ctx)) return run_gamma<T>(ctx, side, PMF_PASS_FUSED, false, nullptr, pr);
+        // several ranks (pmf_comm.hip): finalize is element-wise (cheap) and writes 3 Kpad + 2 values per row for 2 Kpad of
+        // statistics, so the plain all-reduce is the default exchange here
+        const PmfExchange ex = {false, pr.hierarchical ? 5 : 3,
+                                {PMF_ARR_FACTOR, PMF_ARR_SHAPE, PMF_ARR_RATE, PMF_ARR_PRIOR_RATE, PMF_ARR_HYPER_RATE}};
+        int rc;
+        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SHAPE))) return rc;   // (the gathers address them before finalize runs)
+        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_RATE))) return rc;
+        if (pr.hierarchical && (rc = pmf_alloc_array(ctx, side, PMF_ARR_HYPER_RATE))) return rc;
+        return pmf_comm_half_sweep(ctx, side, 0, (size_t)2 * ctx->kpad, true, ex,
+                                   [&](void *s) { return run_gamma<T>(ctx, side, PMF_PASS_ACCUMULATE, false, s, GammaPriors()); },
+                                   [&](void *s) { return run_gamma<T>(ctx, side, PMF_PASS_FINALIZE, false, s, pr); });
+    });
 }
 
 extern "C" int pmf_gamma_ext_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior) {
-    GAMMA_PROLOGUE("pmf_gamma_ext_sweep");
+    PMF_SIDE_ENTRY("pmf_gamma_ext_sweep");
     PMF_REQUIRE(!pmf_comm_active(ctx), PMF_EINVAL, "pmf_gamma_ext_sweep: the extended model is not available on several ranks");
-    if (ctx->dtype == PMF_F64) return run_gamma<double>(ctx, side, 3, nullptr, shape_prior, rate_prior, 0, 0, 0);
-    return run_gamma<float>(ctx, side, 3, nullptr, shape_prior, rate_prior, 0, 0, 0);
+    const GammaPriors pr = {shape_prior, rate_prior};
+    return pmf_with_dtype(ctx, [&](auto t) { return run_gamma<decltype(t)>(ctx, side, PMF_PASS_FUSED, true, nullptr, pr); });
 }
 
 extern "C" int pmf_gamma_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
-    GAMMA_PROLOGUE("pmf_gamma_accumulate");
+    PMF_SIDE_ENTRY("pmf_gamma_accumulate");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gamma_accumulate: null stats buffer");
-    if (ctx->dtype == PMF_F64) return run_gamma<double>(ctx, side, 1, stats_dev, 0, 0, 0, 0, 0);
-    return run_gamma<float>(ctx, side, 1, stats_dev, 0, 0, 0, 0, 0);
+    return pmf_with_dtype(ctx, [&](auto t) { return run_gamma<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, false, stats_dev, {}); });
 }
 
 extern "C" int pmf_gamma_finalize(pmf_ctx *ctx, int side, const void *stats_dev, double shape_prior,
                                   double rate_prior, int hierarchical, double hyper_shape,
                                   double hyper_rate_prior) {
-    GAMMA_PROLOGUE("pmf_gamma_finalize");
+    PMF_SIDE_ENTRY("pmf_gamma_finalize");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gamma_finalize: null stats buffer");
-    if (ctx->dtype == PMF_F64)
-        return run_gamma<double>(ctx, side, 2, (void *)stats_dev, shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior);
-    return run_gamma<float>(ctx, side, 2, (void *)stats_dev, shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior);
+    const GammaPriors pr = {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior};
+    return pmf_with_dtype(ctx, [&](auto t) { return run_gamma<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, false, (void *)stats_dev, pr); });
 }
 
 // Profiling aid (no reference counterpart): average device time of `repeats` launches of the
 // gather-only twin of the Poisson/HPF half-sweep of `side` -- the ceiling the cache hierarchy sets
 // for this context's gather pattern (bench.py reports the sweep kernel against it).
 extern "C" int pmf_prof_gather_ceiling(pmf_ctx *ctx, int side, int repeats, double *ms_per_launch) {
-    GAMMA_PROLOGUE("pmf_prof_gather_ceiling");
+    PMF_SIDE_ENTRY("pmf_prof_gather_ceiling");
     PMF_REQUIRE(ms_per_launch != nullptr && repeats >= 1, PMF_EINVAL, "pmf_prof_gather_ceiling: bad arguments");
     hipEvent_t a = nullptr, b = nullptr;
     PMF_HIP_CHECK(hipEventCreate(&a));
@@ -493,8 +478,7 @@ extern "C" int pmf_prof_gather_ceiling(pmf_ctx *ctx, int side, int repeats, doub
     int rc = PMF_OK;
     for (int k = 0; k <= repeats && !rc; ++k) {   // launch 0 warms the caches and is not timed
         if (k == 1) (void)hipEventRecord(a, ctx->stream);
-        rc = ctx->dtype == PMF_F64 ? run_gamma<double>(ctx, side, 4, nullptr, 0, 0, 0, 0, 0)
-                                   : run_gamma<float>(ctx, side, 4, nullptr, 0, 0, 0, 0, 0);
+        rc = pmf_with_dtype(ctx, [&](auto t) { return run_gather_probe<decltype(t)>(ctx, side); });
     }
     float ms = 0.f;
     if (!rc) {

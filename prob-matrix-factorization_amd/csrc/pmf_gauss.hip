@@ -1193,17 +1193,7 @@ __global__ void gauss_bias_finalize_all_kernel(BiasParams<T> p) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-#define GAUSS_PROLOGUE(fn)                                                                              \
-    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, fn ": null context");                                       \
-    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, fn ": bad side %d", side);  \
-    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, fn ": the Gaussian path supports n_factors <= 256 (got %d)", ctx->K); \
-    PMF_HIP_CHECK(hipSetDevice(ctx->device));
-
-static bool use_bias(const pmf_ctx *ctx) {
-    return ctx->arr[0][PMF_ARR_BIAS] != nullptr && ctx->arr[1][PMF_ARR_BIAS] != nullptr;
-}
-
-// mode 0: fused (sums in place, then solve)   mode 1: accumulate into stats
+// fuse: sums in place, then solve   !fuse: sums only (into the statistics or in place)
 template <int KB, int NT, int KS = KB>
 static void launch_accum_mfma_nt(pmf_ctx *ctx, const GaussParams<float> &p, dim3 grid, bool fuse, float is2, float ie2,
                                  float *cov, float *fac) {
@@ -1275,14 +1265,51 @@ static void launch_accum_mfma128(pmf_ctx *ctx, const GaussParams<float> &p, dim3
     }
 }
 
-// *fused is set when the kernel also solved every single-task row (K = 64 fp32,
-// not in stats mode); the caller then only solves the split rows.
+// fp32, K <= 128: the MFMA accumulate kernels.  Returns whether they also solved the rows that are one task (`fuse`:
+// the fused pass sums in place, so dst_s / dst_w are COV / FACTOR).
+static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParams<float> &p, int64_t n_tasks, bool fuse, float is2, float ie2) {
+    if (ctx->K <= 64) {
+        launch_accum_mfma(ctx, p, dim3((unsigned)((n_tasks + 3) / 4)), fuse, is2, ie2, p.dst_s, p.dst_w);
+    } else {  // 64 < K <= 128: one 128-thread block (two wavefronts) per task
+        const size_t smem = (size_t)PAIR_LDS_FLOATS * sizeof(float);
+        dim3 g2((unsigned)n_tasks);
+        const int chunks = ctx->cov_stride / PMF_VEC, nt = ((chunks + 1) / 2 + 63) / 64;
+        if (nt <= 9) launch_accum_mfma128<9>(ctx, p, g2, smem, fuse, is2, ie2, p.dst_s, p.dst_w);
+        else if (nt <= 13) launch_accum_mfma128<13>(ctx, p, g2, smem, fuse, is2, ie2, p.dst_s, p.dst_w);
+        else launch_accum_mfma128<17>(ctx, p, g2, smem, fuse, is2, ie2, p.dst_s, p.dst_w);
+    }
+    return fuse;
+}
+
+// fp64, fp32 with PMF_GAUSS_GENERIC, and 128 < K <= 256 (no reference configuration is this large): the generic
+// accumulate kernel.  Returns whether it also solved the rows that are one task (`fuse`, K <= 64: fp64 only -- the
+// fp32 build has no fused generic kernel, so fuse / is2 / ie2 do not apply to it).
 template <typename T>
-static int run_factor_accumulate(pmf_ctx *ctx, int side, void *stats, double sigma2, double eta2, bool *fused) {
-    *fused = false;
+static bool launch_accum_generic(pmf_ctx *ctx, const GaussParams<T> &p, int64_t n_tasks, bool fuse, T is2, T ie2) {
+    dim3 grid((unsigned)((n_tasks + 3) / 4));
+    const size_t plain = (size_t)4 * 2 * ctx->kpad * sizeof(T), lds = plain + (size_t)4 * ctx->cov_stride * sizeof(T);
+    if constexpr (std::is_same<T, double>::value) {
+        if (fuse) {
+            pmf_with_pow2<8>(ctx->K, [&](auto KR) {
+                hipLaunchKernelGGL((gauss_accum_generic_kernel<T, KR>), grid, dim3(256), lds, ctx->stream, p, is2, ie2, p.dst_s, p.dst_w);
+            });
+            return true;
+        }
+    }
+    hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 0>), grid, dim3(256), plain, ctx->stream, p, (T)0, (T)0,
+                       (T *)nullptr, (T *)nullptr);
+    return false;
+}
+
+// The fused pass sums in place into COV / FACTOR, the accumulate pass into `stats`.  *fused (fused pass): the kernel
+// also solved every single-task row, so the caller only solves the split rows.
+template <typename T>
+static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double sigma2, double eta2,
+                                 bool *fused = nullptr) {
     const int other = 1 - side;
     const PmfSideIndex &ix = ctx->index[side];
-    const PmfTaskView tl = pmf_task_view(ctx, side, ix.gauss_tasks, stats != nullptr);
+    const bool acc = pass == PMF_PASS_ACCUMULATE;
+    const PmfTaskView tl = pmf_task_view(ctx, side, ix.gauss_tasks, acc);
     int rc;
     PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_gauss_factor_sweep: ratings have not been set");
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_factor_sweep"))) return rc;
@@ -1290,8 +1317,9 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, void *stats, double sig
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_factor_sweep"))) return rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_COV, "pmf_gauss_factor_sweep"))) return rc;
     const int width = ctx->cov_stride + ctx->kpad;
-    if (tl.n_slots > 0)
-        if ((rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * width * sizeof(T)))) return rc;
+    if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * width * sizeof(T)))) return rc;
+    if (acc && tl.row1 > tl.row0)  // rows without ratings on this rank contribute zeros
+        PMF_HIP_CHECK(hipMemsetAsync((T *)stats + tl.row0 * width, 0, (size_t)(tl.row1 - tl.row0) * width * sizeof(T), ctx->stream));
     GaussParams<T> p;
     p.tasks = tl.d_tasks;
     p.n_tasks = tl.n_tasks;
@@ -1300,80 +1328,30 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, void *stats, double sig
     p.val = (const T *)ix.d_val;
     p.factor_other = (const T *)ctx->arr[other][PMF_ARR_FACTOR];
     p.cov_other = (const T *)ctx->arr[other][PMF_ARR_COV];
-    const bool bias = use_bias(ctx);
+    const bool bias = pmf_has_bias(ctx);
     p.bias_self = bias ? (const T *)ctx->arr[side][PMF_ARR_BIAS] : nullptr;
     p.bias_other = bias ? (const T *)ctx->arr[other][PMF_ARR_BIAS] : nullptr;
     p.partial = (T *)ctx->d_partial;
-    if (stats) {
-        if (tl.row1 > tl.row0)  // rows without ratings on this rank contribute zeros
-            PMF_HIP_CHECK(hipMemsetAsync((T *)stats + tl.row0 * width, 0, (size_t)(tl.row1 - tl.row0) * width * sizeof(T),
-                                         ctx->stream));
-        p.dst_s = (T *)stats;
-        p.dst_s_stride = width;
-        p.dst_w = (T *)stats + ctx->cov_stride;
-        p.dst_w_stride = width;
-    } else {
-        p.dst_s = (T *)ctx->arr[side][PMF_ARR_COV];
-        p.dst_s_stride = ctx->cov_stride;
-        p.dst_w = (T *)ctx->arr[side][PMF_ARR_FACTOR];
-        p.dst_w_stride = ctx->kpad;
-    }
+    p.dst_s = acc ? (T *)stats : (T *)ctx->arr[side][PMF_ARR_COV];
+    p.dst_s_stride = acc ? width : ctx->cov_stride;
+    p.dst_w = acc ? (T *)stats + ctx->cov_stride : (T *)ctx->arr[side][PMF_ARR_FACTOR];
+    p.dst_w_stride = acc ? width : ctx->kpad;
     p.K = ctx->K;
     p.kpad = ctx->kpad;
     p.kp = ctx->kp;
     p.cov_stride = ctx->cov_stride;
+    bool solved = false;
     if (tl.n_tasks > 0) {
         PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_ACCUM);
-        dim3 grid((unsigned)((tl.n_tasks + 3) / 4));
-        bool fast = false;
-        if constexpr (std::is_same<T, float>::value) {
-            if (!ctx->gauss_generic) {
-                fast = true;
-                const bool fuse = !stats && !ctx->gauss_unfused;
-                *fused = fuse;
-                const float is2 = (float)(1.0 / sigma2), ie2 = (float)(1.0 / eta2);
-                float *cov = (float *)ctx->arr[side][PMF_ARR_COV], *fac = (float *)ctx->arr[side][PMF_ARR_FACTOR];
-                if (ctx->K > 128) {
-                    fast = false;       // 128 < K <= 256: the generic kernels (no reference configuration is this large)
-                    *fused = false;
-                } else if (ctx->K <= 64) {
-                    launch_accum_mfma(ctx, p, grid, fuse, is2, ie2, cov, fac);
-                } else {  // 64 < K <= 128: one 128-thread block (two wavefronts) per task
-                    const size_t smem = (size_t)PAIR_LDS_FLOATS * sizeof(float);
-                    dim3 g2((unsigned)tl.n_tasks);
-                    const int chunks = ctx->cov_stride / PMF_VEC, nt = ((chunks + 1) / 2 + 63) / 64;
-                    if (nt <= 9) launch_accum_mfma128<9>(ctx, p, g2, smem, fuse, is2, ie2, cov, fac);
-                    else if (nt <= 13) launch_accum_mfma128<13>(ctx, p, g2, smem, fuse, is2, ie2, cov, fac);
-                    else launch_accum_mfma128<17>(ctx, p, g2, smem, fuse, is2, ie2, cov, fac);
-                }
-            }
-        }
-        if (!fast) {
-            // fp64 contexts (and fp32 with PMF_GAUSS_GENERIC): K <= 64 rows that are one task are solved in the kernel
-            const bool fuse = !stats && !ctx->gauss_unfused && ctx->K <= 64 && std::is_same<T, double>::value;
-            T *cov = (T *)ctx->arr[side][PMF_ARR_COV], *fac = (T *)ctx->arr[side][PMF_ARR_FACTOR];
-            const T is2 = (T)(1.0 / sigma2), ie2 = (T)(1.0 / eta2);
-            const size_t plain = (size_t)4 * 2 * ctx->kpad * sizeof(T), fused_lds = plain + (size_t)4 * ctx->cov_stride * sizeof(T);
-            *fused = fuse;
-            bool launched = false;
-            if constexpr (std::is_same<T, double>::value) {
-                if (fuse) {
-                    launched = true;
-                    if (ctx->K <= 8)
-                        hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 8>), grid, dim3(256), fused_lds, ctx->stream, p, is2, ie2, cov, fac);
-                    else if (ctx->K <= 16)
-                        hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 16>), grid, dim3(256), fused_lds, ctx->stream, p, is2, ie2, cov, fac);
-                    else if (ctx->K <= 32)
-                        hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 32>), grid, dim3(256), fused_lds, ctx->stream, p, is2, ie2, cov, fac);
-                    else
-                        hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 64>), grid, dim3(256), fused_lds, ctx->stream, p, is2, ie2, cov, fac);
-                }
-            }
-            if (!launched)
-                hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 0>), grid, dim3(256), plain, ctx->stream, p, (T)0, (T)0,
-                                   (T *)nullptr, (T *)nullptr);
+        const bool fuse = !acc && !ctx->gauss_unfused;
+        const T is2 = (T)(1.0 / sigma2), ie2 = (T)(1.0 / eta2);
+        if (std::is_same<T, float>::value && !ctx->gauss_generic && ctx->K <= 128) {
+            if constexpr (std::is_same<T, float>::value) solved = launch_accum_mfma_fp32(ctx, p, tl.n_tasks, fuse, is2, ie2);
+        } else {
+            solved = launch_accum_generic(ctx, p, tl.n_tasks, fuse && ctx->K <= 64, is2, ie2);
         }
     }
+    if (fused) *fused = solved;
     if (tl.n_split > 0) {
         PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
         hipLaunchKernelGGL((gauss_combine_kernel<T>), dim3((unsigned)tl.n_split), dim3(256), 0, ctx->stream, p);
@@ -1382,41 +1360,26 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, void *stats, double sig
     return PMF_OK;
 }
 
-template <typename T, int KR>
-static void launch_solve_reg(pmf_ctx *ctx, const SolveParams<T> &sp) {
-    dim3 grid((unsigned)((sp.n + 3) / 4));
-    hipLaunchKernelGGL((gauss_solve_reg_kernel<T, KR>), grid, dim3(256),
-                       (size_t)4 * ctx->cov_stride * sizeof(T), ctx->stream, sp);
-}
-
+// finalize pass: every row of the selected range from `stats`; fused pass: the rows with ratings (the split rows only
+// when the accumulate kernel solved the others) from the sums in COV / FACTOR
 template <typename T>
-static int run_factor_solve(pmf_ctx *ctx, int side, const void *stats, double sigma2, double eta2,
+static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *stats, double sigma2, double eta2,
                             bool split_rows_only = false) {
-    const PmfSideIndex &ix = ctx->index[side];
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0, PMF_EINVAL, "pmf_gauss_factor_sweep: variances must be positive");
     int rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_factor_finalize"))) return rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_factor_finalize"))) return rc;
-    SolveParams<T> sp;
     const int width = ctx->cov_stride + ctx->kpad;
-    const PmfTaskView tl = pmf_task_view(ctx, side, ix.gauss_tasks, stats != nullptr);
-    if (stats) {
-        sp.rows = nullptr;
-        sp.row0 = tl.row0;
-        sp.n = tl.row1 - tl.row0;
-        sp.src_s = (const T *)stats;
-        sp.src_s_stride = width;
-        sp.src_w = (const T *)stats + ctx->cov_stride;
-        sp.src_w_stride = width;
-    } else {
-        sp.rows = split_rows_only ? tl.d_split_rows : tl.d_nonempty;
-        sp.row0 = 0;
-        sp.n = split_rows_only ? tl.n_split : tl.n_nonempty;
-        sp.src_s = (const T *)ctx->arr[side][PMF_ARR_COV];
-        sp.src_s_stride = ctx->cov_stride;
-        sp.src_w = (const T *)ctx->arr[side][PMF_ARR_FACTOR];
-        sp.src_w_stride = ctx->kpad;
-    }
+    const bool fin = pass == PMF_PASS_FINALIZE;
+    const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gauss_tasks, fin);
+    SolveParams<T> sp;
+    sp.rows = fin ? nullptr : split_rows_only ? tl.d_split_rows : tl.d_nonempty;
+    sp.row0 = fin ? tl.row0 : 0;
+    sp.n = fin ? tl.row1 - tl.row0 : split_rows_only ? tl.n_split : tl.n_nonempty;
+    sp.src_s = fin ? (const T *)stats : (const T *)ctx->arr[side][PMF_ARR_COV];
+    sp.src_s_stride = fin ? width : ctx->cov_stride;
+    sp.src_w = fin ? (const T *)stats + ctx->cov_stride : (const T *)ctx->arr[side][PMF_ARR_FACTOR];
+    sp.src_w_stride = fin ? width : ctx->kpad;
     sp.cov = (T *)ctx->arr[side][PMF_ARR_COV];
     sp.factor = (T *)ctx->arr[side][PMF_ARR_FACTOR];
     sp.inv_sigma2 = (T)(1.0 / sigma2);
@@ -1427,10 +1390,11 @@ static int run_factor_solve(pmf_ctx *ctx, int side, const void *stats, double si
     sp.cov_stride = ctx->cov_stride;
     if (sp.n == 0) return PMF_OK;
     PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SOLVE);
-    if (ctx->K <= 8) launch_solve_reg<T, 8>(ctx, sp);
-    else if (ctx->K <= 16) launch_solve_reg<T, 16>(ctx, sp);
-    else if (ctx->K <= 32) launch_solve_reg<T, 32>(ctx, sp);
-    else if (ctx->K <= 64) launch_solve_reg<T, 64>(ctx, sp);
+    if (ctx->K <= 64)
+        pmf_with_pow2<8>(ctx->K, [&](auto KR) {
+            hipLaunchKernelGGL((gauss_solve_reg_kernel<T, KR>), dim3((unsigned)((sp.n + 3) / 4)), dim3(256),
+                               (size_t)4 * ctx->cov_stride * sizeof(T), ctx->stream, sp);
+        });
     else if (std::is_same<T, float>::value && !ctx->gauss_lds_solve && ctx->K <= 128) {
         if constexpr (std::is_same<T, float>::value) {
             const size_t smem = (size_t)PAIR_LDS_FLOATS * sizeof(float);
@@ -1464,84 +1428,56 @@ static int run_factor_solve(pmf_ctx *ctx, int side, const void *stats, double si
     return PMF_OK;
 }
 
-// several ranks: accumulate -> all-reduce -> finalize on the library's statistics buffer (pmf_comm.hip)
-template <typename T>
-static int run_factor_dist(pmf_ctx *ctx, int side, double sigma2, double eta2) {
-    const size_t width = (size_t)ctx->cov_stride + ctx->kpad;
-    void *stats = nullptr;
-    int rc = pmf_comm_stats(ctx, 0, (size_t)ctx->rows[side] * width * sizeof(T), &stats);
-    if (rc) return rc;
-    // finalize = one K x K solve per row, and the finalised state ([Kp + Kpad] per row) is as wide as the statistics:
-    // reduce-scatter -> solve 1/N of the rows -> all-gather moves the same bytes and divides the solves by N
-    PmfExchange ex;
-    ex.prefer_scatter = true;
-    ex.arrays[ex.n_arrays++] = PMF_ARR_FACTOR;
-    ex.arrays[ex.n_arrays++] = PMF_ARR_COV;
-    return pmf_comm_half_sweep(
-        ctx, side, width, stats, true,
-        [&] {
-            bool fused = false;
-            return run_factor_accumulate<T>(ctx, side, stats, 1.0, 1.0, &fused);
-        },
-        [&] { return run_factor_solve<T>(ctx, side, stats, sigma2, eta2); }, ex);
-}
-
 extern "C" int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
-    GAUSS_PROLOGUE("pmf_gauss_factor_sweep");
+    PMF_SIDE_ENTRY("pmf_gauss_factor_sweep");
+    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_factor_sweep: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0, PMF_EINVAL, "pmf_gauss_factor_sweep: variances must be positive");
-    if (side == PMF_SIDE_ITEM && pmf_comm_active(ctx))
-        return ctx->dtype == PMF_F64 ? run_factor_dist<double>(ctx, side, sigma2, eta2)
-                                     : run_factor_dist<float>(ctx, side, sigma2, eta2);
-    int rc;
-    bool fused = false;
-    if (ctx->dtype == PMF_F64) {
-        if ((rc = run_factor_accumulate<double>(ctx, side, nullptr, sigma2, eta2, &fused))) return rc;
-        return run_factor_solve<double>(ctx, side, nullptr, sigma2, eta2, fused);
-    }
-    if ((rc = run_factor_accumulate<float>(ctx, side, nullptr, sigma2, eta2, &fused))) return rc;
-    return run_factor_solve<float>(ctx, side, nullptr, sigma2, eta2, fused);
+    return pmf_with_dtype(ctx, [&](auto t) {
+        using T = decltype(t);
+        if (side == PMF_SIDE_ITEM && pmf_comm_active(ctx)) {
+            // several ranks (pmf_comm.hip): finalize = one K x K solve per row, and the finalised state ([Kp + Kpad] per row) is
+            // as wide as the statistics: reduce-scatter -> solve 1/N of the rows -> all-gather moves the same bytes, 1/N the solves
+            const PmfExchange ex = {true, 2, {PMF_ARR_FACTOR, PMF_ARR_COV}};
+            return pmf_comm_half_sweep(ctx, side, 0, (size_t)ctx->cov_stride + ctx->kpad, true, ex,
+                                       [&](void *s) { return run_factor_accumulate<T>(ctx, side, PMF_PASS_ACCUMULATE, s, 1.0, 1.0); },
+                                       [&](void *s) { return run_factor_solve<T>(ctx, side, PMF_PASS_FINALIZE, s, sigma2, eta2); });
+        }
+        bool fused = false;
+        int rc = run_factor_accumulate<T>(ctx, side, PMF_PASS_FUSED, nullptr, sigma2, eta2, &fused);
+        return rc ? rc : run_factor_solve<T>(ctx, side, PMF_PASS_FUSED, nullptr, sigma2, eta2, fused);
+    });
 }
 
 extern "C" int pmf_gauss_factor_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
-    GAUSS_PROLOGUE("pmf_gauss_factor_accumulate");
+    PMF_SIDE_ENTRY("pmf_gauss_factor_accumulate");
+    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_factor_accumulate: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_factor_accumulate: null stats buffer");
-    bool fused = false;
-    if (ctx->dtype == PMF_F64) return run_factor_accumulate<double>(ctx, side, stats_dev, 1.0, 1.0, &fused);
-    return run_factor_accumulate<float>(ctx, side, stats_dev, 1.0, 1.0, &fused);
+    return pmf_with_dtype(ctx, [&](auto t) { return run_factor_accumulate<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, stats_dev, 1, 1); });
 }
 
 extern "C" int pmf_gauss_factor_finalize(pmf_ctx *ctx, int side, const void *stats_dev, double sigma2,
                                          double eta2) {
-    GAUSS_PROLOGUE("pmf_gauss_factor_finalize");
+    PMF_SIDE_ENTRY("pmf_gauss_factor_finalize");
+    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_factor_finalize: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_factor_finalize: null stats buffer");
-    if (ctx->dtype == PMF_F64) return run_factor_solve<double>(ctx, side, stats_dev, sigma2, eta2);
-    return run_factor_solve<float>(ctx, side, stats_dev, sigma2, eta2);
+    return pmf_with_dtype(ctx, [&](auto t) { return run_factor_solve<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, stats_dev, sigma2, eta2); });
 }
 
 // ---- bias ------------------------------------------------------------------
-template <typename T, int LPR>
-static void launch_bias(pmf_ctx *ctx, const BiasParams<T> &p, bool stats) {
-    constexpr int G = 256 / LPR;
-    dim3 grid((unsigned)((p.n_tasks + G - 1) / G));
-    if (stats) hipLaunchKernelGGL((gauss_bias_kernel<T, LPR, true>), grid, dim3(256), 0, ctx->stream, p);
-    else hipLaunchKernelGGL((gauss_bias_kernel<T, LPR, false>), grid, dim3(256), 0, ctx->stream, p);
-}
-
-// mode 0 fused, 1 accumulate to stats, 2 finalize from stats
 template <typename T>
-static int run_bias(pmf_ctx *ctx, int side, int mode, void *stats, double sigma2, double eta_bias2) {
+static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double sigma2, double eta_bias2) {
     const int other = 1 - side;
     const PmfSideIndex &ix = ctx->index[side];
-    const PmfTaskView tl = pmf_task_view(ctx, side, ix.bias_tasks, mode != 0);
+    const PmfTaskView tl = pmf_task_view(ctx, side, ix.bias_tasks, pass != PMF_PASS_FUSED);
+    const bool acc = pass == PMF_PASS_ACCUMULATE;
     int rc;
     PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_gauss_bias_sweep: ratings have not been set");
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_bias_sweep"))) return rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_bias_sweep"))) return rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_BIAS, "pmf_gauss_bias_sweep"))) return rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_BIAS, "pmf_gauss_bias_sweep"))) return rc;
-    if (mode != 1) PMF_REQUIRE(sigma2 > 0 && eta_bias2 > 0, PMF_EINVAL, "pmf_gauss_bias_sweep: variances must be positive");
-    if (mode != 2 && tl.n_slots > 0)
-        if ((rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * sizeof(T)))) return rc;
+    if (!acc) PMF_REQUIRE(sigma2 > 0 && eta_bias2 > 0, PMF_EINVAL, "pmf_gauss_bias_sweep: variances must be positive");
+    if (pass != PMF_PASS_FINALIZE && tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * sizeof(T)))) return rc;
     BiasParams<T> p;
     p.tasks = tl.d_tasks;
     p.n_tasks = tl.n_tasks;
@@ -1554,76 +1490,59 @@ static int run_bias(pmf_ctx *ctx, int side, int mode, void *stats, double sigma2
     p.bias_other = (const T *)ctx->arr[other][PMF_ARR_BIAS];
     p.partial = (T *)ctx->d_partial;
     p.stats = (T *)stats;
-    p.inv_sigma2 = mode == 1 ? (T)1 : (T)(1.0 / sigma2);
-    p.inv_eta_bias2 = mode == 1 ? (T)1 : (T)(1.0 / eta_bias2);
+    p.inv_sigma2 = acc ? (T)1 : (T)(1.0 / sigma2);
+    p.inv_eta_bias2 = acc ? (T)1 : (T)(1.0 / eta_bias2);
     p.kpad = ctx->kpad;
     p.row0 = tl.row0;
     p.rows = tl.row1;
-    PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_BIAS);
-    if (mode == 2) {
-        if (p.rows > p.row0) {
-            dim3 grid((unsigned)((p.rows - p.row0 + 255) / 256));
-            hipLaunchKernelGGL((gauss_bias_finalize_all_kernel<T>), grid, dim3(256), 0, ctx->stream, p);
+    PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_BIAS);   // (the statistics memset included)
+    if (pass == PMF_PASS_FINALIZE) {
+        if (p.rows > p.row0)
+            hipLaunchKernelGGL((gauss_bias_finalize_all_kernel<T>), dim3((unsigned)((p.rows - p.row0 + 255) / 256)), dim3(256), 0,
+                               ctx->stream, p);
+    } else {
+        if (acc && p.rows > p.row0)
+            PMF_HIP_CHECK(hipMemsetAsync((T *)stats + p.row0 * 2, 0, (size_t)(p.rows - p.row0) * 2 * sizeof(T), ctx->stream));
+        if (tl.n_tasks > 0)
+            pmf_with_pow2<1>(pmf_lanes_per_row(ctx->kpad), [&](auto L) {
+                dim3 grid((unsigned)((p.n_tasks + 256 / L - 1) / (256 / L)));
+                if (acc) hipLaunchKernelGGL((gauss_bias_kernel<T, L, true>), grid, dim3(256), 0, ctx->stream, p);
+                else hipLaunchKernelGGL((gauss_bias_kernel<T, L, false>), grid, dim3(256), 0, ctx->stream, p);
+            });
+        if (tl.n_split > 0) {
+            dim3 grid((unsigned)((tl.n_split + 255) / 256));
+            if (acc) hipLaunchKernelGGL((gauss_bias_split_kernel<T, true>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr);
+            else hipLaunchKernelGGL((gauss_bias_split_kernel<T, false>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr);
         }
-        PMF_HIP_CHECK(hipGetLastError());
-        return PMF_OK;
-    }
-    if (mode == 1 && p.rows > p.row0)
-        PMF_HIP_CHECK(hipMemsetAsync((T *)stats + p.row0 * 2, 0, (size_t)(p.rows - p.row0) * 2 * sizeof(T), ctx->stream));
-    if (tl.n_tasks > 0) {
-        switch (pmf_lanes_per_row(ctx->kpad)) {
-            case 1: launch_bias<T, 1>(ctx, p, mode == 1); break;
-            case 2: launch_bias<T, 2>(ctx, p, mode == 1); break;
-            case 4: launch_bias<T, 4>(ctx, p, mode == 1); break;
-            case 8: launch_bias<T, 8>(ctx, p, mode == 1); break;
-            case 16: launch_bias<T, 16>(ctx, p, mode == 1); break;
-            case 32: launch_bias<T, 32>(ctx, p, mode == 1); break;
-            default: launch_bias<T, 64>(ctx, p, mode == 1); break;
-        }
-    }
-    if (tl.n_split > 0) {
-        dim3 grid((unsigned)((tl.n_split + 255) / 256));
-        if (mode == 1)
-            hipLaunchKernelGGL((gauss_bias_split_kernel<T, true>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr);
-        else
-            hipLaunchKernelGGL((gauss_bias_split_kernel<T, false>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr);
     }
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
 }
 
-template <typename T>
-static int run_bias_dist(pmf_ctx *ctx, int side, double sigma2, double eta_bias2) {
-    void *stats = nullptr;   // [rows x 2]: latency-bound, one message
-    int rc = pmf_comm_stats(ctx, 1, (size_t)ctx->rows[side] * 2 * sizeof(T), &stats);
-    if (rc) return rc;
-    PmfExchange ex;
-    ex.arrays[ex.n_arrays++] = PMF_ARR_BIAS;
-    return pmf_comm_half_sweep(
-        ctx, side, 2, stats, false, [&] { return run_bias<T>(ctx, side, 1, stats, 1, 1); },
-        [&] { return run_bias<T>(ctx, side, 2, stats, sigma2, eta_bias2); }, ex);
-}
-
 extern "C" int pmf_gauss_bias_sweep(pmf_ctx *ctx, int side, double sigma2, double eta_bias2) {
-    GAUSS_PROLOGUE("pmf_gauss_bias_sweep");
-    if (side == PMF_SIDE_ITEM && pmf_comm_active(ctx))
-        return ctx->dtype == PMF_F64 ? run_bias_dist<double>(ctx, side, sigma2, eta_bias2)
-                                     : run_bias_dist<float>(ctx, side, sigma2, eta_bias2);
-    if (ctx->dtype == PMF_F64) return run_bias<double>(ctx, side, 0, nullptr, sigma2, eta_bias2);
-    return run_bias<float>(ctx, side, 0, nullptr, sigma2, eta_bias2);
+    PMF_SIDE_ENTRY("pmf_gauss_bias_sweep");
+    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_bias_sweep: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
+    return pmf_with_dtype(ctx, [&](auto t) {
+        using T = decltype(t);
+        if (side != PMF_SIDE_ITEM || !pmf_comm_active(ctx)) return run_bias<T>(ctx, side, PMF_PASS_FUSED, nullptr, sigma2, eta_bias2);
+        const PmfExchange ex = {false, 1, {PMF_ARR_BIAS}};   // several ranks: statistics [rows x 2], latency-bound, one message
+        return pmf_comm_half_sweep(ctx, side, 1, 2, false, ex,
+                                   [&](void *s) { return run_bias<T>(ctx, side, PMF_PASS_ACCUMULATE, s, 1, 1); },
+                                   [&](void *s) { return run_bias<T>(ctx, side, PMF_PASS_FINALIZE, s, sigma2, eta_bias2); });
+    });
 }
 
 extern "C" int pmf_gauss_bias_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
-    GAUSS_PROLOGUE("pmf_gauss_bias_accumulate");
+    PMF_SIDE_ENTRY("pmf_gauss_bias_accumulate");
+    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_bias_accumulate: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_bias_accumulate: null stats buffer");
-    if (ctx->dtype == PMF_F64) return run_bias<double>(ctx, side, 1, stats_dev, 1, 1);
-    return run_bias<float>(ctx, side, 1, stats_dev, 1, 1);
+    return pmf_with_dtype(ctx, [&](auto t) { return run_bias<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, stats_dev, 1, 1); });
 }
 
 extern "C" int pmf_gauss_bias_finalize(pmf_ctx *ctx, int side, const void *stats_dev, double sigma2,
                                        double eta_bias2) {
-    GAUSS_PROLOGUE("pmf_gauss_bias_finalize");
+    PMF_SIDE_ENTRY("pmf_gauss_bias_finalize");
+    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_bias_finalize: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_bias_finalize: null stats buffer");
-    if (ctx->dtype == PMF_F64) return run_bias<double>(ctx, side, 2, (void *)stats_dev, sigma2, eta_bias2);
-    return run_bias<float>(ctx, side, 2, (void *)stats_dev, sigma2, eta_bias2);
+    return pmf_with_dtype(ctx, [&](auto t) { return run_bias<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, (void *)stats_dev, sigma2, eta_bias2); });
 }

@@ -7,6 +7,7 @@
 
 #include <functional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "pmf_hip.h"
@@ -39,6 +40,15 @@ void pmf_set_error(const char *fmt, ...);
             return (code);                \
         }                                 \
     } while (0)
+
+// prologue of the per-side entry points (`ctx` and `side` are their arguments)
+#define PMF_SIDE_ENTRY(fn)                                                                             \
+    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, fn ": null context");                                      \
+    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, fn ": bad side %d", side); \
+    PMF_HIP_CHECK(hipSetDevice(ctx->device))
+
+// which part of a half-sweep a call runs: all of it, the raw statistics only, or the rows from summed statistics
+enum PmfPass { PMF_PASS_FUSED, PMF_PASS_ACCUMULATE, PMF_PASS_FINALIZE };
 
 // One unit of sweep work: a contiguous run of one row's ratings.
 // slot < 0  : the run is the whole row  -> the kernel finalises the row itself
@@ -203,7 +213,6 @@ void pmf_unpack_rows(const pmf_ctx *ctx, int array, const void *src, double *dst
 // run  accumulate -> all-reduce -> finalize  through pmf_comm_half_sweep.
 bool pmf_comm_active(const pmf_ctx *ctx);
 void pmf_comm_release(pmf_ctx *ctx);   // detach + free the statistics buffers (pmf_ctx_destroy)
-int pmf_comm_stats(pmf_ctx *ctx, int which, size_t bytes, void **out);
 // hipStreamSynchronize for a context with a communicator: polls the stream, RCCL's asynchronous error state and
 // a deadline (PMF_COMM_TIMEOUT_S, default 1800; 0 = wait for ever), so that a peer that died or never arrived
 // ends in PMF_ECOMM on the surviving ranks instead of a hang.
@@ -215,9 +224,9 @@ struct PmfExchange {
     int n_arrays = 0;
     int arrays[6] = {0, 0, 0, 0, 0, 0};
 };
-int pmf_comm_half_sweep(pmf_ctx *ctx, int side, size_t width, void *stats, bool chunked,
-                        const std::function<int()> &accumulate, const std::function<int()> &finalize,
-                        const PmfExchange &ex);
+// `which` = the statistics buffer (pmf_ctx::d_stats), `width` = its elements per row; accumulate / finalize get it
+int pmf_comm_half_sweep(pmf_ctx *ctx, int side, int which, size_t width, bool chunked, const PmfExchange &ex,
+                        const std::function<int(void *)> &accumulate, const std::function<int(void *)> &finalize);
 
 // profiling brackets (the *_on forms time work on another stream than the context's)
 void pmf_prof_begin(pmf_ctx *ctx, int kernel);
@@ -237,3 +246,20 @@ static inline int pmf_lanes_per_row(int kpad) {
     while (l < kv) l <<= 1;
     return l;
 }
+
+// f(float()) or f(double()), by the context's dtype
+template <typename F>
+static inline auto pmf_with_dtype(const pmf_ctx *ctx, F &&f) {
+    if (ctx->dtype == PMF_F64) return f(double());
+    return f(float());
+}
+
+// f(std::integral_constant<int, L>()) for the power of two L in [MIN, 64] that n rounds up to (64 for n > 64):
+// lanes per row, register tiles of K <= 64.  The instantiations are L = MIN, 2 MIN, ..., 64.
+template <int MIN, typename F>
+static inline auto pmf_with_pow2(int n, F &&f) {
+    if (MIN == 64 || n <= MIN) return f(std::integral_constant<int, MIN>());
+    return pmf_with_pow2<MIN < 64 ? 2 * MIN : 64>(n, f);
+}
+
+static inline bool pmf_has_bias(const pmf_ctx *ctx) { return ctx->arr[0][PMF_ARR_BIAS] && ctx->arr[1][PMF_ARR_BIAS]; }

@@ -159,22 +159,15 @@ __global__ void gauss_sgd_finalize_kernel(SgdParams<T> p) {
     else if (p.bias_self) p.bias_self[row] += st[p.kpad] / cnt;
 }
 
-template <typename T, int LPR>
-void launch_sgd(pmf_ctx *ctx, const SgdParams<T> &p) {
-    constexpr int G = 256 / LPR;
-    hipLaunchKernelGGL((gauss_sgd_kernel<T, LPR>), dim3((unsigned)((p.n_tasks + G - 1) / G)), dim3(256), 0, ctx->stream, p);
-}
-
-// mode 1: accumulate into stats; mode 2: finalize from stats
 template <typename T>
-int run_sgd(pmf_ctx *ctx, int side, int mode, void *stats, double lr, double sigma2, double eta2, double eta_bias2) {
+int run_sgd(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double lr, double sigma2, double eta2, double eta_bias2) {
     const int other = 1 - side;
     const PmfSideIndex &ix = ctx->index[side];
     PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_gauss_sgd_sweep: ratings have not been set");
     int rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_sgd_sweep"))) return rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_sgd_sweep"))) return rc;
-    const bool bias = ctx->arr[0][PMF_ARR_BIAS] != nullptr && ctx->arr[1][PMF_ARR_BIAS] != nullptr;
+    const bool bias = pmf_has_bias(ctx);
     const PmfTaskView tl = pmf_task_view(ctx, side, ix.sgd_tasks, true);
     SgdParams<T> p;
     p.tasks = tl.d_tasks;
@@ -193,11 +186,10 @@ int run_sgd(pmf_ctx *ctx, int side, int mode, void *stats, double lr, double sig
     p.stats = (T *)stats;
     p.row0 = tl.row0;
     p.row1 = tl.row1;
-    if (mode == 1) {
+    if (pass == PMF_PASS_ACCUMULATE) {
         PMF_REQUIRE(lr > 0 && sigma2 > 0 && eta2 > 0 && eta_bias2 > 0, PMF_EINVAL,
                     "pmf_gauss_sgd_sweep: lr and the variances must be positive");
-        if (tl.n_slots > 0)
-            if ((rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * p.width * sizeof(T)))) return rc;
+        if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * p.width * sizeof(T)))) return rc;
         p.partial = (T *)ctx->d_partial;
         p.lr = (T)lr;
         p.inv_sigma2 = (T)(1.0 / sigma2);
@@ -207,17 +199,11 @@ int run_sgd(pmf_ctx *ctx, int side, int mode, void *stats, double lr, double sig
             PMF_HIP_CHECK(hipMemsetAsync((T *)stats + tl.row0 * p.width, 0, (size_t)(tl.row1 - tl.row0) * p.width * sizeof(T),
                                          ctx->stream));
         PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SGD);
-        if (tl.n_tasks > 0) {
-            switch (pmf_lanes_per_row(ctx->kpad)) {
-                case 1: launch_sgd<T, 1>(ctx, p); break;
-                case 2: launch_sgd<T, 2>(ctx, p); break;
-                case 4: launch_sgd<T, 4>(ctx, p); break;
-                case 8: launch_sgd<T, 8>(ctx, p); break;
-                case 16: launch_sgd<T, 16>(ctx, p); break;
-                case 32: launch_sgd<T, 32>(ctx, p); break;
-                default: launch_sgd<T, 64>(ctx, p); break;
-            }
-        }
+        if (tl.n_tasks > 0)
+            pmf_with_pow2<1>(pmf_lanes_per_row(ctx->kpad), [&](auto L) {
+                dim3 grid((unsigned)((p.n_tasks + 256 / L - 1) / (256 / L)));
+                hipLaunchKernelGGL((gauss_sgd_kernel<T, L>), grid, dim3(256), 0, ctx->stream, p);
+            });
         if (tl.n_split > 0) {
             int lanes_k = 1;
             while (lanes_k < p.width) lanes_k <<= 1;   // width <= 260 -> at most 512
@@ -236,11 +222,6 @@ int run_sgd(pmf_ctx *ctx, int side, int mode, void *stats, double lr, double sig
 
 }  // namespace
 
-#define SGD_PROLOGUE(fn)                                                                                \
-    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, fn ": null context");                                       \
-    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, fn ": bad side %d", side);  \
-    PMF_HIP_CHECK(hipSetDevice(ctx->device));
-
 extern "C" int pmf_ctx_sgd_stats_width(pmf_ctx *ctx, int *width) {
     PMF_REQUIRE(ctx != nullptr && width != nullptr, PMF_EINVAL, "pmf_ctx_sgd_stats_width: null argument");
     *width = ctx->kpad + PMF_VEC;
@@ -249,34 +230,27 @@ extern "C" int pmf_ctx_sgd_stats_width(pmf_ctx *ctx, int *width) {
 
 extern "C" int pmf_gauss_sgd_accumulate(pmf_ctx *ctx, int side, void *stats_dev, double lr, double sigma2, double eta2,
                                         double eta_bias2) {
-    SGD_PROLOGUE("pmf_gauss_sgd_accumulate");
+    PMF_SIDE_ENTRY("pmf_gauss_sgd_accumulate");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_sgd_accumulate: null stats buffer");
-    if (ctx->dtype == PMF_F64) return run_sgd<double>(ctx, side, 1, stats_dev, lr, sigma2, eta2, eta_bias2);
-    return run_sgd<float>(ctx, side, 1, stats_dev, lr, sigma2, eta2, eta_bias2);
+    return pmf_with_dtype(ctx, [&](auto t) {
+        return run_sgd<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, stats_dev, lr, sigma2, eta2, eta_bias2);
+    });
 }
 
 extern "C" int pmf_gauss_sgd_finalize(pmf_ctx *ctx, int side, const void *stats_dev) {
-    SGD_PROLOGUE("pmf_gauss_sgd_finalize");
+    PMF_SIDE_ENTRY("pmf_gauss_sgd_finalize");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_sgd_finalize: null stats buffer");
-    if (ctx->dtype == PMF_F64) return run_sgd<double>(ctx, side, 2, (void *)stats_dev, 1, 1, 1, 1);
-    return run_sgd<float>(ctx, side, 2, (void *)stats_dev, 1, 1, 1, 1);
+    return pmf_with_dtype(ctx, [&](auto t) { return run_sgd<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, (void *)stats_dev, 1, 1, 1, 1); });
 }
 
 extern "C" int pmf_gauss_sgd_sweep(pmf_ctx *ctx, int side, double lr, double sigma2, double eta2, double eta_bias2) {
-    SGD_PROLOGUE("pmf_gauss_sgd_sweep");
+    PMF_SIDE_ENTRY("pmf_gauss_sgd_sweep");
     if (side == PMF_SIDE_ITEM && pmf_comm_active(ctx)) {
         // several ranks: the items' rating-count-weighted displacement sums are all-reduced (pmf_comm.hip)
-        const size_t width = (size_t)ctx->kpad + PMF_VEC;
-        void *stats = nullptr;
-        int rc = pmf_comm_stats(ctx, 0, (size_t)ctx->rows[side] * width * ctx->elem, &stats);
-        if (rc) return rc;
-        PmfExchange ex;
-        ex.arrays[ex.n_arrays++] = PMF_ARR_FACTOR;
-        if (ctx->arr[0][PMF_ARR_BIAS] != nullptr && ctx->arr[1][PMF_ARR_BIAS] != nullptr) ex.arrays[ex.n_arrays++] = PMF_ARR_BIAS;
-        return pmf_comm_half_sweep(
-            ctx, side, width, stats, true,
-            [&] { return pmf_gauss_sgd_accumulate(ctx, side, stats, lr, sigma2, eta2, eta_bias2); },
-            [&] { return pmf_gauss_sgd_finalize(ctx, side, stats); }, ex);
+        const PmfExchange ex = {false, pmf_has_bias(ctx) ? 2 : 1, {PMF_ARR_FACTOR, PMF_ARR_BIAS}};
+        return pmf_comm_half_sweep(ctx, side, 0, (size_t)ctx->kpad + PMF_VEC, true, ex,
+                                   [&](void *s) { return pmf_gauss_sgd_accumulate(ctx, side, s, lr, sigma2, eta2, eta_bias2); },
+                                   [&](void *s) { return pmf_gauss_sgd_finalize(ctx, side, s); });
     }
     const int saved = ctx->cur_chunk[side];
     ctx->cur_chunk[side] = -1;  // the one-call form always covers every row

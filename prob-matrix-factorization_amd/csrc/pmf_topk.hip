@@ -755,21 +755,6 @@ static hipError_t launch_topk_fused_mode(pmf_ctx *ctx, const TopkParams &p, dim3
     return hipSuccess;
 }
 
-template <int KH>
-static hipError_t launch_topk_fused(pmf_ctx *ctx, const TopkParams &p, dim3 grid, size_t list_bytes, int mode,
-                                    const float *fu, const float *fi, const float *cu, const float *ci, int k,
-                                    int64_t seg_items, int nseg, float *cand_val, int32_t *cand_idx, int32_t *out_items,
-                                    double *out_scores) {
-    if (mode == PMF_PREDICT_BIAS)
-        return launch_topk_fused_mode<KH, PMF_PREDICT_BIAS>(ctx, p, grid, list_bytes, fu, fi, cu, ci, k, seg_items, nseg,
-                                                            cand_val, cand_idx, out_items, out_scores);
-    if (mode == PMF_PREDICT_SCALE)
-        return launch_topk_fused_mode<KH, PMF_PREDICT_SCALE>(ctx, p, grid, list_bytes, fu, fi, cu, ci, k, seg_items, nseg,
-                                                             cand_val, cand_idx, out_items, out_scores);
-    return launch_topk_fused_mode<KH, 0>(ctx, p, grid, list_bytes, fu, fi, cu, ci, k, seg_items, nseg, cand_val, cand_idx,
-                                         out_items, out_scores);
-}
-
 // fp32, Kpad <= 128, k <= 64
 static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int mode, const float *cu,
                           const float *ci, int32_t *out_items, double *out_scores) {
@@ -808,15 +793,17 @@ static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids
         {
             PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
             dim3 grid((unsigned)((nq + 127) / 128), (unsigned)nseg);
-            const int kh = ctx->kpad <= 16 ? 8 : ctx->kpad <= 32 ? 16 : ctx->kpad <= 64 ? 32 : 64;
-            hipError_t le;
-            switch (kh) {
-                case 8: le = launch_topk_fused<8>(ctx, p, grid, list_bytes, mode, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci, d_out_items, d_out_scores); break;
-                case 16: le = launch_topk_fused<16>(ctx, p, grid, list_bytes, mode, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci, d_out_items, d_out_scores); break;
-                case 32: le = launch_topk_fused<32>(ctx, p, grid, list_bytes, mode, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci, d_out_items, d_out_scores); break;
-                default: le = launch_topk_fused<64>(ctx, p, grid, list_bytes, mode, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci, d_out_items, d_out_scores); break;
-            }
-            PMF_HIP_CHECK(le);
+            // the instantiation for the K class KH and the bias mode
+            auto launch = [&](auto kh, auto m) {
+                return launch_topk_fused_mode<kh, m>(ctx, p, grid, list_bytes, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci,
+                                                     d_out_items, d_out_scores);
+            };
+            auto with_mode = [&](auto kh) {
+                if (mode == PMF_PREDICT_BIAS) return launch(kh, std::integral_constant<int, PMF_PREDICT_BIAS>());
+                if (mode == PMF_PREDICT_SCALE) return launch(kh, std::integral_constant<int, PMF_PREDICT_SCALE>());
+                return launch(kh, std::integral_constant<int, 0>());
+            };
+            PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, with_mode));   // KH: kpad / 2 rounded up to 8, 16, 32 or 64
             if (nseg > 1)
                 hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, d_cv, d_ci, nq,
                                    (int)n_cand, k, d_out_items, d_out_scores);
@@ -906,6 +893,5 @@ extern "C" int pmf_topk_items(pmf_ctx *ctx, int64_t n_query, const int32_t *user
                     "pmf_topk_items: user id %d at position %lld outside [0, %lld)", user_ids[n], (long long)n,
                     (long long)ctx->rows[PMF_SIDE_USER]);
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
-    if (ctx->dtype == PMF_F64) return run_topk<double>(ctx, n_query, user_ids, k, use_bias, out_items, out_scores);
-    return run_topk<float>(ctx, n_query, user_ids, k, use_bias, out_items, out_scores);
+    return pmf_with_dtype(ctx, [&](auto t) { return run_topk<decltype(t)>(ctx, n_query, user_ids, k, use_bias, out_items, out_scores); });
 }
