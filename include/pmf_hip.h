@@ -122,6 +122,13 @@ int pmf_ctx_chunk_rows(pmf_ctx *ctx, int side, int chunk, int64_t *row_begin, in
 int pmf_ctx_select_chunk(pmf_ctx *ctx, int side, int chunk);
 /* bytes of device memory currently held by the context */
 int pmf_ctx_device_bytes(pmf_ctx *ctx, int64_t *bytes);
+/* Hot rows of `side` under the Gaussian gather cache policy (fp32, n_factors <= 64): the most-rated rows of the
+ * side, most-rated first (ties: lower id first), as many as fit the PMF_GAUSS_HOT_MB budget (read when the context
+ * is created; 0 turns the policy off) at cov_stride + kpad floats per row.  The opposite side's sweep gathers them
+ * with the default cache policy and every other row non-temporally; results do not depend on it.  Writes the count
+ * to *n_hot and the first min(count, capacity) ids to `rows` (may be NULL when capacity is 0).  Set by
+ * pmf_ctx_set_ratings. */
+int pmf_ctx_hot_rows(pmf_ctx *ctx, int side, int32_t *rows, int64_t capacity, int64_t *n_hot);
 
 /* Training ratings in their original order (COO).  Replaces
  * `_build_index_lists` (hpf_cavi.py:97-107, gaussian_mf_cavi_bias.py:69-86):

@@ -183,6 +183,8 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
     ctx->gauss_generic = getenv("PMF_GAUSS_GENERIC") != nullptr;
     ctx->gauss_unfused = getenv("PMF_GAUSS_UNFUSED") != nullptr;
     ctx->gauss_lds_solve = getenv("PMF_GAUSS_LDS_SOLVE") != nullptr;
+    const char *hot_mb = getenv("PMF_GAUSS_HOT_MB");
+    ctx->gauss_hot_bytes = (hot_mb ? std::max(atoll(hot_mb), 0LL) : (long long)PMF_GAUSS_HOT_MB_DEFAULT) << 20;
     ctx->topk_two_phase = getenv("PMF_TOPK_TWO_PHASE") != nullptr;
     if (const char *nb = getenv("PMF_TOPK_STAGE_BUFFERS")) ctx->topk_stage_buffers = atoi(nb);
     if (const char *mb = getenv("PMF_TOPK_MAX_BLOCKS")) ctx->topk_max_blocks = atoi(mb);
@@ -214,6 +216,9 @@ static void free_index(pmf_ctx *ctx) {
         ix.d_nonempty = nullptr;
         ix.n_nonempty = 0;
         ix.h_ptr.clear();
+        pmf_dev_free(ctx, ix.d_other_hot, (size_t)ctx->nnz);
+        ix.d_other_hot = nullptr;
+        ix.h_hot.clear();
         ix.h_nonempty.clear();
         ix.nonempty_off.clear();
         free_tasks(ctx, ix.gamma_tasks);
@@ -276,6 +281,16 @@ extern "C" int pmf_ctx_device_bytes(pmf_ctx *ctx, int64_t *bytes) {
     CHECK_CTX(ctx, "pmf_ctx_device_bytes");
     PMF_REQUIRE(bytes, PMF_EINVAL, "pmf_ctx_device_bytes: null argument");
     *bytes = ctx->device_bytes;
+    return PMF_OK;
+}
+
+extern "C" int pmf_ctx_hot_rows(pmf_ctx *ctx, int side, int32_t *rows, int64_t capacity, int64_t *n_hot) {
+    CHECK_CTX(ctx, "pmf_ctx_hot_rows");
+    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, "pmf_ctx_hot_rows: bad side %d", side);
+    PMF_REQUIRE(n_hot && capacity >= 0 && (rows || capacity == 0), PMF_EINVAL, "pmf_ctx_hot_rows: bad argument");
+    const std::vector<int32_t> &hot = ctx->index[side].h_hot;
+    *n_hot = (int64_t)hot.size();
+    std::copy_n(hot.begin(), (size_t)std::min(capacity, *n_hot), rows);
     return PMF_OK;
 }
 
@@ -464,6 +479,51 @@ static int build_work_lists(pmf_ctx *ctx, int side) {
     return PMF_OK;
 }
 
+__global__ void hot_flags_kernel(const int32_t *other, const uint8_t *hot_rows, uint8_t *flags, int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        flags[i] = hot_rows[other[i]];
+}
+
+// Gaussian gather cache policy (pmf_gauss.hip, gauss_accum_mfma_kernel): per side, the most-rated rows whose gathered
+// bytes (packed covariance row + mean row) fit ctx->gauss_hot_bytes, then for each side's index one flag per rating
+// telling whether the row it gathers is hot.  fp32 and K <= 64 only (the kernel that reads the flags).
+static int build_hot_rows(pmf_ctx *ctx) {
+    if (ctx->gauss_hot_bytes <= 0 || ctx->dtype != PMF_F32 || ctx->K > 64 || ctx->nnz == 0) return PMF_OK;
+    const int64_t row_bytes = (int64_t)(ctx->cov_stride + ctx->kpad) * (int64_t)sizeof(float);
+    for (int side = 0; side < 2; ++side) {
+        PmfSideIndex &ix = ctx->index[side];
+        const int64_t n = std::min(ctx->gauss_hot_bytes / row_bytes, ix.n_nonempty);   // degree 0: never gathered
+        std::vector<int32_t> ids(ix.h_nonempty);
+        auto deg = [&](int32_t r) { return ix.h_ptr[(size_t)r + 1] - ix.h_ptr[(size_t)r]; };
+        std::partial_sort(ids.begin(), ids.begin() + n, ids.end(), [&](int32_t a, int32_t b) {
+            return deg(a) != deg(b) ? deg(a) > deg(b) : a < b;
+        });
+        ids.resize((size_t)n);
+        ix.h_hot.swap(ids);
+    }
+    int rc;
+    for (int side = 0; side < 2; ++side) {
+        PmfSideIndex &ix = ctx->index[side];
+        const int other = 1 - side;
+        std::vector<uint8_t> mask((size_t)ctx->rows[other], 0);
+        for (int32_t r : ctx->index[other].h_hot) mask[(size_t)r] = 1;
+        uint8_t *d_mask = nullptr;
+        if ((rc = pmf_dev_alloc(ctx, (void **)&ix.d_other_hot, (size_t)ctx->nnz))) return rc;
+        if ((rc = pmf_dev_alloc(ctx, (void **)&d_mask, mask.size()))) return rc;
+        hipError_t e = hipMemcpy(d_mask, mask.data(), mask.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            const int64_t blocks = std::min<int64_t>((ctx->nnz + 255) / 256, 65536);
+            hipLaunchKernelGGL(hot_flags_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ix.d_other, d_mask,
+                               ix.d_other_hot, ctx->nnz);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        pmf_dev_free(ctx, d_mask, mask.size());
+        PMF_HIP_CHECK(e);
+    }
+    return PMF_OK;
+}
+
 static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, const int32_t *item_ids,
                             const double *ratings);
 
@@ -571,7 +631,7 @@ static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, 
         ix.h_nonempty.swap(nonempty);
         if ((rc = build_work_lists(ctx, side))) return rc;
     }
-    return PMF_OK;
+    return build_hot_rows(ctx);
 }
 
 // ---------------------------------------------------------------------------

@@ -42,6 +42,9 @@ struct GaussParams {
     T *dst_w;
     int64_t dst_w_stride;
     int K, kpad, kp, cov_stride;
+    // [nnz] per rating of `other`: 1 if that row of the opposite side is hot (PMF_GAUSS_HOT_MB), null = all hot.
+    // Read by the fp32 K <= 64 accumulate only: cold rows are gathered with non-temporal loads.
+    const uint8_t *hot = nullptr;
 };
 
 __device__ __forceinline__ void wave_lds_fence() {
@@ -803,6 +806,31 @@ __global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams
 // per lane outstanding.  The MFMA blocks are folded into the packed image through
 // LDS once per task; a task that is a whole row is solved on the spot (FUSE).
 // KS = register rows of the fused solve (8 / 16 for K <= 8 / 16: a quarter / half of the 32-row sweep).
+//
+// Cache policy of the gathers (p.hot): the most-rated rows of the gathered table, as many as fit the
+// PMF_GAUSS_HOT_MB budget, are loaded with the default policy and all others non-temporally, so that
+// once-touched cold rows do not evict the hot set from the Infinity Cache under its recency-based
+// replacement.  The per-rating flags come 64 at a time with the ids and are ballot-ed into one
+// uniform mask; each trip runs the variant of its pair's (hot, hot) case.  Only the load
+// instructions differ: the sums and their order are those of the uniform default policy.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <bool HOT>
+__device__ __forceinline__ float4 gather_ld(const float4 *ptr) {
+    if constexpr (HOT) {
+        return *ptr;
+    } else {
+        const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(ptr));
+        return make_float4(v.x, v.y, v.z, v.w);
+    }
+}
+
+template <bool HOT>
+__device__ __forceinline__ float gather_ld(const float *ptr) {
+    if constexpr (HOT) return *ptr;
+    else return __builtin_nontemporal_load(ptr);
+}
+
 template <int KB, int NT, bool FUSE, int KS = KB>
 __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel(GaussParams<float> p, float inv_sigma2,
                                                                                 float inv_eta2, float *cov_self,
@@ -814,8 +842,11 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
     //  epoch by less than the box-to-box noise (128.2 / 128.9 against 128.1 / 128.3 ms);
     //  issuing pair t+1 before consuming pair t needs 2 x 75 load registers and spills at NT >= 8)
     // (measured at K = 64 / NT = 9: two pairs in flight 1-2 % slower; one rating at a time at 3 waves
-    //  per SIMD 2.5 % slower than one pair at 2 waves per SIMD; non-temporal loads of the item side's
-    //  streamed-once covariance rows: no difference)
+    //  per SIMD 2.5 % slower than one pair at 2 waves per SIMD.  Non-temporal loads of ALL the item
+    //  side's covariance rows made no difference: they only traded the ~6 % of gathers that LRU kept
+    //  in the Infinity Cache for none.  Non-temporal loads of the COLD rows only (p.hot) keep the
+    //  most-rated rows resident instead: item side 67.7 -> 60.1 ms, user side 57.3 -> 56.0 ms at the
+    //  224 MB default budget)
     constexpr int PU = NT >= 5 ? 1 : (NT >= 3 ? 2 : (NT == 2 ? 4 : 8));
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -845,15 +876,22 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
     // PU = 8 trip of K <= 16 used to wait for eight of them in turn).
     int idx_b = 0;
     float val_b = 0.f;
-    auto trip = [&](int j, auto full_tag) {
-        constexpr bool FULL = decltype(full_tag)::value;
-        float4 a[PU][NT], b[PU][NT];
-        float mlo[PU], mhi[PU], res[PU];
+    uint64_t hot_b = ~0ull;   // bit l: rating l of the batch gathers a hot row
+    const uint8_t *hot = p.hot ? p.hot + t.start : nullptr;
+    auto fetch = [&](int j) {
         if ((j & 63) == 0) {   // a trip never straddles a batch: 2 PU divides 64
             const int jj = min(j + lane, t.len - 1);
             idx_b = col[jj];
             val_b = val[jj];
+            if (hot) hot_b = __builtin_amdgcn_ballot_w64(__builtin_nontemporal_load(hot + jj) != 0);
         }
+    };
+    // POL: the (hot0, hot1) case of the trip's pair as bits 0 / 1 (PU = 1); -1 = per pair (PU > 1)
+    auto trip = [&](int j, auto full_tag, auto pol_tag) {
+        constexpr bool FULL = decltype(full_tag)::value;
+        constexpr int POL = decltype(pol_tag)::value;
+        float4 a[PU][NT], b[PU][NT];
+        float mlo[PU], mhi[PU], res[PU];
 #pragma unroll
         for (int u = 0; u < PU; ++u) {
             const int j0 = j + 2 * u, l0 = j0 & 63;
@@ -865,23 +903,34 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
             const int oh = h ? o1 : o0;
             const bool live = h ? has1 : has0;
             const float *mrow = p.factor_other + (int64_t)oh * kpad;
-            mlo[u] = (live && lo_ok) ? mrow[c] : 0.f;
-            mhi[u] = (live && hi_ok) ? mrow[32 + c] : 0.f;
             const float xh = h ? x1 : x0;
             res[u] = live ? xh - b_self - (p.bias_other ? p.bias_other[oh] : 0.f) : 0.f;
             const float4 *v0 = reinterpret_cast<const float4 *>(p.cov_other + (int64_t)o0 * stride);
             const float4 *v1 = reinterpret_cast<const float4 *>(p.cov_other + (int64_t)o1 * stride);
+            auto loads = [&](auto h0_tag, auto h1_tag) {
+                constexpr bool H0 = decltype(h0_tag)::value, H1 = decltype(h1_tag)::value;
+                // one mean-row load serves both ratings: non-temporal only when both rows are cold
+                mlo[u] = (live && lo_ok) ? gather_ld<H0 || H1>(mrow + c) : 0.f;
+                mhi[u] = (live && hi_ok) ? gather_ld<H0 || H1>(mrow + 32 + c) : 0.f;
 #pragma unroll
-            for (int s = 0; s < NT; ++s) {
-                // only the last chunk column can run past the row: those lanes re-read the row's
-                // last chunk (same cache line, no extra traffic) and their sums are never stored,
-                // which keeps the whole trip free of divergent branches
-                const int q = (s + 1 < NT) ? lane + 64 * s : min(lane + 64 * s, chunks - 1);
-                a[u][s] = make_float4(0.f, 0.f, 0.f, 0.f);
-                b[u][s] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (has0) a[u][s] = v0[q];
-                if (has1) b[u][s] = v1[q];
-            }
+                for (int s = 0; s < NT; ++s) {
+                    // only the last chunk column can run past the row: those lanes re-read the row's
+                    // last chunk (same cache line, no extra traffic) and their sums are never stored,
+                    // which keeps the whole trip free of divergent branches
+                    const int q = (s + 1 < NT) ? lane + 64 * s : min(lane + 64 * s, chunks - 1);
+                    a[u][s] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    b[u][s] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (has0) a[u][s] = gather_ld<H0>(v0 + q);
+                    if (has1) b[u][s] = gather_ld<H1>(v1 + q);
+                }
+            };
+            using T_ = std::true_type;
+            using F_ = std::false_type;
+            const int pol = POL >= 0 ? POL : (int)((hot_b >> l0) & 3);   // uniform
+            if (pol == 3) loads(T_{}, T_{});
+            else if (pol == 2) loads(F_{}, T_{});
+            else if (pol == 1) loads(T_{}, F_{});
+            else loads(F_{}, F_{});
         }
 #pragma unroll
         for (int u = 0; u < PU; ++u) {
@@ -901,9 +950,24 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
             }
         }
     };
+    // PU = 1 (K > 48): the whole trip, adds included, is specialised on its pair's case, so that the
+    // scheduler interleaves the 18 loads with the adds exactly as in the single-policy trip.  PU > 1
+    // issues all of a trip's loads before its adds anyway: there each pair picks its loads' variant.
+    auto run = [&](int j, auto full_tag) {
+        fetch(j);
+        if constexpr (PU > 1) {
+            trip(j, full_tag, std::integral_constant<int, -1>{});
+        } else {
+            const int pol = (int)((hot_b >> (j & 63)) & 3);
+            if (pol == 3) trip(j, full_tag, std::integral_constant<int, 3>{});
+            else if (pol == 2) trip(j, full_tag, std::integral_constant<int, 2>{});
+            else if (pol == 1) trip(j, full_tag, std::integral_constant<int, 1>{});
+            else trip(j, full_tag, std::integral_constant<int, 0>{});
+        }
+    };
     int j = 0;
-    for (; j + 2 * PU <= t.len; j += 2 * PU) trip(j, std::true_type{});
-    if (j < t.len) trip(j, std::false_type{});
+    for (; j + 2 * PU <= t.len; j += 2 * PU) run(j, std::true_type{});
+    if (j < t.len) run(j, std::false_type{});
 
     // fold the outer-product blocks into the packed image via LDS
     float *img = reinterpret_cast<float *>(smem_raw) + (int64_t)wave * stride;
@@ -1328,6 +1392,7 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *sta
     p.val = (const T *)ix.d_val;
     p.factor_other = (const T *)ctx->arr[other][PMF_ARR_FACTOR];
     p.cov_other = (const T *)ctx->arr[other][PMF_ARR_COV];
+    p.hot = ix.d_other_hot;
     const bool bias = pmf_has_bias(ctx);
     p.bias_self = bias ? (const T *)ctx->arr[side][PMF_ARR_BIAS] : nullptr;
     p.bias_other = bias ? (const T *)ctx->arr[other][PMF_ARR_BIAS] : nullptr;

@@ -107,6 +107,11 @@ struct PmfSideIndex {
     PmfTaskList gauss_tasks;     // chunk = PMF_GAUSS_CHUNK, empty rows excluded
     PmfTaskList bias_tasks;      // chunk <= PMF_GAMMA_CHUNK, empty rows excluded
     PmfTaskList sgd_tasks;       // chunk = PMF_SGD_CHUNK exactly (the gradient mode is defined by it), empty rows excluded
+    // Gaussian gather cache policy (PMF_GAUSS_HOT_MB; fp32, K <= 64): this side's most-rated rows, as many as fit
+    // the budget, most-rated first (ties: lower id first) ...
+    std::vector<int32_t> h_hot;
+    // ... and per entry of d_other: 1 if that row of the OPPOSITE side is hot.  Null when the policy is off.
+    uint8_t *d_other_hot = nullptr;
 };
 
 struct PmfEvalSet {
@@ -156,6 +161,7 @@ struct pmf_ctx {
     bool gauss_generic = false;    // PMF_GAUSS_GENERIC: the generic accumulate kernel instead of the MFMA ones
     bool gauss_unfused = false;    // PMF_GAUSS_UNFUSED: accumulate and solve as separate launches
     bool gauss_lds_solve = false;  // PMF_GAUSS_LDS_SOLVE: the block-per-row LDS solve for 64 < K <= 128
+    int64_t gauss_hot_bytes = 0;   // PMF_GAUSS_HOT_MB: budget of the hot gathered rows per side (0: policy off)
     int topk_max_blocks = 0;       // PMF_TOPK_MAX_BLOCKS=n caps the fused kernel's persistent grid (tests: many tiles per block)
     int topk_stage_buffers = 0;    // PMF_TOPK_STAGE_BUFFERS=1|2 pins the fused kernel's stage buffering (0: by residency)
     bool topk_two_phase = false;   // PMF_TOPK_TWO_PHASE: score matrix in HBM + select instead of the fused kernel
@@ -181,6 +187,7 @@ struct pmf_ctx {
 #define PMF_GAMMA_CHUNK 512   // (256 until round 2: 512 halves the split-row slots; HPF K=64 at C3: gamma_final 0.16 -> 0.08 ms)
 #define PMF_SGD_CHUNK 256     // the gradient mode's piece length is part of its definition (include/pmf_hip.h)
 #define PMF_GAUSS_CHUNK 512
+#define PMF_GAUSS_HOT_MB_DEFAULT 224   // hot-row budget when PMF_GAUSS_HOT_MB is unset
 
 // first row of chunk c of a side (c = n_chunks gives the row count)
 static inline int64_t pmf_chunk_row0(const pmf_ctx *ctx, int side, int c) {

@@ -139,6 +139,16 @@ class Context:
         check(self._lib.pmf_ctx_device_bytes(self._h, C.byref(n)), "pmf_ctx_device_bytes")
         return n.value
 
+    def hot_rows(self, side):
+        """Row ids of `side` that the opposite side's Gaussian sweep gathers with the default cache policy
+        (PMF_GAUSS_HOT_MB), most-rated first."""
+        n = C.c_int64(0)
+        check(self._lib.pmf_ctx_hot_rows(self._h, side, None, 0, C.byref(n)), "pmf_ctx_hot_rows")
+        out = np.empty(n.value, dtype=np.int32)
+        check(self._lib.pmf_ctx_hot_rows(self._h, side, out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)),
+              "pmf_ctx_hot_rows")
+        return out
+
     # ---- data -----------------------------------------------------------
     def set_ratings(self, user_ids, item_ids, ratings):
         u, i, x = as_i32(user_ids, "user_ids"), as_i32(item_ids, "item_ids"), as_f64(ratings)
