@@ -79,8 +79,8 @@ struct PmfComm {
     hipStream_t stream = nullptr;             // the collectives' stream
     hipStream_t fin_stream = nullptr;         // finalize(c) runs here, beside the accumulation of later chunks
     std::vector<hipEvent_t> ev_ready, ev_done, ev_fin, ev_gath;  // per row chunk: statistics ready / reduced / finalized / state gathered
-    void *d_small = nullptr;                  // kSmallBytes, host-value collectives
-    void *h_small = nullptr;                  // pinned twin
+    PmfBuf d_small;                           // kSmallBytes, host-value collectives
+    PmfBuf h_small{PmfBuf::PINNED};           // pinned twin
     bool failed = false;                      // a collective failed or timed out: every later call returns PMF_ECOMM
     double timeout_s = 1800.0;                // PMF_COMM_TIMEOUT_S
     bool timeout_from_env = false;
@@ -90,7 +90,7 @@ struct PmfComm {
     void *shm = nullptr;
     size_t shm_bytes = 0;
     bool shm_registered = false;
-    void *h_result = nullptr;                 // pinned, kShmStage: this rank's reduced piece
+    PmfBuf h_result{PmfBuf::PINNED};          // kShmStage: this rank's reduced piece
     ShmHeader *hdr() const { return (ShmHeader *)shm; }
     char *stage(int r) const { return (char *)shm + kShmHeader + (size_t)r * kShmStage; }
     // deadline of a rendezvous / barrier: PMF_COMM_TIMEOUT_S when the environment sets it (a rank whose accumulate
@@ -145,7 +145,7 @@ struct ShmOp {
 
 template <typename T>
 void shm_reduce(PmfComm *cm, size_t lo, size_t hi, int op) {   // element range [lo, hi) of the staged piece
-    T *out = (T *)cm->h_result;
+    T *out = cm->h_result.as<T>();
     const T *first = (const T *)cm->stage(0);
     for (size_t k = lo; k < hi; ++k) out[k] = first[k];
     for (int r = 1; r < cm->nranks; ++r) {   // rank order: every rank gets bit-identical sums
@@ -162,7 +162,7 @@ void shm_host_step(void *arg) {
     ShmOp *o = (ShmOp *)arg;
     PmfComm *cm = o->cm;
     if (shm_barrier(cm)) {                     // every rank's piece is staged
-        if (o->dtype < 0) memcpy(cm->h_result, cm->stage(o->root), o->bytes);
+        if (o->dtype < 0) memcpy(cm->h_result.as(), cm->stage(o->root), o->bytes);
         else if (o->dtype == PMF_F64) shm_reduce<double>(cm, o->lo / 8, o->hi / 8, o->op);
         else shm_reduce<float>(cm, o->lo / 4, o->hi / 4, o->op);
         (void)shm_barrier(cm);                 // nobody overwrites a staging area that is still being read
@@ -191,9 +191,9 @@ int shm_collective(PmfComm *cm, const void *send, void *recv, size_t bytes, int 
             return PMF_EHIP;
         }
         if (bcast)
-            PMF_HIP_CHECK(hipMemcpyAsync((char *)recv + off, cm->h_result, n, hipMemcpyHostToDevice, cm->stream));
+            PMF_HIP_CHECK(hipMemcpyAsync((char *)recv + off, cm->h_result.as(), n, hipMemcpyHostToDevice, cm->stream));
         else if (hi > lo)
-            PMF_HIP_CHECK(hipMemcpyAsync((char *)recv + off + lo, (char *)cm->h_result + lo, hi - lo, hipMemcpyHostToDevice, cm->stream));
+            PMF_HIP_CHECK(hipMemcpyAsync((char *)recv + off + lo, cm->h_result.as<char>() + lo, hi - lo, hipMemcpyHostToDevice, cm->stream));
     }
     return PMF_OK;
 }
@@ -245,11 +245,7 @@ int shm_open_region(PmfComm *cm, const void *unique_id) {
     // pinned staging makes the D2H / H2D legs truly asynchronous; pageable still works
     cm->shm_registered = hipHostRegister(cm->shm, cm->shm_bytes, hipHostRegisterDefault) == hipSuccess;
     if (!cm->shm_registered) (void)hipGetLastError();
-    hipError_t he = hipHostMalloc(&cm->h_result, kShmStage, hipHostMallocDefault);
-    if (he != hipSuccess) {
-        pmf_set_error("hipHostMalloc failed: %s", hipGetErrorString(he));
-        return fail(PMF_EHIP);
-    }
+    if (int rc = cm->h_result.alloc(nullptr, kShmStage)) return fail(rc);
     // rendezvous: the name can go once every rank has mapped the region
     cm->hdr()->attached.fetch_add(1);
     const double t0 = now_s();
@@ -385,17 +381,14 @@ void comm_free(PmfComm *cm) {
         (void)hipStreamSynchronize(cm->fin_stream);
         (void)hipStreamDestroy(cm->fin_stream);
     }
-    if (cm->d_small) (void)hipFree(cm->d_small);
-    if (cm->h_small) (void)hipHostFree(cm->h_small);
 #ifdef PMF_TEST_TRANSPORT
-    if (cm->h_result) (void)hipHostFree(cm->h_result);
     if (cm->shm) {
         if (cm->shm_registered) (void)hipHostUnregister(cm->shm);
         munmap(cm->shm, cm->shm_bytes);
     }
 #endif
     if (cm->stream) (void)hipStreamDestroy(cm->stream);
-    delete cm;
+    delete cm;   // (and with it the staging buffers)
 }
 
 int comm_create(pmf_ctx *ctx, int nranks, int rank, const void *unique_id, int transport) {
@@ -430,8 +423,7 @@ int comm_create(pmf_ctx *ctx, int nranks, int rank, const void *unique_id, int t
             rc = PMF_EHIP;
             break;
         }
-        if (hipMalloc(&cm->d_small, kSmallBytes) != hipSuccess ||
-            hipHostMalloc(&cm->h_small, kSmallBytes, hipHostMallocDefault) != hipSuccess) {
+        if (cm->d_small.alloc(nullptr, kSmallBytes) || cm->h_small.alloc(nullptr, kSmallBytes)) {
             pmf_set_error("pmf_comm_init: cannot allocate the collective staging buffers");
             rc = PMF_ENOMEM;
             break;
@@ -496,33 +488,10 @@ bool pmf_comm_active(const pmf_ctx *ctx) { return ctx->comm != nullptr; }
 int pmf_comm_wait_stream(pmf_ctx *ctx, hipStream_t stream, const char *what) { return comm_wait(ctx->comm, stream, what); }
 
 void pmf_comm_release(pmf_ctx *ctx) {
-    for (int k = 0; k < 2; ++k) {
-        pmf_dev_free(ctx, ctx->d_stats[k], ctx->stats_bytes[k]);
-        ctx->d_stats[k] = nullptr;
-        ctx->stats_bytes[k] = 0;
-    }
+    for (PmfBuf &b : ctx->d_stats) b.reset();
     PmfComm *cm = ctx->comm;
     ctx->comm = nullptr;
     if (cm && --cm->refs == 0) comm_free(cm);
-}
-
-static int comm_stats(pmf_ctx *ctx, int which, size_t bytes, void **out) {
-    *out = nullptr;
-    if (ctx->stats_bytes[which] < bytes) {
-        if (ctx->d_stats[which]) {
-            PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            PMF_HIP_CHECK(hipStreamSynchronize(ctx->comm->stream));
-            PMF_HIP_CHECK(hipStreamSynchronize(ctx->comm->fin_stream));
-            pmf_dev_free(ctx, ctx->d_stats[which], ctx->stats_bytes[which]);
-            ctx->d_stats[which] = nullptr;
-            ctx->stats_bytes[which] = 0;
-        }
-        int rc = pmf_dev_alloc(ctx, &ctx->d_stats[which], bytes);
-        if (rc) return rc;
-        ctx->stats_bytes[which] = bytes;
-    }
-    *out = ctx->d_stats[which];
-    return PMF_OK;
 }
 
 // accumulate(c) -> exchange(c) -> finalize(c) on statistics buffer `which`, pipelined over the row chunks of `side`
@@ -545,10 +514,11 @@ int pmf_comm_half_sweep(pmf_ctx *ctx, int side, int which, size_t width, bool ch
                         const std::function<int(void *)> &accumulate, const std::function<int(void *)> &finalize) {
     PmfComm *cm = ctx->comm;
     const int n = chunked ? ctx->n_chunks[side] : 1;
-    void *stats = nullptr;
-    int rc = comm_stats(ctx, which, (size_t)ctx->rows[side] * width * ctx->elem, &stats);
+    int rc = ctx->d_stats[which].reserve(ctx, (size_t)ctx->rows[side] * width * ctx->elem,
+                                         {ctx->stream, cm->stream, cm->fin_stream});
     if (!rc) rc = ensure_events(cm, (size_t)n);
     if (rc) return rc;
+    void *const stats = ctx->d_stats[which].as();
     const bool sg = ex.n_arrays > 0 && (ctx->exchange == PMF_EXCHANGE_SCATTER_GATHER ||
                                         (ctx->exchange == PMF_EXCHANGE_AUTO && ex.prefer_scatter && cm->nranks > 1));
     const int64_t N = cm->nranks;
@@ -586,7 +556,7 @@ int pmf_comm_half_sweep(pmf_ctx *ctx, int side, int which, size_t width, bool ch
             int host_width, stride;
             pmf_array_shape(ctx, ex.arrays[k], &host_width, &stride);
             const size_t row_bytes = (size_t)stride * ctx->elem;
-            r = comm_all_gather(cm, (char *)ctx->arr[side][ex.arrays[k]] + (size_t)r0 * row_bytes, (size_t)per * row_bytes);
+            r = comm_all_gather(cm, ctx->arr[side][ex.arrays[k]].as<char>() + (size_t)r0 * row_bytes, (size_t)per * row_bytes);
         }
         pmf_prof_end_on(ctx, cm->stream);
         if (r) return r;
@@ -728,14 +698,14 @@ extern "C" int pmf_comm_allreduce_host(pmf_ctx *ctx, double *values, int64_t n, 
     const int64_t step = (int64_t)(kSmallBytes / sizeof(double));
     for (int64_t at = 0; at < n; at += step) {
         const int64_t m = std::min(step, n - at);
-        memcpy(cm->h_small, values + at, (size_t)m * sizeof(double));
-        PMF_HIP_CHECK(hipMemcpyAsync(cm->d_small, cm->h_small, (size_t)m * sizeof(double), hipMemcpyHostToDevice, cm->stream));
-        int rc = comm_allreduce(cm, cm->d_small, (size_t)m, PMF_F64, op);
+        memcpy(cm->h_small.as(), values + at, (size_t)m * sizeof(double));
+        PMF_HIP_CHECK(hipMemcpyAsync(cm->d_small.as(), cm->h_small.as(), (size_t)m * sizeof(double), hipMemcpyHostToDevice, cm->stream));
+        int rc = comm_allreduce(cm, cm->d_small.as(), (size_t)m, PMF_F64, op);
         if (rc) return rc;
-        PMF_HIP_CHECK(hipMemcpyAsync(cm->h_small, cm->d_small, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, cm->stream));
+        PMF_HIP_CHECK(hipMemcpyAsync(cm->h_small.as(), cm->d_small.as(), (size_t)m * sizeof(double), hipMemcpyDeviceToHost, cm->stream));
         if ((rc = comm_wait(cm, cm->stream, "pmf_comm_allreduce_host"))) return rc;
         PMF_REQUIRE(!cm->peer_failed(), PMF_ECOMM, "hostshm transport: a peer failed or timed out");
-        memcpy(values + at, cm->h_small, (size_t)m * sizeof(double));
+        memcpy(values + at, cm->h_small.as(), (size_t)m * sizeof(double));
     }
     return PMF_OK;
 }
@@ -787,12 +757,12 @@ extern "C" int pmf_comm_gather_user_rows(pmf_ctx *ctx, int array, const int64_t 
         for (int64_t r0 = 0; r0 < rows; r0 += step) {
             const int64_t nr = std::min(step, rows - r0);
             const size_t bytes = (size_t)(nr * row_bytes);
-            const char *src = r == cm->rank ? (const char *)ctx->arr[PMF_SIDE_USER][array] + r0 * row_bytes
-                                            : (const char *)ctx->d_scratch;
-            if ((rc = comm_broadcast(cm, src, ctx->d_scratch, bytes, r))) return rc;
-            PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned, ctx->d_scratch, bytes, hipMemcpyDeviceToHost, cm->stream));
+            const char *src = r == cm->rank ? ctx->arr[PMF_SIDE_USER][array].as<const char>() + r0 * row_bytes
+                                            : ctx->d_scratch.as<const char>();
+            if ((rc = comm_broadcast(cm, src, ctx->d_scratch.as(), bytes, r))) return rc;
+            PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned.as(), ctx->d_scratch.as(), bytes, hipMemcpyDeviceToHost, cm->stream));
             if ((rc = comm_wait(cm, cm->stream, "pmf_comm_gather_user_rows"))) return rc;
-            pmf_unpack_rows(ctx, array, ctx->h_pinned, host_full + (bounds[r] + r0) * width, nr);
+            pmf_unpack_rows(ctx, array, ctx->h_pinned.as(), host_full + (bounds[r] + r0) * width, nr);
         }
     }
     PMF_REQUIRE(!cm->peer_failed(), PMF_ECOMM, "hostshm transport: a peer failed or timed out");

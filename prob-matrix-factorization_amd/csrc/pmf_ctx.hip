@@ -43,56 +43,53 @@ extern "C" int pmf_device_count(int *count) {
 // ---------------------------------------------------------------------------
 // memory helpers
 // ---------------------------------------------------------------------------
-int pmf_dev_alloc(pmf_ctx *ctx, void **p, size_t bytes) {
-    *p = nullptr;
+int PmfBuf::alloc(pmf_ctx *owner, size_t bytes) {
+    reset();
     if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(p, bytes);
+    hipError_t e = pinned_ ? hipHostMalloc(&p_, bytes, hipHostMallocDefault) : hipMalloc(&p_, bytes);
     if (e != hipSuccess) {
-        pmf_set_error("hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        p_ = nullptr;
+        pmf_set_error("%s(%zu bytes) failed: %s", pinned_ ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? PMF_ENOMEM : PMF_EHIP;
     }
-    ctx->device_bytes += (int64_t)bytes;
+    bytes_ = bytes;
+    owner_ = owner;
+    if (owner_) owner_->device_bytes += (int64_t)bytes_;
     return PMF_OK;
 }
 
-void pmf_dev_free(pmf_ctx *ctx, void *p, size_t bytes) {
-    if (!p) return;
-    (void)hipFree(p);
-    ctx->device_bytes -= (int64_t)(bytes ? bytes : 16);
+void PmfBuf::reset() {
+    if (!p_) return;
+    (void)(pinned_ ? hipHostFree(p_) : hipFree(p_));
+    if (owner_) owner_->device_bytes -= (int64_t)bytes_;
+    p_ = nullptr;
+    bytes_ = 0;
+    owner_ = nullptr;
 }
 
-static int grow(pmf_ctx *ctx, void **p, size_t *have, size_t want) {
-    if (*have >= want) return PMF_OK;
-    if (*p) {
-        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        pmf_dev_free(ctx, *p, *have);
-        *p = nullptr;
-        *have = 0;
+PmfBuf &PmfBuf::operator=(PmfBuf &&o) noexcept {
+    if (this != &o) {
+        reset();
+        p_ = std::exchange(o.p_, nullptr);
+        bytes_ = std::exchange(o.bytes_, 0);
+        owner_ = std::exchange(o.owner_, nullptr);
+        pinned_ = o.pinned_;
     }
-    int rc = pmf_dev_alloc(ctx, p, want);
-    if (rc) return rc;
-    *have = want;
-    return PMF_OK;
+    return *this;
 }
 
-int pmf_ensure_partial(pmf_ctx *ctx, size_t bytes) {
-    return grow(ctx, &ctx->d_partial, &ctx->partial_bytes, bytes);
-}
-int pmf_ensure_scratch(pmf_ctx *ctx, size_t bytes) {
-    return grow(ctx, &ctx->d_scratch, &ctx->scratch_bytes, bytes);
-}
-int pmf_ensure_pinned(pmf_ctx *ctx, size_t bytes) {
-    if (ctx->pinned_bytes >= bytes) return PMF_OK;
-    if (ctx->h_pinned) {
-        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        (void)hipHostFree(ctx->h_pinned);
-        ctx->h_pinned = nullptr;
-        ctx->pinned_bytes = 0;
+int PmfBuf::reserve(pmf_ctx *owner, size_t bytes, std::initializer_list<hipStream_t> sync) {
+    if (bytes_ >= bytes) return PMF_OK;
+    if (p_) {
+        for (hipStream_t s : sync) PMF_HIP_CHECK(hipStreamSynchronize(s));
+        reset();
     }
-    PMF_HIP_CHECK(hipHostMalloc(&ctx->h_pinned, bytes, hipHostMallocDefault));
-    ctx->pinned_bytes = bytes;
-    return PMF_OK;
+    return alloc(owner, bytes);
 }
+
+int pmf_ensure_partial(pmf_ctx *ctx, size_t bytes) { return ctx->d_partial.reserve(ctx, bytes, {ctx->stream}); }
+int pmf_ensure_scratch(pmf_ctx *ctx, size_t bytes) { return ctx->d_scratch.reserve(ctx, bytes, {ctx->stream}); }
+int pmf_ensure_pinned(pmf_ctx *ctx, size_t bytes) { return ctx->h_pinned.reserve(nullptr, bytes, {ctx->stream}); }
 
 size_t pmf_array_elems(const pmf_ctx *ctx, int side, int array) {
     size_t rows = (size_t)ctx->rows[side];
@@ -123,9 +120,9 @@ int pmf_require_array(pmf_ctx *ctx, int side, int array, const char *what) {
 int pmf_alloc_array(pmf_ctx *ctx, int side, int array) {
     if (ctx->arr[side][array]) return PMF_OK;
     size_t bytes = pmf_array_elems(ctx, side, array) * ctx->elem;
-    int rc = pmf_dev_alloc(ctx, &ctx->arr[side][array], bytes);
+    int rc = ctx->arr[side][array].alloc(ctx, bytes);
     if (rc) return rc;
-    PMF_HIP_CHECK(hipMemsetAsync(ctx->arr[side][array], 0, bytes ? bytes : 16, ctx->stream));
+    PMF_HIP_CHECK(hipMemsetAsync(ctx->arr[side][array].as(), 0, bytes ? bytes : 16, ctx->stream));
     return PMF_OK;
 }
 
@@ -173,13 +170,13 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
     }
     ctx->kp = n_factors * (n_factors + 1) / 2;
     ctx->cov_stride = (ctx->kp + PMF_VEC - 1) / PMF_VEC * PMF_VEC;
-    hipError_t e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking);
+    hipError_t e = hipStreamCreateWithFlags(&ctx->own_stream.s, hipStreamNonBlocking);
     if (e != hipSuccess) {
         pmf_set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
         delete ctx;
         return PMF_EHIP;
     }
-    ctx->stream = ctx->own_stream;
+    ctx->stream = ctx->own_stream.s;
     ctx->gauss_generic = getenv("PMF_GAUSS_GENERIC") != nullptr;
     ctx->gauss_unfused = getenv("PMF_GAUSS_UNFUSED") != nullptr;
     ctx->gauss_lds_solve = getenv("PMF_GAUSS_LDS_SOLVE") != nullptr;
@@ -196,67 +193,40 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
     return PMF_OK;
 }
 
-static void free_tasks(pmf_ctx *ctx, PmfTaskList &t) {
-    pmf_dev_free(ctx, t.d_tasks, (size_t)t.n_tasks * sizeof(PmfTask));
-    pmf_dev_free(ctx, t.d_split, (size_t)t.n_split * sizeof(PmfSplitRow));
-    pmf_dev_free(ctx, t.d_split_rows, (size_t)t.n_split * sizeof(int32_t));
-    t = PmfTaskList();
-}
-
-static void free_index(pmf_ctx *ctx) {
-    for (int s = 0; s < 2; ++s) {
-        PmfSideIndex &ix = ctx->index[s];
-        pmf_dev_free(ctx, ix.d_ptr, (size_t)(ctx->rows[s] + 1) * sizeof(int64_t));
-        pmf_dev_free(ctx, ix.d_other, (size_t)ctx->nnz * sizeof(int32_t));
-        pmf_dev_free(ctx, ix.d_val, (size_t)ctx->nnz * ctx->elem);
-        ix.d_ptr = nullptr;
-        ix.d_other = nullptr;
-        ix.d_val = nullptr;
-        pmf_dev_free(ctx, ix.d_nonempty, (size_t)ix.n_nonempty * sizeof(int32_t));
-        ix.d_nonempty = nullptr;
-        ix.n_nonempty = 0;
-        ix.h_ptr.clear();
-        pmf_dev_free(ctx, ix.d_other_hot, (size_t)ctx->nnz);
-        ix.d_other_hot = nullptr;
-        ix.h_hot.clear();
-        ix.h_nonempty.clear();
-        ix.nonempty_off.clear();
-        free_tasks(ctx, ix.gamma_tasks);
-        free_tasks(ctx, ix.gauss_tasks);
-        free_tasks(ctx, ix.bias_tasks);
-        free_tasks(ctx, ix.sgd_tasks);
-    }
+// Drop the ratings: both sides' index, work lists and hot-row flags.  The sweeps refuse a context in this state.
+static void drop_ratings(pmf_ctx *ctx) {
+    ctx->index[0] = PmfSideIndex();
+    ctx->index[1] = PmfSideIndex();
     ctx->nnz = 0;
 }
 
-static void free_eval(pmf_ctx *ctx) {
-    PmfEvalSet &ev = ctx->eval;
-    pmf_dev_free(ctx, ev.d_u, (size_t)ev.n * 4);
-    pmf_dev_free(ctx, ev.d_i, (size_t)ev.n * 4);
-    pmf_dev_free(ctx, ev.d_y, (size_t)ev.n * 8);
-    pmf_dev_free(ctx, ev.d_label, (size_t)ev.n * 4);
-    ev = PmfEvalSet();
+// Armed once the old index (or its work lists) has been dropped: a rebuild that fails or throws leaves the context
+// without ratings, which every sweep refuses, rather than with half an index.
+struct RatingsGuard {
+    pmf_ctx *ctx;
+    int finish(int rc) {
+        if (rc == PMF_OK) ctx = nullptr;
+        return rc;
+    }
+    ~RatingsGuard() {
+        if (ctx) drop_ratings(ctx);
+    }
+};
+
+pmf_ctx::~pmf_ctx() {
+    if (!stream) return;   // pmf_ctx_create failed before anything was queued or allocated
+    (void)hipStreamSynchronize(stream);
+    pmf_comm_release(this);
+    for (auto &r : prof_pending) {
+        (void)hipEventDestroy(r.a);
+        (void)hipEventDestroy(r.b);
+    }
+    for (auto &e : prof_pool) (void)hipEventDestroy(e);
 }
 
 extern "C" int pmf_ctx_destroy(pmf_ctx *ctx) {
     if (!ctx) return PMF_OK;
     (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    pmf_comm_release(ctx);
-    for (auto &r : ctx->prof_pending) {
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    for (auto &e : ctx->prof_pool) (void)hipEventDestroy(e);
-    free_index(ctx);
-    free_eval(ctx);
-    for (int s = 0; s < 2; ++s)
-        for (int a = 0; a < PMF_ARR_COUNT; ++a)
-            if (ctx->arr[s][a]) pmf_dev_free(ctx, ctx->arr[s][a], pmf_array_elems(ctx, s, a) * ctx->elem);
-    pmf_dev_free(ctx, ctx->d_partial, ctx->partial_bytes);
-    pmf_dev_free(ctx, ctx->d_scratch, ctx->scratch_bytes);
-    if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
-    (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
     return PMF_OK;
 }
@@ -265,7 +235,7 @@ extern "C" int pmf_ctx_set_stream(pmf_ctx *ctx, void *hip_stream) {
     CHECK_CTX(ctx, "pmf_ctx_set_stream");
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
+    ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream.s;
     return PMF_OK;
 }
 
@@ -286,7 +256,7 @@ extern "C" int pmf_ctx_device_bytes(pmf_ctx *ctx, int64_t *bytes) {
 
 extern "C" int pmf_ctx_hot_rows(pmf_ctx *ctx, int side, int32_t *rows, int64_t capacity, int64_t *n_hot) {
     CHECK_CTX(ctx, "pmf_ctx_hot_rows");
-    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, "pmf_ctx_hot_rows: bad side %d", side);
+    CHECK_SIDE(side, "pmf_ctx_hot_rows");
     PMF_REQUIRE(n_hot && capacity >= 0 && (rows || capacity == 0), PMF_EINVAL, "pmf_ctx_hot_rows: bad argument");
     const std::vector<int32_t> &hot = ctx->index[side].h_hot;
     *n_hot = (int64_t)hot.size();
@@ -393,27 +363,27 @@ PmfTaskView pmf_task_view(const pmf_ctx *ctx, int side, const PmfTaskList &tl, b
         }
     };
     if (c < 0 || tl.task_off.empty()) {
-        v.d_tasks = tl.d_tasks;
-        v.d_split = tl.d_split;
-        v.d_split_rows = tl.d_split_rows;
+        v.d_tasks = tl.d_tasks.as<PmfTask>();
+        v.d_split = tl.d_split.as<PmfSplitRow>();
+        v.d_split_rows = tl.d_split_rows.as<int32_t>();
         v.n_tasks = tl.n_tasks;
         v.n_split = tl.n_split;
         v.row0 = 0;
         v.row1 = ctx->rows[side];
-        v.d_nonempty = ix.d_nonempty;
+        v.d_nonempty = ix.d_nonempty.as<int32_t>();
         v.n_nonempty = ix.n_nonempty;
         clip(v);
         return v;
     }
     const size_t g = (size_t)c;
-    v.d_tasks = tl.d_tasks + tl.task_off[g];
+    v.d_tasks = tl.d_tasks.as<PmfTask>() + tl.task_off[g];
     v.n_tasks = tl.task_off[g + 1] - tl.task_off[g];
-    v.d_split = tl.d_split + tl.split_off[g];
-    v.d_split_rows = tl.d_split_rows + tl.split_off[g];
+    v.d_split = tl.d_split.as<PmfSplitRow>() + tl.split_off[g];
+    v.d_split_rows = tl.d_split_rows.as<int32_t>() + tl.split_off[g];
     v.n_split = tl.split_off[g + 1] - tl.split_off[g];
     v.row0 = pmf_chunk_row0(ctx, side, c);
     v.row1 = pmf_chunk_row0(ctx, side, c + 1);
-    v.d_nonempty = ix.d_nonempty + ix.nonempty_off[g];
+    v.d_nonempty = ix.d_nonempty.as<int32_t>() + ix.nonempty_off[g];
     v.n_nonempty = ix.nonempty_off[g + 1] - ix.nonempty_off[g];
     clip(v);
     return v;
@@ -430,19 +400,19 @@ static int upload_tasks(pmf_ctx *ctx, int side, const std::vector<int64_t> &ptr,
     out.n_split = (int64_t)split.size();
     out.n_slots = n_slots;
     out.max_len = tasks.empty() ? 0 : tasks.front().len;
-    int rc = pmf_dev_alloc(ctx, (void **)&out.d_tasks, tasks.size() * sizeof(PmfTask));
+    int rc = out.d_tasks.alloc(ctx, tasks.size() * sizeof(PmfTask));
     if (rc) return rc;
-    rc = pmf_dev_alloc(ctx, (void **)&out.d_split, split.size() * sizeof(PmfSplitRow));
+    rc = out.d_split.alloc(ctx, split.size() * sizeof(PmfSplitRow));
     if (rc) return rc;
     if (!tasks.empty())
-        PMF_HIP_CHECK(hipMemcpy(out.d_tasks, tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
-    rc = pmf_dev_alloc(ctx, (void **)&out.d_split_rows, split.size() * sizeof(int32_t));
+        PMF_HIP_CHECK(hipMemcpy(out.d_tasks.as(), tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
+    rc = out.d_split_rows.alloc(ctx, split.size() * sizeof(int32_t));
     if (rc) return rc;
     if (!split.empty()) {
-        PMF_HIP_CHECK(hipMemcpy(out.d_split, split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
+        PMF_HIP_CHECK(hipMemcpy(out.d_split.as(), split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
         std::vector<int32_t> ids(split.size());
         for (size_t k = 0; k < split.size(); ++k) ids[k] = split[k].row;
-        PMF_HIP_CHECK(hipMemcpy(out.d_split_rows, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        PMF_HIP_CHECK(hipMemcpy(out.d_split_rows.as(), ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     return PMF_OK;
 }
@@ -451,10 +421,7 @@ static int upload_tasks(pmf_ctx *ctx, int side, const std::vector<int64_t> &ptr,
 static int build_work_lists(pmf_ctx *ctx, int side) {
     PmfSideIndex &ix = ctx->index[side];
     const int64_t rows = ctx->rows[side];
-    free_tasks(ctx, ix.gamma_tasks);
-    free_tasks(ctx, ix.gauss_tasks);
-    free_tasks(ctx, ix.bias_tasks);
-    free_tasks(ctx, ix.sgd_tasks);
+    for (PmfTaskList *t : {&ix.gamma_tasks, &ix.gauss_tasks, &ix.bias_tasks, &ix.sgd_tasks}) *t = PmfTaskList();
     const std::vector<int64_t> bounds = chunk_bounds(ctx, side);
     ix.nonempty_off.assign(bounds.size(), (int64_t)ix.h_nonempty.size());
     for (size_t g = 0; g + 1 < bounds.size(); ++g)
@@ -507,19 +474,15 @@ static int build_hot_rows(pmf_ctx *ctx) {
         const int other = 1 - side;
         std::vector<uint8_t> mask((size_t)ctx->rows[other], 0);
         for (int32_t r : ctx->index[other].h_hot) mask[(size_t)r] = 1;
-        uint8_t *d_mask = nullptr;
-        if ((rc = pmf_dev_alloc(ctx, (void **)&ix.d_other_hot, (size_t)ctx->nnz))) return rc;
-        if ((rc = pmf_dev_alloc(ctx, (void **)&d_mask, mask.size()))) return rc;
-        hipError_t e = hipMemcpy(d_mask, mask.data(), mask.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            const int64_t blocks = std::min<int64_t>((ctx->nnz + 255) / 256, 65536);
-            hipLaunchKernelGGL(hot_flags_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ix.d_other, d_mask,
-                               ix.d_other_hot, ctx->nnz);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        pmf_dev_free(ctx, d_mask, mask.size());
-        PMF_HIP_CHECK(e);
+        PmfBuf d_mask;
+        if ((rc = ix.d_other_hot.alloc(ctx, (size_t)ctx->nnz))) return rc;
+        if ((rc = d_mask.alloc(ctx, mask.size()))) return rc;
+        PMF_HIP_CHECK(hipMemcpy(d_mask.as(), mask.data(), mask.size(), hipMemcpyHostToDevice));
+        const int64_t blocks = std::min<int64_t>((ctx->nnz + 255) / 256, 65536);
+        hipLaunchKernelGGL(hot_flags_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, ix.d_other.as<int32_t>(),
+                           d_mask.as<uint8_t>(), ix.d_other_hot.as<uint8_t>(), ctx->nnz);
+        PMF_HIP_CHECK(hipGetLastError());
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // d_mask goes at the end of the iteration
     }
     return PMF_OK;
 }
@@ -558,10 +521,10 @@ static int fill_side_host(pmf_ctx *ctx, int side, int64_t nnz, const int32_t *ke
             v[d] = (decltype(t))ratings[n];
         }
     });
-    PMF_HIP_CHECK(hipMemcpy(ix.d_ptr, ix.h_ptr.data(), (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    PMF_HIP_CHECK(hipMemcpy(ix.d_ptr.as(), ix.h_ptr.data(), (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (nnz) {
-        PMF_HIP_CHECK(hipMemcpy(ix.d_other, other.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-        PMF_HIP_CHECK(hipMemcpy(ix.d_val, val.data(), (size_t)nnz * ctx->elem, hipMemcpyHostToDevice));
+        PMF_HIP_CHECK(hipMemcpy(ix.d_other.as(), other.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+        PMF_HIP_CHECK(hipMemcpy(ix.d_val.as(), val.data(), (size_t)nnz * ctx->elem, hipMemcpyHostToDevice));
     }
     return PMF_OK;
 }
@@ -598,13 +561,14 @@ static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, 
         if ((rc = pmf_index_device_begin(ctx, nnz, user_ids, item_ids, ratings, &build, &bad))) return rc;
         if (bad >= 0) return bad_id_error(ctx, user_ids, item_ids, bad);
     }
-    free_index(ctx);
+    drop_ratings(ctx);
+    RatingsGuard guard{ctx};
     ctx->nnz = nnz;
     for (int side = 0; side < 2; ++side) {
         PmfSideIndex &ix = ctx->index[side];
-        rc = pmf_dev_alloc(ctx, (void **)&ix.d_ptr, (size_t)(ctx->rows[side] + 1) * sizeof(int64_t));
-        if (!rc) rc = pmf_dev_alloc(ctx, (void **)&ix.d_other, (size_t)nnz * sizeof(int32_t));
-        if (!rc) rc = pmf_dev_alloc(ctx, &ix.d_val, (size_t)nnz * ctx->elem);
+        rc = ix.d_ptr.alloc(ctx, (size_t)(ctx->rows[side] + 1) * sizeof(int64_t));
+        if (!rc) rc = ix.d_other.alloc(ctx, (size_t)nnz * sizeof(int32_t));
+        if (!rc) rc = ix.d_val.alloc(ctx, (size_t)nnz * ctx->elem);
         if (rc) {
             pmf_index_device_abort(build);
             return rc;
@@ -625,13 +589,13 @@ static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, 
         for (int64_t r = 0; r < rows; ++r)
             if (ix.h_ptr[(size_t)r + 1] > ix.h_ptr[(size_t)r]) nonempty.push_back((int32_t)r);
         ix.n_nonempty = (int64_t)nonempty.size();
-        if ((rc = pmf_dev_alloc(ctx, (void **)&ix.d_nonempty, nonempty.size() * sizeof(int32_t)))) return rc;
+        if ((rc = ix.d_nonempty.alloc(ctx, nonempty.size() * sizeof(int32_t)))) return rc;
         if (!nonempty.empty())
-            PMF_HIP_CHECK(hipMemcpy(ix.d_nonempty, nonempty.data(), nonempty.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            PMF_HIP_CHECK(hipMemcpy(ix.d_nonempty.as(), nonempty.data(), nonempty.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         ix.h_nonempty.swap(nonempty);
         if ((rc = build_work_lists(ctx, side))) return rc;
     }
-    return build_hot_rows(ctx);
+    return guard.finish(build_hot_rows(ctx));
 }
 
 // ---------------------------------------------------------------------------
@@ -640,7 +604,7 @@ static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, 
 // ---------------------------------------------------------------------------
 static int set_row_chunks_impl(pmf_ctx *ctx, int side, int n_chunks) {
     CHECK_CTX(ctx, "pmf_ctx_set_row_chunks");
-    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, "pmf_ctx_set_row_chunks: bad side %d", side);
+    CHECK_SIDE(side, "pmf_ctx_set_row_chunks");
     PMF_REQUIRE(n_chunks >= 1 && n_chunks <= 1024, PMF_EINVAL,
                 "pmf_ctx_set_row_chunks: n_chunks = %d outside [1, 1024]", n_chunks);
     if ((int64_t)n_chunks > ctx->rows[side]) n_chunks = (int)(ctx->rows[side] > 0 ? ctx->rows[side] : 1);
@@ -648,8 +612,9 @@ static int set_row_chunks_impl(pmf_ctx *ctx, int side, int n_chunks) {
     PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     ctx->n_chunks[side] = n_chunks;
     ctx->cur_chunk[side] = -1;
-    if (ctx->index[side].d_ptr) return build_work_lists(ctx, side);
-    return PMF_OK;
+    if (!ctx->index[side].d_ptr) return PMF_OK;
+    RatingsGuard guard{ctx};
+    return guard.finish(build_work_lists(ctx, side));
 }
 
 extern "C" int pmf_ctx_set_row_chunks(pmf_ctx *ctx, int side, int n_chunks) {
@@ -663,7 +628,7 @@ extern "C" int pmf_ctx_set_row_chunks(pmf_ctx *ctx, int side, int n_chunks) {
 
 extern "C" int pmf_ctx_chunk_rows(pmf_ctx *ctx, int side, int chunk, int64_t *row_begin, int64_t *row_end) {
     CHECK_CTX(ctx, "pmf_ctx_chunk_rows");
-    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, "pmf_ctx_chunk_rows: bad side %d", side);
+    CHECK_SIDE(side, "pmf_ctx_chunk_rows");
     PMF_REQUIRE(row_begin && row_end, PMF_EINVAL, "pmf_ctx_chunk_rows: null argument");
     PMF_REQUIRE(chunk >= 0 && chunk < ctx->n_chunks[side], PMF_ERANGE,
                 "pmf_ctx_chunk_rows: chunk %d outside [0, %d)", chunk, ctx->n_chunks[side]);
@@ -674,7 +639,7 @@ extern "C" int pmf_ctx_chunk_rows(pmf_ctx *ctx, int side, int chunk, int64_t *ro
 
 extern "C" int pmf_ctx_select_chunk(pmf_ctx *ctx, int side, int chunk) {
     CHECK_CTX(ctx, "pmf_ctx_select_chunk");
-    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, "pmf_ctx_select_chunk: bad side %d", side);
+    CHECK_SIDE(side, "pmf_ctx_select_chunk");
     PMF_REQUIRE(chunk >= -1 && chunk < ctx->n_chunks[side], PMF_ERANGE,
                 "pmf_ctx_select_chunk: chunk %d outside [-1, %d)", chunk, ctx->n_chunks[side]);
     ctx->cur_chunk[side] = chunk;
@@ -778,11 +743,11 @@ extern "C" int pmf_set_array(pmf_ctx *ctx, int side, int array, const double *ho
         int64_t nr = std::min(step, rows - r0);
         const double *src = host + r0 * width;
         pmf_with_dtype(ctx, [&](auto t) {
-            if (array == PMF_ARR_COV) pack_cov(src, (decltype(t) *)ctx->h_pinned, nr, ctx->K, stride);
-            else pack_rows(src, (decltype(t) *)ctx->h_pinned, nr, width, stride);
+            if (array == PMF_ARR_COV) pack_cov(src, ctx->h_pinned.as<decltype(t)>(), nr, ctx->K, stride);
+            else pack_rows(src, ctx->h_pinned.as<decltype(t)>(), nr, width, stride);
         });
-        char *dst = (char *)ctx->arr[side][array] + r0 * row_bytes;
-        PMF_HIP_CHECK(hipMemcpyAsync(dst, ctx->h_pinned, (size_t)(nr * row_bytes), hipMemcpyHostToDevice, ctx->stream));
+        char *dst = ctx->arr[side][array].as<char>() + r0 * row_bytes;
+        PMF_HIP_CHECK(hipMemcpyAsync(dst, ctx->h_pinned.as(), (size_t)(nr * row_bytes), hipMemcpyHostToDevice, ctx->stream));
         PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     return PMF_OK;
@@ -804,10 +769,10 @@ extern "C" int pmf_get_array(pmf_ctx *ctx, int side, int array, double *host) {
     if ((rc = pmf_ensure_pinned(ctx, (size_t)(std::min(step, rows) * row_bytes)))) return rc;
     for (int64_t r0 = 0; r0 < rows; r0 += step) {
         int64_t nr = std::min(step, rows - r0);
-        const char *src = (const char *)ctx->arr[side][array] + r0 * row_bytes;
-        PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned, src, (size_t)(nr * row_bytes), hipMemcpyDeviceToHost, ctx->stream));
+        const char *src = ctx->arr[side][array].as<char>() + r0 * row_bytes;
+        PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned.as(), src, (size_t)(nr * row_bytes), hipMemcpyDeviceToHost, ctx->stream));
         PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        pmf_unpack_rows(ctx, array, ctx->h_pinned, host + r0 * width, nr);
+        pmf_unpack_rows(ctx, array, ctx->h_pinned.as(), host + r0 * width, nr);
     }
     return PMF_OK;
 }
@@ -868,29 +833,29 @@ static int array_rows_impl(pmf_ctx *ctx, int side, int array, int64_t n, const i
     const size_t data_bytes = (size_t)((step * row_bytes + 15) / 16 * 16);
     if ((rc = pmf_ensure_scratch(ctx, data_bytes + (size_t)step * sizeof(int64_t)))) return rc;
     if ((rc = pmf_ensure_pinned(ctx, std::max(data_bytes, (size_t)step * sizeof(int64_t))))) return rc;
-    char *d_data = (char *)ctx->d_scratch;
+    char *d_data = ctx->d_scratch.as<char>();
     int64_t *d_rows = (int64_t *)(d_data + data_bytes);
     for (int64_t r0 = 0; r0 < n; r0 += step) {
         const int64_t nr = std::min(step, n - r0);
-        memcpy(ctx->h_pinned, rows + r0, (size_t)nr * sizeof(int64_t));
-        PMF_HIP_CHECK(hipMemcpyAsync(d_rows, ctx->h_pinned, (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+        memcpy(ctx->h_pinned.as(), rows + r0, (size_t)nr * sizeof(int64_t));
+        PMF_HIP_CHECK(hipMemcpyAsync(d_rows, ctx->h_pinned.as(), (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
         PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // the pinned buffer is reused below
         if (host_in) {
             const double *src = host_in + r0 * width;
             pmf_with_dtype(ctx, [&](auto t) {
-                if (array == PMF_ARR_COV) pack_cov(src, (decltype(t) *)ctx->h_pinned, nr, ctx->K, stride);
-                else pack_rows(src, (decltype(t) *)ctx->h_pinned, nr, width, stride);
+                if (array == PMF_ARR_COV) pack_cov(src, ctx->h_pinned.as<decltype(t)>(), nr, ctx->K, stride);
+                else pack_rows(src, ctx->h_pinned.as<decltype(t)>(), nr, width, stride);
             });
-            PMF_HIP_CHECK(hipMemcpyAsync(d_data, ctx->h_pinned, (size_t)(nr * row_bytes), hipMemcpyHostToDevice, ctx->stream));
-            launch_rows_copy<true>(ctx, ctx->arr[side][array], d_data, d_rows, nr, row_bytes);
+            PMF_HIP_CHECK(hipMemcpyAsync(d_data, ctx->h_pinned.as(), (size_t)(nr * row_bytes), hipMemcpyHostToDevice, ctx->stream));
+            launch_rows_copy<true>(ctx, ctx->arr[side][array].as(), d_data, d_rows, nr, row_bytes);
             PMF_HIP_CHECK(hipGetLastError());
             PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         } else {
-            launch_rows_copy<false>(ctx, ctx->arr[side][array], d_data, d_rows, nr, row_bytes);
+            launch_rows_copy<false>(ctx, ctx->arr[side][array].as(), d_data, d_rows, nr, row_bytes);
             PMF_HIP_CHECK(hipGetLastError());
-            PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned, d_data, (size_t)(nr * row_bytes), hipMemcpyDeviceToHost, ctx->stream));
+            PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned.as(), d_data, (size_t)(nr * row_bytes), hipMemcpyDeviceToHost, ctx->stream));
             PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            pmf_unpack_rows(ctx, array, ctx->h_pinned, host_out + r0 * width, nr);
+            pmf_unpack_rows(ctx, array, ctx->h_pinned.as(), host_out + r0 * width, nr);
         }
     }
     return PMF_OK;
@@ -927,7 +892,7 @@ extern "C" int pmf_set_cov_identity(pmf_ctx *ctx, int side, double scale) {
     int grid = (int)std::min<int64_t>((total + 255) / 256, 4096);
     pmf_with_dtype(ctx, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL(cov_identity_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, (T *)ctx->arr[side][PMF_ARR_COV],
+        hipLaunchKernelGGL(cov_identity_kernel<T>, dim3(grid), dim3(256), 0, ctx->stream, ctx->arr[side][PMF_ARR_COV].as<T>(),
                            ctx->rows[side], ctx->K, ctx->cov_stride, (T)scale);
     });
     PMF_HIP_CHECK(hipGetLastError());

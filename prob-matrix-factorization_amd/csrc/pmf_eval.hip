@@ -129,12 +129,12 @@ static int fill_params(pmf_ctx *ctx, int use_bias, double offset, PredictParams<
         if ((rc = pmf_require_array(ctx, PMF_SIDE_USER, PMF_ARR_SCALE, fn))) return rc;
         if ((rc = pmf_require_array(ctx, PMF_SIDE_ITEM, PMF_ARR_SCALE, fn))) return rc;
     }
-    p.su = scale ? (const T *)ctx->arr[PMF_SIDE_USER][PMF_ARR_SCALE] : nullptr;
-    p.si = scale ? (const T *)ctx->arr[PMF_SIDE_ITEM][PMF_ARR_SCALE] : nullptr;
-    p.fu = (const T *)ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR];
-    p.fi = (const T *)ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR];
-    p.bu = use_bias ? (const T *)ctx->arr[PMF_SIDE_USER][PMF_ARR_BIAS] : nullptr;
-    p.bi = use_bias ? (const T *)ctx->arr[PMF_SIDE_ITEM][PMF_ARR_BIAS] : nullptr;
+    p.su = scale ? ctx->arr[PMF_SIDE_USER][PMF_ARR_SCALE].as<const T>() : nullptr;
+    p.si = scale ? ctx->arr[PMF_SIDE_ITEM][PMF_ARR_SCALE].as<const T>() : nullptr;
+    p.fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const T>();
+    p.fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const T>();
+    p.bu = use_bias ? ctx->arr[PMF_SIDE_USER][PMF_ARR_BIAS].as<const T>() : nullptr;
+    p.bi = use_bias ? ctx->arr[PMF_SIDE_ITEM][PMF_ARR_BIAS].as<const T>() : nullptr;
     p.n_users = ctx->rows[0];
     p.n_items = ctx->rows[1];
     p.kpad = ctx->kpad;
@@ -151,7 +151,7 @@ static int run_predict(pmf_ctx *ctx, int64_t n, const int32_t *u, const int32_t 
     const int64_t step = 4 << 20;  // pairs per staging round
     const int64_t m = std::min(n, step);
     if ((rc = pmf_ensure_scratch(ctx, (size_t)m * 16))) return rc;
-    int32_t *d_u = (int32_t *)ctx->d_scratch;
+    int32_t *d_u = ctx->d_scratch.as<int32_t>();
     int32_t *d_i = d_u + m;
     double *d_out = (double *)(d_i + m);
     for (int64_t at = 0; at < n; at += step) {
@@ -198,23 +198,20 @@ extern "C" int pmf_eval_set(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, co
                     (long long)k, n_labels);
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    PmfEvalSet &ev = ctx->eval;
-    pmf_dev_free(ctx, ev.d_u, (size_t)ev.n * 4);
-    pmf_dev_free(ctx, ev.d_i, (size_t)ev.n * 4);
-    pmf_dev_free(ctx, ev.d_y, (size_t)ev.n * 8);
-    pmf_dev_free(ctx, ev.d_label, (size_t)ev.n * 4);
-    ev = PmfEvalSet();
+    ctx->eval = PmfEvalSet();   // the old set goes first; a failure below leaves the context without one
+    PmfEvalSet ev;
     int rc;
-    if ((rc = pmf_dev_alloc(ctx, (void **)&ev.d_u, (size_t)n * 4))) return rc;
-    if ((rc = pmf_dev_alloc(ctx, (void **)&ev.d_i, (size_t)n * 4))) return rc;
-    if ((rc = pmf_dev_alloc(ctx, (void **)&ev.d_y, (size_t)n * 8))) return rc;
-    if ((rc = pmf_dev_alloc(ctx, (void **)&ev.d_label, (size_t)n * 4))) return rc;
+    if ((rc = ev.d_u.alloc(ctx, (size_t)n * 4))) return rc;
+    if ((rc = ev.d_i.alloc(ctx, (size_t)n * 4))) return rc;
+    if ((rc = ev.d_y.alloc(ctx, (size_t)n * 8))) return rc;
+    if ((rc = ev.d_label.alloc(ctx, (size_t)n * 4))) return rc;
     ev.n = n;
     ev.n_labels = n_labels;
-    PMF_HIP_CHECK(hipMemcpy(ev.d_u, user_ids, (size_t)n * 4, hipMemcpyHostToDevice));
-    PMF_HIP_CHECK(hipMemcpy(ev.d_i, item_ids, (size_t)n * 4, hipMemcpyHostToDevice));
-    PMF_HIP_CHECK(hipMemcpy(ev.d_y, y_true, (size_t)n * 8, hipMemcpyHostToDevice));
-    PMF_HIP_CHECK(hipMemcpy(ev.d_label, label_index, (size_t)n * 4, hipMemcpyHostToDevice));
+    PMF_HIP_CHECK(hipMemcpy(ev.d_u.as(), user_ids, (size_t)n * 4, hipMemcpyHostToDevice));
+    PMF_HIP_CHECK(hipMemcpy(ev.d_i.as(), item_ids, (size_t)n * 4, hipMemcpyHostToDevice));
+    PMF_HIP_CHECK(hipMemcpy(ev.d_y.as(), y_true, (size_t)n * 8, hipMemcpyHostToDevice));
+    PMF_HIP_CHECK(hipMemcpy(ev.d_label.as(), label_index, (size_t)n * 4, hipMemcpyHostToDevice));
+    ctx->eval = std::move(ev);
     return PMF_OK;
 }
 
@@ -224,8 +221,8 @@ static int run_eval(pmf_ctx *ctx, int use_bias, double offset, double *sse, doub
     int rc = fill_params(ctx, use_bias, offset, p, "pmf_eval_run");
     if (rc) return rc;
     const PmfEvalSet &ev = ctx->eval;
-    p.u = ev.d_u;
-    p.i = ev.d_i;
+    p.u = ev.d_u.as<int32_t>();
+    p.i = ev.d_i.as<int32_t>();
     p.n = ev.n;
     const int lpr = std::max(4, pmf_lanes_per_row(ctx->kpad));
     const int G = 256 / lpr;
@@ -234,18 +231,18 @@ static int run_eval(pmf_ctx *ctx, int use_bias, double offset, double *sse, doub
     const size_t bytes = (size_t)grid * rec * sizeof(double);
     if ((rc = pmf_ensure_scratch(ctx, bytes))) return rc;
     if ((rc = pmf_ensure_pinned(ctx, bytes))) return rc;
-    double *block_out = (double *)ctx->d_scratch;
+    double *block_out = ctx->d_scratch.as<double>();
     {
         PmfProfScope prof(ctx, PMF_KERNEL_EVAL);
         pmf_with_pow2<4>(lpr, [&](auto L) {
-            hipLaunchKernelGGL((eval_kernel<T, L>), dim3(grid), dim3(256), 0, ctx->stream, p, ev.d_y, ev.d_label, ev.n_labels,
+            hipLaunchKernelGGL((eval_kernel<T, L>), dim3(grid), dim3(256), 0, ctx->stream, p, ev.d_y.as<double>(), ev.d_label.as<int32_t>(), ev.n_labels,
                                block_out);
         });
     }
     PMF_HIP_CHECK(hipGetLastError());
-    PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned, block_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned.as(), block_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
     PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const double *h = (const double *)ctx->h_pinned;
+    const double *h = ctx->h_pinned.as<const double>();
     double s = 0.0;
     for (int l = 0; l < ev.n_labels; ++l) {
         abs_l[l] = 0.0;

@@ -336,20 +336,20 @@ static GammaParams<T> gamma_params(const pmf_ctx *ctx, int side, const PmfTaskVi
     p.tasks = tl.d_tasks;
     p.n_tasks = tl.n_tasks;
     p.split = tl.d_split;
-    p.other = ix.d_other;
-    p.val = (const T *)ix.d_val;
-    p.factor_self = (T *)ctx->arr[side][PMF_ARR_FACTOR];
-    p.factor_other = (const T *)ctx->arr[other][PMF_ARR_FACTOR];
-    p.shape = (T *)ctx->arr[side][PMF_ARR_SHAPE];
-    p.rate = (T *)ctx->arr[side][PMF_ARR_RATE];
-    p.prior_rate_vec = (T *)ctx->arr[side][PMF_ARR_PRIOR_RATE];
-    p.hyper_rate = (T *)ctx->arr[side][PMF_ARR_HYPER_RATE];
-    p.scale_other = (const T *)ctx->arr[other][PMF_ARR_SCALE];
-    p.scale_self = (T *)ctx->arr[side][PMF_ARR_SCALE];
-    p.scale_shape = (T *)ctx->arr[side][PMF_ARR_SCALE_SHAPE];
-    p.scale_rate = (T *)ctx->arr[side][PMF_ARR_SCALE_RATE];
+    p.other = ix.d_other.as<int32_t>();
+    p.val = ix.d_val.as<const T>();
+    p.factor_self = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
+    p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
+    p.shape = ctx->arr[side][PMF_ARR_SHAPE].as<T>();
+    p.rate = ctx->arr[side][PMF_ARR_RATE].as<T>();
+    p.prior_rate_vec = ctx->arr[side][PMF_ARR_PRIOR_RATE].as<T>();
+    p.hyper_rate = ctx->arr[side][PMF_ARR_HYPER_RATE].as<T>();
+    p.scale_other = ctx->arr[other][PMF_ARR_SCALE].as<const T>();
+    p.scale_self = ctx->arr[side][PMF_ARR_SCALE].as<T>();
+    p.scale_shape = ctx->arr[side][PMF_ARR_SCALE_SHAPE].as<T>();
+    p.scale_rate = ctx->arr[side][PMF_ARR_SCALE_RATE].as<T>();
     p.pw = pw;
-    p.partial = (T *)ctx->d_partial;
+    p.partial = ctx->d_partial.as<T>();
     p.stats = (T *)stats;
     p.shape_prior = (T)pr.shape;
     p.rate_prior = (T)pr.rate;
@@ -414,7 +414,7 @@ static int run_gather_probe(pmf_ctx *ctx, int side) {
         constexpr int G = 256 / L;
         if (tl.n_tasks > 0)
             hipLaunchKernelGGL((gamma_gather_probe_kernel<T, L>), dim3((unsigned)((tl.n_tasks + G - 1) / G)), dim3(256), 0,
-                               ctx->stream, p, (T *)ctx->d_scratch);
+                               ctx->stream, p, ctx->d_scratch.as<T>());
     });
 }
 

@@ -1388,18 +1388,18 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *sta
     p.tasks = tl.d_tasks;
     p.n_tasks = tl.n_tasks;
     p.split = tl.d_split;
-    p.other = ix.d_other;
-    p.val = (const T *)ix.d_val;
-    p.factor_other = (const T *)ctx->arr[other][PMF_ARR_FACTOR];
-    p.cov_other = (const T *)ctx->arr[other][PMF_ARR_COV];
-    p.hot = ix.d_other_hot;
+    p.other = ix.d_other.as<int32_t>();
+    p.val = ix.d_val.as<const T>();
+    p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
+    p.cov_other = ctx->arr[other][PMF_ARR_COV].as<const T>();
+    p.hot = ix.d_other_hot.as<uint8_t>();
     const bool bias = pmf_has_bias(ctx);
-    p.bias_self = bias ? (const T *)ctx->arr[side][PMF_ARR_BIAS] : nullptr;
-    p.bias_other = bias ? (const T *)ctx->arr[other][PMF_ARR_BIAS] : nullptr;
-    p.partial = (T *)ctx->d_partial;
-    p.dst_s = acc ? (T *)stats : (T *)ctx->arr[side][PMF_ARR_COV];
+    p.bias_self = bias ? ctx->arr[side][PMF_ARR_BIAS].as<const T>() : nullptr;
+    p.bias_other = bias ? ctx->arr[other][PMF_ARR_BIAS].as<const T>() : nullptr;
+    p.partial = ctx->d_partial.as<T>();
+    p.dst_s = acc ? (T *)stats : ctx->arr[side][PMF_ARR_COV].as<T>();
     p.dst_s_stride = acc ? width : ctx->cov_stride;
-    p.dst_w = acc ? (T *)stats + ctx->cov_stride : (T *)ctx->arr[side][PMF_ARR_FACTOR];
+    p.dst_w = acc ? (T *)stats + ctx->cov_stride : ctx->arr[side][PMF_ARR_FACTOR].as<T>();
     p.dst_w_stride = acc ? width : ctx->kpad;
     p.K = ctx->K;
     p.kpad = ctx->kpad;
@@ -1441,12 +1441,12 @@ static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *st
     sp.rows = fin ? nullptr : split_rows_only ? tl.d_split_rows : tl.d_nonempty;
     sp.row0 = fin ? tl.row0 : 0;
     sp.n = fin ? tl.row1 - tl.row0 : split_rows_only ? tl.n_split : tl.n_nonempty;
-    sp.src_s = fin ? (const T *)stats : (const T *)ctx->arr[side][PMF_ARR_COV];
+    sp.src_s = fin ? (const T *)stats : ctx->arr[side][PMF_ARR_COV].as<const T>();
     sp.src_s_stride = fin ? width : ctx->cov_stride;
-    sp.src_w = fin ? (const T *)stats + ctx->cov_stride : (const T *)ctx->arr[side][PMF_ARR_FACTOR];
+    sp.src_w = fin ? (const T *)stats + ctx->cov_stride : ctx->arr[side][PMF_ARR_FACTOR].as<const T>();
     sp.src_w_stride = fin ? width : ctx->kpad;
-    sp.cov = (T *)ctx->arr[side][PMF_ARR_COV];
-    sp.factor = (T *)ctx->arr[side][PMF_ARR_FACTOR];
+    sp.cov = ctx->arr[side][PMF_ARR_COV].as<T>();
+    sp.factor = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
     sp.inv_sigma2 = (T)(1.0 / sigma2);
     sp.inv_eta2 = (T)(1.0 / eta2);
     sp.K = ctx->K;
@@ -1478,7 +1478,7 @@ static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *st
         T *scratch = nullptr;
         if (!in_lds) {   // one matrix per resident block in global scratch (<= 2048 x 264 KB)
             if ((rc = pmf_ensure_scratch(ctx, (size_t)blocks * mat))) return rc;
-            scratch = (T *)ctx->d_scratch;
+            scratch = ctx->d_scratch.as<T>();
         }
         const size_t smem = in_lds ? mat + vecs : vecs;
         hipError_t e = hipFuncSetAttribute((const void *)gauss_solve_lds_kernel<T>,
@@ -1547,13 +1547,13 @@ static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double si
     p.tasks = tl.d_tasks;
     p.n_tasks = tl.n_tasks;
     p.split = tl.d_split;
-    p.other = ix.d_other;
-    p.val = (const T *)ix.d_val;
-    p.factor_self = (const T *)ctx->arr[side][PMF_ARR_FACTOR];
-    p.factor_other = (const T *)ctx->arr[other][PMF_ARR_FACTOR];
-    p.bias_self = (T *)ctx->arr[side][PMF_ARR_BIAS];
-    p.bias_other = (const T *)ctx->arr[other][PMF_ARR_BIAS];
-    p.partial = (T *)ctx->d_partial;
+    p.other = ix.d_other.as<int32_t>();
+    p.val = ix.d_val.as<const T>();
+    p.factor_self = ctx->arr[side][PMF_ARR_FACTOR].as<const T>();
+    p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
+    p.bias_self = ctx->arr[side][PMF_ARR_BIAS].as<T>();
+    p.bias_other = ctx->arr[other][PMF_ARR_BIAS].as<const T>();
+    p.partial = ctx->d_partial.as<T>();
     p.stats = (T *)stats;
     p.inv_sigma2 = acc ? (T)1 : (T)(1.0 / sigma2);
     p.inv_eta_bias2 = acc ? (T)1 : (T)(1.0 / eta_bias2);
@@ -1576,8 +1576,8 @@ static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double si
             });
         if (tl.n_split > 0) {
             dim3 grid((unsigned)((tl.n_split + 255) / 256));
-            if (acc) hipLaunchKernelGGL((gauss_bias_split_kernel<T, true>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr);
-            else hipLaunchKernelGGL((gauss_bias_split_kernel<T, false>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr);
+            if (acc) hipLaunchKernelGGL((gauss_bias_split_kernel<T, true>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr.as<int64_t>());
+            else hipLaunchKernelGGL((gauss_bias_split_kernel<T, false>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr.as<int64_t>());
         }
     }
     PMF_HIP_CHECK(hipGetLastError());

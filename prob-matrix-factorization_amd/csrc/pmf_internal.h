@@ -6,8 +6,10 @@
 #include <stdint.h>
 
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "pmf_hip.h"
@@ -50,6 +52,33 @@ void pmf_set_error(const char *fmt, ...);
 // which part of a half-sweep a call runs: all of it, the raw statistics only, or the rows from summed statistics
 enum PmfPass { PMF_PASS_FUSED, PMF_PASS_ACCUMULATE, PMF_PASS_FINALIZE };
 
+// Owner of one allocation (hipMalloc, or hipHostMalloc for a PINNED one): the pointer, its byte count and the context
+// whose device_bytes counts it (null: counted nowhere -- pinned memory, the communicator's and the index build's
+// buffers).  Move-only; the destructor releases.  Everything that is handed to a kernel is a raw view from as<T>().
+class PmfBuf {
+public:
+    enum Kind { DEVICE, PINNED };
+    explicit PmfBuf(Kind kind = DEVICE) : pinned_(kind == PINNED) {}
+    PmfBuf(PmfBuf &&o) noexcept : pinned_(o.pinned_) { *this = std::move(o); }
+    PmfBuf &operator=(PmfBuf &&o) noexcept;
+    ~PmfBuf() { reset(); }
+    // a fresh allocation of `bytes` (0 -> 16) in place of what the buffer held
+    int alloc(pmf_ctx *owner, size_t bytes);
+    // grow-only: nothing happens while `bytes` fit; else the streams in `sync` (work queued on them may still use
+    // the buffer) are waited for and the buffer is replaced by a larger one -- its content is not kept
+    int reserve(pmf_ctx *owner, size_t bytes, std::initializer_list<hipStream_t> sync);
+    void reset();
+    template <typename T = void>
+    T *as() const { return static_cast<T *>(p_); }
+    explicit operator bool() const { return p_ != nullptr; }
+
+private:
+    void *p_ = nullptr;
+    size_t bytes_ = 0;
+    pmf_ctx *owner_ = nullptr;
+    bool pinned_;
+};
+
 // One unit of sweep work: a contiguous run of one row's ratings.
 // slot < 0  : the run is the whole row  -> the kernel finalises the row itself
 // slot >= 0 : the row is split          -> raw sums go to partial slot `slot`
@@ -74,9 +103,9 @@ struct PmfTaskList {
     int64_t n_slots = 0;
     int64_t n_split = 0;
     int32_t max_len = 0;
-    PmfTask *d_tasks = nullptr;
-    PmfSplitRow *d_split = nullptr;
-    int32_t *d_split_rows = nullptr;  // row id of every split row (solve list)
+    PmfBuf d_tasks;       // PmfTask [n_tasks]
+    PmfBuf d_split;       // PmfSplitRow [n_split]
+    PmfBuf d_split_rows;  // int32_t [n_split]: row id of every split row (solve list)
     // row chunks (pmf_ctx_set_row_chunks): tasks are grouped by the chunk of their row,
     // longest-first inside each group; [n_chunks + 1] offsets into d_tasks / d_split
     std::vector<int64_t> task_off, split_off;
@@ -93,13 +122,14 @@ struct PmfTaskView {
     int64_t n_nonempty = 0;
 };
 
-// Ratings ordered by one side (CSR when side = user, CSC when side = item).
+// Ratings ordered by one side (CSR when side = user, CSC when side = item).  A default-constructed value is
+// "no ratings": d_ptr is what the sweeps test.
 struct PmfSideIndex {
-    int64_t *d_ptr = nullptr;    // [rows + 1]
-    int32_t *d_other = nullptr;  // [nnz] id on the opposite side
-    void *d_val = nullptr;       // [nnz] rating, context dtype
+    PmfBuf d_ptr;                // int64_t [rows + 1]
+    PmfBuf d_other;              // int32_t [nnz] id on the opposite side
+    PmfBuf d_val;                // [nnz] rating, context dtype
     std::vector<int64_t> h_ptr;  // host copy of ptr (task building)
-    int32_t *d_nonempty = nullptr;  // rows with at least one rating (Gaussian solve list)
+    PmfBuf d_nonempty;           // int32_t [n_nonempty]: rows with at least one rating (Gaussian solve list)
     int64_t n_nonempty = 0;
     std::vector<int32_t> h_nonempty;    // host copy of d_nonempty
     std::vector<int64_t> nonempty_off;  // [n_chunks + 1] offsets into d_nonempty
@@ -111,16 +141,15 @@ struct PmfSideIndex {
     // the budget, most-rated first (ties: lower id first) ...
     std::vector<int32_t> h_hot;
     // ... and per entry of d_other: 1 if that row of the OPPOSITE side is hot.  Null when the policy is off.
-    uint8_t *d_other_hot = nullptr;
+    PmfBuf d_other_hot;          // uint8_t [nnz]
 };
 
 struct PmfEvalSet {
     int64_t n = 0;
     int n_labels = 0;
-    int32_t *d_u = nullptr;
-    int32_t *d_i = nullptr;
-    double *d_y = nullptr;
-    int32_t *d_label = nullptr;
+    PmfBuf d_u, d_i;   // int32_t [n]
+    PmfBuf d_y;        // double [n]
+    PmfBuf d_label;    // int32_t [n]
 };
 
 struct pmf_ctx {
@@ -132,9 +161,17 @@ struct pmf_ctx {
     int kp = 0;          // K(K+1)/2
     int cov_stride = 0;  // kp rounded up to PMF_VEC
     int64_t nnz = 0;
-    hipStream_t own_stream = nullptr;
+    // Members are destroyed in reverse order: every buffer below goes (and is taken off device_bytes) before the
+    // context's own stream does.
+    struct OwnStream {
+        hipStream_t s = nullptr;
+        ~OwnStream() {
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } own_stream;
     hipStream_t stream = nullptr;
     size_t elem = 4;
+    int64_t device_bytes = 0;   // what the context's device buffers hold (pmf_ctx_device_bytes); kept by PmfBuf
 
     int n_chunks[2] = {1, 1};    // row chunks per side (multi-GPU pipelining of a half-sweep)
     int cur_chunk[2] = {-1, -1};  // chunk the accumulate / finalize calls act on; -1 = all rows
@@ -143,19 +180,13 @@ struct pmf_ctx {
     int64_t fin_row0 = -1, fin_row1 = -1;
     int exchange = PMF_EXCHANGE_AUTO;   // pmf_comm_set_exchange
 
-    void *arr[2][PMF_ARR_COUNT] = {};
+    PmfBuf arr[2][PMF_ARR_COUNT];   // model state, pmf_array_elems(side, array) elements of the context dtype
     PmfSideIndex index[2];
     PmfEvalSet eval;
 
-    // scratch, grown on demand
-    void *d_partial = nullptr;
-    size_t partial_bytes = 0;
-    void *d_scratch = nullptr;
-    size_t scratch_bytes = 0;
-    void *h_pinned = nullptr;
-    size_t pinned_bytes = 0;
-
-    int64_t device_bytes = 0;
+    // scratch, grown on demand (pmf_ensure_*)
+    PmfBuf d_partial, d_scratch;
+    PmfBuf h_pinned{PmfBuf::PINNED};
 
     // diagnostic switches, read from the environment once when the context is created
     bool gauss_generic = false;    // PMF_GAUSS_GENERIC: the generic accumulate kernel instead of the MFMA ones
@@ -170,8 +201,7 @@ struct pmf_ctx {
     // and the library-owned statistics buffers of the item half-sweeps
     // (0: factor / gamma / gradient statistics, 1: Gaussian bias statistics)
     struct PmfComm *comm = nullptr;
-    void *d_stats[2] = {nullptr, nullptr};
-    size_t stats_bytes[2] = {0, 0};
+    PmfBuf d_stats[2];
 
     bool prof = false;
     struct ProfRec {
@@ -182,6 +212,8 @@ struct pmf_ctx {
     std::vector<hipEvent_t> prof_pool;
     double prof_ms[PMF_KERNEL_COUNT] = {};
     int64_t prof_n[PMF_KERNEL_COUNT] = {};
+
+    ~pmf_ctx();   // with the context's device current: waits for the stream, releases the communicator, then the members
 };
 
 #define PMF_GAMMA_CHUNK 512   // (256 until round 2: 512 halves the split-row slots; HPF K=64 at C3: gamma_final 0.16 -> 0.08 ms)
@@ -196,8 +228,6 @@ static inline int64_t pmf_chunk_row0(const pmf_ctx *ctx, int side, int c) {
 // `select` = honour pmf_ctx_select_chunk (accumulate / finalize); fused sweeps pass false
 PmfTaskView pmf_task_view(const pmf_ctx *ctx, int side, const PmfTaskList &tl, bool select);
 
-int pmf_dev_alloc(pmf_ctx *ctx, void **p, size_t bytes);
-void pmf_dev_free(pmf_ctx *ctx, void *p, size_t bytes);
 int pmf_ensure_partial(pmf_ctx *ctx, size_t bytes);
 int pmf_ensure_scratch(pmf_ctx *ctx, size_t bytes);
 int pmf_ensure_pinned(pmf_ctx *ctx, size_t bytes);
@@ -219,7 +249,7 @@ void pmf_unpack_rows(const pmf_ctx *ctx, int array, const void *src, double *dst
 // multi-GPU (pmf_comm.hip).  With an attached communicator of more than one rank the ITEM half-sweeps
 // run  accumulate -> all-reduce -> finalize  through pmf_comm_half_sweep.
 bool pmf_comm_active(const pmf_ctx *ctx);
-void pmf_comm_release(pmf_ctx *ctx);   // detach + free the statistics buffers (pmf_ctx_destroy)
+void pmf_comm_release(pmf_ctx *ctx);   // detach + free the statistics buffers (~pmf_ctx)
 // hipStreamSynchronize for a context with a communicator: polls the stream, RCCL's asynchronous error state and
 // a deadline (PMF_COMM_TIMEOUT_S, default 1800; 0 = wait for ever), so that a peer that died or never arrived
 // ends in PMF_ECOMM on the surviving ranks instead of a hang.

@@ -174,13 +174,13 @@ int run_sgd(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double lr, double
     p.n_tasks = tl.n_tasks;
     p.split = tl.d_split;
     p.n_split = tl.n_split;
-    p.ptr = ix.d_ptr;
-    p.other = ix.d_other;
-    p.val = (const T *)ix.d_val;
-    p.factor_self = (T *)ctx->arr[side][PMF_ARR_FACTOR];
-    p.factor_other = (const T *)ctx->arr[other][PMF_ARR_FACTOR];
-    p.bias_self = bias ? (T *)ctx->arr[side][PMF_ARR_BIAS] : nullptr;
-    p.bias_other = bias ? (const T *)ctx->arr[other][PMF_ARR_BIAS] : nullptr;
+    p.ptr = ix.d_ptr.as<int64_t>();
+    p.other = ix.d_other.as<int32_t>();
+    p.val = ix.d_val.as<const T>();
+    p.factor_self = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
+    p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
+    p.bias_self = bias ? ctx->arr[side][PMF_ARR_BIAS].as<T>() : nullptr;
+    p.bias_other = bias ? ctx->arr[other][PMF_ARR_BIAS].as<const T>() : nullptr;
     p.kpad = ctx->kpad;
     p.width = ctx->kpad + PMF_VEC;
     p.stats = (T *)stats;
@@ -190,7 +190,7 @@ int run_sgd(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double lr, double
         PMF_REQUIRE(lr > 0 && sigma2 > 0 && eta2 > 0 && eta_bias2 > 0, PMF_EINVAL,
                     "pmf_gauss_sgd_sweep: lr and the variances must be positive");
         if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * p.width * sizeof(T)))) return rc;
-        p.partial = (T *)ctx->d_partial;
+        p.partial = ctx->d_partial.as<T>();
         p.lr = (T)lr;
         p.inv_sigma2 = (T)(1.0 / sigma2);
         p.inv_eta2 = (T)(1.0 / eta2);
@@ -256,8 +256,8 @@ extern "C" int pmf_gauss_sgd_sweep(pmf_ctx *ctx, int side, double lr, double sig
     ctx->cur_chunk[side] = -1;  // the one-call form always covers every row
     const size_t bytes = (size_t)ctx->rows[side] * (ctx->kpad + PMF_VEC) * ctx->elem;
     int rc = pmf_ensure_scratch(ctx, bytes);
-    if (!rc) rc = pmf_gauss_sgd_accumulate(ctx, side, ctx->d_scratch, lr, sigma2, eta2, eta_bias2);
-    if (!rc) rc = pmf_gauss_sgd_finalize(ctx, side, ctx->d_scratch);
+    if (!rc) rc = pmf_gauss_sgd_accumulate(ctx, side, ctx->d_scratch.as(), lr, sigma2, eta2, eta_bias2);
+    if (!rc) rc = pmf_gauss_sgd_finalize(ctx, side, ctx->d_scratch.as());
     ctx->cur_chunk[side] = saved;
     return rc;
 }

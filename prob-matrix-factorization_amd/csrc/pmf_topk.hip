@@ -759,8 +759,8 @@ static hipError_t launch_topk_fused_mode(pmf_ctx *ctx, const TopkParams &p, dim3
 static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int mode, const float *cu,
                           const float *ci, int32_t *out_items, double *out_scores) {
     const int64_t I = ctx->rows[PMF_SIDE_ITEM];
-    const float *fu = (const float *)ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR];
-    const float *fi = (const float *)ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR];
+    const float *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const float>();
+    const float *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const float>();
     const int64_t Q = std::min<int64_t>(n_query, 1 << 20);   // query users per launch
     // few users: cut the item range so that the grid still has a few thousand wavefronts
     const int64_t waves = (Q + 31) / 32;
@@ -774,7 +774,7 @@ static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids
     const size_t cv_bytes = ((size_t)Q * n_cand * sizeof(float) + 15) / 16 * 16;
     int rc;
     if ((rc = pmf_ensure_scratch(ctx, id_bytes + out_s + out_i + 2 * cv_bytes + 64))) return rc;
-    char *base = (char *)ctx->d_scratch;
+    char *base = ctx->d_scratch.as<char>();
     double *d_out_scores = (double *)base;
     int32_t *d_out_items = (int32_t *)(base + out_s);
     int32_t *d_users = (int32_t *)(base + out_s + out_i);
@@ -830,10 +830,10 @@ static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int 
         if ((rc = pmf_require_array(ctx, PMF_SIDE_USER, carr, "pmf_topk_items"))) return rc;
         if ((rc = pmf_require_array(ctx, PMF_SIDE_ITEM, carr, "pmf_topk_items"))) return rc;
     }
-    const T *fu = (const T *)ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR];
-    const T *fi = (const T *)ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR];
-    const T *bu = use_bias ? (const T *)ctx->arr[PMF_SIDE_USER][carr] : nullptr;
-    const T *bi = use_bias ? (const T *)ctx->arr[PMF_SIDE_ITEM][carr] : nullptr;
+    const T *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const T>();
+    const T *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const T>();
+    const T *bu = use_bias ? ctx->arr[PMF_SIDE_USER][carr].as<const T>() : nullptr;
+    const T *bi = use_bias ? ctx->arr[PMF_SIDE_ITEM][carr].as<const T>() : nullptr;
     if constexpr (std::is_same<T, float>::value) {
         if (ctx->kpad <= 128 && k <= 64 && I <= (int64_t)INT32_MAX - 64 && !ctx->topk_two_phase)   // (the fused scan counts items in ints)
             return run_topk_fused(ctx, n_query, user_ids, k, use_bias, bu, bi, out_items, out_scores);
@@ -845,7 +845,7 @@ static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int 
     const size_t id_bytes = (size_t)Q * sizeof(int32_t);
     const size_t out_bytes = (size_t)Q * k * (sizeof(int32_t) + sizeof(double));
     if ((rc = pmf_ensure_scratch(ctx, score_bytes + id_bytes + out_bytes + 64))) return rc;
-    char *base = (char *)ctx->d_scratch;
+    char *base = ctx->d_scratch.as<char>();
     T *d_scores = (T *)base;
     double *d_out_scores = (double *)(base + score_bytes);
     int32_t *d_out_items = (int32_t *)(base + score_bytes + (size_t)Q * k * sizeof(double));
