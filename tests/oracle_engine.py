@@ -373,9 +373,10 @@ class OracleContext(OracleEngine):
         out = np.zeros(len(u))
         A, B = self.raw[(USER, 0)], self.raw[(ITEM, 0)]
         out[ok] = np.einsum("nk,nk->n", A[u[ok]], B[i[ok]])
-        if use_bias == 2:      # PREDICT_SCALE: the extended Poisson model's phi_u psi_i theta_u.beta_i
+        # the two bits of pmf_predict's flag are independent (include/pmf_hip.h): scale first, then the biases
+        if int(use_bias) & 2:  # PREDICT_SCALE: the extended Poisson model's phi_u psi_i theta_u.beta_i
             out[ok] *= self.raw[(USER, 7)][u[ok]] * self.raw[(ITEM, 7)][i[ok]]
-        elif use_bias:
+        if int(use_bias) & 1:  # PREDICT_BIAS
             out[ok] += self.raw[(USER, 6)][u[ok]] + self.raw[(ITEM, 6)][i[ok]]
         return out + offset
 

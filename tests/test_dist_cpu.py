@@ -273,6 +273,27 @@ def test_sharded_model_fit_host_logic_over_gloo(kind, tmp_path):
         assert np.load(os.path.join(tmp_path, "w2_rank0.npz"))["V_theta"].shape == (300, 5, 5)
 
 
+def test_oracle_context_predict_treats_the_two_flag_bits_independently():
+    """`OracleContext.predict` follows pmf_predict's flag (include/pmf_hip.h): bit 1 multiplies the dot product by
+    SCALE_user[u] SCALE_item[i], bit 0 then adds BIAS_user[u] + BIAS_item[i]; the value 3 does both.  Ids outside the
+    trained dimensions give `offset`."""
+    from oracle_engine import OracleContext
+    rng = np.random.default_rng(3)
+    U, I, K, n = 13, 7, 5, 200
+    A, B = rng.standard_normal((U, K)), rng.standard_normal((I, K))
+    bu, bi, su, si = rng.standard_normal(U), rng.standard_normal(I), rng.standard_normal(U), rng.standard_normal(I)
+    ctx = OracleContext(U, I, K)
+    for side, (f, b, s) in enumerate(((A, bu, su), (B, bi, si))):
+        ctx.set_array(side, 0, f); ctx.set_array(side, 6, b); ctx.set_array(side, 7, s)
+    u, i = rng.integers(0, U, n), rng.integers(0, I, n)
+    dot = (A[u] * B[i]).sum(axis=1)
+    want = {0: dot, 1: bu[u] + bi[i] + dot, 2: su[u] * si[i] * dot, 3: bu[u] + bi[i] + su[u] * si[i] * dot}
+    for flag, w in want.items():
+        np.testing.assert_allclose(ctx.predict(u, i, flag, 0.25), w + 0.25, rtol=1e-13, atol=1e-13, err_msg=str(flag))
+    np.testing.assert_allclose(ctx.predict(u, i, True, 0.0), want[1], rtol=1e-13, atol=1e-13)
+    assert np.array_equal(ctx.predict([U, 0, -1], [0, I, 0], 3, 0.25), np.full(3, 0.25))
+
+
 def _contract_worker(rank, world, port, out_dir):
     sys.path[:0] = [ROOT, os.path.join(ROOT, "prob-matrix-factorization_amd"), os.path.join(ROOT, "tests")]
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
