@@ -129,6 +129,17 @@ int pmf_ctx_device_bytes(pmf_ctx *ctx, int64_t *bytes);
  * to *n_hot and the first min(count, capacity) ids to `rows` (may be NULL when capacity is 0).  Set by
  * pmf_ctx_set_ratings. */
 int pmf_ctx_hot_rows(pmf_ctx *ctx, int side, int32_t *rows, int64_t capacity, int64_t *n_hot);
+/* Length in ratings of the longest task of one of `side`'s work lists (a task is a contiguous run of one row's
+ * ratings that one wavefront / lane group walks; rows longer than the list's task length are split evenly).  The
+ * task length of the GAMMA, GAUSS and BIAS lists grows with the rating count (32 up to 2^21 ratings, doubling to
+ * at most 512) or is fixed by PMF_TASK_CHUNK (a power of two in [32, 512], read when the context is created); the
+ * SGD list's is always 256.  Results depend on it through the summation order of split rows only.  Set by
+ * pmf_ctx_set_ratings. */
+#define PMF_TASKS_GAMMA 0
+#define PMF_TASKS_GAUSS 1
+#define PMF_TASKS_BIAS 2
+#define PMF_TASKS_SGD 3
+int pmf_ctx_task_max_len(pmf_ctx *ctx, int side, int list, int *max_len);
 
 /* Training ratings in their original order (COO).  Replaces
  * `_build_index_lists` (hpf_cavi.py:97-107, gaussian_mf_cavi_bias.py:69-86):

@@ -185,6 +185,10 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
     ctx->topk_two_phase = getenv("PMF_TOPK_TWO_PHASE") != nullptr;
     if (const char *nb = getenv("PMF_TOPK_STAGE_BUFFERS")) ctx->topk_stage_buffers = atoi(nb);
     if (const char *mb = getenv("PMF_TOPK_MAX_BLOCKS")) ctx->topk_max_blocks = atoi(mb);
+    if (const char *tc = getenv("PMF_TASK_CHUNK")) {
+        const int n = atoi(tc);
+        if (n >= 32 && n <= 512 && (n & (n - 1)) == 0) ctx->task_chunk = n;   // anything else: the nnz rule
+    }
     if (const char *ex = getenv("PMF_COMM_EXCHANGE")) {
         if (!strcmp(ex, "allreduce")) ctx->exchange = PMF_EXCHANGE_ALLREDUCE;
         else if (!strcmp(ex, "scatter_gather")) ctx->exchange = PMF_EXCHANGE_SCATTER_GATHER;
@@ -261,6 +265,18 @@ extern "C" int pmf_ctx_hot_rows(pmf_ctx *ctx, int side, int32_t *rows, int64_t c
     const std::vector<int32_t> &hot = ctx->index[side].h_hot;
     *n_hot = (int64_t)hot.size();
     std::copy_n(hot.begin(), (size_t)std::min(capacity, *n_hot), rows);
+    return PMF_OK;
+}
+
+extern "C" int pmf_ctx_task_max_len(pmf_ctx *ctx, int side, int list, int *max_len) {
+    CHECK_CTX(ctx, "pmf_ctx_task_max_len");
+    CHECK_SIDE(side, "pmf_ctx_task_max_len");
+    PMF_REQUIRE(max_len, PMF_EINVAL, "pmf_ctx_task_max_len: null argument");
+    const PmfSideIndex &ix = ctx->index[side];
+    const PmfTaskList *lists[] = {&ix.gamma_tasks, &ix.gauss_tasks, &ix.bias_tasks, &ix.sgd_tasks};
+    PMF_REQUIRE(list >= 0 && list < 4, PMF_EINVAL, "pmf_ctx_task_max_len: bad task list %d", list);
+    PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_ctx_task_max_len: ratings have not been set");
+    *max_len = lists[list]->max_len;
     return PMF_OK;
 }
 
@@ -432,8 +448,10 @@ static int build_work_lists(pmf_ctx *ctx, int side) {
     // sweep).  Small problems therefore get shorter tasks -- enough of them to occupy the chip -- and
     // large ones keep the maximum, which minimises partial-sum traffic.  (Chunking only changes the
     // summation order of rows longer than a chunk.)  The gradient mode has its own list with the fixed
-    // 256: its result is defined in terms of that piece length.
+    // 256: its result is defined in terms of that piece length.  PMF_TASK_CHUNK (ctx->task_chunk) overrides the
+    // rule for the other three lists.
     auto task_chunk = [&](int max_chunk) {
+        if (ctx->task_chunk) return std::min(ctx->task_chunk, max_chunk);
         int64_t c = 32;
         while (c < max_chunk && c * 65536 < ctx->nnz) c <<= 1;
         return (int)c;

@@ -32,6 +32,7 @@ TRANSPORT_RCCL, TRANSPORT_HOSTSHM = 0, 1
 OP_SUM, OP_MAX = 0, 1
 EXCHANGE = {"auto": 0, "allreduce": 1, "scatter_gather": 2}
 MAX_LABELS = 32
+TASK_LISTS = {"gamma": 0, "gauss": 1, "bias": 2, "sgd": 3}
 
 
 class PmfLibraryError(RuntimeError):
@@ -65,6 +66,7 @@ SIGNATURES = {
     "pmf_ctx_select_chunk": (C.c_int, [_p, C.c_int, C.c_int]),
     "pmf_ctx_device_bytes": (C.c_int, [_p, _i64p]),
     "pmf_ctx_hot_rows": (C.c_int, [_p, C.c_int, _i32p, C.c_int64, _i64p]),
+    "pmf_ctx_task_max_len": (C.c_int, [_p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pmf_ctx_set_ratings": (C.c_int, [_p, C.c_int64, _i32p, _i32p, _f64p]),
     "pmf_set_array": (C.c_int, [_p, C.c_int, C.c_int, _f64p]),
     "pmf_get_array": (C.c_int, [_p, C.c_int, C.c_int, _f64p]),

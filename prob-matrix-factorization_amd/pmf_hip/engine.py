@@ -10,8 +10,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import (ARR_COV, EXCHANGE, F32, F64, ITEM, KERNEL_NAMES, MAX_LABELS, OP_MAX, OP_SUM, TEST_LIB_PATH, UNIQUE_ID_BYTES,
-               USER, PmfError, PmfLibraryError, as_f64, as_i32, check, load, ptr)
+from . import (ARR_COV, EXCHANGE, F32, F64, ITEM, KERNEL_NAMES, MAX_LABELS, OP_MAX, OP_SUM, TASK_LISTS, TEST_LIB_PATH,
+               UNIQUE_ID_BYTES, USER, PmfError, PmfLibraryError, as_f64, as_i32, check, load, ptr)
 
 
 class Context:
@@ -148,6 +148,13 @@ class Context:
         check(self._lib.pmf_ctx_hot_rows(self._h, side, out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)),
               "pmf_ctx_hot_rows")
         return out
+
+    def task_max_len(self, side, kind):
+        """Ratings in the longest task of `side`'s work list `kind` ('gamma', 'gauss', 'bias' or 'sgd'): the task
+        length in force (by rating count, or PMF_TASK_CHUNK), capped by the longest row."""
+        n = C.c_int(0)
+        check(self._lib.pmf_ctx_task_max_len(self._h, side, TASK_LISTS[kind], C.byref(n)), "pmf_ctx_task_max_len")
+        return n.value
 
     # ---- data -----------------------------------------------------------
     def set_ratings(self, user_ids, item_ids, ratings):

@@ -325,9 +325,11 @@ def sweep_index(n_trials, seed):
 
 
 def sweep_medium(n_trials, seed):
-    """Medium problems -- 2.2M to 9M ratings, where the work lists use 64-, 128- and 256-rating tasks (the small
-    sweeps above see 32, the full-size tests 512) -- against the oracle's vectorised form: direct C-ABI sweeps,
-    one iteration, f64 and f32.  Returns (failures, worst f64 deviation)."""
+    """Medium problems -- 2.2M to 9M ratings, where the HPF trials' work lists use 64-, 128- and 256-rating tasks (the
+    small sweeps above see 32, the full-size tests 512) -- against the oracle's vectorised form: direct C-ABI sweeps,
+    one iteration, f64 and f32.  The Gaussian trials stay below 4M ratings (the oracle is O(N K^2)), i.e. at 64-rating
+    tasks: one batch of the accumulate kernels per task; longer Gaussian tasks are tests/test_gauss_long_tasks_gpu.py's.
+    Returns (failures, worst f64 deviation)."""
     import pmf_hip
     from pmf_hip import ARR_BIAS, ARR_COV, ARR_FACTOR, ARR_PRIOR_RATE, ARR_RATE, ARR_SHAPE, ITEM, USER
     rng = np.random.default_rng(seed)

@@ -105,6 +105,8 @@ def _oracle_vs_device(K, dtype, bias, U=1500, I=300, N=40000, iters=2, env=None,
     u, i, x = skewed_problem(100 + K, U, I, N, rating_kind="centered")
     init = orc.init_gaussian(U, I, K, seed=5, bias=bias)
     idx = (orc.group_positions(u, U), orc.group_positions(i, I))
+    # (the task length follows the rating count: 32 at this size, so these rows are cut into many 32-rating tasks and
+    #  no task is longer than one 64-rating batch -- tests/test_gauss_long_tasks_gpu.py covers the longer ones)
     assert np.diff(idx[1][0]).max() > 2 * 512, "need rows split over several accumulate tasks"
     with pmf_hip.Context(U, I, K, dtype=dtype) as ctx:
         ctx.set_ratings(u, i, x)

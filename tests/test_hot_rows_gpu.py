@@ -40,6 +40,8 @@ def _run(K, budget_mb, monkeypatch, dtype="f32", iters=3):
 @pytest.mark.parametrize("K", [64, 48, 16])   # one pair per trip (K = 64) and 2 / 8 pairs per trip (K = 48 / 16)
 def test_states_bit_identical_for_every_budget(K, monkeypatch):
     _, _, _, (du, di) = _run(K, 0, monkeypatch, iters=0)
+    # (split into 32-rating tasks: the task length at N = 40 000.  Hot and cold rows inside the later 64-rating batches
+    #  of one task are the business of tests/test_gauss_long_tasks_gpu.py)
     assert du.max() > 512 and di.max() > 512, "need rows split over several accumulate tasks"
     off, hot_off, _, _ = _run(K, 0, monkeypatch)
     assert all(len(h) == 0 for h in hot_off.values())
