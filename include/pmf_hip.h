@@ -86,7 +86,8 @@ extern "C" {
 #define PMF_KERNEL_GAUSS_SGD 9     /* MAP gradient half-sweep (no reference counterpart) */
 #define PMF_KERNEL_COMM_ALLREDUCE 10 /* item-statistics all-reduce, timed on the collective stream */
 #define PMF_KERNEL_COMM_WAIT 11    /* compute stream idle until a chunk's all-reduce has landed = exposed communication */
-#define PMF_KERNEL_COUNT 12
+#define PMF_KERNEL_PREDICT_VAR 12   /* posterior predictive variance: per pair and the fused validation form */
+#define PMF_KERNEL_COUNT 13
 
 typedef struct pmf_ctx pmf_ctx;
 
@@ -343,6 +344,27 @@ int pmf_eval_set(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, const int32_t
  * rmse = sqrt(sse / n) (metrics.py:6-10) and macro_mae = mean_l(abs_l / cnt_l). */
 int pmf_eval_run(pmf_ctx *ctx, int use_bias, double offset, double *sum_sq_err,
                  double *abs_err_per_label, int64_t *count_per_label);
+
+/* Posterior predictive variance of the Gaussian models (no reference counterpart: the reference's predict returns
+ * the mean and its GaussianLogPredictiveLikelihood plugs the factor means in).  With q(theta_u) = N(m_u, V_u) and
+ * q(beta_i) = N(m_i, V_i) independent (FACTOR / COV of the two sides; the biases are point values) and
+ * f = theta_u . beta_i:
+ *     E[f]   = m_u . m_i                                          (pmf_predict)
+ *     Var[f] = m_u' V_i m_u + m_i' V_u m_i + tr(V_u V_i)
+ * evaluated in one pass over the two packed rows, w_p = 1 on the diagonal and 2 off it, p = (r, c):
+ *     out_var[n] = sum_p w_p ( V_i[p] m_u[r] m_u[c] + V_u[p] m_i[r] m_i[c] + V_u[p] V_i[p] )
+ * for ids inside the trained dimensions, 0 otherwise (pmf_predict treats such a pair as the point 0).  The rating's
+ * predictive variance is sigma2 + out_var.  Needs FACTOR and COV of both sides (PMF_EINVAL names a missing one);
+ * n = 0 touches nothing. */
+int pmf_predict_var(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, const int32_t *item_ids, double *out_var);
+/* The same over the stored validation set (pmf_eval_set), fused with pmf_predict: with v = Var[f] of a pair and
+ * e = y_true - predict (`use_bias`, `offset` as for pmf_eval_run),
+ *     *sum_var         = sum v
+ *     *sum_log_density = sum ( -1/2 log(2 pi (sigma2 + v)) - e^2 / (2 (sigma2 + v)) ),      sigma2 > 0,
+ * the total log density of the ratings under N(predict, sigma2 + v).  Per-block partial sums combined in block
+ * order on the host: two calls give the same bits. */
+int pmf_eval_run_var(pmf_ctx *ctx, int use_bias, double offset, double sigma2, double *sum_var,
+                     double *sum_log_density);
 
 /* Top-k items per user from the dense reconstruction FACTOR_user . FACTOR_item^T
  * (the "identical top-k item rankings" check of the north star; the reference

@@ -25,6 +25,23 @@ __device__ __forceinline__ Vec4<double> load4(const double *p) {
     r.v[0] = a.x; r.v[1] = a.y; r.v[2] = b.x; r.v[3] = b.y;
     return r;
 }
+// The same chunk with the non-temporal cache policy: rows that are touched once per use (the packed
+// covariance rows of a predicted pair) and should not displace what other loads keep in the caches.
+__device__ __forceinline__ Vec4<float> load4_nt(const float *p) {
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    const v4 t = __builtin_nontemporal_load(reinterpret_cast<const v4 *>(p));
+    Vec4<float> r;
+    r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+    return r;
+}
+__device__ __forceinline__ Vec4<double> load4_nt(const double *p) {
+    typedef double v2 __attribute__((ext_vector_type(2)));
+    const v2 a = __builtin_nontemporal_load(reinterpret_cast<const v2 *>(p));
+    const v2 b = __builtin_nontemporal_load(reinterpret_cast<const v2 *>(p + 2));
+    Vec4<double> r;
+    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = b.x; r.v[3] = b.y;
+    return r;
+}
 __device__ __forceinline__ void store4(float *p, const Vec4<float> &r) {
     *reinterpret_cast<float4 *>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
 }

@@ -26,7 +26,7 @@ USER, ITEM = 0, 1
  ARR_SCALE_RATE) = range(10)
 PREDICT_BIAS, PREDICT_SCALE = 1, 2
 KERNEL_NAMES = ("gamma_sweep", "gamma_final", "gauss_accum", "gauss_solve", "gauss_bias",
-                "eval", "predict", "topk", "gauss_combine", "gauss_sgd", "comm_allreduce", "comm_wait")
+                "eval", "predict", "topk", "gauss_combine", "gauss_sgd", "comm_allreduce", "comm_wait", "predict_var")
 UNIQUE_ID_BYTES = 128
 TRANSPORT_RCCL, TRANSPORT_HOSTSHM = 0, 1
 OP_SUM, OP_MAX = 0, 1
@@ -88,6 +88,8 @@ SIGNATURES = {
     "pmf_predict": (C.c_int, [_p, C.c_int64, _i32p, _i32p, C.c_int, C.c_double, _f64p]),
     "pmf_eval_set": (C.c_int, [_p, C.c_int64, _i32p, _i32p, _f64p, _i32p, C.c_int]),
     "pmf_eval_run": (C.c_int, [_p, C.c_int, C.c_double, _f64p, _f64p, _i64p]),
+    "pmf_predict_var": (C.c_int, [_p, C.c_int64, _i32p, _i32p, _f64p]),
+    "pmf_eval_run_var": (C.c_int, [_p, C.c_int, C.c_double, C.c_double, _f64p, _f64p]),
     "pmf_topk_items": (C.c_int, [_p, C.c_int64, _i32p, C.c_int, C.c_int, _i32p, _f64p]),
     "pmf_prof_enable": (C.c_int, [_p, C.c_int]),
     "pmf_prof_reset": (C.c_int, [_p]),

@@ -334,6 +334,26 @@ class Context:
         """(rmse, macro_mae) over the stored validation set."""
         return self.metrics_from_sums(self.eval_sums(use_bias, offset))
 
+    def predict_var(self, user_ids, item_ids):
+        """Var[theta_u . beta_i] under the Gaussian posterior (FACTOR and COV of both sides), float64; 0 for ids
+        outside the trained dimensions.  The rating's predictive variance adds sigma2."""
+        u, i = self._clip_ids(user_ids), self._clip_ids(item_ids)
+        if len(u) != len(i):
+            raise ValueError("user_ids and item_ids must have the same length")
+        out = np.zeros(len(u), dtype=np.float64)
+        if len(u):
+            check(self._lib.pmf_predict_var(self._h, len(u), ptr(u, C.c_int32), ptr(i, C.c_int32), ptr(out, C.c_double)),
+                  "pmf_predict_var")
+        return out
+
+    def eval_var_sums(self, use_bias=False, offset=0.0, sigma2=1.0):
+        """(n, sum of Var[f], sum of the log predictive density N(y; predict, sigma2 + Var[f])) over the stored
+        validation set (additive across the shards of a multi-GPU run)."""
+        sv, sl = C.c_double(0.0), C.c_double(0.0)
+        check(self._lib.pmf_eval_run_var(self._h, int(use_bias), float(offset), float(sigma2), C.byref(sv), C.byref(sl)),
+              "pmf_eval_run_var")
+        return getattr(self, "_eval_n", 0), sv.value, sl.value
+
     def topk_items(self, user_ids, k, use_bias=False):
         """`use_bias`: False / 0, PREDICT_BIAS (scores + b_u + b_i) or PREDICT_SCALE (scores * s_u * s_i):
         the same flag `predict` takes, so the ranking follows the model's own score."""

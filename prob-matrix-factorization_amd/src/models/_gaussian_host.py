@@ -12,6 +12,8 @@ from pmf_hip import ARR_BIAS, ARR_COV, ARR_FACTOR, dist as pdist
 
 
 class GaussianHost(DeviceModel):
+    _has_covariances = True      # False for the MAP / gradient subclass: no posterior, no predictive variance
+
     def __init__(self, config, dtype=None, device=None, comm=None, presharded=False):
         super().__init__(config, dtype, device, comm, presharded)
         self.m_theta = self.m_beta = None
@@ -167,6 +169,45 @@ class GaussianHost(DeviceModel):
     def predict(self, user_ids, item_ids, global_mean=0.0):
         return self._need_ctx().predict(np.asarray(user_ids, dtype=int), np.asarray(item_ids, dtype=int),
                                         use_bias=self._uses_bias, offset=global_mean)
+
+    # ---- posterior predictive variance / density (extension: no reference counterpart) ----
+    def _cov_ctx(self, what):
+        """The context that holds FACTOR and COV of both sides for all users, or the reason there is none."""
+        if not self._has_covariances:
+            raise NotImplementedError(f"{type(self).__name__} keeps point estimates, no covariances: {what} is not defined")
+        ctx = self._need_ctx()
+        if self._shard_ctx is not None:
+            raise NotImplementedError(f"{what} after a sharded fit: the full-size context holds no covariances "
+                                      "(they stay on the ranks' shard contexts)")
+        return ctx
+
+    def predict_variance(self, user_ids, item_ids, include_noise=True):
+        """Var[theta_u . beta_i] = m_u' V_i m_u + m_i' V_u m_i + tr(V_u V_i) under the fitted q (float64; the biases
+        are point values; 0 for ids outside the trained dimensions, which `predict` treats as the point 0), plus
+        `config.sigma2` when `include_noise`: the variance of the rating itself.  One pass over the packed covariance
+        rows on the device (`pmf_predict_var`); nothing K x K reaches the host."""
+        var = self._cov_ctx("predict_variance").predict_var(np.asarray(user_ids, dtype=int), np.asarray(item_ids, dtype=int))
+        return var + self.config.sigma2 if include_noise else var
+
+    def log_predictive_density(self, df, global_mean=0.0):
+        """TOTAL over the rows of `df` with seen ids (as the reference's GaussianLogPredictiveLikelihood returns a
+        total) of log N(rating + global_mean; predict, sigma2 + Var[f]).  Row filter and target as in
+        `evaluate_rmse`; nan (with its warning) when no row is left.  Fused on the device (`pmf_eval_run_var`); the
+        stored validation set of the context is replaced."""
+        ctx = self._cov_ctx("log_predictive_density")
+        df = self._seen(df)
+        if df.empty:
+            print("Warning: No valid (u,i) pairs.")
+            return np.nan
+        u, i = df["u"].to_numpy(dtype=int), df["i"].to_numpy(dtype=int)
+        y = df["rating"].to_numpy(dtype=float) + global_mean
+        sigma2 = self.config.sigma2
+        if ctx.eval_set(u, i, y):
+            return ctx.eval_var_sums(self._uses_bias, global_mean, sigma2)[2]
+        # more distinct ratings than the stored set's label table takes: device predict / predict_var, host sum
+        d = sigma2 + ctx.predict_var(u, i)
+        e = y - ctx.predict(u, i, use_bias=self._uses_bias, offset=global_mean)
+        return float(np.sum(-0.5 * np.log(2.0 * np.pi * d) - e * e / (2.0 * d)))
 
     def _seen(self, df):
         keep = (df["u"] < self.n_users) & (df["i"] < self.n_items)

@@ -36,6 +36,7 @@ class GaussianMFSGD(GaussianHost):
     _uses_bias = True
     _gaussian = False            # exchanged item statistics are [I x (Kpad + 4)], not covariances
     _iteration_label = "SGD epoch"
+    _has_covariances = False     # predict_variance / log_predictive_density raise NotImplementedError
 
     def __init__(self, config: GaussianMFSGDConfig, dtype=None, device=None, comm=None, presharded=False):
         super().__init__(config, dtype, device, comm, presharded)
