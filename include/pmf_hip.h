@@ -225,6 +225,32 @@ int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2);
  *     var = 1 / (1/eta_bias2 + n_r/sigma2);   rows without ratings keep their value. */
 int pmf_gauss_bias_sweep(pmf_ctx *ctx, int side, double sigma2, double eta_bias2);
 
+/* Fold-in: the posterior of NEW rows of `side` against the fitted opposite side, whose FACTOR, COV and (bias model)
+ * BIAS stay frozen.  No reference counterpart as an operation (the reference serves an unseen id by refitting); per
+ * row it restates the reference's own row updates -- the factor update of gaussian_mf_cavi_bias.py:132-165 followed
+ * by the bias update of :206-232 (items: :170-201, :237-263), `n_iter` times from b = 0.  The batch is CSR:
+ * `row_ptr[n_rows + 1]` (row_ptr[0] = 0, non-decreasing), `other_ids` / `ratings` [row_ptr[n_rows]] = ids on the
+ * opposite side and ratings in pmf_ctx_set_ratings' convention.  For a row with n > 0 ratings (o_j, x_j), m_j =
+ * FACTOR_other[o_j]:
+ *     S = sum_j ( COV_other[o_j] + m_j m_j^T ),      V = inv( I/eta2 + S/sigma2 ),      b^0 = 0
+ *     m^t = V . sum_j m_j (x_j - b^(t-1) - BIAS_other[o_j]) / sigma2
+ *     b^t = kappa . sum_j (x_j - BIAS_other[o_j] - m_j . m^t),     kappa = 1 / (sigma2 (1/eta_bias2 + n/sigma2))
+ * out_factor[r] = m^n_iter, out_cov[r] = V (full K x K), out_bias[r] = b^n_iter.  V does not depend on b and m is
+ * affine in it, so the covariance rows are gathered once per call whatever n_iter is.  Unless both sides have a
+ * BIAS array, b = 0 throughout, n_iter has no effect and out_bias is zeros.  A row without ratings gets the prior:
+ * m = 0, V = eta2 I, b = 0.  out_cov / out_bias may be NULL (nothing K x K is then expanded or copied).
+ * Reads the context's model state only: state, ratings, work lists and the stored validation set stay as they
+ * are; FACTOR / COV of `side` itself are not needed; never a collective, with or without a communicator.
+ * PMF_EINVAL: null context (whatever n_rows is), bad side, n_rows < 0, a null array that is needed, row_ptr[0] != 0
+ * or a decreasing row_ptr, a variance <= 0, n_iter < 1, FACTOR or COV of the opposite side not set (named).
+ * PMF_ERANGE: an other_ids entry outside the opposite side, or n_factors > 256.  An argument error writes no output
+ * buffer; n_rows = 0 touches nothing.  Rows are processed in blocks of bounded scratch (PMF_FOLD_IN_ROWS=n, read
+ * when the context is created, caps the rows of a block). */
+int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
+                      const double *ratings, double sigma2, double eta2, double eta_bias2, int n_iter,
+                      double *out_factor /* n_rows x K */, double *out_cov /* n_rows x K x K, may be NULL */,
+                      double *out_bias /* n_rows, may be NULL */);
+
 /* Multi-GPU forms: raw per-row sums into / from a caller-owned DEVICE buffer.
  * Factor: [rows x (Kp + Kpad)] = packed lower triangle of S, then the
  * right-hand side (Kp = K(K+1)/2 rounded up to a multiple of 4, see

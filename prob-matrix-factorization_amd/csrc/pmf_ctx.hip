@@ -189,6 +189,7 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
         const int n = atoi(tc);
         if (n >= 32 && n <= 512 && (n & (n - 1)) == 0) ctx->task_chunk = n;   // anything else: the nnz rule
     }
+    if (const char *fr = getenv("PMF_FOLD_IN_ROWS")) ctx->fold_in_rows = std::max(atoll(fr), 0LL);
     if (const char *ex = getenv("PMF_COMM_EXCHANGE")) {
         if (!strcmp(ex, "allreduce")) ctx->exchange = PMF_EXCHANGE_ALLREDUCE;
         else if (!strcmp(ex, "scatter_gather")) ctx->exchange = PMF_EXCHANGE_SCATTER_GATHER;
@@ -307,10 +308,10 @@ extern "C" int pmf_ctx_cov_stride(pmf_ctx *ctx, int *stride) {
 // With row chunks (pmf_ctx_set_row_chunks) the tasks are grouped by the chunk of
 // their row -- longest-first inside every group -- and `task_off` / `split_off`
 // hold the group boundaries (the split list is in row order, hence grouped too).
-static void build_tasks(const std::vector<int64_t> &ptr, int64_t rows, int chunk, bool keep_empty,
-                        const std::vector<int64_t> &row_bounds, std::vector<PmfTask> &tasks,
-                        std::vector<PmfSplitRow> &split, int64_t &n_slots, std::vector<int64_t> &task_off,
-                        std::vector<int64_t> &split_off) {
+void pmf_build_tasks(const std::vector<int64_t> &ptr, int64_t rows, int chunk, bool keep_empty,
+                     const std::vector<int64_t> &row_bounds, std::vector<PmfTask> &tasks,
+                     std::vector<PmfSplitRow> &split, int64_t &n_slots, std::vector<int64_t> &task_off,
+                     std::vector<int64_t> &split_off) {
     std::vector<PmfTask> raw;
     raw.reserve((size_t)rows + 1024);
     n_slots = 0;
@@ -410,8 +411,8 @@ static int upload_tasks(pmf_ctx *ctx, int side, const std::vector<int64_t> &ptr,
     std::vector<PmfTask> tasks;
     std::vector<PmfSplitRow> split;
     int64_t n_slots = 0;
-    build_tasks(ptr, rows, chunk, keep_empty, chunk_bounds(ctx, side), tasks, split, n_slots, out.task_off,
-                out.split_off);
+    pmf_build_tasks(ptr, rows, chunk, keep_empty, chunk_bounds(ctx, side), tasks, split, n_slots, out.task_off,
+                    out.split_off);
     out.n_tasks = (int64_t)tasks.size();
     out.n_split = (int64_t)split.size();
     out.n_slots = n_slots;
@@ -433,6 +434,13 @@ static int upload_tasks(pmf_ctx *ctx, int side, const std::vector<int64_t> &ptr,
     return PMF_OK;
 }
 
+int pmf_task_chunk(const pmf_ctx *ctx, int max_chunk) {
+    if (ctx->task_chunk) return std::min(ctx->task_chunk, max_chunk);
+    int64_t c = 32;
+    while (c < max_chunk && c * 65536 < ctx->nnz) c <<= 1;
+    return (int)c;
+}
+
 // (re)build the three task lists of one side for the current row chunking
 static int build_work_lists(pmf_ctx *ctx, int side) {
     PmfSideIndex &ix = ctx->index[side];
@@ -449,17 +457,11 @@ static int build_work_lists(pmf_ctx *ctx, int side) {
     // large ones keep the maximum, which minimises partial-sum traffic.  (Chunking only changes the
     // summation order of rows longer than a chunk.)  The gradient mode has its own list with the fixed
     // 256: its result is defined in terms of that piece length.  PMF_TASK_CHUNK (ctx->task_chunk) overrides the
-    // rule for the other three lists.
-    auto task_chunk = [&](int max_chunk) {
-        if (ctx->task_chunk) return std::min(ctx->task_chunk, max_chunk);
-        int64_t c = 32;
-        while (c < max_chunk && c * 65536 < ctx->nnz) c <<= 1;
-        return (int)c;
-    };
+    // rule for the other three lists (pmf_task_chunk).
     int rc;
-    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, task_chunk(PMF_GAMMA_CHUNK), true, ix.gamma_tasks))) return rc;
-    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, task_chunk(PMF_GAUSS_CHUNK), false, ix.gauss_tasks))) return rc;
-    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, task_chunk(PMF_GAMMA_CHUNK), false, ix.bias_tasks))) return rc;
+    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAMMA_CHUNK), true, ix.gamma_tasks))) return rc;
+    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAUSS_CHUNK), false, ix.gauss_tasks))) return rc;
+    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAMMA_CHUNK), false, ix.bias_tasks))) return rc;
     if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, PMF_SGD_CHUNK, false, ix.sgd_tasks))) return rc;
     return PMF_OK;
 }

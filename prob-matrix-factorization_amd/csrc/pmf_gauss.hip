@@ -18,7 +18,9 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <new>
 #include <type_traits>
+#include <vector>
 
 #include "pmf_device.h"
 
@@ -1255,6 +1257,131 @@ __global__ void gauss_bias_finalize_all_kernel(BiasParams<T> p) {
 }
 
 // ---------------------------------------------------------------------------
+// fold-in (pmf_gauss_fold_in): the factor / bias alternation of NEW rows, bias model
+// ---------------------------------------------------------------------------
+// The accumulate and solve kernels above have left V and m0 = V w0 / sigma2, w0 = sum_j m_j (x_j - b_o), of every
+// row of the block.  V does not depend on the row's bias b, and m is affine in it, so the alternation
+// (gaussian_mf_cavi_bias.py:132-165 then :206-232, n_iter times from b = 0) is a scalar recursion:
+//     g = sum_j m_j,  c0 = sum_j (x_j - b_o),  h = V g / sigma2,  alpha = g . m0,  beta = g . h
+//     m^t = m0 - b^(t-1) h,   b^t = kappa (c0 - alpha + beta b^(t-1)),   kappa = 1 / (sigma2 (1/eta_bias2 + n/sigma2))
+// One lane group per row, lane c owning elements 4c .. 4c+3 of the K-vectors as in gauss_bias_kernel.  The row's
+// ratings are walked by that one group whatever their number: only the mean row (K values) and one bias are
+// gathered per rating here, the covariance rows were gathered once by the accumulate.  h is a symmetric mat-vec
+// over the packed lower triangle, four rows at a time: the lanes left of the diagonal block read their four columns
+// of those rows; an entry V[i][j] adds V g_j to the row sum of i (reduced over the group, kept by the lane that owns
+// i) and, for j < i, V g_i to the owner's own element j.
+template <typename T>
+struct FoldBiasParams {
+    const int64_t *ptr;   // [n + 1] offsets of the block's rows into other / val
+    int64_t n;
+    const int32_t *other;
+    const T *val;
+    const T *factor_other;
+    const T *bias_other;
+    const T *cov;         // [n][cov_stride] packed V of the rows
+    T *factor;            // [n][kpad] in: m0, out: m
+    T *bias;              // [n] out
+    T inv_sigma2, inv_eta_bias2;
+    int n_iter, K, kpad, cov_stride;
+};
+
+template <typename T, int LPR>
+__global__ __launch_bounds__(256) void gauss_fold_bias_kernel(FoldBiasParams<T> p) {
+    constexpr int G = 256 / LPR;
+    constexpr int UN = LPR < 4 ? LPR : 4;
+    const int c = threadIdx.x % LPR;
+    const int64_t row = (int64_t)blockIdx.x * G + threadIdx.x / LPR;
+    if (row >= p.n) return;
+    const int64_t start = p.ptr[row], n = p.ptr[row + 1] - start;
+    if (n == 0) {   // (the host writes the prior)
+        if (c == 0) p.bias[row] = (T)0;
+        return;
+    }
+    const int koff = c * PMF_VEC;
+    const bool active = koff < p.kpad;
+    const int32_t *col = p.other + start;
+    const T *val = p.val + start;
+    Vec4<T> g = zero4<T>();
+    T c0 = (T)0;
+    for (int64_t base = 0; base < n; base += LPR) {
+        const int cnt = (int)min((int64_t)LPR, n - base);
+        int my_o = 0;
+        if (c < cnt) {
+            my_o = col[base + c];
+            c0 += val[base + c] - p.bias_other[my_o];
+        }
+        for (int tt = 0; tt < cnt; tt += UN) {
+            Vec4<T> b[UN];
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                const int o = __shfl(my_o, tt + q, LPR);   // (lanes past the batch hold id 0: never loaded)
+                b[q] = (active && tt + q < cnt) ? load4(p.factor_other + (int64_t)o * p.kpad + koff) : zero4<T>();
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q)
+#pragma unroll
+                for (int e = 0; e < PMF_VEC; ++e) g.v[e] += b[q].v[e];
+        }
+    }
+    c0 = group_sum<LPR>(c0);
+    const T *V = p.cov + row * p.cov_stride;
+    Vec4<T> h = zero4<T>();
+    for (int b = 0; b * PMF_VEC < p.K; ++b) {   // (b < LPR: the group has a lane for every four elements of a row)
+        T gi[PMF_VEC], d[PMF_VEC];
+#pragma unroll
+        for (int r = 0; r < PMF_VEC; ++r) gi[r] = __shfl(g.v[r], b, LPR);
+#pragma unroll
+        for (int r = 0; r < PMF_VEC; ++r) {
+            const int i = b * PMF_VEC + r;
+            T dot = (T)0;
+            if (i < p.K && c <= b) {
+                const T *vr = V + i * (i + 1) / 2 + koff;
+#pragma unroll
+                for (int e = 0; e < PMF_VEC; ++e) {
+                    if (koff + e <= i) {
+                        const T v = vr[e];
+                        dot = fma(v, g.v[e], dot);
+                        if (koff + e < i) h.v[e] = fma(v, gi[r], h.v[e]);
+                    }
+                }
+            }
+            d[r] = dot;
+        }
+#pragma unroll
+        for (int r = 0; r < PMF_VEC; ++r) d[r] = group_sum<LPR>(d[r]);
+        if (c == b) {
+#pragma unroll
+            for (int r = 0; r < PMF_VEC; ++r) h.v[r] += d[r];
+        }
+    }
+    T *mrow = p.factor + row * p.kpad + koff;
+    const Vec4<T> m0 = active ? load4(mrow) : zero4<T>();
+    T alpha = (T)0, beta = (T)0;
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) {
+        h.v[e] *= p.inv_sigma2;
+        alpha = fma(g.v[e], m0.v[e], alpha);
+        beta = fma(g.v[e], h.v[e], beta);
+    }
+    alpha = group_sum<LPR>(alpha);
+    beta = group_sum<LPR>(beta);
+    // gaussian_mf_cavi_bias.py:222-230: var = 1/(1/eta_b2 + n/sigma2); b = var/sigma2 * sum
+    const T kappa = p.inv_sigma2 / (p.inv_eta_bias2 + (T)n * p.inv_sigma2);
+    T b_prev = (T)0, b_cur = (T)0;
+    for (int t = 0; t < p.n_iter; ++t) {
+        b_prev = b_cur;
+        b_cur = kappa * (c0 - alpha + beta * b_prev);
+    }
+    if (active) {
+        Vec4<T> m;
+#pragma unroll
+        for (int e = 0; e < PMF_VEC; ++e) m.v[e] = fma(-b_prev, h.v[e], m0.v[e]);
+        store4(mrow, m);
+    }
+    if (c == 0) p.bias[row] = b_cur;
+}
+
+// ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
 // fuse: sums in place, then solve   !fuse: sums only (into the statistics or in place)
@@ -1425,34 +1552,10 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *sta
     return PMF_OK;
 }
 
-// finalize pass: every row of the selected range from `stats`; fused pass: the rows with ratings (the split rows only
-// when the accumulate kernel solved the others) from the sums in COV / FACTOR
+// the row solver for the context's K and dtype over the rows `sp` names
 template <typename T>
-static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *stats, double sigma2, double eta2,
-                            bool split_rows_only = false) {
-    PMF_REQUIRE(sigma2 > 0 && eta2 > 0, PMF_EINVAL, "pmf_gauss_factor_sweep: variances must be positive");
+static int launch_solve(pmf_ctx *ctx, const SolveParams<T> &sp) {
     int rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_factor_finalize"))) return rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_factor_finalize"))) return rc;
-    const int width = ctx->cov_stride + ctx->kpad;
-    const bool fin = pass == PMF_PASS_FINALIZE;
-    const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gauss_tasks, fin);
-    SolveParams<T> sp;
-    sp.rows = fin ? nullptr : split_rows_only ? tl.d_split_rows : tl.d_nonempty;
-    sp.row0 = fin ? tl.row0 : 0;
-    sp.n = fin ? tl.row1 - tl.row0 : split_rows_only ? tl.n_split : tl.n_nonempty;
-    sp.src_s = fin ? (const T *)stats : ctx->arr[side][PMF_ARR_COV].as<const T>();
-    sp.src_s_stride = fin ? width : ctx->cov_stride;
-    sp.src_w = fin ? (const T *)stats + ctx->cov_stride : ctx->arr[side][PMF_ARR_FACTOR].as<const T>();
-    sp.src_w_stride = fin ? width : ctx->kpad;
-    sp.cov = ctx->arr[side][PMF_ARR_COV].as<T>();
-    sp.factor = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
-    sp.inv_sigma2 = (T)(1.0 / sigma2);
-    sp.inv_eta2 = (T)(1.0 / eta2);
-    sp.K = ctx->K;
-    sp.kpad = ctx->kpad;
-    sp.kp = ctx->kp;
-    sp.cov_stride = ctx->cov_stride;
     if (sp.n == 0) return PMF_OK;
     PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SOLVE);
     if (ctx->K <= 64)
@@ -1491,6 +1594,37 @@ static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *st
     }
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
+}
+
+// finalize pass: every row of the selected range from `stats`; fused pass: the rows with ratings (the split rows only
+// when the accumulate kernel solved the others) from the sums in COV / FACTOR
+template <typename T>
+static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *stats, double sigma2, double eta2,
+                            bool split_rows_only = false) {
+    PMF_REQUIRE(sigma2 > 0 && eta2 > 0, PMF_EINVAL, "pmf_gauss_factor_sweep: variances must be positive");
+    int rc;
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_factor_finalize"))) return rc;
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_factor_finalize"))) return rc;
+    const int width = ctx->cov_stride + ctx->kpad;
+    const bool fin = pass == PMF_PASS_FINALIZE;
+    const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gauss_tasks, fin);
+    SolveParams<T> sp;
+    sp.rows = fin ? nullptr : split_rows_only ? tl.d_split_rows : tl.d_nonempty;
+    sp.row0 = fin ? tl.row0 : 0;
+    sp.n = fin ? tl.row1 - tl.row0 : split_rows_only ? tl.n_split : tl.n_nonempty;
+    sp.src_s = fin ? (const T *)stats : ctx->arr[side][PMF_ARR_COV].as<const T>();
+    sp.src_s_stride = fin ? width : ctx->cov_stride;
+    sp.src_w = fin ? (const T *)stats + ctx->cov_stride : ctx->arr[side][PMF_ARR_FACTOR].as<const T>();
+    sp.src_w_stride = fin ? width : ctx->kpad;
+    sp.cov = ctx->arr[side][PMF_ARR_COV].as<T>();
+    sp.factor = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
+    sp.inv_sigma2 = (T)(1.0 / sigma2);
+    sp.inv_eta2 = (T)(1.0 / eta2);
+    sp.K = ctx->K;
+    sp.kpad = ctx->kpad;
+    sp.kp = ctx->kp;
+    sp.cov_stride = ctx->cov_stride;
+    return launch_solve<T>(ctx, sp);
 }
 
 extern "C" int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
@@ -1610,4 +1744,227 @@ extern "C" int pmf_gauss_bias_finalize(pmf_ctx *ctx, int side, const void *stats
     PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_bias_finalize: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_bias_finalize: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_bias<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, (void *)stats_dev, sigma2, eta_bias2); });
+}
+
+// ---- fold-in ---------------------------------------------------------------
+static const int64_t kFoldInStatsBytes = 256ll << 20;   // statistics + partial slots of one row block
+static const int64_t kFoldInBlockNnz = 32ll << 20;      // staged ratings of one row block (a longer single row still goes)
+static const int64_t kFoldInStageBytes = 64ll << 20;    // pinned staging of the download
+
+// `rows` rows of a device array laid out like `array` of the model state -> host float64
+static int fold_in_download(pmf_ctx *ctx, int array, const void *dev, double *host, int64_t rows) {
+    int width, stride, rc;
+    pmf_array_shape(ctx, array, &width, &stride);
+    const int64_t row_bytes = (int64_t)stride * (int64_t)ctx->elem;
+    const int64_t step = std::max<int64_t>(1, kFoldInStageBytes / row_bytes);
+    if ((rc = pmf_ensure_pinned(ctx, (size_t)(std::min(step, rows) * row_bytes)))) return rc;
+    for (int64_t r0 = 0; r0 < rows; r0 += step) {
+        const int64_t nr = std::min(step, rows - r0);
+        PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned.as(), (const char *)dev + r0 * row_bytes, (size_t)(nr * row_bytes),
+                                     hipMemcpyDeviceToHost, ctx->stream));
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        pmf_unpack_rows(ctx, array, ctx->h_pinned.as(), host + r0 * width, nr);
+    }
+    return PMF_OK;
+}
+
+struct FoldInBatch {
+    int64_t n_rows;
+    const int64_t *row_ptr;
+    const int32_t *other_ids;
+    const double *ratings;
+    double sigma2, eta2, eta_bias2;
+    int n_iter;
+    double *out_factor, *out_cov, *out_bias;
+};
+
+// The batch in row blocks whose statistics ([cov_stride + kpad + 1] per row) and partial slots ([cov_stride + kpad] per
+// task of a split row) fit kFoldInStatsBytes.  Per block: stage ratings and a task list, accumulate S and w0 with the
+// sweep's kernels (accumulate-only form), solve in place, run the bias alternation, download.  Everything lives in
+// buffers of this call: the context's model state, index and work lists are only read.
+template <typename T>
+static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
+    const int other = 1 - side;
+    const int K = ctx->K, kpad = ctx->kpad, cs = ctx->cov_stride, width = cs + kpad;
+    const bool bias = pmf_has_bias(ctx);
+    const int chunk = pmf_task_chunk(ctx, PMF_GAUSS_CHUNK);
+    const int64_t max_units = std::max<int64_t>(1, kFoldInStatsBytes / ((int64_t)(width + 1) * (int64_t)sizeof(T)));
+    const int64_t max_rows = ctx->fold_in_rows > 0 ? ctx->fold_in_rows : (int64_t)INT32_MAX;
+    PmfBuf d_tasks, d_split, d_ptr, d_other, d_val, d_s, d_w, d_b, d_partial;
+    std::vector<int64_t> ptr, task_off, split_off;
+    std::vector<PmfTask> tasks;
+    std::vector<PmfSplitRow> split;
+    std::vector<T> val;
+    int rc;
+    for (int64_t r0 = 0, r1; r0 < a.n_rows; r0 = r1) {
+        int64_t units = 0, nnz = 0;
+        bool has_empty = false;
+        for (r1 = r0; r1 < a.n_rows && r1 - r0 < max_rows; ++r1) {
+            const int64_t n = a.row_ptr[r1 + 1] - a.row_ptr[r1];
+            const int64_t u = 1 + (n > chunk ? (n + chunk - 1) / chunk : 0);
+            if (r1 > r0 && (units + u > max_units || nnz + n > kFoldInBlockNnz)) break;
+            units += u;
+            nnz += n;
+            has_empty |= n == 0;
+        }
+        const int64_t B = r1 - r0, at = a.row_ptr[r0];
+        ptr.resize((size_t)B + 1);
+        for (int64_t r = 0; r <= B; ++r) ptr[(size_t)r] = a.row_ptr[r0 + r] - at;
+        val.resize((size_t)nnz);
+        for (int64_t k = 0; k < nnz; ++k) val[(size_t)k] = (T)a.ratings[at + k];
+        tasks.clear();
+        split.clear();
+        int64_t n_slots = 0;
+        pmf_build_tasks(ptr, B, chunk, false, {0, B}, tasks, split, n_slots, task_off, split_off);
+        // (the previous block ended with a stream synchronise: nothing queued still reads these buffers)
+        if ((rc = d_tasks.reserve(ctx, tasks.size() * sizeof(PmfTask), {ctx->stream}))) return rc;
+        if ((rc = d_split.reserve(ctx, split.size() * sizeof(PmfSplitRow), {ctx->stream}))) return rc;
+        if ((rc = d_ptr.reserve(ctx, ptr.size() * sizeof(int64_t), {ctx->stream}))) return rc;
+        if ((rc = d_other.reserve(ctx, (size_t)nnz * sizeof(int32_t), {ctx->stream}))) return rc;
+        if ((rc = d_val.reserve(ctx, (size_t)nnz * sizeof(T), {ctx->stream}))) return rc;
+        if ((rc = d_s.reserve(ctx, (size_t)B * cs * sizeof(T), {ctx->stream}))) return rc;
+        if ((rc = d_w.reserve(ctx, (size_t)B * kpad * sizeof(T), {ctx->stream}))) return rc;
+        if ((rc = d_b.reserve(ctx, (size_t)B * sizeof(T), {ctx->stream}))) return rc;
+        if ((rc = d_partial.reserve(ctx, (size_t)n_slots * width * sizeof(T), {ctx->stream}))) return rc;
+        PMF_HIP_CHECK(hipMemcpy(d_ptr.as(), ptr.data(), ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (nnz) {
+            PMF_HIP_CHECK(hipMemcpy(d_tasks.as(), tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
+            PMF_HIP_CHECK(hipMemcpy(d_other.as(), a.other_ids + at, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+            PMF_HIP_CHECK(hipMemcpy(d_val.as(), val.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
+        }
+        if (!split.empty())
+            PMF_HIP_CHECK(hipMemcpy(d_split.as(), split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
+        if (has_empty) {   // no task writes an empty row: zero sums, which the solvers skip
+            PMF_HIP_CHECK(hipMemsetAsync(d_s.as(), 0, (size_t)B * cs * sizeof(T), ctx->stream));
+            PMF_HIP_CHECK(hipMemsetAsync(d_w.as(), 0, (size_t)B * kpad * sizeof(T), ctx->stream));
+        }
+        GaussParams<T> p;
+        p.tasks = d_tasks.as<PmfTask>();
+        p.n_tasks = (int64_t)tasks.size();
+        p.split = d_split.as<PmfSplitRow>();
+        p.other = d_other.as<int32_t>();
+        p.val = d_val.as<const T>();
+        p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
+        p.cov_other = ctx->arr[other][PMF_ARR_COV].as<const T>();
+        p.bias_self = nullptr;
+        p.bias_other = bias ? ctx->arr[other][PMF_ARR_BIAS].as<const T>() : nullptr;
+        p.partial = d_partial.as<T>();
+        p.dst_s = d_s.as<T>();
+        p.dst_s_stride = cs;
+        p.dst_w = d_w.as<T>();
+        p.dst_w_stride = kpad;
+        p.K = K;
+        p.kpad = kpad;
+        p.kp = ctx->kp;
+        p.cov_stride = cs;
+        p.hot = nullptr;
+        if (p.n_tasks > 0) {
+            PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_ACCUM);
+            if (std::is_same<T, float>::value && !ctx->gauss_generic && K <= 128) {
+                if constexpr (std::is_same<T, float>::value) launch_accum_mfma_fp32(ctx, p, p.n_tasks, false, 0.f, 0.f);
+            } else {
+                launch_accum_generic(ctx, p, p.n_tasks, false, (T)0, (T)0);
+            }
+        }
+        if (!split.empty()) {
+            PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
+            hipLaunchKernelGGL((gauss_combine_kernel<T>), dim3((unsigned)split.size()), dim3(256), 0, ctx->stream, p);
+        }
+        PMF_HIP_CHECK(hipGetLastError());
+        SolveParams<T> sp;
+        sp.rows = nullptr;
+        sp.row0 = 0;
+        sp.n = B;
+        sp.src_s = d_s.as<const T>();
+        sp.src_s_stride = cs;
+        sp.src_w = d_w.as<const T>();
+        sp.src_w_stride = kpad;
+        sp.cov = d_s.as<T>();
+        sp.factor = d_w.as<T>();
+        sp.inv_sigma2 = (T)(1.0 / a.sigma2);
+        sp.inv_eta2 = (T)(1.0 / a.eta2);
+        sp.K = K;
+        sp.kpad = kpad;
+        sp.kp = ctx->kp;
+        sp.cov_stride = cs;
+        if ((rc = launch_solve<T>(ctx, sp))) return rc;
+        if (bias) {
+            FoldBiasParams<T> q;
+            q.ptr = d_ptr.as<const int64_t>();
+            q.n = B;
+            q.other = p.other;
+            q.val = p.val;
+            q.factor_other = p.factor_other;
+            q.bias_other = p.bias_other;
+            q.cov = d_s.as<const T>();
+            q.factor = d_w.as<T>();
+            q.bias = d_b.as<T>();
+            q.inv_sigma2 = (T)(1.0 / a.sigma2);
+            q.inv_eta_bias2 = (T)(1.0 / a.eta_bias2);
+            q.n_iter = a.n_iter;
+            q.K = K;
+            q.kpad = kpad;
+            q.cov_stride = cs;
+            PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_BIAS);
+            pmf_with_pow2<1>(pmf_lanes_per_row(kpad), [&](auto L) {
+                dim3 grid((unsigned)((B + 256 / L - 1) / (256 / L)));
+                hipLaunchKernelGGL((gauss_fold_bias_kernel<T, L>), grid, dim3(256), 0, ctx->stream, q);
+            });
+        }
+        PMF_HIP_CHECK(hipGetLastError());
+        double *of = a.out_factor + r0 * K;
+        double *oc = a.out_cov ? a.out_cov + r0 * (int64_t)K * K : nullptr;
+        double *ob = a.out_bias ? a.out_bias + r0 : nullptr;
+        // (every download ends with a stream synchronise: the block's kernels are done with the staging buffers)
+        if ((rc = fold_in_download(ctx, PMF_ARR_FACTOR, d_w.as(), of, B))) return rc;
+        if (oc && (rc = fold_in_download(ctx, PMF_ARR_COV, d_s.as(), oc, B))) return rc;
+        if (ob && bias && (rc = fold_in_download(ctx, PMF_ARR_BIAS, d_b.as(), ob, B))) return rc;
+        if (ob && !bias) std::fill_n(ob, (size_t)B, 0.0);
+        for (int64_t r = 0; has_empty && r < B; ++r) {
+            if (ptr[(size_t)r + 1] > ptr[(size_t)r]) continue;
+            // a row without ratings gets the prior: m = 0, V = eta2 I, b = 0
+            std::fill_n(of + r * K, (size_t)K, 0.0);
+            if (ob) ob[r] = 0.0;
+            if (oc) {
+                double *v = oc + r * (int64_t)K * K;
+                std::fill_n(v, (size_t)K * K, 0.0);
+                for (int k = 0; k < K; ++k) v[(size_t)k * K + k] = a.eta2;
+            }
+        }
+    }
+    return PMF_OK;
+}
+
+extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
+                                 const double *ratings, double sigma2, double eta2, double eta_bias2, int n_iter,
+                                 double *out_factor, double *out_cov, double *out_bias) {
+    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "pmf_gauss_fold_in: null context");
+    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, "pmf_gauss_fold_in: bad side %d", side);
+    PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_gauss_fold_in: negative row count");
+    if (n_rows == 0) return PMF_OK;
+    PMF_REQUIRE(row_ptr && out_factor, PMF_EINVAL, "pmf_gauss_fold_in: null argument");
+    PMF_REQUIRE(row_ptr[0] == 0, PMF_EINVAL, "pmf_gauss_fold_in: row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
+    for (int64_t r = 0; r < n_rows; ++r)
+        PMF_REQUIRE(row_ptr[r + 1] >= row_ptr[r], PMF_EINVAL, "pmf_gauss_fold_in: row_ptr decreases at row %lld", (long long)r);
+    const int64_t nnz = row_ptr[n_rows];
+    PMF_REQUIRE(nnz == 0 || (other_ids && ratings), PMF_EINVAL, "pmf_gauss_fold_in: null argument");
+    PMF_REQUIRE(sigma2 > 0 && eta2 > 0 && eta_bias2 > 0, PMF_EINVAL, "pmf_gauss_fold_in: variances must be positive");
+    PMF_REQUIRE(n_iter >= 1, PMF_EINVAL, "pmf_gauss_fold_in: n_iter = %d, must be at least 1", n_iter);
+    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_fold_in: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
+    const int other = 1 - side;
+    int rc;
+    if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_fold_in"))) return rc;
+    if ((rc = pmf_require_array(ctx, other, PMF_ARR_COV, "pmf_gauss_fold_in"))) return rc;
+    for (int64_t k = 0; k < nnz; ++k)
+        PMF_REQUIRE(other_ids[k] >= 0 && other_ids[k] < ctx->rows[other], PMF_ERANGE,
+                    "pmf_gauss_fold_in: id %d at position %lld outside [0, %lld)", other_ids[k], (long long)k,
+                    (long long)ctx->rows[other]);
+    PMF_HIP_CHECK(hipSetDevice(ctx->device));
+    const FoldInBatch a = {n_rows, row_ptr, other_ids, ratings, sigma2, eta2, eta_bias2, n_iter, out_factor, out_cov, out_bias};
+    try {  // host containers may throw: nothing propagates across the C boundary
+        return pmf_with_dtype(ctx, [&](auto t) { return run_fold_in<decltype(t)>(ctx, side, a); });
+    } catch (const std::bad_alloc &) {
+        pmf_set_error("pmf_gauss_fold_in: out of host memory");
+        return PMF_ENOMEM;
+    }
 }

@@ -196,6 +196,7 @@ struct pmf_ctx {
     int topk_max_blocks = 0;       // PMF_TOPK_MAX_BLOCKS=n caps the fused kernel's persistent grid (tests: many tiles per block)
     int topk_stage_buffers = 0;    // PMF_TOPK_STAGE_BUFFERS=1|2 pins the fused kernel's stage buffering (0: by residency)
     bool topk_two_phase = false;   // PMF_TOPK_TWO_PHASE: score matrix in HBM + select instead of the fused kernel
+    int64_t fold_in_rows = 0;      // PMF_FOLD_IN_ROWS=n caps the rows of one block of pmf_gauss_fold_in (tests: many blocks on a small batch; 0: by scratch size)
     int task_chunk = 0;            // PMF_TASK_CHUNK=n (power of two in [32, 512]) fixes the task length of the gamma / Gaussian / bias lists (tests: long tasks on small problems; 0: by nnz)
 
     // multi-GPU (pmf_comm.hip): the communicator (shared between contexts of one process, refcounted)
@@ -226,6 +227,13 @@ struct pmf_ctx {
 static inline int64_t pmf_chunk_row0(const pmf_ctx *ctx, int side, int c) {
     return ctx->rows[side] * (int64_t)c / ctx->n_chunks[side];
 }
+// Work list of `rows` rows given by their offsets `ptr` (pmf_ctx.hip): runs of at most `chunk` ratings, longest first
+// inside each row group of `row_bounds`; rows longer than `chunk` are split evenly and listed in `split`.
+void pmf_build_tasks(const std::vector<int64_t> &ptr, int64_t rows, int chunk, bool keep_empty,
+                     const std::vector<int64_t> &row_bounds, std::vector<PmfTask> &tasks, std::vector<PmfSplitRow> &split,
+                     int64_t &n_slots, std::vector<int64_t> &task_off, std::vector<int64_t> &split_off);
+// task length of the context's gamma / Gaussian / bias lists: PMF_TASK_CHUNK, or by the rating count, at most `max_chunk`
+int pmf_task_chunk(const pmf_ctx *ctx, int max_chunk);
 // `select` = honour pmf_ctx_select_chunk (accumulate / finalize); fused sweeps pass false
 PmfTaskView pmf_task_view(const pmf_ctx *ctx, int side, const PmfTaskList &tl, bool select);
 

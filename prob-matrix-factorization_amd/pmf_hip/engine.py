@@ -252,6 +252,23 @@ class Context:
         check(self._lib.pmf_gauss_bias_finalize(self._h, side, C.c_void_p(stats_ptr), float(sigma2),
                                                 float(eta_bias2)), "pmf_gauss_bias_finalize")
 
+    def gauss_fold_in(self, side, row_ptr, other_ids, ratings, sigma2, eta2, eta_bias2=1.0, n_iter=1, want_cov=True):
+        """Posterior of new rows of `side` (CSR batch: `row_ptr`, ids on the opposite side, ratings) against the
+        fitted opposite side: (factor [n, K], cov [n, K, K] or None, bias [n]) as float64.  The context is only read."""
+        rp = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.int64).reshape(-1))
+        o, x = as_i32(other_ids, "other_ids"), as_f64(ratings)
+        if len(rp) < 1 or len(o) != len(x) or (len(rp) > 1 and rp[-1] != len(o)):
+            raise ValueError("row_ptr must hold n_rows + 1 offsets ending at len(other_ids) == len(ratings)")
+        n = len(rp) - 1
+        factor = np.zeros((n, self.K), dtype=np.float64)
+        cov = np.zeros((n, self.K, self.K), dtype=np.float64) if want_cov else None
+        bias = np.zeros(n, dtype=np.float64)
+        check(self._lib.pmf_gauss_fold_in(self._h, side, n, ptr(rp, C.c_int64), ptr(o, C.c_int32), ptr(x, C.c_double),
+                                          float(sigma2), float(eta2), float(eta_bias2), int(n_iter), ptr(factor, C.c_double),
+                                          ptr(cov, C.c_double) if want_cov else None, ptr(bias, C.c_double)),
+              "pmf_gauss_fold_in")
+        return factor, cov, bias
+
     # ---- Gaussian MAP by gradient steps (no reference counterpart) -------
     def gauss_sgd_sweep(self, side, lr, sigma2, eta2, eta_bias2=1.0):
         check(self._lib.pmf_gauss_sgd_sweep(self._h, side, float(lr), float(sigma2), float(eta2), float(eta_bias2)),

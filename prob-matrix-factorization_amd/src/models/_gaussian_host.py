@@ -4,11 +4,31 @@ Iteration order, early-stop rule and verbose lines follow the reference
 (`gaussian_mf_cavi_bias.py:91-286`, bias-free twin `gaussian_mf_cavi.py:81-200`);
 each half-sweep is one C-ABI call (`pmf_gauss_factor_sweep`,
 `pmf_gauss_bias_sweep`)."""
+from dataclasses import dataclass
+from typing import Optional
+
 import numpy as np
 
 from src.evaluation.metrics import macro_mae, rmse
 from src.models._device_model import ITEM, USER, DeviceModel, frame_arrays
 from pmf_hip import ARR_BIAS, ARR_COV, ARR_FACTOR, dist as pdist
+
+
+@dataclass
+class FoldIn:
+    """Posterior of folded-in rows (`fold_in_users` / `fold_in_items`): row r belongs to label `ids[r]`."""
+    ids: np.ndarray            # the new side's labels, sorted
+    mean: np.ndarray           # (n, K)
+    cov: Optional[np.ndarray]  # (n, K, K), or None unless asked for
+    bias: np.ndarray           # (n,), zeros for the bias-free model
+    m_other: np.ndarray        # the fitted opposite side's means (and biases, or None)
+    b_other: Optional[np.ndarray]
+
+    def predict(self, rows, other_ids, global_mean=0.0):
+        """mean[rows] . m_other[other_ids] + bias[rows] + b_other[other_ids] + global_mean, on the host."""
+        rows, other_ids = np.asarray(rows, dtype=int), np.asarray(other_ids, dtype=int)
+        out = np.einsum("nk,nk->n", self.mean[rows], self.m_other[other_ids]) + self.bias[rows] + global_mean
+        return out if self.b_other is None else out + self.b_other[other_ids]
 
 
 class GaussianHost(DeviceModel):
@@ -208,6 +228,38 @@ class GaussianHost(DeviceModel):
         d = sigma2 + ctx.predict_var(u, i)
         e = y - ctx.predict(u, i, use_bias=self._uses_bias, offset=global_mean)
         return float(np.sum(-0.5 * np.log(2.0 * np.pi * d) - e * e / (2.0 * d)))
+
+    # ---- fold-in of unseen users / items (extension: no reference counterpart as an operation) ----
+    def _fold_in(self, what, side, df, n_iter, return_cov):
+        ctx = self._cov_ctx(what)
+        new_col, old_col = ("u", "i") if side == USER else ("i", "u")
+        n_other = self.n_items if side == USER else self.n_users
+        ids, row = np.unique(df[new_col].to_numpy(), return_inverse=True)
+        other = df[old_col].to_numpy(dtype=int)
+        keep = (other >= 0) & (other < n_other)          # ids the fit has not seen are dropped, as `_seen` does
+        row, other, x = row[keep], other[keep], df["rating"].to_numpy(dtype=float)[keep]
+        order = np.argsort(row, kind="stable")           # every row keeps its ratings in frame order
+        row_ptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=len(ids)))])
+        cfg = self.config
+        mean, cov, bias = ctx.gauss_fold_in(side, row_ptr, other[order], x[order], cfg.sigma2,
+                                            cfg.eta_theta2 if side == USER else cfg.eta_beta2,
+                                            cfg.eta_bias2 if self._uses_bias else 1.0, n_iter, want_cov=return_cov)
+        m_other = self.m_beta if side == USER else self.m_theta
+        b_other = (self.m_item_bias if side == USER else self.m_user_bias) if self._uses_bias else None
+        return FoldIn(ids, mean, cov, bias, m_other, b_other)
+
+    def fold_in_users(self, df, n_iter=10, return_cov=False):
+        """Posterior of users the fit has not seen, from their ratings of fitted items: `df` has columns u, i, rating
+        in `fit`'s rating convention; `u` holds arbitrary labels.  The item side stays frozen; each user gets the
+        factor update and (bias model) `n_iter` factor / bias alternations from a zero bias -- the reference's own
+        row updates, on the device (`pmf_gauss_fold_in`), without a refit.  Rows with an item id the fit has not seen
+        are dropped; a user left without ratings gets the prior.  Returns a `FoldIn`, one row per label in sorted
+        order."""
+        return self._fold_in("fold_in_users", USER, df, n_iter, return_cov)
+
+    def fold_in_items(self, df, n_iter=10, return_cov=False):
+        """The same for new items (labels in column `i`) against the fitted users."""
+        return self._fold_in("fold_in_items", ITEM, df, n_iter, return_cov)
 
     def _seen(self, df):
         keep = (df["u"] < self.n_users) & (df["i"] < self.n_items)
