@@ -251,6 +251,47 @@ int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row
                       double *out_factor /* n_rows x K */, double *out_cov /* n_rows x K x K, may be NULL */,
                       double *out_bias /* n_rows, may be NULL */);
 
+/* Evidence lower bound of the Gaussian models: the per-row sums that do not depend on the hyperparameters.  No
+ * reference counterpart (the reference never evaluates its objective).  q is what the reference's updates imply:
+ * q(theta_u) = N(m_u, V_u), q(beta_i) = N(m_i, V_i) and, in the bias model, q(b_r) = N(BIAS[r], v_r) with
+ * v_r = 1 / (1/eta_bias2 + n_r/sigma2) -- the `var` of gaussian_mf_cavi_bias.py:206-263, which the reference computes
+ * and drops; a row with n_r = 0 ratings has v_r = eta_bias2.  With N ratings, R rows of a side, K factors and, over the
+ * ratings (o_j, x_j) of row r,
+ *     S_r = sum_j ( COV_other[o_j] + m_j m_j^T ),   w_r = sum_j m_j (x_j - BIAS[r] - BIAS_other[o_j]),
+ *     c_r = sum_j (x_j - BIAS[r] - BIAS_other[o_j])^2          (m_j = FACTOR_other[o_j]; biases 0 without BIAS arrays)
+ * the call returns for `side`, per row and summed over all its rows (with or without ratings),
+ *     PMF_ELBO_SQNORM   |m_r|^2 + tr V_r
+ *     PMF_ELBO_LOGDET   log det V_r
+ *     PMF_ELBO_BIAS_SQ  BIAS[r]^2
+ *     PMF_ELBO_ESS      c_r - 2 m_r . w_r + < V_r + m_r m_r^T, S_r >   = the expected squared residual of the row's ratings
+ *                       under q, the bias variances aside (with_data != 0 only)
+ * and the caller assembles, with ESS taken from ONE side (either gives the same sum) and eta2 = eta_theta2 for users,
+ * eta_beta2 for items:
+ *     ESS' = ESS + sum_u n_u v_u + sum_i n_i v_i                                                   (bias model only)
+ *     L = -N/2 log(2 pi sigma2) - ESS' / (2 sigma2)
+ *         + sum_side [ -R K/2 log(2 pi eta2) - SQNORM / (2 eta2) + R K/2 (1 + log 2 pi) + LOGDET / 2 ]
+ *         + sum_side [ -R/2 log(2 pi eta_bias2) - (BIAS_SQ + sum_r v_r) / (2 eta_bias2) + 1/2 sum_r (1 + log(2 pi v_r)) ]
+ *                                                                                                  (bias model only)
+ * (src/models/_gaussian_host.py:elbo_from_terms is this formula).  `totals[t]` is the sum of the per-row values in row
+ * order, in double: two calls give the same bits, whatever the row windows are.  `per_row` (rows x PMF_ELBO_TERMS,
+ * row-major) may be NULL.  Sums inside a row are in the context's dtype.  With a data term the rows go in windows whose
+ * statistics fit a fixed scratch budget (PMF_ELBO_ROWS=n, read when the context is created, caps the rows of a window);
+ * per window the sweep's own accumulate kernels run on the sweep's own task cuts; measured at K = 64 fp32 on 1M users
+ * and 50M ratings, one call with a data term takes 1.3 times an accumulate of `side`.  Reads the context only: model state, ratings, work lists and the stored validation set stay
+ * as they are; never a collective, with or without a communicator.  Needs FACTOR and COV of `side`; with_data != 0
+ * also FACTOR and COV of the other side and the ratings.  PMF_EINVAL: null context, bad side, null totals, a missing
+ * array (named), with_data without ratings.  (n_factors > 256 would be PMF_ERANGE, but pmf_ctx_create already refuses
+ * such a context.)  An argument error writes nothing.  A row
+ * whose COV is not positive definite gives NaN in its LOGDET and in that total; the call still returns 0 and the
+ * other rows are unaffected. */
+#define PMF_ELBO_SQNORM 0    /* |m_r|^2 + tr V_r */
+#define PMF_ELBO_LOGDET 1    /* log det V_r; NaN for a row whose COV is not positive definite */
+#define PMF_ELBO_BIAS_SQ 2   /* BIAS[r]^2; 0 unless both sides have a BIAS array */
+#define PMF_ELBO_ESS 3       /* c_r - 2 m_r.w_r + <V_r + m_r m_r', S_r>; 0 for a row without ratings or when with_data == 0 */
+#define PMF_ELBO_TERMS 4
+int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, double *totals /* [PMF_ELBO_TERMS] */,
+                         double *per_row /* rows x PMF_ELBO_TERMS, may be NULL */);
+
 /* Multi-GPU forms: raw per-row sums into / from a caller-owned DEVICE buffer.
  * Factor: [rows x (Kp + Kpad)] = packed lower triangle of S, then the
  * right-hand side (Kp = K(K+1)/2 rounded up to a multiple of 4, see

@@ -190,6 +190,7 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
         if (n >= 32 && n <= 512 && (n & (n - 1)) == 0) ctx->task_chunk = n;   // anything else: the nnz rule
     }
     if (const char *fr = getenv("PMF_FOLD_IN_ROWS")) ctx->fold_in_rows = std::max(atoll(fr), 0LL);
+    if (const char *er = getenv("PMF_ELBO_ROWS")) ctx->elbo_rows = std::max(atoll(er), 0LL);
     if (const char *ex = getenv("PMF_COMM_EXCHANGE")) {
         if (!strcmp(ex, "allreduce")) ctx->exchange = PMF_EXCHANGE_ALLREDUCE;
         else if (!strcmp(ex, "scatter_gather")) ctx->exchange = PMF_EXCHANGE_SCATTER_GATHER;

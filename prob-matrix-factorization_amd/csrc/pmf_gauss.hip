@@ -1968,3 +1968,503 @@ extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
         return PMF_ENOMEM;
     }
 }
+
+// ---------------------------------------------------------------------------
+// evidence lower bound (pmf_gauss_elbo_terms): the per-row sums that do not depend on the hyperparameters
+// ---------------------------------------------------------------------------
+// No reference counterpart.  Per row r of a side, with q(row) = N(m_r, V_r) and the user-side statistics the sweep
+// builds (S_r, w_r over the row's ratings, residuals x_j - b_r - b_o):
+//     SQNORM = |m_r|^2 + tr V_r      LOGDET = log det V_r      BIAS_SQ = BIAS[r]^2
+//     ESS    = c_r - 2 m_r . w_r + <V_r + m_r m_r^T, S_r>,     c_r = sum_j (x_j - b_r - b_o)^2
+// ESS is the expected squared residual of all of the row's ratings (bias variances aside: the host adds them).
+// The rows go in windows whose statistics ([rows x (cov_stride + kpad)]) fit a fixed budget: per window run the
+// sweep's accumulate kernels (accumulate-only form) and the split-row combine on the window's tasks, then c_r and the
+// row reduction.  The task list is the Gaussian one again (same task length, so every row is cut and summed as in the
+// sweep), grouped by window.  Sums inside a row are in the context dtype; the logarithms and everything across rows are
+// double.
+static const int64_t kElboStatsBytes = 256ll << 20;   // statistics of one row window
+
+template <typename T>
+struct ElboParams {
+    int64_t row0, n;       // rows [row0, row0 + n) of the side
+    const T *stats;        // the window: row row0 + i at stats + i * (cov_stride + kpad), packed S then w; null = no data term
+    const T *csum;         // [n] c_r of the window's rows (with stats)
+    const int64_t *ptr;    // the side's row offsets (with stats)
+    const T *cov, *factor;
+    const T *bias;         // null unless both sides have a BIAS array
+    double *out;           // [rows of the side][PMF_ELBO_TERMS]
+    int K, kpad, kp, cov_stride;
+};
+
+template <typename T>
+struct ElboSqParams {
+    const PmfTask *tasks;
+    int64_t n_tasks;
+    const int32_t *other;
+    const T *val;
+    const T *bias_self, *bias_other;   // null when the model has no biases
+    T *partial;                        // [n_slots] of split rows
+    T *csum;                           // row r of the window at csum[r - row0]
+    int64_t row0;
+};
+
+// c_r: 16 lanes per task (a task is at most the context's task length), lane c takes ratings c, c + 16, ...
+template <typename T>
+__global__ __launch_bounds__(256) void gauss_elbo_sq_kernel(ElboSqParams<T> p) {
+    constexpr int LPR = 16, G = 256 / LPR;
+    const int c = threadIdx.x % LPR;
+    const int64_t task_id = (int64_t)blockIdx.x * G + threadIdx.x / LPR;
+    if (task_id >= p.n_tasks) return;
+    const PmfTask t = p.tasks[task_id];
+    const T bs = p.bias_self ? p.bias_self[t.row] : (T)0;
+    const int32_t *col = p.other + t.start;
+    const T *val = p.val + t.start;
+    T sum = (T)0;
+    for (int j = c; j < t.len; j += LPR) {
+        const T e = val[j] - bs - (p.bias_other ? p.bias_other[col[j]] : (T)0);
+        sum = fma(e, e, sum);
+    }
+    sum = group_sum<LPR>(sum);
+    if (c != 0) return;
+    if (t.slot >= 0) p.partial[t.slot] = sum;
+    else p.csum[(int64_t)t.row - p.row0] = sum;
+}
+
+// split rows: the slots of a row in slot order
+template <typename T>
+__global__ void gauss_elbo_sq_split_kernel(const PmfSplitRow *split, int64_t n_split, const T *partial, T *csum, int64_t row0) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n_split) return;
+    const PmfSplitRow sr = split[s];
+    T sum = (T)0;
+    for (int k = 0; k < sr.n_slots; ++k) sum += partial[sr.first_slot + k];
+    csum[(int64_t)sr.row - row0] = sum;
+}
+
+// One 16-byte chunk (packed entries q .. q + 3, (r, c) = position of entry q) of the walk over a row's packed V and S:
+// tr += V_rr,  acc[e] += w (V + m_r m_c) S  with w = 1 on the diagonal and 2 off it.
+template <typename T>
+__device__ __forceinline__ void elbo_walk_chunk(const Vec4<T> &v, const Vec4<T> &s, const T *ms, int q, int kp, int r, int c,
+                                                T *acc, T &tr) {
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) {
+        if (q + e < kp) {
+            const T t = fma(ms[r], ms[c], v.v[e]);
+            if (r == c) {
+                tr += v.v[e];
+                acc[e] = fma(t, s.v[e], acc[e]);
+            } else {
+                acc[e] = fma(t + t, s.v[e], acc[e]);
+            }
+        }
+        if (++c > r) {
+            ++r;
+            c = 0;
+        }
+    }
+}
+
+__device__ __forceinline__ double elbo_log_term(double piv, double g) {
+    // log of a pivot of the scaled matrix, and the scale added back; a pivot that is not positive: not positive definite
+    return (piv > 0.0 ? log(piv) : __builtin_nan("")) - 2.0 * log(g);
+}
+
+// Pivots of the symmetric elimination (LDL^T without L) of the matrix held as B[i] = row k0 + i, lane j = column j.
+// The pivot row is always register 0: every update writes row i into register i - 1, as the solver's sweep does; after
+// 8 steps (N / 2 below 16 rows) the live rows are registers 0 .. N - 9 and the same code runs at that width: 2 240 update
+// instructions at 64 rows where a full-width sweep has 4 032 and the triangle 2 016.  Lane k keeps pivot k.
+template <typename T, int N>
+__device__ __forceinline__ void elbo_eliminate(T *B, int k0, int lane, T &piv) {
+    constexpr int STEPS = N > 8 ? 8 : (N > 1 ? N / 2 : 1);
+#pragma unroll 1
+    for (int s = 0; s < STEPS; ++s) {
+        const int k = k0 + s;
+        const T v = B[0];
+        const T d = readlane_dyn(v, k);
+        if (lane == k) piv = d;
+        if constexpr (N > 1) {
+            const T u = v * ((T)1 / d);
+#pragma unroll
+            for (int i = 1; i < N; ++i) B[i - 1] = fma(-readlane_dyn(B[i], k), u, B[i]);
+            B[N - 1] = (T)0;
+        }
+    }
+    if constexpr (N > 1) elbo_eliminate<T, N - STEPS>(B, k0 + STEPS, lane, piv);
+}
+
+// K <= 64: one wavefront per row, the matrix in registers (lane j = column j) as in solve_from_image
+template <typename T, int KR>
+__global__ __launch_bounds__(256) void gauss_elbo_row_reg_kernel(ElboParams<T> p) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t idx = (int64_t)blockIdx.x * 4 + wave;
+    if (idx >= p.n) return;
+    const int64_t row = p.row0 + idx;
+    const int K = p.K, width = p.cov_stride + p.kpad;
+    T *img = reinterpret_cast<T *>(smem_raw) + (int64_t)wave * width;
+    T *ms = img + p.cov_stride;
+    const T *V = p.cov + row * p.cov_stride;
+    const T *m = p.factor + row * p.kpad;
+    for (int k = lane; k < p.kpad; k += 64) ms[k] = m[k];
+    wave_lds_fence();
+    const bool data = p.stats != nullptr && p.ptr[row + 1] > p.ptr[row];
+    const T *S = p.stats ? p.stats + idx * width : nullptr;
+    T acc[PMF_VEC] = {(T)0, (T)0, (T)0, (T)0}, tr = (T)0;
+    for (int q = lane * PMF_VEC; q < p.cov_stride; q += 64 * PMF_VEC) {
+        const Vec4<T> v = load4(V + q);
+        const Vec4<T> s = data ? load4(S + q) : zero4<T>();
+        store4(img + q, v);
+        int r, c;
+        tri_rc(q, r, c);
+        elbo_walk_chunk(v, s, ms, q, p.kp, r, c, acc, tr);
+    }
+    T ess = (acc[0] + acc[1]) + (acc[2] + acc[3]), sq = tr;
+    if (lane < K) {
+        const T mk = ms[lane];
+        sq = fma(mk, mk, sq);
+        if (data) ess = fma((T)-2 * mk, S[p.cov_stride + lane], ess);
+    }
+    ess = group_sum<64>(ess);
+    sq = group_sum<64>(sq);
+    if (data) ess += p.csum[idx];
+    wave_lds_fence();
+    // the matrix, Jacobi-scaled to a unit diagonal; rows and columns >= K are the identity
+    const int j = lane, jc = j < K ? j : 0;
+    T B[KR];
+#pragma unroll
+    for (int i = 0; i < KR; ++i) {
+        const int ic = i < K ? i : 0;
+        const int lo = ic < jc ? ic : jc, hi = ic < jc ? jc : ic;
+        T s = img[hi * (hi + 1) / 2 + lo];
+        if (!(i < K && j < K)) s = (i == j) ? (T)1 : (T)0;
+        B[i] = s;
+    }
+    T diag = (T)1;
+#pragma unroll
+    for (int i = 0; i < KR; ++i) {
+        const T dii = readlane_dyn(B[i], i);
+        if (j == i) diag = dii;
+    }
+    const T g = (T)1 / sqrt(diag);
+#pragma unroll
+    for (int i = 0; i < KR; ++i) B[i] = B[i] * g * readlane_dyn(g, i);
+    T piv = (T)1;
+    elbo_eliminate<T, KR>(B, 0, lane, piv);
+    double ld = lane < K ? elbo_log_term((double)piv, (double)g) : 0.0;
+    ld = group_sum<64>(ld);
+    if (lane == 0) {
+        double *o = p.out + row * PMF_ELBO_TERMS;
+        const T b = p.bias ? p.bias[row] : (T)0;
+        o[PMF_ELBO_SQNORM] = (double)sq;
+        o[PMF_ELBO_LOGDET] = ld;
+        o[PMF_ELBO_BIAS_SQ] = (double)(b * b);
+        o[PMF_ELBO_ESS] = data ? (double)ess : 0.0;
+    }
+}
+
+// sum over the 256 threads of a block, the four wavefronts' sums added in order; every thread gets it
+template <typename T>
+__device__ __forceinline__ T elbo_block_sum(T x, T *red) {
+    x = group_sum<64>(x);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// K > 64: one block per row, the packed lower triangle in LDS -- or, where it does not fit the CU's 160 KB (`scratch`
+// != null: fp64 at large K), in the block's own slice of a global scratch buffer, as gauss_solve_lds_kernel does.
+template <typename T>
+__global__ __launch_bounds__(256) void gauss_elbo_row_lds_kernel(ElboParams<T> p, T *scratch) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    __shared__ double red_d[4];
+    __shared__ T red_t[4];
+    const int K = p.K, kp = p.kp, width = p.cov_stride + p.kpad;
+    T *lds = reinterpret_cast<T *>(smem_raw);
+    T *A = scratch ? scratch + (int64_t)blockIdx.x * p.cov_stride : lds;   // packed lower triangle
+    T *ms = scratch ? lds : lds + p.cov_stride;                            // [kpad] the row's mean
+    T *g = ms + p.kpad;                                                    // [K] Jacobi scales
+    T *pv = g + K;                                                         // [K] pivots
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int64_t idx = blockIdx.x; idx < p.n; idx += gridDim.x) {
+        const int64_t row = p.row0 + idx;
+        const T *V = p.cov + row * p.cov_stride;
+        const T *m = p.factor + row * p.kpad;
+        __syncthreads();
+        for (int k = tid; k < p.kpad; k += 256) ms[k] = m[k];
+        __syncthreads();
+        const bool data = p.stats != nullptr && p.ptr[row + 1] > p.ptr[row];
+        const T *S = p.stats ? p.stats + idx * width : nullptr;
+        T acc[PMF_VEC] = {(T)0, (T)0, (T)0, (T)0}, tr = (T)0;
+        for (int q = tid * PMF_VEC; q < p.cov_stride; q += 256 * PMF_VEC) {
+            const Vec4<T> v = load4(V + q);
+            const Vec4<T> s = data ? load4(S + q) : zero4<T>();
+            store4(A + q, v);
+            int r, c;
+            tri_rc(q, r, c);
+            elbo_walk_chunk(v, s, ms, q, kp, r, c, acc, tr);
+        }
+        T ess = (acc[0] + acc[1]) + (acc[2] + acc[3]), sq = tr;
+        for (int k = tid; k < K; k += 256) {
+            const T mk = ms[k];
+            sq = fma(mk, mk, sq);
+            if (data) ess = fma((T)-2 * mk, S[p.cov_stride + k], ess);
+        }
+        ess = elbo_block_sum(ess, red_t);
+        sq = elbo_block_sum(sq, red_t);
+        if (data) ess += p.csum[idx];
+        __syncthreads();
+        for (int i = tid; i < K; i += 256) g[i] = (T)1 / sqrt(A[i * (i + 3) / 2]);
+        __syncthreads();
+        for (int e = tid; e < kp; e += 256) {
+            int r, c;
+            tri_rc(e, r, c);
+            A[e] *= g[r] * g[c];
+        }
+        // right-looking elimination on the lower triangle: wavefront w takes rows k + 1 + w, k + 5 + w, ...
+        for (int k = 0; k < K; ++k) {
+            __syncthreads();
+            const T d = A[k * (k + 3) / 2];
+            if (tid == 0) pv[k] = d;
+            const T pinv = (T)1 / d;
+            for (int i = k + 1 + wave; i < K; i += 4) {
+                const T f = A[i * (i + 1) / 2 + k] * pinv;
+                for (int jj = k + 1 + lane; jj <= i; jj += 64)
+                    A[i * (i + 1) / 2 + jj] = fma(-f, A[jj * (jj + 1) / 2 + k], A[i * (i + 1) / 2 + jj]);
+            }
+        }
+        __syncthreads();
+        double ld = 0.0;
+        for (int k = tid; k < K; k += 256) ld += elbo_log_term((double)pv[k], (double)g[k]);
+        ld = elbo_block_sum(ld, red_d);
+        if (tid == 0) {
+            double *o = p.out + row * PMF_ELBO_TERMS;
+            const T b = p.bias ? p.bias[row] : (T)0;
+            o[PMF_ELBO_SQNORM] = (double)sq;
+            o[PMF_ELBO_LOGDET] = ld;
+            o[PMF_ELBO_BIAS_SQ] = (double)(b * b);
+            o[PMF_ELBO_ESS] = data ? (double)ess : 0.0;
+        }
+    }
+}
+
+template <typename T>
+static int launch_elbo_rows(pmf_ctx *ctx, const ElboParams<T> &e) {
+    int rc;
+    if (e.n == 0) return PMF_OK;
+    const int K = ctx->K;
+    if (K <= 64) {
+        const size_t smem = (size_t)4 * (ctx->cov_stride + ctx->kpad) * sizeof(T);
+        hipError_t err = hipSuccess;
+        pmf_with_pow2<8>(K, [&](auto KR) {
+            if (smem > (size_t)48 * 1024 && ctx->elbo_lds_bytes != smem)   // fp64 at K = 64: 67 KB; once per context
+                err = hipFuncSetAttribute((const void *)gauss_elbo_row_reg_kernel<T, KR>,
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            if (err == hipSuccess)
+                hipLaunchKernelGGL((gauss_elbo_row_reg_kernel<T, KR>), dim3((unsigned)((e.n + 3) / 4)), dim3(256), smem,
+                                   ctx->stream, e);
+        });
+        if (err != hipSuccess) {
+            pmf_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", smem, hipGetErrorString(err));
+            return PMF_EHIP;
+        }
+        ctx->elbo_lds_bytes = smem;
+    } else {
+        const size_t mat = (size_t)ctx->cov_stride * sizeof(T), vecs = (size_t)(ctx->kpad + 2 * K) * sizeof(T);
+        const bool in_lds = mat + vecs + 64 <= (size_t)160 * 1024;
+        const unsigned blocks = (unsigned)std::min<int64_t>(e.n, in_lds ? e.n : 1024);
+        T *scratch = nullptr;
+        if (!in_lds) {   // one packed triangle per resident block in global scratch (<= 1024 x 263 KB)
+            if ((rc = pmf_ensure_scratch(ctx, (size_t)blocks * mat))) return rc;
+            scratch = ctx->d_scratch.as<T>();
+        }
+        const size_t smem = in_lds ? mat + vecs : vecs;
+        if (ctx->elbo_lds_bytes != smem) {   // once per context, not once per window (K and the dtype are the context's)
+            hipError_t err = hipFuncSetAttribute((const void *)gauss_elbo_row_lds_kernel<T>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+            if (err != hipSuccess) {
+                pmf_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", smem, hipGetErrorString(err));
+                return PMF_EHIP;
+            }
+            ctx->elbo_lds_bytes = smem;
+        }
+        hipLaunchKernelGGL((gauss_elbo_row_lds_kernel<T>), dim3(blocks), dim3(256), smem, ctx->stream, e, scratch);
+    }
+    PMF_HIP_CHECK(hipGetLastError());
+    return PMF_OK;
+}
+
+// rows of one statistics window
+template <typename T>
+static int64_t elbo_window_rows(const pmf_ctx *ctx) {
+    const int64_t by_bytes = std::max<int64_t>(1, kElboStatsBytes / ((int64_t)(ctx->cov_stride + ctx->kpad) * (int64_t)sizeof(T)));
+    return ctx->elbo_rows > 0 ? std::min(ctx->elbo_rows, by_bytes) : by_bytes;
+}
+
+// the side's Gaussian tasks grouped by row window (built once per set of ratings)
+static int ensure_elbo_tasks(pmf_ctx *ctx, int side, int64_t win_rows) {
+    PmfSideIndex &ix = ctx->index[side];
+    if (!ix.elbo_bounds.empty()) return PMF_OK;
+    const int64_t rows = ctx->rows[side];
+    std::vector<int64_t> bounds;
+    for (int64_t r = 0; r < rows; r += win_rows) bounds.push_back(r);
+    bounds.push_back(rows);
+    std::vector<PmfTask> tasks;
+    std::vector<PmfSplitRow> split;
+    PmfTaskList tl;
+    pmf_build_tasks(ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAUSS_CHUNK), false, bounds, tasks, split, tl.n_slots, tl.task_off,
+                    tl.split_off);
+    tl.n_tasks = (int64_t)tasks.size();
+    tl.n_split = (int64_t)split.size();
+    for (const PmfTask &t : tasks) tl.max_len = std::max(tl.max_len, t.len);
+    int rc;
+    if ((rc = tl.d_tasks.alloc(ctx, tasks.size() * sizeof(PmfTask)))) return rc;
+    if ((rc = tl.d_split.alloc(ctx, split.size() * sizeof(PmfSplitRow)))) return rc;
+    if (!tasks.empty())
+        PMF_HIP_CHECK(hipMemcpy(tl.d_tasks.as(), tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
+    if (!split.empty())
+        PMF_HIP_CHECK(hipMemcpy(tl.d_split.as(), split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
+    ix.elbo_tasks = std::move(tl);
+    ix.elbo_bounds.swap(bounds);
+    return PMF_OK;
+}
+
+template <typename T>
+static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals, double *per_row) {
+    const int other = 1 - side;
+    const int64_t rows = ctx->rows[side];
+    const int cs = ctx->cov_stride, kpad = ctx->kpad, width = cs + kpad;
+    const bool bias = pmf_has_bias(ctx);
+    PmfSideIndex &ix = ctx->index[side];
+    PmfBuf d_out, d_win, d_c, d_cpart;
+    int rc;
+    if ((rc = d_out.alloc(ctx, (size_t)rows * PMF_ELBO_TERMS * sizeof(double)))) return rc;
+    ElboParams<T> e;
+    e.stats = nullptr;
+    e.csum = nullptr;
+    e.ptr = nullptr;
+    e.cov = ctx->arr[side][PMF_ARR_COV].as<const T>();
+    e.factor = ctx->arr[side][PMF_ARR_FACTOR].as<const T>();
+    e.bias = bias ? ctx->arr[side][PMF_ARR_BIAS].as<const T>() : nullptr;
+    e.out = d_out.as<double>();
+    e.K = ctx->K;
+    e.kpad = kpad;
+    e.kp = ctx->kp;
+    e.cov_stride = cs;
+    if (!with_data) {
+        e.row0 = 0;
+        e.n = rows;
+        PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SOLVE);
+        if ((rc = launch_elbo_rows<T>(ctx, e))) return rc;
+    } else {
+        const int64_t win_rows = std::min(elbo_window_rows<T>(ctx), rows);
+        if ((rc = ensure_elbo_tasks(ctx, side, win_rows))) return rc;
+        const PmfTaskList &tl = ix.elbo_tasks;
+        if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * width * sizeof(T)))) return rc;
+        if ((rc = d_cpart.alloc(ctx, (size_t)tl.n_slots * sizeof(T)))) return rc;
+        if ((rc = d_win.alloc(ctx, (size_t)win_rows * width * sizeof(T)))) return rc;
+        if ((rc = d_c.alloc(ctx, (size_t)win_rows * sizeof(T)))) return rc;
+        GaussParams<T> p;
+        p.other = ix.d_other.as<int32_t>();
+        p.val = ix.d_val.as<const T>();
+        p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
+        p.cov_other = ctx->arr[other][PMF_ARR_COV].as<const T>();
+        p.hot = ix.d_other_hot.as<uint8_t>();
+        p.bias_self = bias ? ctx->arr[side][PMF_ARR_BIAS].as<const T>() : nullptr;
+        p.bias_other = bias ? ctx->arr[other][PMF_ARR_BIAS].as<const T>() : nullptr;
+        p.partial = ctx->d_partial.as<T>();
+        p.dst_s_stride = width;
+        p.dst_w_stride = width;
+        p.K = ctx->K;
+        p.kpad = kpad;
+        p.kp = ctx->kp;
+        p.cov_stride = cs;
+        e.stats = d_win.as<const T>();
+        e.csum = d_c.as<const T>();
+        e.ptr = ix.d_ptr.as<const int64_t>();
+        for (size_t w = 0; w + 1 < ix.elbo_bounds.size(); ++w) {
+            const int64_t r0 = ix.elbo_bounds[w], n = ix.elbo_bounds[w + 1] - r0;
+            const int64_t nt = tl.task_off[w + 1] - tl.task_off[w], ns = tl.split_off[w + 1] - tl.split_off[w];
+            // (the window is not zeroed: every row with a rating is written whole by its task or by the combine, and
+            //  the row kernel does not read the statistics or c_r of a row without ratings)
+            // tasks carry the row's id in the side: the window's row r0 is the buffer's row 0
+            p.tasks = tl.d_tasks.as<PmfTask>() + tl.task_off[w];
+            p.n_tasks = nt;
+            p.split = tl.d_split.as<PmfSplitRow>() + tl.split_off[w];
+            p.dst_s = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(d_win.as<T>()) - (uintptr_t)r0 * width * sizeof(T));
+            p.dst_w = p.dst_s + cs;
+            if (nt > 0) {
+                PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_ACCUM);
+                if (std::is_same<T, float>::value && !ctx->gauss_generic && ctx->K <= 128) {
+                    if constexpr (std::is_same<T, float>::value) launch_accum_mfma_fp32(ctx, p, nt, false, 0.f, 0.f);
+                } else {
+                    launch_accum_generic(ctx, p, nt, false, (T)0, (T)0);
+                }
+            }
+            if (ns > 0) {
+                PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
+                hipLaunchKernelGGL((gauss_combine_kernel<T>), dim3((unsigned)ns), dim3(256), 0, ctx->stream, p);
+            }
+            PMF_HIP_CHECK(hipGetLastError());
+            PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SOLVE);
+            if (nt > 0) {
+                ElboSqParams<T> q;
+                q.tasks = p.tasks;
+                q.n_tasks = nt;
+                q.other = p.other;
+                q.val = p.val;
+                q.bias_self = p.bias_self;
+                q.bias_other = p.bias_other;
+                q.partial = d_cpart.as<T>();
+                q.csum = d_c.as<T>();
+                q.row0 = r0;
+                hipLaunchKernelGGL((gauss_elbo_sq_kernel<T>), dim3((unsigned)((nt + 15) / 16)), dim3(256), 0, ctx->stream, q);
+            }
+            if (ns > 0)
+                hipLaunchKernelGGL((gauss_elbo_sq_split_kernel<T>), dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream,
+                                   p.split, ns, d_cpart.as<const T>(), d_c.as<T>(), r0);
+            PMF_HIP_CHECK(hipGetLastError());
+            e.row0 = r0;
+            e.n = n;
+            if ((rc = launch_elbo_rows<T>(ctx, e))) return rc;
+        }
+    }
+    // per-row terms to the host; the totals are their sums in row order, whatever the windows were
+    std::vector<double> host;
+    double *dst = per_row;
+    if (!dst) {
+        host.resize((size_t)rows * PMF_ELBO_TERMS);
+        dst = host.data();
+    }
+    PMF_HIP_CHECK(hipMemcpyAsync(dst, d_out.as(), (size_t)rows * PMF_ELBO_TERMS * sizeof(double), hipMemcpyDeviceToHost,
+                                 ctx->stream));
+    PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    double sum[PMF_ELBO_TERMS] = {};
+    for (int64_t r = 0; r < rows; ++r)
+        for (int t = 0; t < PMF_ELBO_TERMS; ++t) sum[t] += dst[r * PMF_ELBO_TERMS + t];
+    std::copy_n(sum, PMF_ELBO_TERMS, totals);
+    return PMF_OK;
+}
+
+extern "C" int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, double *totals, double *per_row) {
+    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "pmf_gauss_elbo_terms: null context");
+    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, "pmf_gauss_elbo_terms: bad side %d", side);
+    PMF_REQUIRE(totals, PMF_EINVAL, "pmf_gauss_elbo_terms: null totals");
+    // (a guard only: pmf_ctx_create refuses n_factors > 256, so no context reaches this)
+    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_elbo_terms: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
+    int rc;
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_elbo_terms"))) return rc;
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_elbo_terms"))) return rc;
+    if (with_data) {
+        if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_FACTOR, "pmf_gauss_elbo_terms"))) return rc;
+        if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_COV, "pmf_gauss_elbo_terms"))) return rc;
+        PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gauss_elbo_terms: ratings have not been set");
+    }
+    PMF_HIP_CHECK(hipSetDevice(ctx->device));
+    try {  // host containers may throw: nothing propagates across the C boundary
+        return pmf_with_dtype(ctx, [&](auto t) { return run_elbo_terms<decltype(t)>(ctx, side, with_data != 0, totals, per_row); });
+    } catch (const std::bad_alloc &) {
+        pmf_set_error("pmf_gauss_elbo_terms: out of host memory");
+        return PMF_ENOMEM;
+    }
+}

@@ -137,6 +137,10 @@ struct PmfSideIndex {
     PmfTaskList gauss_tasks;     // chunk = PMF_GAUSS_CHUNK, empty rows excluded
     PmfTaskList bias_tasks;      // chunk <= PMF_GAMMA_CHUNK, empty rows excluded
     PmfTaskList sgd_tasks;       // chunk = PMF_SGD_CHUNK exactly (the gradient mode is defined by it), empty rows excluded
+    // pmf_gauss_elbo_terms: the Gaussian list again (same task length, same cuts), grouped by the row windows of
+    // elbo_bounds instead of the row chunks.  Built on the first call with a data term; goes with the ratings.
+    PmfTaskList elbo_tasks;
+    std::vector<int64_t> elbo_bounds;   // [n_windows + 1] first row of every window; empty = not built
     // Gaussian gather cache policy (PMF_GAUSS_HOT_MB; fp32, K <= 64): this side's most-rated rows, as many as fit
     // the budget, most-rated first (ties: lower id first) ...
     std::vector<int32_t> h_hot;
@@ -197,6 +201,8 @@ struct pmf_ctx {
     int topk_stage_buffers = 0;    // PMF_TOPK_STAGE_BUFFERS=1|2 pins the fused kernel's stage buffering (0: by residency)
     bool topk_two_phase = false;   // PMF_TOPK_TWO_PHASE: score matrix in HBM + select instead of the fused kernel
     int64_t fold_in_rows = 0;      // PMF_FOLD_IN_ROWS=n caps the rows of one block of pmf_gauss_fold_in (tests: many blocks on a small batch; 0: by scratch size)
+    int64_t elbo_rows = 0;         // PMF_ELBO_ROWS=n caps the rows of one statistics window of pmf_gauss_elbo_terms (tests: many windows on a small problem; 0: by scratch size)
+    size_t elbo_lds_bytes = 0;     // dynamic LDS size the ELBO row kernel of this context's K and dtype has been allowed (0: not yet asked)
     int task_chunk = 0;            // PMF_TASK_CHUNK=n (power of two in [32, 512]) fixes the task length of the gamma / Gaussian / bias lists (tests: long tasks on small problems; 0: by nnz)
 
     // multi-GPU (pmf_comm.hip): the communicator (shared between contexts of one process, refcounted)

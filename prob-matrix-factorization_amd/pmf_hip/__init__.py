@@ -32,6 +32,7 @@ TRANSPORT_RCCL, TRANSPORT_HOSTSHM = 0, 1
 OP_SUM, OP_MAX = 0, 1
 EXCHANGE = {"auto": 0, "allreduce": 1, "scatter_gather": 2}
 MAX_LABELS = 32
+ELBO_SQNORM, ELBO_LOGDET, ELBO_BIAS_SQ, ELBO_ESS, ELBO_TERMS = 0, 1, 2, 3, 4      # columns of pmf_gauss_elbo_terms
 TASK_LISTS = {"gamma": 0, "gauss": 1, "bias": 2, "sgd": 3}
 
 
@@ -82,6 +83,7 @@ SIGNATURES = {
     "pmf_gauss_bias_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),
     "pmf_gauss_fold_in": (C.c_int, [_p, C.c_int, C.c_int64, _i64p, _i32p, _f64p, C.c_double, C.c_double, C.c_double, C.c_int,
                                     _f64p, _f64p, _f64p]),
+    "pmf_gauss_elbo_terms": (C.c_int, [_p, C.c_int, C.c_int, _f64p, _f64p]),
     "pmf_ctx_cov_stride": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "pmf_gauss_factor_accumulate": (C.c_int, [_p, C.c_int, _p]),
     "pmf_gauss_factor_finalize": (C.c_int, [_p, C.c_int, _p, C.c_double, C.c_double]),

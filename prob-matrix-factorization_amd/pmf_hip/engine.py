@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import (ARR_COV, EXCHANGE, F32, F64, ITEM, KERNEL_NAMES, MAX_LABELS, OP_MAX, OP_SUM, TASK_LISTS, TEST_LIB_PATH,
+from . import (ARR_COV, ELBO_TERMS, EXCHANGE, F32, F64, ITEM, KERNEL_NAMES, MAX_LABELS, OP_MAX, OP_SUM, TASK_LISTS, TEST_LIB_PATH,
                UNIQUE_ID_BYTES, USER, PmfError, PmfLibraryError, as_f64, as_i32, check, load, ptr)
 
 
@@ -268,6 +268,16 @@ class Context:
                                           ptr(cov, C.c_double) if want_cov else None, ptr(bias, C.c_double)),
               "pmf_gauss_fold_in")
         return factor, cov, bias
+
+    def gauss_elbo_terms(self, side, with_data=False, per_row=False):
+        """The sums of `side` the Gaussian ELBO is assembled from (`pmf_gauss_elbo_terms`; columns `pmf_hip.ELBO_*`):
+        the totals [ELBO_TERMS] as float64 and, when asked, the (rows, ELBO_TERMS) per-row array as well.  The ESS column
+        is the data term and is zero unless `with_data`.  The context is only read."""
+        totals = np.zeros(ELBO_TERMS, dtype=np.float64)
+        rows = np.zeros((self.rows(side), ELBO_TERMS), dtype=np.float64) if per_row else None
+        check(self._lib.pmf_gauss_elbo_terms(self._h, side, int(bool(with_data)), ptr(totals, C.c_double),
+                                             ptr(rows, C.c_double) if per_row else None), "pmf_gauss_elbo_terms")
+        return (totals, rows) if per_row else totals
 
     # ---- Gaussian MAP by gradient steps (no reference counterpart) -------
     def gauss_sgd_sweep(self, side, lr, sigma2, eta2, eta_bias2=1.0):

@@ -11,7 +11,37 @@ import numpy as np
 
 from src.evaluation.metrics import macro_mae, rmse
 from src.models._device_model import ITEM, USER, DeviceModel, frame_arrays
-from pmf_hip import ARR_BIAS, ARR_COV, ARR_FACTOR, dist as pdist
+from pmf_hip import ARR_BIAS, ARR_COV, ARR_FACTOR, ELBO_BIAS_SQ, ELBO_ESS, ELBO_LOGDET, ELBO_SQNORM, dist as pdist
+
+
+def elbo_from_terms(user_terms, item_terms, user_counts, item_counts, n_ratings, n_factors, sigma2, eta_theta2, eta_beta2,
+                    eta_bias2=None, data_side=USER):
+    """The evidence lower bound of a Gaussian CAVI model from the sums `pmf_gauss_elbo_terms` returns (include/pmf_hip.h
+    has the definition): `user_terms` / `item_terms` are the two sides' total vectors (columns `pmf_hip.ELBO_*`),
+    `user_counts` / `item_counts` the ratings per row of each side (their lengths are the row counts), `eta_bias2=None`
+    the bias-free model.  The data term takes the ESS entry of `data_side`; either side's gives the same sum.  Pure
+    host arithmetic in float64.  Returns (L, parts): parts names the data term and, per block of q, the expected log
+    prior and the entropy; the parts add up to L."""
+    terms = (np.asarray(user_terms, dtype=np.float64), np.asarray(item_terms, dtype=np.float64))
+    counts = (np.asarray(user_counts, dtype=np.float64), np.asarray(item_counts, dtype=np.float64))
+    K, two_pi = int(n_factors), 2.0 * np.pi
+    ess = float(terms[data_side][ELBO_ESS])
+    parts = {}
+    if eta_bias2 is not None:
+        var = [1.0 / (1.0 / eta_bias2 + n / sigma2) for n in counts]       # gaussian_mf_cavi_bias.py:222 / :253
+        ess += sum(float(np.sum(n * v)) for n, v in zip(counts, var))
+    parts["data"] = -0.5 * n_ratings * np.log(two_pi * sigma2) - ess / (2.0 * sigma2)
+    for name, t, n, eta2 in (("theta", terms[0], counts[0], eta_theta2), ("beta", terms[1], counts[1], eta_beta2)):
+        rk = len(n) * K
+        parts["prior_" + name] = -0.5 * rk * np.log(two_pi * eta2) - float(t[ELBO_SQNORM]) / (2.0 * eta2)
+        parts["entropy_" + name] = 0.5 * rk * (1.0 + np.log(two_pi)) + 0.5 * float(t[ELBO_LOGDET])
+    if eta_bias2 is not None:
+        for name, t, v in (("user_bias", terms[0], var[0]), ("item_bias", terms[1], var[1])):
+            parts["prior_" + name] = (-0.5 * len(v) * np.log(two_pi * eta_bias2)
+                                      - (float(t[ELBO_BIAS_SQ]) + float(np.sum(v))) / (2.0 * eta_bias2))
+            parts["entropy_" + name] = 0.5 * float(np.sum(1.0 + np.log(two_pi * v)))
+    parts = {k: float(v) for k, v in parts.items()}
+    return float(sum(parts.values())), parts
 
 
 @dataclass
@@ -38,6 +68,7 @@ class GaussianHost(DeviceModel):
         super().__init__(config, dtype, device, comm, presharded)
         self.m_theta = self.m_beta = None
         self._V_theta = self._V_beta = None
+        self._elbo_counts = None     # (ratings per user, per item) of the last single-process fit
         self.global_mean = 0.0
         if self._uses_bias:
             self.m_user_bias = self.m_item_bias = None
@@ -143,13 +174,28 @@ class GaussianHost(DeviceModel):
         pdist.gaussian_iteration(ctx, self._comm, None, None, cfg.sigma2, cfg.eta_theta2,
                                  cfg.eta_beta2, cfg.eta_bias2 if self._uses_bias else None)
 
-    def fit(self, train_df, val_df=None, global_mean=0.0):
+    def fit(self, train_df, val_df=None, global_mean=0.0, *, track_elbo=False, elbo_tol=None):
+        """`track_elbo`: evaluate the evidence lower bound after every iteration (`history_["elbo"]`; about 1.3
+        accumulates of the user side more per iteration).  `elbo_tol` (implies `track_elbo`): stop when the relative increase
+        (L_t - L_{t-1}) / |L_{t-1}| falls below it -- an early stop that needs no `val_df`."""
         cfg = self.config
+        track_elbo = bool(track_elbo) or elbo_tol is not None
+        if track_elbo:
+            if not self._has_covariances:
+                raise NotImplementedError(f"{type(self).__name__} keeps point estimates, no covariances: the ELBO is not defined")
+            if self._comm is not None:
+                raise NotImplementedError("track_elbo under a communicator: the ELBO of a sharded fit is not implemented")
         self.global_mean = global_mean
         self._infer_dimensions(train_df)
         self._initialize_variational_params()
         u, i, x = frame_arrays(train_df)
         ctx = self._open_context(u, i, x)
+        self.history_.pop("elbo", None)
+        self._elbo_counts = None
+        if self._comm is None:      # rating counts per row: what `elbo` needs besides the device's sums
+            self._elbo_counts = (np.bincount(u, minlength=self.n_users), np.bincount(i, minlength=self.n_items))
+        if track_elbo:
+            self.history_["elbo"] = []
         ctx.set_array(USER, ARR_FACTOR, self._mine(self.m_theta))
         ctx.set_array(ITEM, ARR_FACTOR, self.m_beta)
         if self._uses_bias:
@@ -163,15 +209,29 @@ class GaussianHost(DeviceModel):
                 print(f"\n{self._iteration_label} {it}/{cfg.max_iter}")
             self._run_iteration(lambda: self._iterate(ctx))
             self._tick(it)
+            elbo_stop = False
+            if track_elbo:
+                self.history_["elbo"].append(self._elbo_of(ctx)[0])
+                if cfg.verbose:
+                    print(f"ELBO: {self.history_['elbo'][-1]:.4f}")
+                if elbo_tol is not None and it > 1:
+                    before, now = self.history_["elbo"][-2:]
+                    elbo_stop = (now - before) / abs(before) < elbo_tol
+            if monitor is not None:    # (before the ELBO stop: every iteration that ran has its validation entries)
+                val_rmse, val_macro_mae = monitor()
+                self._record(val_rmse, val_macro_mae)
+                if cfg.verbose:
+                    if self._uses_bias:
+                        print(f"Validation RMSE: {val_rmse:.4f} | MacroMAE: {val_macro_mae:.4f}")
+                    else:
+                        print(f"Validation RMSE: {val_rmse:.4f}")
+            if elbo_stop:
+                if cfg.verbose:
+                    print("Early stopping: small increase of the ELBO.")
+                self.history_["stopped_early"] = True
+                break
             if monitor is None:
                 continue
-            val_rmse, val_macro_mae = monitor()
-            self._record(val_rmse, val_macro_mae)
-            if cfg.verbose:
-                if self._uses_bias:
-                    print(f"Validation RMSE: {val_rmse:.4f} | MacroMAE: {val_macro_mae:.4f}")
-                else:
-                    print(f"Validation RMSE: {val_rmse:.4f}")
             if previous is not None:
                 improvement = previous - val_rmse
                 if cfg.verbose:
@@ -228,6 +288,26 @@ class GaussianHost(DeviceModel):
         d = sigma2 + ctx.predict_var(u, i)
         e = y - ctx.predict(u, i, use_bias=self._uses_bias, offset=global_mean)
         return float(np.sum(-0.5 * np.log(2.0 * np.pi * d) - e * e / (2.0 * d)))
+
+    # ---- evidence lower bound (extension: the reference never evaluates its objective) ----
+    def _elbo_of(self, ctx):
+        cfg = self.config
+        user = ctx.gauss_elbo_terms(USER, with_data=True)      # the data term from the user side: its gathers hit the smaller item table
+        item = ctx.gauss_elbo_terms(ITEM, with_data=False)
+        if self._elbo_counts is None:
+            raise NotImplementedError("elbo after a fit under a communicator: the ELBO of a sharded fit is not implemented")
+        nu, ni = self._elbo_counts
+        return elbo_from_terms(user, item, nu, ni, int(nu.sum()), cfg.n_factors, cfg.sigma2, cfg.eta_theta2, cfg.eta_beta2,
+                               cfg.eta_bias2 if self._uses_bias else None)
+
+    def elbo(self, parts=False):
+        """The evidence lower bound of the fitted q on the training ratings, for the config's sigma2 / eta2 (float64):
+        E_q[log p(ratings | theta, beta, biases)] + E_q[log prior] + entropy of q, where q is Gaussian per row with the
+        fitted means and covariances (and, in the bias model, the bias variances the updates imply).  The sums over
+        rows and ratings are formed on the device (`pmf_gauss_elbo_terms`: 1.3 times an accumulate of the user side, DESIGN.md section 4.8);
+        `parts=True` also returns the dict of `elbo_from_terms`."""
+        value, named = self._elbo_of(self._cov_ctx("elbo"))
+        return (value, named) if parts else value
 
     # ---- fold-in of unseen users / items (extension: no reference counterpart as an operation) ----
     def _fold_in(self, what, side, df, n_iter, return_cov):
