@@ -217,7 +217,7 @@ int pmf_gamma_finalize(pmf_ctx *ctx, int side, const void *stats_dev, double sha
  *     S      = sum_j ( COV_other[o_j] + FACTOR_other[o_j] FACTOR_other[o_j]^T )
  *     COV[r] = inv( I/eta2 + S/sigma2 )
  *     FACTOR[r] = (1/sigma2) COV[r] . sum_j FACTOR_other[o_j] (x_j - BIAS_side[r] - BIAS_other[o_j])
- * Rows without ratings keep their mean and covariance.  n_factors <= 256 (PMF_ERANGE above; the reference
+ * Rows without ratings keep their mean and covariance.  n_factors <= 256 (pmf_ctx_create refuses more; the reference
  * has no limit, its grids stop at 70); the MFMA kernels cover K <= 128 in fp32, K > 128 and fp64 run generic ones. */
 int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2);
 /* Bias half-sweep (gaussian_mf_cavi_bias.py:206-232 users, :237-263 items):
@@ -243,7 +243,7 @@ int pmf_gauss_bias_sweep(pmf_ctx *ctx, int side, double sigma2, double eta_bias2
  * are; FACTOR / COV of `side` itself are not needed; never a collective, with or without a communicator.
  * PMF_EINVAL: null context (whatever n_rows is), bad side, n_rows < 0, a null array that is needed, row_ptr[0] != 0
  * or a decreasing row_ptr, a variance <= 0, n_iter < 1, FACTOR or COV of the opposite side not set (named).
- * PMF_ERANGE: an other_ids entry outside the opposite side, or n_factors > 256.  An argument error writes no output
+ * PMF_ERANGE: an other_ids entry outside the opposite side.  An argument error writes no output
  * buffer; n_rows = 0 touches nothing.  Rows are processed in blocks of bounded scratch (PMF_FOLD_IN_ROWS=n, read
  * when the context is created, caps the rows of a block). */
 int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
@@ -280,8 +280,7 @@ int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row
  * and 50M ratings, one call with a data term takes 1.3 times an accumulate of `side`.  Reads the context only: model state, ratings, work lists and the stored validation set stay
  * as they are; never a collective, with or without a communicator.  Needs FACTOR and COV of `side`; with_data != 0
  * also FACTOR and COV of the other side and the ratings.  PMF_EINVAL: null context, bad side, null totals, a missing
- * array (named), with_data without ratings.  (n_factors > 256 would be PMF_ERANGE, but pmf_ctx_create already refuses
- * such a context.)  An argument error writes nothing.  A row
+ * array (named), with_data without ratings.  An argument error writes nothing.  A row
  * whose COV is not positive definite gives NaN in its LOGDET and in that total; the call still returns 0 and the
  * other rows are unaffected. */
 #define PMF_ELBO_SQNORM 0    /* |m_r|^2 + tr V_r */

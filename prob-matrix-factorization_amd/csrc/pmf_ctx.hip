@@ -91,6 +91,15 @@ int pmf_ensure_partial(pmf_ctx *ctx, size_t bytes) { return ctx->d_partial.reser
 int pmf_ensure_scratch(pmf_ctx *ctx, size_t bytes) { return ctx->d_scratch.reserve(ctx, bytes, {ctx->stream}); }
 int pmf_ensure_pinned(pmf_ctx *ctx, size_t bytes) { return ctx->h_pinned.reserve(nullptr, bytes, {ctx->stream}); }
 
+int pmf_allow_dynamic_lds(const void *kernel, size_t bytes) {
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+        pmf_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", bytes, hipGetErrorString(e));
+        return PMF_EHIP;
+    }
+    return PMF_OK;
+}
+
 size_t pmf_array_elems(const pmf_ctx *ctx, int side, int array) {
     size_t rows = (size_t)ctx->rows[side];
     switch (array) {
@@ -407,13 +416,12 @@ PmfTaskView pmf_task_view(const pmf_ctx *ctx, int side, const PmfTaskList &tl, b
     return v;
 }
 
-static int upload_tasks(pmf_ctx *ctx, int side, const std::vector<int64_t> &ptr, int64_t rows, int chunk,
-                        bool keep_empty, PmfTaskList &out) {
+int pmf_upload_tasks(pmf_ctx *ctx, const std::vector<int64_t> &ptr, int64_t rows, int chunk, bool keep_empty,
+                     const std::vector<int64_t> &row_bounds, bool solve_list, PmfTaskList &out) {
     std::vector<PmfTask> tasks;
     std::vector<PmfSplitRow> split;
     int64_t n_slots = 0;
-    pmf_build_tasks(ptr, rows, chunk, keep_empty, chunk_bounds(ctx, side), tasks, split, n_slots, out.task_off,
-                    out.split_off);
+    pmf_build_tasks(ptr, rows, chunk, keep_empty, row_bounds, tasks, split, n_slots, out.task_off, out.split_off);
     out.n_tasks = (int64_t)tasks.size();
     out.n_split = (int64_t)split.size();
     out.n_slots = n_slots;
@@ -424,10 +432,12 @@ static int upload_tasks(pmf_ctx *ctx, int side, const std::vector<int64_t> &ptr,
     if (rc) return rc;
     if (!tasks.empty())
         PMF_HIP_CHECK(hipMemcpy(out.d_tasks.as(), tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
+    if (!split.empty())
+        PMF_HIP_CHECK(hipMemcpy(out.d_split.as(), split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
+    if (!solve_list) return PMF_OK;
     rc = out.d_split_rows.alloc(ctx, split.size() * sizeof(int32_t));
     if (rc) return rc;
     if (!split.empty()) {
-        PMF_HIP_CHECK(hipMemcpy(out.d_split.as(), split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
         std::vector<int32_t> ids(split.size());
         for (size_t k = 0; k < split.size(); ++k) ids[k] = split[k].row;
         PMF_HIP_CHECK(hipMemcpy(out.d_split_rows.as(), ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -460,10 +470,10 @@ static int build_work_lists(pmf_ctx *ctx, int side) {
     // 256: its result is defined in terms of that piece length.  PMF_TASK_CHUNK (ctx->task_chunk) overrides the
     // rule for the other three lists (pmf_task_chunk).
     int rc;
-    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAMMA_CHUNK), true, ix.gamma_tasks))) return rc;
-    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAUSS_CHUNK), false, ix.gauss_tasks))) return rc;
-    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAMMA_CHUNK), false, ix.bias_tasks))) return rc;
-    if ((rc = upload_tasks(ctx, side, ix.h_ptr, rows, PMF_SGD_CHUNK, false, ix.sgd_tasks))) return rc;
+    if ((rc = pmf_upload_tasks(ctx, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAMMA_CHUNK), true, bounds, true, ix.gamma_tasks))) return rc;
+    if ((rc = pmf_upload_tasks(ctx, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAUSS_CHUNK), false, bounds, true, ix.gauss_tasks))) return rc;
+    if ((rc = pmf_upload_tasks(ctx, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAMMA_CHUNK), false, bounds, true, ix.bias_tasks))) return rc;
+    if ((rc = pmf_upload_tasks(ctx, ix.h_ptr, rows, PMF_SGD_CHUNK, false, bounds, true, ix.sgd_tasks))) return rc;
     return PMF_OK;
 }
 

@@ -327,6 +327,20 @@ __global__ __launch_bounds__(256) void gauss_solve_reg_kernel(SolveParams<T> p) 
 
 __device__ __forceinline__ float pair_pad_diag(float inv_sigma2, float inv_eta2) { return (1.f - inv_eta2) / inv_sigma2; }
 
+// the entries at or past kp (the padding rows) of chunk q .. q + 3 of the image: pad_diag on the diagonal, zero off it
+__device__ __forceinline__ void pair_pad_chunk(Vec4<float> &v, int q, int kp, float pad_diag) {
+    if (q + PMF_VEC > kp) {
+#pragma unroll
+        for (int e = 0; e < PMF_VEC; ++e)
+            if (q + e >= kp) {
+                int r, c;
+                tri_rc(q + e, r, c);
+                if (r == c) v.v[e] = pad_diag;
+                else v.v[e] = 0.f;
+            }
+    }
+}
+
 // ---- 64 < K <= 128 on the matrix cores: block sweep, four pivots per step ------------------------------------------
 // The symmetric sweep of the K x K matrix as RANK-4 updates on v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains).  The
 // Jacobi-scaled matrix B (padded to 16 TT rows with the identity) lives in the accumulator tiles of the block's two
@@ -554,15 +568,7 @@ __global__ __launch_bounds__(128, 2) void gauss_solve_pair_kernel(SolveParams<fl
     const float pad_diag = pair_pad_diag(p.inv_sigma2, p.inv_eta2);
     for (int q = threadIdx.x * PMF_VEC; q < PAIR_IMG; q += 128 * PMF_VEC) {
         Vec4<float> v = q < p.cov_stride ? load4(S + q) : zero4<float>();
-        if (q + PMF_VEC > p.kp) {
-#pragma unroll
-            for (int e = 0; e < PMF_VEC; ++e)
-                if (q + e >= p.kp) {
-                    int r, c;
-                    tri_rc(q + e, r, c);
-                    v.v[e] = (r == c) ? pad_diag : 0.f;
-                }
-        }
+        pair_pad_chunk(v, q, p.kp, pad_diag);
         store4(img + q, v);
     }
     wbuf[j] = j < K ? p.src_w[(int64_t)row * p.src_w_stride + j] : 0.f;
@@ -721,15 +727,7 @@ __global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams
     const float pad_diag = pair_pad_diag(inv_sigma2, inv_eta2);
     for (int q = threadIdx.x * PMF_VEC; q < PAIR_IMG; q += 128 * PMF_VEC) {
         Vec4<float> v = zero4<float>();
-        if (FUSE && q + PMF_VEC > p.kp) {
-#pragma unroll
-            for (int e = 0; e < PMF_VEC; ++e)
-                if (q + e >= p.kp) {
-                    int r, cc;
-                    tri_rc(q + e, r, cc);
-                    if (r == cc) v.v[e] = pad_diag;
-                }
-        }
+        if (FUSE) pair_pad_chunk(v, q, p.kp, pad_diag);
         store4(img + q, v);
     }
     __syncthreads();
@@ -815,7 +813,6 @@ __global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams
 // replacement.  The per-rating flags come 64 at a time with the ids and are ballot-ed into one
 // uniform mask; each trip runs the variant of its pair's (hot, hot) case.  Only the load
 // instructions differ: the sums and their order are those of the uniform default policy.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <bool HOT>
 __device__ __forceinline__ float4 gather_ld(const float4 *ptr) {
@@ -1458,12 +1455,12 @@ static void launch_accum_mfma128(pmf_ctx *ctx, const GaussParams<float> &p, dim3
 
 // fp32, K <= 128: the MFMA accumulate kernels.  Returns whether they also solved the rows that are one task (`fuse`:
 // the fused pass sums in place, so dst_s / dst_w are COV / FACTOR).
-static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParams<float> &p, int64_t n_tasks, bool fuse, float is2, float ie2) {
+static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParams<float> &p, bool fuse, float is2, float ie2) {
     if (ctx->K <= 64) {
-        launch_accum_mfma(ctx, p, dim3((unsigned)((n_tasks + 3) / 4)), fuse, is2, ie2, p.dst_s, p.dst_w);
+        launch_accum_mfma(ctx, p, dim3((unsigned)((p.n_tasks + 3) / 4)), fuse, is2, ie2, p.dst_s, p.dst_w);
     } else {  // 64 < K <= 128: one 128-thread block (two wavefronts) per task
         const size_t smem = (size_t)PAIR_LDS_FLOATS * sizeof(float);
-        dim3 g2((unsigned)n_tasks);
+        dim3 g2((unsigned)p.n_tasks);
         const int chunks = ctx->cov_stride / PMF_VEC, nt = ((chunks + 1) / 2 + 63) / 64;
         if (nt <= 9) launch_accum_mfma128<9>(ctx, p, g2, smem, fuse, is2, ie2, p.dst_s, p.dst_w);
         else if (nt <= 13) launch_accum_mfma128<13>(ctx, p, g2, smem, fuse, is2, ie2, p.dst_s, p.dst_w);
@@ -1476,8 +1473,8 @@ static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParams<float> &p, in
 // accumulate kernel.  Returns whether it also solved the rows that are one task (`fuse`, K <= 64: fp64 only -- the
 // fp32 build has no fused generic kernel, so fuse / is2 / ie2 do not apply to it).
 template <typename T>
-static bool launch_accum_generic(pmf_ctx *ctx, const GaussParams<T> &p, int64_t n_tasks, bool fuse, T is2, T ie2) {
-    dim3 grid((unsigned)((n_tasks + 3) / 4));
+static bool launch_accum_generic(pmf_ctx *ctx, const GaussParams<T> &p, bool fuse, T is2, T ie2) {
+    dim3 grid((unsigned)((p.n_tasks + 3) / 4));
     const size_t plain = (size_t)4 * 2 * ctx->kpad * sizeof(T), lds = plain + (size_t)4 * ctx->cov_stride * sizeof(T);
     if constexpr (std::is_same<T, double>::value) {
         if (fuse) {
@@ -1490,6 +1487,54 @@ static bool launch_accum_generic(pmf_ctx *ctx, const GaussParams<T> &p, int64_t 
     hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 0>), grid, dim3(256), plain, ctx->stream, p, (T)0, (T)0,
                        (T *)nullptr, (T *)nullptr);
     return false;
+}
+
+// What the accumulate kernels take from the context: the gathered tables of the other side, `side`'s ratings, hot
+// flags and bias, the partial slots and the geometry.  The caller sets the tasks, the split rows and the destination.
+template <typename T>
+static GaussParams<T> gauss_params(const pmf_ctx *ctx, int side) {
+    const int other = 1 - side;
+    const PmfSideIndex &ix = ctx->index[side];
+    const bool bias = pmf_has_bias(ctx);
+    GaussParams<T> p;
+    p.other = ix.d_other.as<int32_t>();
+    p.val = ix.d_val.as<const T>();
+    p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
+    p.cov_other = ctx->arr[other][PMF_ARR_COV].as<const T>();
+    p.hot = ix.d_other_hot.as<uint8_t>();
+    p.bias_self = bias ? ctx->arr[side][PMF_ARR_BIAS].as<const T>() : nullptr;
+    p.bias_other = bias ? ctx->arr[other][PMF_ARR_BIAS].as<const T>() : nullptr;
+    p.partial = ctx->d_partial.as<T>();
+    p.K = ctx->K;
+    p.kpad = ctx->kpad;
+    p.kp = ctx->kp;
+    p.cov_stride = ctx->cov_stride;
+    return p;
+}
+
+// S and w of p's tasks by the accumulate kernel for the context's K and dtype, then the combine of the `n_split` split
+// rows p.split lists.  `fuse`: the sums go in place (dst_s / dst_w are COV / FACTOR) and the kernel, where it has a fused
+// form, also solves every row that is one task; *solved tells whether it did, so that the caller solves the rest.
+template <typename T>
+static int launch_accumulate(pmf_ctx *ctx, const GaussParams<T> &p, int64_t n_split, bool fuse = false, double sigma2 = 1,
+                             double eta2 = 1, bool *solved = nullptr) {
+    bool did = false;
+    if (p.n_tasks > 0) {
+        PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_ACCUM);
+        const T is2 = (T)(1.0 / sigma2), ie2 = (T)(1.0 / eta2);
+        if (std::is_same<T, float>::value && !ctx->gauss_generic && ctx->K <= 128) {
+            if constexpr (std::is_same<T, float>::value) did = launch_accum_mfma_fp32(ctx, p, fuse, is2, ie2);
+        } else {
+            did = launch_accum_generic(ctx, p, fuse && ctx->K <= 64, is2, ie2);
+        }
+    }
+    if (solved) *solved = did;
+    if (n_split > 0) {
+        PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
+        hipLaunchKernelGGL((gauss_combine_kernel<T>), dim3((unsigned)n_split), dim3(256), 0, ctx->stream, p);
+    }
+    PMF_HIP_CHECK(hipGetLastError());
+    return PMF_OK;
 }
 
 // The fused pass sums in place into COV / FACTOR, the accumulate pass into `stats`.  *fused (fused pass): the kernel
@@ -1511,45 +1556,15 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *sta
     if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * width * sizeof(T)))) return rc;
     if (acc && tl.row1 > tl.row0)  // rows without ratings on this rank contribute zeros
         PMF_HIP_CHECK(hipMemsetAsync((T *)stats + tl.row0 * width, 0, (size_t)(tl.row1 - tl.row0) * width * sizeof(T), ctx->stream));
-    GaussParams<T> p;
+    GaussParams<T> p = gauss_params<T>(ctx, side);
     p.tasks = tl.d_tasks;
     p.n_tasks = tl.n_tasks;
     p.split = tl.d_split;
-    p.other = ix.d_other.as<int32_t>();
-    p.val = ix.d_val.as<const T>();
-    p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
-    p.cov_other = ctx->arr[other][PMF_ARR_COV].as<const T>();
-    p.hot = ix.d_other_hot.as<uint8_t>();
-    const bool bias = pmf_has_bias(ctx);
-    p.bias_self = bias ? ctx->arr[side][PMF_ARR_BIAS].as<const T>() : nullptr;
-    p.bias_other = bias ? ctx->arr[other][PMF_ARR_BIAS].as<const T>() : nullptr;
-    p.partial = ctx->d_partial.as<T>();
     p.dst_s = acc ? (T *)stats : ctx->arr[side][PMF_ARR_COV].as<T>();
     p.dst_s_stride = acc ? width : ctx->cov_stride;
     p.dst_w = acc ? (T *)stats + ctx->cov_stride : ctx->arr[side][PMF_ARR_FACTOR].as<T>();
     p.dst_w_stride = acc ? width : ctx->kpad;
-    p.K = ctx->K;
-    p.kpad = ctx->kpad;
-    p.kp = ctx->kp;
-    p.cov_stride = ctx->cov_stride;
-    bool solved = false;
-    if (tl.n_tasks > 0) {
-        PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_ACCUM);
-        const bool fuse = !acc && !ctx->gauss_unfused;
-        const T is2 = (T)(1.0 / sigma2), ie2 = (T)(1.0 / eta2);
-        if (std::is_same<T, float>::value && !ctx->gauss_generic && ctx->K <= 128) {
-            if constexpr (std::is_same<T, float>::value) solved = launch_accum_mfma_fp32(ctx, p, tl.n_tasks, fuse, is2, ie2);
-        } else {
-            solved = launch_accum_generic(ctx, p, tl.n_tasks, fuse && ctx->K <= 64, is2, ie2);
-        }
-    }
-    if (fused) *fused = solved;
-    if (tl.n_split > 0) {
-        PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
-        hipLaunchKernelGGL((gauss_combine_kernel<T>), dim3((unsigned)tl.n_split), dim3(256), 0, ctx->stream, p);
-    }
-    PMF_HIP_CHECK(hipGetLastError());
-    return PMF_OK;
+    return launch_accumulate<T>(ctx, p, tl.n_split, !acc && !ctx->gauss_unfused, sigma2, eta2, fused);
 }
 
 // the row solver for the context's K and dtype over the rows `sp` names
@@ -1584,16 +1599,24 @@ static int launch_solve(pmf_ctx *ctx, const SolveParams<T> &sp) {
             scratch = ctx->d_scratch.as<T>();
         }
         const size_t smem = in_lds ? mat + vecs : vecs;
-        hipError_t e = hipFuncSetAttribute((const void *)gauss_solve_lds_kernel<T>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) {
-            pmf_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", smem, hipGetErrorString(e));
-            return PMF_EHIP;
-        }
+        if ((rc = pmf_allow_dynamic_lds((const void *)gauss_solve_lds_kernel<T>, smem))) return rc;
         hipLaunchKernelGGL((gauss_solve_lds_kernel<T>), dim3(blocks), dim3(256), smem, ctx->stream, sp, scratch);
     }
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
+}
+
+// the geometry and the two inverse variances of a row solve; the caller sets rows, sources and destinations
+template <typename T>
+static SolveParams<T> solve_params(const pmf_ctx *ctx, double sigma2, double eta2) {
+    SolveParams<T> sp;
+    sp.inv_sigma2 = (T)(1.0 / sigma2);
+    sp.inv_eta2 = (T)(1.0 / eta2);
+    sp.K = ctx->K;
+    sp.kpad = ctx->kpad;
+    sp.kp = ctx->kp;
+    sp.cov_stride = ctx->cov_stride;
+    return sp;
 }
 
 // finalize pass: every row of the selected range from `stats`; fused pass: the rows with ratings (the split rows only
@@ -1608,7 +1631,7 @@ static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *st
     const int width = ctx->cov_stride + ctx->kpad;
     const bool fin = pass == PMF_PASS_FINALIZE;
     const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gauss_tasks, fin);
-    SolveParams<T> sp;
+    SolveParams<T> sp = solve_params<T>(ctx, sigma2, eta2);
     sp.rows = fin ? nullptr : split_rows_only ? tl.d_split_rows : tl.d_nonempty;
     sp.row0 = fin ? tl.row0 : 0;
     sp.n = fin ? tl.row1 - tl.row0 : split_rows_only ? tl.n_split : tl.n_nonempty;
@@ -1618,18 +1641,11 @@ static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *st
     sp.src_w_stride = fin ? width : ctx->kpad;
     sp.cov = ctx->arr[side][PMF_ARR_COV].as<T>();
     sp.factor = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
-    sp.inv_sigma2 = (T)(1.0 / sigma2);
-    sp.inv_eta2 = (T)(1.0 / eta2);
-    sp.K = ctx->K;
-    sp.kpad = ctx->kpad;
-    sp.kp = ctx->kp;
-    sp.cov_stride = ctx->cov_stride;
     return launch_solve<T>(ctx, sp);
 }
 
 extern "C" int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
     PMF_SIDE_ENTRY("pmf_gauss_factor_sweep");
-    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_factor_sweep: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0, PMF_EINVAL, "pmf_gauss_factor_sweep: variances must be positive");
     return pmf_with_dtype(ctx, [&](auto t) {
         using T = decltype(t);
@@ -1649,7 +1665,6 @@ extern "C" int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, dou
 
 extern "C" int pmf_gauss_factor_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
     PMF_SIDE_ENTRY("pmf_gauss_factor_accumulate");
-    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_factor_accumulate: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_factor_accumulate: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_factor_accumulate<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, stats_dev, 1, 1); });
 }
@@ -1657,7 +1672,6 @@ extern "C" int pmf_gauss_factor_accumulate(pmf_ctx *ctx, int side, void *stats_d
 extern "C" int pmf_gauss_factor_finalize(pmf_ctx *ctx, int side, const void *stats_dev, double sigma2,
                                          double eta2) {
     PMF_SIDE_ENTRY("pmf_gauss_factor_finalize");
-    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_factor_finalize: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_factor_finalize: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_factor_solve<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, stats_dev, sigma2, eta2); });
 }
@@ -1720,7 +1734,6 @@ static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double si
 
 extern "C" int pmf_gauss_bias_sweep(pmf_ctx *ctx, int side, double sigma2, double eta_bias2) {
     PMF_SIDE_ENTRY("pmf_gauss_bias_sweep");
-    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_bias_sweep: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     return pmf_with_dtype(ctx, [&](auto t) {
         using T = decltype(t);
         if (side != PMF_SIDE_ITEM || !pmf_comm_active(ctx)) return run_bias<T>(ctx, side, PMF_PASS_FUSED, nullptr, sigma2, eta_bias2);
@@ -1733,7 +1746,6 @@ extern "C" int pmf_gauss_bias_sweep(pmf_ctx *ctx, int side, double sigma2, doubl
 
 extern "C" int pmf_gauss_bias_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
     PMF_SIDE_ENTRY("pmf_gauss_bias_accumulate");
-    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_bias_accumulate: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_bias_accumulate: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_bias<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, stats_dev, 1, 1); });
 }
@@ -1741,7 +1753,6 @@ extern "C" int pmf_gauss_bias_accumulate(pmf_ctx *ctx, int side, void *stats_dev
 extern "C" int pmf_gauss_bias_finalize(pmf_ctx *ctx, int side, const void *stats_dev, double sigma2,
                                        double eta_bias2) {
     PMF_SIDE_ENTRY("pmf_gauss_bias_finalize");
-    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_bias_finalize: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_bias_finalize: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_bias<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, (void *)stats_dev, sigma2, eta_bias2); });
 }
@@ -1784,7 +1795,6 @@ struct FoldInBatch {
 // buffers of this call: the context's model state, index and work lists are only read.
 template <typename T>
 static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
-    const int other = 1 - side;
     const int K = ctx->K, kpad = ctx->kpad, cs = ctx->cov_stride, width = cs + kpad;
     const bool bias = pmf_has_bias(ctx);
     const int chunk = pmf_task_chunk(ctx, PMF_GAUSS_CHUNK);
@@ -1838,40 +1848,21 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
             PMF_HIP_CHECK(hipMemsetAsync(d_s.as(), 0, (size_t)B * cs * sizeof(T), ctx->stream));
             PMF_HIP_CHECK(hipMemsetAsync(d_w.as(), 0, (size_t)B * kpad * sizeof(T), ctx->stream));
         }
-        GaussParams<T> p;
+        GaussParams<T> p = gauss_params<T>(ctx, side);   // over the block's own buffers; no hot flags, and b = 0
         p.tasks = d_tasks.as<PmfTask>();
         p.n_tasks = (int64_t)tasks.size();
         p.split = d_split.as<PmfSplitRow>();
         p.other = d_other.as<int32_t>();
         p.val = d_val.as<const T>();
-        p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
-        p.cov_other = ctx->arr[other][PMF_ARR_COV].as<const T>();
+        p.hot = nullptr;
         p.bias_self = nullptr;
-        p.bias_other = bias ? ctx->arr[other][PMF_ARR_BIAS].as<const T>() : nullptr;
         p.partial = d_partial.as<T>();
         p.dst_s = d_s.as<T>();
         p.dst_s_stride = cs;
         p.dst_w = d_w.as<T>();
         p.dst_w_stride = kpad;
-        p.K = K;
-        p.kpad = kpad;
-        p.kp = ctx->kp;
-        p.cov_stride = cs;
-        p.hot = nullptr;
-        if (p.n_tasks > 0) {
-            PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_ACCUM);
-            if (std::is_same<T, float>::value && !ctx->gauss_generic && K <= 128) {
-                if constexpr (std::is_same<T, float>::value) launch_accum_mfma_fp32(ctx, p, p.n_tasks, false, 0.f, 0.f);
-            } else {
-                launch_accum_generic(ctx, p, p.n_tasks, false, (T)0, (T)0);
-            }
-        }
-        if (!split.empty()) {
-            PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
-            hipLaunchKernelGGL((gauss_combine_kernel<T>), dim3((unsigned)split.size()), dim3(256), 0, ctx->stream, p);
-        }
-        PMF_HIP_CHECK(hipGetLastError());
-        SolveParams<T> sp;
+        if ((rc = launch_accumulate<T>(ctx, p, (int64_t)split.size()))) return rc;
+        SolveParams<T> sp = solve_params<T>(ctx, a.sigma2, a.eta2);
         sp.rows = nullptr;
         sp.row0 = 0;
         sp.n = B;
@@ -1881,12 +1872,6 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         sp.src_w_stride = kpad;
         sp.cov = d_s.as<T>();
         sp.factor = d_w.as<T>();
-        sp.inv_sigma2 = (T)(1.0 / a.sigma2);
-        sp.inv_eta2 = (T)(1.0 / a.eta2);
-        sp.K = K;
-        sp.kpad = kpad;
-        sp.kp = ctx->kp;
-        sp.cov_stride = cs;
         if ((rc = launch_solve<T>(ctx, sp))) return rc;
         if (bias) {
             FoldBiasParams<T> q;
@@ -1938,8 +1923,7 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
 extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
                                  const double *ratings, double sigma2, double eta2, double eta_bias2, int n_iter,
                                  double *out_factor, double *out_cov, double *out_bias) {
-    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "pmf_gauss_fold_in: null context");
-    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, "pmf_gauss_fold_in: bad side %d", side);
+    PMF_SIDE_ENTRY("pmf_gauss_fold_in");
     PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_gauss_fold_in: negative row count");
     if (n_rows == 0) return PMF_OK;
     PMF_REQUIRE(row_ptr && out_factor, PMF_EINVAL, "pmf_gauss_fold_in: null argument");
@@ -1950,7 +1934,6 @@ extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
     PMF_REQUIRE(nnz == 0 || (other_ids && ratings), PMF_EINVAL, "pmf_gauss_fold_in: null argument");
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0 && eta_bias2 > 0, PMF_EINVAL, "pmf_gauss_fold_in: variances must be positive");
     PMF_REQUIRE(n_iter >= 1, PMF_EINVAL, "pmf_gauss_fold_in: n_iter = %d, must be at least 1", n_iter);
-    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_fold_in: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     const int other = 1 - side;
     int rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_fold_in"))) return rc;
@@ -1959,7 +1942,6 @@ extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
         PMF_REQUIRE(other_ids[k] >= 0 && other_ids[k] < ctx->rows[other], PMF_ERANGE,
                     "pmf_gauss_fold_in: id %d at position %lld outside [0, %lld)", other_ids[k], (long long)k,
                     (long long)ctx->rows[other]);
-    PMF_HIP_CHECK(hipSetDevice(ctx->device));
     const FoldInBatch a = {n_rows, row_ptr, other_ids, ratings, sigma2, eta2, eta_bias2, n_iter, out_factor, out_cov, out_bias};
     try {  // host containers may throw: nothing propagates across the C boundary
         return pmf_with_dtype(ctx, [&](auto t) { return run_fold_in<decltype(t)>(ctx, side, a); });
@@ -2250,24 +2232,19 @@ __global__ __launch_bounds__(256) void gauss_elbo_row_lds_kernel(ElboParams<T> p
 
 template <typename T>
 static int launch_elbo_rows(pmf_ctx *ctx, const ElboParams<T> &e) {
-    int rc;
+    int rc = PMF_OK;
     if (e.n == 0) return PMF_OK;
     const int K = ctx->K;
     if (K <= 64) {
         const size_t smem = (size_t)4 * (ctx->cov_stride + ctx->kpad) * sizeof(T);
-        hipError_t err = hipSuccess;
         pmf_with_pow2<8>(K, [&](auto KR) {
             if (smem > (size_t)48 * 1024 && ctx->elbo_lds_bytes != smem)   // fp64 at K = 64: 67 KB; once per context
-                err = hipFuncSetAttribute((const void *)gauss_elbo_row_reg_kernel<T, KR>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (err == hipSuccess)
+                rc = pmf_allow_dynamic_lds((const void *)gauss_elbo_row_reg_kernel<T, KR>, smem);
+            if (rc == PMF_OK)
                 hipLaunchKernelGGL((gauss_elbo_row_reg_kernel<T, KR>), dim3((unsigned)((e.n + 3) / 4)), dim3(256), smem,
                                    ctx->stream, e);
         });
-        if (err != hipSuccess) {
-            pmf_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", smem, hipGetErrorString(err));
-            return PMF_EHIP;
-        }
+        if (rc) return rc;
         ctx->elbo_lds_bytes = smem;
     } else {
         const size_t mat = (size_t)ctx->cov_stride * sizeof(T), vecs = (size_t)(ctx->kpad + 2 * K) * sizeof(T);
@@ -2279,15 +2256,9 @@ static int launch_elbo_rows(pmf_ctx *ctx, const ElboParams<T> &e) {
             scratch = ctx->d_scratch.as<T>();
         }
         const size_t smem = in_lds ? mat + vecs : vecs;
-        if (ctx->elbo_lds_bytes != smem) {   // once per context, not once per window (K and the dtype are the context's)
-            hipError_t err = hipFuncSetAttribute((const void *)gauss_elbo_row_lds_kernel<T>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (err != hipSuccess) {
-                pmf_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", smem, hipGetErrorString(err));
-                return PMF_EHIP;
-            }
-            ctx->elbo_lds_bytes = smem;
-        }
+        // once per context, not once per window (K and the dtype are the context's)
+        if (ctx->elbo_lds_bytes != smem && (rc = pmf_allow_dynamic_lds((const void *)gauss_elbo_row_lds_kernel<T>, smem))) return rc;
+        ctx->elbo_lds_bytes = smem;
         hipLaunchKernelGGL((gauss_elbo_row_lds_kernel<T>), dim3(blocks), dim3(256), smem, ctx->stream, e, scratch);
     }
     PMF_HIP_CHECK(hipGetLastError());
@@ -2309,21 +2280,9 @@ static int ensure_elbo_tasks(pmf_ctx *ctx, int side, int64_t win_rows) {
     std::vector<int64_t> bounds;
     for (int64_t r = 0; r < rows; r += win_rows) bounds.push_back(r);
     bounds.push_back(rows);
-    std::vector<PmfTask> tasks;
-    std::vector<PmfSplitRow> split;
-    PmfTaskList tl;
-    pmf_build_tasks(ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAUSS_CHUNK), false, bounds, tasks, split, tl.n_slots, tl.task_off,
-                    tl.split_off);
-    tl.n_tasks = (int64_t)tasks.size();
-    tl.n_split = (int64_t)split.size();
-    for (const PmfTask &t : tasks) tl.max_len = std::max(tl.max_len, t.len);
+    PmfTaskList tl;   // (no solve list: the ELBO solves nothing)
     int rc;
-    if ((rc = tl.d_tasks.alloc(ctx, tasks.size() * sizeof(PmfTask)))) return rc;
-    if ((rc = tl.d_split.alloc(ctx, split.size() * sizeof(PmfSplitRow)))) return rc;
-    if (!tasks.empty())
-        PMF_HIP_CHECK(hipMemcpy(tl.d_tasks.as(), tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
-    if (!split.empty())
-        PMF_HIP_CHECK(hipMemcpy(tl.d_split.as(), split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
+    if ((rc = pmf_upload_tasks(ctx, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAUSS_CHUNK), false, bounds, false, tl))) return rc;
     ix.elbo_tasks = std::move(tl);
     ix.elbo_bounds.swap(bounds);
     return PMF_OK;
@@ -2331,7 +2290,6 @@ static int ensure_elbo_tasks(pmf_ctx *ctx, int side, int64_t win_rows) {
 
 template <typename T>
 static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals, double *per_row) {
-    const int other = 1 - side;
     const int64_t rows = ctx->rows[side];
     const int cs = ctx->cov_stride, kpad = ctx->kpad, width = cs + kpad;
     const bool bias = pmf_has_bias(ctx);
@@ -2364,21 +2322,9 @@ static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals
         if ((rc = d_cpart.alloc(ctx, (size_t)tl.n_slots * sizeof(T)))) return rc;
         if ((rc = d_win.alloc(ctx, (size_t)win_rows * width * sizeof(T)))) return rc;
         if ((rc = d_c.alloc(ctx, (size_t)win_rows * sizeof(T)))) return rc;
-        GaussParams<T> p;
-        p.other = ix.d_other.as<int32_t>();
-        p.val = ix.d_val.as<const T>();
-        p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
-        p.cov_other = ctx->arr[other][PMF_ARR_COV].as<const T>();
-        p.hot = ix.d_other_hot.as<uint8_t>();
-        p.bias_self = bias ? ctx->arr[side][PMF_ARR_BIAS].as<const T>() : nullptr;
-        p.bias_other = bias ? ctx->arr[other][PMF_ARR_BIAS].as<const T>() : nullptr;
-        p.partial = ctx->d_partial.as<T>();
+        GaussParams<T> p = gauss_params<T>(ctx, side);
         p.dst_s_stride = width;
         p.dst_w_stride = width;
-        p.K = ctx->K;
-        p.kpad = kpad;
-        p.kp = ctx->kp;
-        p.cov_stride = cs;
         e.stats = d_win.as<const T>();
         e.csum = d_c.as<const T>();
         e.ptr = ix.d_ptr.as<const int64_t>();
@@ -2393,19 +2339,7 @@ static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals
             p.split = tl.d_split.as<PmfSplitRow>() + tl.split_off[w];
             p.dst_s = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(d_win.as<T>()) - (uintptr_t)r0 * width * sizeof(T));
             p.dst_w = p.dst_s + cs;
-            if (nt > 0) {
-                PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_ACCUM);
-                if (std::is_same<T, float>::value && !ctx->gauss_generic && ctx->K <= 128) {
-                    if constexpr (std::is_same<T, float>::value) launch_accum_mfma_fp32(ctx, p, nt, false, 0.f, 0.f);
-                } else {
-                    launch_accum_generic(ctx, p, nt, false, (T)0, (T)0);
-                }
-            }
-            if (ns > 0) {
-                PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
-                hipLaunchKernelGGL((gauss_combine_kernel<T>), dim3((unsigned)ns), dim3(256), 0, ctx->stream, p);
-            }
-            PMF_HIP_CHECK(hipGetLastError());
+            if ((rc = launch_accumulate<T>(ctx, p, ns))) return rc;
             PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SOLVE);
             if (nt > 0) {
                 ElboSqParams<T> q;
@@ -2447,11 +2381,8 @@ static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals
 }
 
 extern "C" int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, double *totals, double *per_row) {
-    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "pmf_gauss_elbo_terms: null context");
-    PMF_REQUIRE(side == PMF_SIDE_USER || side == PMF_SIDE_ITEM, PMF_EINVAL, "pmf_gauss_elbo_terms: bad side %d", side);
+    PMF_SIDE_ENTRY("pmf_gauss_elbo_terms");
     PMF_REQUIRE(totals, PMF_EINVAL, "pmf_gauss_elbo_terms: null totals");
-    // (a guard only: pmf_ctx_create refuses n_factors > 256, so no context reaches this)
-    PMF_REQUIRE(ctx->K <= 256, PMF_ERANGE, "pmf_gauss_elbo_terms: the Gaussian path supports n_factors <= 256 (got %d)", ctx->K);
     int rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_elbo_terms"))) return rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_elbo_terms"))) return rc;
@@ -2460,7 +2391,6 @@ extern "C" int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, doubl
         if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_COV, "pmf_gauss_elbo_terms"))) return rc;
         PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gauss_elbo_terms: ratings have not been set");
     }
-    PMF_HIP_CHECK(hipSetDevice(ctx->device));
     try {  // host containers may throw: nothing propagates across the C boundary
         return pmf_with_dtype(ctx, [&](auto t) { return run_elbo_terms<decltype(t)>(ctx, side, with_data != 0, totals, per_row); });
     } catch (const std::bad_alloc &) {

@@ -238,6 +238,9 @@ static inline int64_t pmf_chunk_row0(const pmf_ctx *ctx, int side, int c) {
 void pmf_build_tasks(const std::vector<int64_t> &ptr, int64_t rows, int chunk, bool keep_empty,
                      const std::vector<int64_t> &row_bounds, std::vector<PmfTask> &tasks, std::vector<PmfSplitRow> &split,
                      int64_t &n_slots, std::vector<int64_t> &task_off, std::vector<int64_t> &split_off);
+// pmf_build_tasks into `out` and onto the device.  `solve_list`: also d_split_rows, the ids of the split rows.
+int pmf_upload_tasks(pmf_ctx *ctx, const std::vector<int64_t> &ptr, int64_t rows, int chunk, bool keep_empty,
+                     const std::vector<int64_t> &row_bounds, bool solve_list, PmfTaskList &out);
 // task length of the context's gamma / Gaussian / bias lists: PMF_TASK_CHUNK, or by the rating count, at most `max_chunk`
 int pmf_task_chunk(const pmf_ctx *ctx, int max_chunk);
 // `select` = honour pmf_ctx_select_chunk (accumulate / finalize); fused sweeps pass false
@@ -246,6 +249,8 @@ PmfTaskView pmf_task_view(const pmf_ctx *ctx, int side, const PmfTaskList &tl, b
 int pmf_ensure_partial(pmf_ctx *ctx, size_t bytes);
 int pmf_ensure_scratch(pmf_ctx *ctx, size_t bytes);
 int pmf_ensure_pinned(pmf_ctx *ctx, size_t bytes);
+// allow `kernel` `bytes` of dynamic LDS (past the default limit); PMF_EHIP with the runtime's message if it refuses
+int pmf_allow_dynamic_lds(const void *kernel, size_t bytes);
 size_t pmf_array_elems(const pmf_ctx *ctx, int side, int array);  // device elements
 int pmf_require_array(pmf_ctx *ctx, int side, int array, const char *what);
 int pmf_alloc_array(pmf_ctx *ctx, int side, int array);  // no-op if present (zero-filled)
