@@ -199,6 +199,47 @@ int pmf_gamma_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prio
  * FACTOR and SCALE (the reference `continue`s before recomputing them). */
 int pmf_gamma_ext_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior);
 
+/* Fold-in: the variational parameters of NEW rows of `side` against the fitted opposite side, whose FACTOR stays
+ * frozen.  No reference counterpart as an operation (the reference serves an unseen id by refitting); per row it
+ * restates the reference's own row update -- poisson_mf_cavi.py:135-167 / hpf_cavi.py:126-159 (items: :173-197 /
+ * :162-193) -- `n_iter` times with the other side fixed.  The batch is CSR as for pmf_gauss_fold_in: `row_ptr[n_rows + 1]`
+ * (row_ptr[0] = 0, non-decreasing), `other_ids` / `ratings` [row_ptr[n_rows]] = ids on the opposite side and ratings.
+ * The prior arguments mean what they mean in pmf_gamma_sweep; `rate_prior` is ignored when hierarchical != 0.  For a
+ * row with ratings (o_j, x_j), j = 1 .. n (n may be 0), b_j = FACTOR_other[o_j]:
+ *     rho^0   = init_prior_rate[r], else hyper_shape / hyper_rate_prior          (hierarchical)
+ *     rho^t   = rate_prior for every t                                           (not hierarchical)
+ *     theta^0 = init_factor[r], else shape_prior / rho^0 in every element
+ *     B       = sum_j b_j                                                        (formed once per call)
+ *     for t = 1 .. n_iter:
+ *         rate_j = max(b_j . theta^(t-1), 1e-10)
+ *         s^t = shape_prior + sum_j (x_j / rate_j) b_j * theta^(t-1),    r^t = rho^(t-1) + B,    theta^t = s^t / r^t
+ *         hierarchical:  h^t = hyper_rate_prior + sum_k theta^t_k,   rho^t = hyper_shape / h^t
+ *     out_factor[r] = theta^n_iter, out_shape[r] = s^n_iter, out_rate[r] = r^n_iter,
+ *     out_prior_rate[r] = rho^n_iter, out_hyper_rate[r] = h^n_iter     (the last two: hierarchical only, else not written)
+ * A row without ratings runs the same recursion with empty sums (the reference's empty-row rule).  With `init_factor`
+ * and `init_prior_rate` given the call is a warm start: the known state of an existing row refreshed from new ratings.
+ * One kernel launch covers all n_iter passes of a row block: a row's theta, B, rho and h stay in registers, B is summed
+ * in the first pass only and nothing is written before the end.  A lane group owns a row; a row with more than
+ * PMF_GAMMA_FOLD_LONG ratings (read when the context is created; default in DESIGN.md section 4.9) gets a whole block,
+ * whose groups' partial sums are added in a fixed order: two calls give the same bits, whatever the row blocks are.
+ * Reads the context's model state only: state, ratings, work lists and the stored validation set stay as they are;
+ * FACTOR of `side` itself is not needed; never a collective, with or without a communicator.  The extended Poisson
+ * model (SCALE arrays) is not covered.
+ * PMF_EINVAL: null context (whatever n_rows is), bad side, n_rows < 0, a null array that is needed, row_ptr[0] != 0 or a
+ * decreasing row_ptr, shape_prior <= 0, rate_prior <= 0 when not hierarchical, hyper_shape <= 0 or hyper_rate_prior <= 0
+ * when hierarchical, n_iter < 1, FACTOR of the opposite side not set (named).  PMF_ERANGE: an other_ids entry outside
+ * the opposite side (id and position named).  An argument error writes no output buffer; n_rows = 0 touches nothing.
+ * Rows are processed in blocks of bounded staging (PMF_FOLD_IN_ROWS=n, read when the context is created, caps the rows
+ * of a block of this call and of pmf_gauss_fold_in alike). */
+int pmf_gamma_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
+                      const double *ratings, double shape_prior, double rate_prior, int hierarchical,
+                      double hyper_shape, double hyper_rate_prior, int n_iter,
+                      const double *init_factor /* n_rows x K, may be NULL */,
+                      const double *init_prior_rate /* n_rows, may be NULL; hierarchical only */,
+                      double *out_factor /* n_rows x K */, double *out_shape /* n_rows x K, may be NULL */,
+                      double *out_rate /* n_rows x K, may be NULL */, double *out_prior_rate /* n_rows, may be NULL */,
+                      double *out_hyper_rate /* n_rows, may be NULL */);
+
 /* Multi-GPU form of the same half-sweep (ratings sharded by user range,
  * SURVEY.md section 8e).  `accumulate` writes this rank's raw sums
  * [rows x 2 x Kpad] (shape sums, then rate sums; Kpad from pmf_ctx_kpad) into
@@ -245,7 +286,7 @@ int pmf_gauss_bias_sweep(pmf_ctx *ctx, int side, double sigma2, double eta_bias2
  * or a decreasing row_ptr, a variance <= 0, n_iter < 1, FACTOR or COV of the opposite side not set (named).
  * PMF_ERANGE: an other_ids entry outside the opposite side.  An argument error writes no output
  * buffer; n_rows = 0 touches nothing.  Rows are processed in blocks of bounded scratch (PMF_FOLD_IN_ROWS=n, read
- * when the context is created, caps the rows of a block). */
+ * when the context is created, caps the rows of a block -- of this call and of pmf_gamma_fold_in alike). */
 int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
                       const double *ratings, double sigma2, double eta2, double eta_bias2, int n_iter,
                       double *out_factor /* n_rows x K */, double *out_cov /* n_rows x K x K, may be NULL */,

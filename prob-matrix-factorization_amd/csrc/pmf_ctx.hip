@@ -199,6 +199,7 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
         if (n >= 32 && n <= 512 && (n & (n - 1)) == 0) ctx->task_chunk = n;   // anything else: the nnz rule
     }
     if (const char *fr = getenv("PMF_FOLD_IN_ROWS")) ctx->fold_in_rows = std::max(atoll(fr), 0LL);
+    if (const char *fl = getenv("PMF_GAMMA_FOLD_LONG")) ctx->gamma_fold_long = std::max(atoll(fl), 0LL);
     if (const char *er = getenv("PMF_ELBO_ROWS")) ctx->elbo_rows = std::max(atoll(er), 0LL);
     if (const char *ex = getenv("PMF_COMM_EXCHANGE")) {
         if (!strcmp(ex, "allreduce")) ctx->exchange = PMF_EXCHANGE_ALLREDUCE;
@@ -802,6 +803,23 @@ extern "C" int pmf_get_array(pmf_ctx *ctx, int side, int array, double *host) {
         int64_t nr = std::min(step, rows - r0);
         const char *src = ctx->arr[side][array].as<char>() + r0 * row_bytes;
         PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned.as(), src, (size_t)(nr * row_bytes), hipMemcpyDeviceToHost, ctx->stream));
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        pmf_unpack_rows(ctx, array, ctx->h_pinned.as(), host + r0 * width, nr);
+    }
+    return PMF_OK;
+}
+
+// `rows` rows of a device array laid out like `array` of the model state -> host float64 (the fold-ins' outputs)
+int pmf_fold_in_download(pmf_ctx *ctx, int array, const void *dev, double *host, int64_t rows) {
+    int width, stride, rc;
+    pmf_array_shape(ctx, array, &width, &stride);
+    const int64_t row_bytes = (int64_t)stride * (int64_t)ctx->elem;
+    const int64_t step = std::max<int64_t>(1, kStageBytes / row_bytes);
+    if ((rc = pmf_ensure_pinned(ctx, (size_t)(std::min(step, rows) * row_bytes)))) return rc;
+    for (int64_t r0 = 0; r0 < rows; r0 += step) {
+        const int64_t nr = std::min(step, rows - r0);
+        PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned.as(), (const char *)dev + r0 * row_bytes, (size_t)(nr * row_bytes),
+                                     hipMemcpyDeviceToHost, ctx->stream));
         PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         pmf_unpack_rows(ctx, array, ctx->h_pinned.as(), host + r0 * width, nr);
     }

@@ -10,6 +10,9 @@
 // rating costs exactly one index, one value and one gathered row of HBM traffic.
 // No atomics: rows that exceed one chunk write per-chunk partial sums that a
 // second kernel adds in chunk order, so results are bitwise reproducible.
+#include <algorithm>
+#include <new>
+
 #include "pmf_device.h"
 
 template <typename T>
@@ -290,6 +293,207 @@ __global__ __launch_bounds__(256) void gamma_finalize_all_kernel(GammaParams<T> 
 }
 
 // ---------------------------------------------------------------------------
+// fold-in (pmf_gamma_fold_in): the whole n_iter recursion of NEW rows against the frozen other side
+// ---------------------------------------------------------------------------
+// A fold-in row depends on no other row, so its recursion
+//     s = shape_prior + sum_j (x_j / max(b_j . theta, floor)) b_j * theta,   r = rho + sum_j b_j,   theta = s / r,
+//     h = hyper_rate_prior + sum_k theta_k,   rho = hyper_shape / h                                   (hierarchical)
+// stays with the lanes that own the row: theta, sum_j b_j, the running shape sums, rho and h live in registers from the
+// first pass to the last, sum_j b_j is formed in the first pass only, and nothing is written before the end.  The
+// access shape is gamma_sweep_kernel's (lane c owns elements 4c .. 4c+3, one 16-byte load per lane per gathered row,
+// ids and ratings handed out by __shfl, UN gathers in flight).  Only K values are gathered per rating and every pass
+// after the first finds them in the caches, so a row is not cut into tasks: LONG = false gives each lane group one
+// row whatever its length (256 / LPR rows per block); LONG = true gives one row to a whole block, group g walking the
+// LPR-rating batches g, g + G, ..., for the rows whose serial walk by one group would outlast the rest of the batch.
+template <typename T>
+struct GammaFoldParams {
+    const int32_t *rows;       // [n] rows of the block this launch covers (the short or the long list)
+    int64_t n;
+    const int64_t *ptr;        // [rows of the block + 1] offsets into other / val
+    const int32_t *other;
+    const T *val;
+    const T *factor_other;
+    const T *init_factor;      // [rows][kpad] or null: shape_prior / rho in every element
+    const T *init_prior_rate;  // [rows] or null: hyper_shape / hyper_rate_prior
+    T *factor, *shape, *rate;  // [rows][kpad]
+    T *prior_rate, *hyper_rate;   // [rows], hierarchical only
+    T shape_prior, rate_prior, hyper_shape, hyper_rate_prior;
+    int hierarchical, n_iter, K, kpad;
+};
+
+// what a lane keeps of its row between the passes
+template <typename T>
+struct GammaFoldRow {
+    Vec4<T> theta, shape, rate;
+    T rho, hyper;
+};
+
+template <typename T>
+__device__ __forceinline__ GammaFoldRow<T> gamma_fold_start(const GammaFoldParams<T> &p, int64_t row, int c, bool active) {
+    const int koff = c * PMF_VEC;
+    GammaFoldRow<T> st;
+    st.hyper = (T)0;
+    st.rho = !p.hierarchical ? p.rate_prior : p.init_prior_rate ? p.init_prior_rate[row] : p.hyper_shape / p.hyper_rate_prior;
+    st.shape = st.rate = zero4<T>();
+    if (p.init_factor) {   // (staged with zero pad elements)
+        st.theta = active ? load4(p.init_factor + row * p.kpad + koff) : zero4<T>();
+    } else {
+        const T t0 = p.shape_prior / st.rho;
+#pragma unroll
+        for (int e = 0; e < PMF_VEC; ++e) st.theta.v[e] = (active && koff + e < p.K) ? t0 : (T)0;
+    }
+    return st;
+}
+
+// The ratings [0, n) of one row in batches of LPR, batch `first`, first + step, ...: acc += (x_j / rate_j) b_j * theta and,
+// in the call's first pass (`with_b`), bsum += b_j.  All lanes of the group call it together.
+template <typename T, int LPR>
+__device__ __forceinline__ void gamma_fold_pass(const GammaFoldParams<T> &p, const int32_t *col, const T *val, int64_t n, int first,
+                                                int step, int c, bool active, bool with_b, const Vec4<T> &theta, Vec4<T> &acc,
+                                                Vec4<T> &bsum) {
+    constexpr int UN = LPR < 4 ? LPR : 4;
+    const int koff = c * PMF_VEC;
+    for (int64_t base = (int64_t)first * LPR; base < n; base += (int64_t)step * LPR) {
+        const int cnt = (int)min((int64_t)LPR, n - base);
+        int my_o = 0;
+        T my_x = (T)0;
+        if (c < cnt) {
+            my_o = col[base + c];
+            my_x = val[base + c];
+        }
+        for (int tt = 0; tt < cnt; tt += UN) {
+            int o[UN];
+            T xv[UN];
+            Vec4<T> b[UN];
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                o[q] = __shfl(my_o, tt + q, LPR);   // (lanes past the batch hold id 0: a valid row, loaded and not used)
+                xv[q] = __shfl(my_x, tt + q, LPR);
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q) b[q] = active ? load4(p.factor_other + (int64_t)o[q] * p.kpad + koff) : zero4<T>();
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                if (tt + q < cnt) {
+                    T d = b[q].v[0] * theta.v[0];
+                    d = fma(b[q].v[1], theta.v[1], d);
+                    d = fma(b[q].v[2], theta.v[2], d);
+                    d = fma(b[q].v[3], theta.v[3], d);
+                    d = vmax(group_sum<LPR>(d), (T)PMF_RATE_FLOOR);
+                    const T w = xv[q] / d;
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) {
+                        acc.v[e] += (w * b[q].v[e]) * theta.v[e];
+                        if (with_b) bsum.v[e] += b[q].v[e];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// theta, rho of the next pass from the row's sums (the arithmetic of gamma_finalize_row)
+template <typename T, int LPR>
+__device__ __forceinline__ void gamma_fold_update(const GammaFoldParams<T> &p, int c, bool active, const Vec4<T> &acc,
+                                                  const Vec4<T> &bsum, GammaFoldRow<T> &st) {
+    const int koff = c * PMF_VEC;
+    T esum = (T)0;
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) {
+        const bool ok = active && (koff + e) < p.K;
+        const T s = p.shape_prior + acc.v[e];
+        const T r = st.rho + bsum.v[e];
+        st.shape.v[e] = ok ? s : (T)0;
+        st.rate.v[e] = ok ? r : (T)0;
+        st.theta.v[e] = ok ? s / r : (T)0;
+        esum += st.theta.v[e];
+    }
+    if (p.hierarchical) {
+        st.hyper = p.hyper_rate_prior + group_sum<LPR>(esum);
+        st.rho = p.hyper_shape / st.hyper;
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void gamma_fold_store(const GammaFoldParams<T> &p, int64_t row, int c, bool active, const GammaFoldRow<T> &st) {
+    if (active) {
+        const int64_t at = row * p.kpad + c * PMF_VEC;
+        store4(p.factor + at, st.theta);
+        store4(p.shape + at, st.shape);
+        store4(p.rate + at, st.rate);
+    }
+    if (p.hierarchical && c == 0) {
+        p.prior_rate[row] = st.rho;
+        p.hyper_rate[row] = st.hyper;
+    }
+}
+
+template <typename T, int LPR, bool LONG>
+__global__ __launch_bounds__(256) void gamma_fold_kernel(GammaFoldParams<T> p) {
+    constexpr int G = 256 / LPR;
+    const int c = threadIdx.x % LPR;
+    const int g = threadIdx.x / LPR;
+    const int koff = c * PMF_VEC;
+    const int kpad = p.kpad;
+    const bool active = koff < kpad;
+    if constexpr (!LONG) {
+        const int64_t at = (int64_t)blockIdx.x * G + g;
+        if (at >= p.n) return;
+        const int64_t row = p.rows[at];
+        const int64_t start = p.ptr[row], n = p.ptr[row + 1] - start;
+        const int32_t *col = p.other + start;
+        const T *val = p.val + start;
+        GammaFoldRow<T> st = gamma_fold_start(p, row, c, active);
+        Vec4<T> bsum = zero4<T>();
+        for (int t = 0; t < p.n_iter; ++t) {
+            Vec4<T> acc = zero4<T>();
+            gamma_fold_pass<T, LPR>(p, col, val, n, 0, 1, c, active, t == 0, st.theta, acc, bsum);
+            gamma_fold_update<T, LPR>(p, c, active, acc, bsum, st);
+        }
+        gamma_fold_store(p, row, c, active, st);
+    } else {
+        // One block per row (the grid is the long list exactly: every thread reaches every barrier).  Per pass each
+        // group leaves its partial sums in LDS; after the barrier EVERY group adds the G partials in group order, so
+        // all groups hold the same theta / rho bit for bit without a broadcast; the second barrier keeps the next
+        // pass's partials off the ones still being read.
+        extern __shared__ __align__(16) unsigned char smem_raw[];
+        T *part = reinterpret_cast<T *>(smem_raw);   // [G][kpad] shape partials, then [G][kpad] sum_j b_j partials (first pass)
+        const int64_t row = p.rows[blockIdx.x];
+        const int64_t start = p.ptr[row], n = p.ptr[row + 1] - start;
+        const int32_t *col = p.other + start;
+        const T *val = p.val + start;
+        GammaFoldRow<T> st = gamma_fold_start(p, row, c, active);
+        Vec4<T> bsum = zero4<T>();
+        for (int t = 0; t < p.n_iter; ++t) {
+            Vec4<T> acc = zero4<T>(), bpart = zero4<T>();
+            gamma_fold_pass<T, LPR>(p, col, val, n, g, G, c, active, t == 0, st.theta, acc, bpart);
+            if (active) {
+                store4(part + g * kpad + koff, acc);
+                if (t == 0) store4(part + (G + g) * kpad + koff, bpart);
+            }
+            __syncthreads();
+            acc = zero4<T>();
+            if (active) {
+#pragma unroll 4   // (unrolled whole, G = 32 partials in flight cost 150 registers)
+                for (int s = 0; s < G; ++s) {
+                    const Vec4<T> a = load4(part + s * kpad + koff);
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) acc.v[e] += a.v[e];
+                    if (t == 0) {
+                        const Vec4<T> b = load4(part + (G + s) * kpad + koff);
+#pragma unroll
+                        for (int e = 0; e < PMF_VEC; ++e) bsum.v[e] += b.v[e];
+                    }
+                }
+            }
+            gamma_fold_update<T, LPR>(p, c, active, acc, bsum, st);
+            __syncthreads();
+        }
+        if (g == 0) gamma_fold_store(p, row, c, active, st);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
 struct GammaPriors { double shape = 0, rate = 0; int hierarchical = 0; double hyper_shape = 0, hyper_rate = 0; };
@@ -459,6 +663,189 @@ extern "C" int pmf_gamma_finalize(pmf_ctx *ctx, int side, const void *stats_dev,
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gamma_finalize: null stats buffer");
     const GammaPriors pr = {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior};
     return pmf_with_dtype(ctx, [&](auto t) { return run_gamma<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, false, (void *)stats_dev, pr); });
+}
+
+// ---- fold-in -----------------------------------------------------------------
+// Rows with more than this many ratings take the block-per-row kernel (PMF_GAMMA_FOLD_LONG=n overrides it).
+// Measured on one MI355X (tools/probe_gamma_fold_in.py, K = 64 fp32, n_iter = 10; tables in DESIGN.md section 4.9):
+//  - 256 rows of 2^6 .. 2^16 ratings, nothing else on the chip: the block kernel wins at every length (64 ratings: 0.045
+//    against 0.138 ms; 1024: 0.22 against 2.64 ms; 65536: 11.1 against 167.3 ms).  That sweep has no crossover, because
+//    256 lane groups fill 16 of the 256 CUs: it shows one group's serial walk, 0.26 us per rating and update.
+//  - the batch a threshold is for, 100 000 rows x 50 ratings (1.27 ms) plus ONE long row: with 256 ratings the row
+//    variant alone is faster (1.271 against 1.332 ms), with 512 the long row is the tail (1.85 against 1.35 ms), with
+//    1024 it takes 2.98 against 1.44 ms.  The crossover lies between 256 and 512 ratings for this batch and moves in
+//    proportion to the batch's own kernel time.
+// The tests pin rows of up to 700 ratings to the row variant under the default, so the default is the smallest
+// multiple of 256 above that, not the 512 the second measurement would suggest: a 768-rating row costs a batch of this
+// size about 1 ms more than it would in a block of its own.
+static const int64_t kGammaFoldLongRow = 768;
+static const int64_t kGammaFoldRowBytes = 256ll << 20;   // one [rows][kpad] buffer of a row block
+
+struct GammaFoldBatch {
+    int64_t n_rows;
+    const int64_t *row_ptr;
+    const int32_t *other_ids;
+    const double *ratings;
+    GammaPriors pr;
+    int n_iter;
+    const double *init_factor, *init_prior_rate;
+    double *out_factor, *out_shape, *out_rate, *out_prior_rate, *out_hyper_rate;
+};
+
+// The batch in row blocks of at most PMF_FOLD_IN_BLOCK_NNZ staged ratings (a longer single row still goes), ctx->fold_in_rows
+// rows and kGammaFoldRowBytes per row buffer.  Per block: stage offsets, ids, ratings and start values in the context
+// dtype, list the short and the long rows, one launch of each kernel at most, download.  Everything lives in buffers
+// of this call: the context's model state, index and work lists are only read.
+template <typename T>
+static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
+    const int K = ctx->K, kpad = ctx->kpad;
+    const int lpr = pmf_lanes_per_row(kpad);
+    PMF_REQUIRE(lpr <= 64, PMF_ERANGE, "pmf_gamma_fold_in: unsupported n_factors %d", K);
+    const int64_t long_row = ctx->gamma_fold_long > 0 ? ctx->gamma_fold_long : kGammaFoldLongRow;
+    const int64_t by_bytes = std::max<int64_t>(1, kGammaFoldRowBytes / ((int64_t)kpad * (int64_t)sizeof(T)));
+    const int64_t max_rows = std::min(by_bytes, ctx->fold_in_rows > 0 ? ctx->fold_in_rows : (int64_t)INT32_MAX);
+    const bool hier = a.pr.hierarchical != 0;
+    PmfBuf d_ptr, d_other, d_val, d_list, d_init, d_init_rate, d_factor, d_shape, d_rate, d_prior_rate, d_hyper_rate;
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> list;   // the short rows, then the long rows
+    std::vector<T> val, init, init_rate;
+    int rc;
+    for (int64_t r0 = 0, r1; r0 < a.n_rows; r0 = r1) {
+        int64_t nnz = 0;
+        for (r1 = r0; r1 < a.n_rows && r1 - r0 < max_rows; ++r1) {
+            const int64_t n = a.row_ptr[r1 + 1] - a.row_ptr[r1];
+            if (r1 > r0 && nnz + n > PMF_FOLD_IN_BLOCK_NNZ) break;
+            nnz += n;
+        }
+        const int64_t B = r1 - r0, at = a.row_ptr[r0];
+        ptr.resize((size_t)B + 1);
+        for (int64_t r = 0; r <= B; ++r) ptr[(size_t)r] = a.row_ptr[r0 + r] - at;
+        val.resize((size_t)nnz);
+        for (int64_t k = 0; k < nnz; ++k) val[(size_t)k] = (T)a.ratings[at + k];
+        list.clear();
+        for (int64_t r = 0; r < B; ++r)
+            if (ptr[(size_t)r + 1] - ptr[(size_t)r] <= long_row) list.push_back((int32_t)r);
+        const int64_t n_short = (int64_t)list.size(), n_long = B - n_short;
+        // longest first (as the sweeps' task lists): the lane group with the longest walk starts with the launch
+        const auto longer = [&](int32_t x, int32_t y) { return ptr[(size_t)x + 1] - ptr[(size_t)x] > ptr[(size_t)y + 1] - ptr[(size_t)y]; };
+        if (!std::is_sorted(list.begin(), list.end(), longer)) std::stable_sort(list.begin(), list.end(), longer);
+        for (int64_t r = 0; r < B; ++r)
+            if (ptr[(size_t)r + 1] - ptr[(size_t)r] > long_row) list.push_back((int32_t)r);
+        if (a.init_factor) {
+            init.assign((size_t)B * kpad, (T)0);
+            for (int64_t r = 0; r < B; ++r)
+                for (int k = 0; k < K; ++k) init[(size_t)(r * kpad + k)] = (T)a.init_factor[(r0 + r) * K + k];
+        }
+        if (hier && a.init_prior_rate) {
+            init_rate.resize((size_t)B);
+            for (int64_t r = 0; r < B; ++r) init_rate[(size_t)r] = (T)a.init_prior_rate[r0 + r];
+        }
+        // (the previous block ended with a stream synchronise: nothing queued still reads these buffers)
+        const size_t row_bytes = (size_t)B * kpad * sizeof(T);
+        if ((rc = d_ptr.reserve(ctx, ptr.size() * sizeof(int64_t), {ctx->stream}))) return rc;
+        if ((rc = d_other.reserve(ctx, (size_t)nnz * sizeof(int32_t), {ctx->stream}))) return rc;
+        if ((rc = d_val.reserve(ctx, (size_t)nnz * sizeof(T), {ctx->stream}))) return rc;
+        if ((rc = d_list.reserve(ctx, (size_t)B * sizeof(int32_t), {ctx->stream}))) return rc;
+        if ((rc = d_factor.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
+        if ((rc = d_shape.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
+        if ((rc = d_rate.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
+        if (a.init_factor && (rc = d_init.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
+        if (hier) {
+            if ((rc = d_prior_rate.reserve(ctx, (size_t)B * sizeof(T), {ctx->stream}))) return rc;
+            if ((rc = d_hyper_rate.reserve(ctx, (size_t)B * sizeof(T), {ctx->stream}))) return rc;
+            if (a.init_prior_rate && (rc = d_init_rate.reserve(ctx, (size_t)B * sizeof(T), {ctx->stream}))) return rc;
+        }
+        PMF_HIP_CHECK(hipMemcpy(d_ptr.as(), ptr.data(), ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        PMF_HIP_CHECK(hipMemcpy(d_list.as(), list.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (nnz) {
+            PMF_HIP_CHECK(hipMemcpy(d_other.as(), a.other_ids + at, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+            PMF_HIP_CHECK(hipMemcpy(d_val.as(), val.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
+        }
+        if (a.init_factor) PMF_HIP_CHECK(hipMemcpy(d_init.as(), init.data(), row_bytes, hipMemcpyHostToDevice));
+        if (hier && a.init_prior_rate)
+            PMF_HIP_CHECK(hipMemcpy(d_init_rate.as(), init_rate.data(), (size_t)B * sizeof(T), hipMemcpyHostToDevice));
+        GammaFoldParams<T> p;
+        p.ptr = d_ptr.as<const int64_t>();
+        p.other = d_other.as<const int32_t>();
+        p.val = d_val.as<const T>();
+        p.factor_other = ctx->arr[1 - side][PMF_ARR_FACTOR].as<const T>();
+        p.init_factor = a.init_factor ? d_init.as<const T>() : nullptr;
+        p.init_prior_rate = hier && a.init_prior_rate ? d_init_rate.as<const T>() : nullptr;
+        p.factor = d_factor.as<T>();
+        p.shape = d_shape.as<T>();
+        p.rate = d_rate.as<T>();
+        p.prior_rate = hier ? d_prior_rate.as<T>() : nullptr;
+        p.hyper_rate = hier ? d_hyper_rate.as<T>() : nullptr;
+        p.shape_prior = (T)a.pr.shape;
+        p.rate_prior = (T)a.pr.rate;
+        p.hyper_shape = (T)a.pr.hyper_shape;
+        p.hyper_rate_prior = (T)a.pr.hyper_rate;
+        p.hierarchical = a.pr.hierarchical;
+        p.n_iter = a.n_iter;
+        p.K = K;
+        p.kpad = kpad;
+        pmf_with_pow2<1>(lpr, [&](auto L) {
+            constexpr int G = 256 / L;
+            if (n_short > 0) {
+                PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
+                p.rows = d_list.as<const int32_t>();
+                p.n = n_short;
+                hipLaunchKernelGGL((gamma_fold_kernel<T, L, false>), dim3((unsigned)((n_short + G - 1) / G)), dim3(256), 0, ctx->stream, p);
+            }
+            if (n_long > 0) {
+                PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
+                p.rows = d_list.as<const int32_t>() + n_short;
+                p.n = n_long;
+                hipLaunchKernelGGL((gamma_fold_kernel<T, L, true>), dim3((unsigned)n_long), dim3(256), (size_t)G * 2 * kpad * sizeof(T),
+                                   ctx->stream, p);
+            }
+        });
+        PMF_HIP_CHECK(hipGetLastError());
+        // (every download ends with a stream synchronise: the block's kernels are done with the staging buffers)
+        if ((rc = pmf_fold_in_download(ctx, PMF_ARR_FACTOR, d_factor.as(), a.out_factor + r0 * K, B))) return rc;
+        if (a.out_shape && (rc = pmf_fold_in_download(ctx, PMF_ARR_SHAPE, d_shape.as(), a.out_shape + r0 * K, B))) return rc;
+        if (a.out_rate && (rc = pmf_fold_in_download(ctx, PMF_ARR_RATE, d_rate.as(), a.out_rate + r0 * K, B))) return rc;
+        if (hier && a.out_prior_rate && (rc = pmf_fold_in_download(ctx, PMF_ARR_PRIOR_RATE, d_prior_rate.as(), a.out_prior_rate + r0, B))) return rc;
+        if (hier && a.out_hyper_rate && (rc = pmf_fold_in_download(ctx, PMF_ARR_HYPER_RATE, d_hyper_rate.as(), a.out_hyper_rate + r0, B))) return rc;
+    }
+    return PMF_OK;
+}
+
+extern "C" int pmf_gamma_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
+                                 const double *ratings, double shape_prior, double rate_prior, int hierarchical,
+                                 double hyper_shape, double hyper_rate_prior, int n_iter, const double *init_factor,
+                                 const double *init_prior_rate, double *out_factor, double *out_shape, double *out_rate,
+                                 double *out_prior_rate, double *out_hyper_rate) {
+    PMF_SIDE_ENTRY("pmf_gamma_fold_in");
+    PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_gamma_fold_in: negative row count");
+    if (n_rows == 0) return PMF_OK;
+    PMF_REQUIRE(row_ptr && out_factor, PMF_EINVAL, "pmf_gamma_fold_in: null argument");
+    PMF_REQUIRE(row_ptr[0] == 0, PMF_EINVAL, "pmf_gamma_fold_in: row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
+    for (int64_t r = 0; r < n_rows; ++r)
+        PMF_REQUIRE(row_ptr[r + 1] >= row_ptr[r], PMF_EINVAL, "pmf_gamma_fold_in: row_ptr decreases at row %lld", (long long)r);
+    const int64_t nnz = row_ptr[n_rows];
+    PMF_REQUIRE(nnz == 0 || (other_ids && ratings), PMF_EINVAL, "pmf_gamma_fold_in: null argument");
+    PMF_REQUIRE(shape_prior > 0, PMF_EINVAL, "pmf_gamma_fold_in: shape_prior must be positive");
+    if (hierarchical)
+        PMF_REQUIRE(hyper_shape > 0 && hyper_rate_prior > 0, PMF_EINVAL, "pmf_gamma_fold_in: hyper_shape and hyper_rate_prior must be positive");
+    else
+        PMF_REQUIRE(rate_prior > 0, PMF_EINVAL, "pmf_gamma_fold_in: rate_prior must be positive");
+    PMF_REQUIRE(n_iter >= 1, PMF_EINVAL, "pmf_gamma_fold_in: n_iter = %d, must be at least 1", n_iter);
+    const int other = 1 - side;
+    int rc;
+    if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gamma_fold_in"))) return rc;
+    for (int64_t k = 0; k < nnz; ++k)
+        PMF_REQUIRE(other_ids[k] >= 0 && other_ids[k] < ctx->rows[other], PMF_ERANGE,
+                    "pmf_gamma_fold_in: id %d at position %lld outside [0, %lld)", other_ids[k], (long long)k,
+                    (long long)ctx->rows[other]);
+    const GammaFoldBatch a = {n_rows, row_ptr, other_ids, ratings, {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior},
+                              n_iter, init_factor, init_prior_rate, out_factor, out_shape, out_rate, out_prior_rate, out_hyper_rate};
+    try {  // host containers may throw: nothing propagates across the C boundary
+        return pmf_with_dtype(ctx, [&](auto t) { return run_gamma_fold_in<decltype(t)>(ctx, side, a); });
+    } catch (const std::bad_alloc &) {
+        pmf_set_error("pmf_gamma_fold_in: out of host memory");
+        return PMF_ENOMEM;
+    }
 }
 
 // Profiling aid (no reference counterpart): average device time of `repeats` launches of the

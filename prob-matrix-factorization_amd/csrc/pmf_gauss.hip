@@ -1759,26 +1759,6 @@ extern "C" int pmf_gauss_bias_finalize(pmf_ctx *ctx, int side, const void *stats
 
 // ---- fold-in ---------------------------------------------------------------
 static const int64_t kFoldInStatsBytes = 256ll << 20;   // statistics + partial slots of one row block
-static const int64_t kFoldInBlockNnz = 32ll << 20;      // staged ratings of one row block (a longer single row still goes)
-static const int64_t kFoldInStageBytes = 64ll << 20;    // pinned staging of the download
-
-// `rows` rows of a device array laid out like `array` of the model state -> host float64
-static int fold_in_download(pmf_ctx *ctx, int array, const void *dev, double *host, int64_t rows) {
-    int width, stride, rc;
-    pmf_array_shape(ctx, array, &width, &stride);
-    const int64_t row_bytes = (int64_t)stride * (int64_t)ctx->elem;
-    const int64_t step = std::max<int64_t>(1, kFoldInStageBytes / row_bytes);
-    if ((rc = pmf_ensure_pinned(ctx, (size_t)(std::min(step, rows) * row_bytes)))) return rc;
-    for (int64_t r0 = 0; r0 < rows; r0 += step) {
-        const int64_t nr = std::min(step, rows - r0);
-        PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned.as(), (const char *)dev + r0 * row_bytes, (size_t)(nr * row_bytes),
-                                     hipMemcpyDeviceToHost, ctx->stream));
-        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        pmf_unpack_rows(ctx, array, ctx->h_pinned.as(), host + r0 * width, nr);
-    }
-    return PMF_OK;
-}
-
 struct FoldInBatch {
     int64_t n_rows;
     const int64_t *row_ptr;
@@ -1812,7 +1792,7 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         for (r1 = r0; r1 < a.n_rows && r1 - r0 < max_rows; ++r1) {
             const int64_t n = a.row_ptr[r1 + 1] - a.row_ptr[r1];
             const int64_t u = 1 + (n > chunk ? (n + chunk - 1) / chunk : 0);
-            if (r1 > r0 && (units + u > max_units || nnz + n > kFoldInBlockNnz)) break;
+            if (r1 > r0 && (units + u > max_units || nnz + n > PMF_FOLD_IN_BLOCK_NNZ)) break;
             units += u;
             nnz += n;
             has_empty |= n == 0;
@@ -1901,9 +1881,9 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         double *oc = a.out_cov ? a.out_cov + r0 * (int64_t)K * K : nullptr;
         double *ob = a.out_bias ? a.out_bias + r0 : nullptr;
         // (every download ends with a stream synchronise: the block's kernels are done with the staging buffers)
-        if ((rc = fold_in_download(ctx, PMF_ARR_FACTOR, d_w.as(), of, B))) return rc;
-        if (oc && (rc = fold_in_download(ctx, PMF_ARR_COV, d_s.as(), oc, B))) return rc;
-        if (ob && bias && (rc = fold_in_download(ctx, PMF_ARR_BIAS, d_b.as(), ob, B))) return rc;
+        if ((rc = pmf_fold_in_download(ctx, PMF_ARR_FACTOR, d_w.as(), of, B))) return rc;
+        if (oc && (rc = pmf_fold_in_download(ctx, PMF_ARR_COV, d_s.as(), oc, B))) return rc;
+        if (ob && bias && (rc = pmf_fold_in_download(ctx, PMF_ARR_BIAS, d_b.as(), ob, B))) return rc;
         if (ob && !bias) std::fill_n(ob, (size_t)B, 0.0);
         for (int64_t r = 0; has_empty && r < B; ++r) {
             if (ptr[(size_t)r + 1] > ptr[(size_t)r]) continue;

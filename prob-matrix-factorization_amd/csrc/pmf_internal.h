@@ -200,7 +200,8 @@ struct pmf_ctx {
     int topk_max_blocks = 0;       // PMF_TOPK_MAX_BLOCKS=n caps the fused kernel's persistent grid (tests: many tiles per block)
     int topk_stage_buffers = 0;    // PMF_TOPK_STAGE_BUFFERS=1|2 pins the fused kernel's stage buffering (0: by residency)
     bool topk_two_phase = false;   // PMF_TOPK_TWO_PHASE: score matrix in HBM + select instead of the fused kernel
-    int64_t fold_in_rows = 0;      // PMF_FOLD_IN_ROWS=n caps the rows of one block of pmf_gauss_fold_in (tests: many blocks on a small batch; 0: by scratch size)
+    int64_t fold_in_rows = 0;      // PMF_FOLD_IN_ROWS=n caps the rows of one block of pmf_gauss_fold_in and pmf_gamma_fold_in (tests: many blocks on a small batch; 0: by scratch size)
+    int64_t gamma_fold_long = 0;   // PMF_GAMMA_FOLD_LONG=n: rows of pmf_gamma_fold_in with more than n ratings take the block-per-row kernel (tests: both kernels on small rows; 0: kGammaFoldLongRow)
     int64_t elbo_rows = 0;         // PMF_ELBO_ROWS=n caps the rows of one statistics window of pmf_gauss_elbo_terms (tests: many windows on a small problem; 0: by scratch size)
     size_t elbo_lds_bytes = 0;     // dynamic LDS size the ELBO row kernel of this context's K and dtype has been allowed (0: not yet asked)
     int task_chunk = 0;            // PMF_TASK_CHUNK=n (power of two in [32, 512]) fixes the task length of the gamma / Gaussian / bias lists (tests: long tasks on small problems; 0: by nnz)
@@ -227,6 +228,7 @@ struct pmf_ctx {
 #define PMF_GAMMA_CHUNK 512   // (256 until round 2: 512 halves the split-row slots; HPF K=64 at C3: gamma_final 0.16 -> 0.08 ms)
 #define PMF_SGD_CHUNK 256     // the gradient mode's piece length is part of its definition (include/pmf_hip.h)
 #define PMF_GAUSS_CHUNK 512
+#define PMF_FOLD_IN_BLOCK_NNZ (32ll << 20)   // staged ratings of one row block of the fold-ins (a longer single row still goes)
 #define PMF_GAUSS_HOT_MB_DEFAULT 224   // hot-row budget when PMF_GAUSS_HOT_MB is unset
 
 // first row of chunk c of a side (c = n_chunks gives the row count)
@@ -265,6 +267,9 @@ int pmf_index_device_finish(pmf_ctx *ctx, PmfIndexBuild *b, int64_t nnz);
 // host <-> device layout helpers (pmf_ctx.hip)
 void pmf_array_shape(const pmf_ctx *ctx, int array, int *host_width, int *dev_stride);
 void pmf_unpack_rows(const pmf_ctx *ctx, int array, const void *src, double *dst, int64_t rows);
+// `rows` rows of a device array laid out like `array` of the model state -> host float64, in pinned steps (ends with a
+// stream synchronise)
+int pmf_fold_in_download(pmf_ctx *ctx, int array, const void *dev, double *host, int64_t rows);
 
 // multi-GPU (pmf_comm.hip).  With an attached communicator of more than one rank the ITEM half-sweeps
 // run  accumulate -> all-reduce -> finalize  through pmf_comm_half_sweep.

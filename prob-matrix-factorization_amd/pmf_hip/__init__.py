@@ -76,6 +76,8 @@ SIGNATURES = {
     "pmf_set_cov_identity": (C.c_int, [_p, C.c_int, C.c_double]),
     "pmf_gamma_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]),
     "pmf_gamma_ext_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),
+    "pmf_gamma_fold_in": (C.c_int, [_p, C.c_int, C.c_int64, _i64p, _i32p, _f64p, C.c_double, C.c_double, C.c_int, C.c_double,
+                                    C.c_double, C.c_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
     "pmf_ctx_kpad": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "pmf_gamma_accumulate": (C.c_int, [_p, C.c_int, _p]),
     "pmf_gamma_finalize": (C.c_int, [_p, C.c_int, _p, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]),

@@ -217,6 +217,37 @@ class Context:
         check(self._lib.pmf_gamma_ext_sweep(self._h, side, float(shape_prior), float(rate_prior)),
               "pmf_gamma_ext_sweep")
 
+    def gamma_fold_in(self, side, row_ptr, other_ids, ratings, shape_prior, rate_prior=0.0, hierarchical=False, hyper_shape=0.0,
+                      hyper_rate_prior=0.0, n_iter=10, init_factor=None, init_prior_rate=None, want_params=True):
+        """Variational parameters of new rows of `side` (CSR batch: `row_ptr`, ids on the opposite side, ratings) after
+        `n_iter` row updates against the fitted opposite side (`pmf_gamma_fold_in`; priors as for `gamma_sweep`):
+        (factor [n, K], shape [n, K], rate [n, K], prior_rate [n], hyper_rate [n]) as float64.  `shape` and `rate` are None
+        unless `want_params`, `prior_rate` and `hyper_rate` are None unless `hierarchical`.  `init_factor` [n, K] /
+        `init_prior_rate` [n] warm-start the rows.  The context is only read."""
+        rp = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.int64).reshape(-1))
+        o, x = as_i32(other_ids, "other_ids"), as_f64(ratings)
+        if len(rp) < 1 or len(o) != len(x) or (len(rp) > 1 and rp[-1] != len(o)):
+            raise ValueError("row_ptr must hold n_rows + 1 offsets ending at len(other_ids) == len(ratings)")
+        n = len(rp) - 1
+        init_f = None if init_factor is None else as_f64(init_factor)
+        init_r = None if init_prior_rate is None else as_f64(init_prior_rate)
+        if init_f is not None and init_f.shape != (n, self.K):
+            raise ValueError(f"init_factor: expected shape {(n, self.K)}, got {init_f.shape}")
+        if init_r is not None and init_r.shape != (n,):
+            raise ValueError(f"init_prior_rate: expected shape {(n,)}, got {init_r.shape}")
+        hier = bool(hierarchical)
+        factor = np.zeros((n, self.K), dtype=np.float64)
+        shape = np.zeros((n, self.K), dtype=np.float64) if want_params else None
+        rate = np.zeros((n, self.K), dtype=np.float64) if want_params else None
+        prior_rate = np.zeros(n, dtype=np.float64) if hier else None
+        hyper_rate = np.zeros(n, dtype=np.float64) if hier else None
+        opt = lambda a: None if a is None else ptr(a, C.c_double)
+        check(self._lib.pmf_gamma_fold_in(self._h, side, n, ptr(rp, C.c_int64), ptr(o, C.c_int32), ptr(x, C.c_double),
+                                          float(shape_prior), float(rate_prior), int(hier), float(hyper_shape),
+                                          float(hyper_rate_prior), int(n_iter), opt(init_f), opt(init_r), ptr(factor, C.c_double),
+                                          opt(shape), opt(rate), opt(prior_rate), opt(hyper_rate)), "pmf_gamma_fold_in")
+        return factor, shape, rate, prior_rate, hyper_rate
+
     def gamma_accumulate(self, side, stats_ptr):
         check(self._lib.pmf_gamma_accumulate(self._h, side, C.c_void_p(stats_ptr)), "pmf_gamma_accumulate")
 

@@ -34,6 +34,21 @@ def frame_arrays(df):
             df["rating"].to_numpy(dtype=float))
 
 
+def fold_in_batch(df, side, n_other):
+    """The CSR batch of a fold-in frame (columns u, i, rating; the new rows of `side` carry arbitrary labels in their
+    column): (ids, row_ptr, other_ids, ratings).  `ids` are the labels, sorted; row r of the batch belongs to ids[r].
+    Rows of the frame whose id on the fitted side lies outside [0, n_other) are dropped, as ids the fit has not seen
+    are everywhere else; every row of the batch keeps its ratings in frame order."""
+    new_col, old_col = ("u", "i") if side == USER else ("i", "u")
+    ids, row = np.unique(df[new_col].to_numpy(), return_inverse=True)
+    other = df[old_col].to_numpy(dtype=int)
+    keep = (other >= 0) & (other < n_other)
+    row, other, x = row[keep], other[keep], df["rating"].to_numpy(dtype=float)[keep]
+    order = np.argsort(row, kind="stable")
+    row_ptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=len(ids)))])
+    return ids, row_ptr, other[order], x[order]
+
+
 class DeviceModel:
     """Base of the four CAVI classes.  Subclasses set `_uses_bias`."""
 
@@ -312,4 +327,4 @@ class DeviceModel:
                 setattr(self, name, None)
 
 
-__all__ = ["DeviceModel", "frame_arrays", "USER", "ITEM"]
+__all__ = ["DeviceModel", "frame_arrays", "fold_in_batch", "USER", "ITEM"]

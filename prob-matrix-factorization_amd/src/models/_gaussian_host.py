@@ -10,7 +10,7 @@ from typing import Optional
 import numpy as np
 
 from src.evaluation.metrics import macro_mae, rmse
-from src.models._device_model import ITEM, USER, DeviceModel, frame_arrays
+from src.models._device_model import ITEM, USER, DeviceModel, fold_in_batch, frame_arrays
 from pmf_hip import ARR_BIAS, ARR_COV, ARR_FACTOR, ELBO_BIAS_SQ, ELBO_ESS, ELBO_LOGDET, ELBO_SQNORM, dist as pdist
 
 
@@ -312,16 +312,9 @@ class GaussianHost(DeviceModel):
     # ---- fold-in of unseen users / items (extension: no reference counterpart as an operation) ----
     def _fold_in(self, what, side, df, n_iter, return_cov):
         ctx = self._cov_ctx(what)
-        new_col, old_col = ("u", "i") if side == USER else ("i", "u")
-        n_other = self.n_items if side == USER else self.n_users
-        ids, row = np.unique(df[new_col].to_numpy(), return_inverse=True)
-        other = df[old_col].to_numpy(dtype=int)
-        keep = (other >= 0) & (other < n_other)          # ids the fit has not seen are dropped, as `_seen` does
-        row, other, x = row[keep], other[keep], df["rating"].to_numpy(dtype=float)[keep]
-        order = np.argsort(row, kind="stable")           # every row keeps its ratings in frame order
-        row_ptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=len(ids)))])
+        ids, row_ptr, other, x = fold_in_batch(df, side, self.n_items if side == USER else self.n_users)
         cfg = self.config
-        mean, cov, bias = ctx.gauss_fold_in(side, row_ptr, other[order], x[order], cfg.sigma2,
+        mean, cov, bias = ctx.gauss_fold_in(side, row_ptr, other, x, cfg.sigma2,
                                             cfg.eta_theta2 if side == USER else cfg.eta_beta2,
                                             cfg.eta_bias2 if self._uses_bias else 1.0, n_iter, want_cov=return_cov)
         m_other = self.m_beta if side == USER else self.m_theta

@@ -12,6 +12,7 @@ import numpy as np
 
 from src.evaluation.metrics import macro_mae, rmse
 from src.models._device_model import ITEM, USER, DeviceModel, frame_arrays
+from src.models._gamma_fold_in import gamma_fold_in
 from pmf_hip import ARR_FACTOR, ARR_RATE, ARR_SHAPE, dist as pdist
 
 
@@ -90,6 +91,20 @@ class PoissonMFCAVI(DeviceModel):
         if self.history_["iterations"] > 0:
             self._pull_state()
         return self
+
+    def fold_in_users(self, df, n_iter=10):
+        """Variational parameters of users the fit has not seen, from their ratings of fitted items: `df` has columns
+        u, i, rating; `u` holds arbitrary labels.  The item side stays frozen; each user gets `n_iter` row updates
+        (poisson_mf_cavi.py:135-167) from the prior mean a0 / b0, on the device (`pmf_gamma_fold_in`), without a refit.
+        Rows with an item id the fit has not seen are dropped; a user left without ratings runs the same updates on
+        empty sums.  Returns a `GammaFoldIn`, one row per label in sorted order."""
+        cfg = self.config
+        return gamma_fold_in(self, USER, df, n_iter, (cfg.a0, cfg.b0, False, 0.0, 0.0))
+
+    def fold_in_items(self, df, n_iter=10):
+        """The same for new items (labels in column `i`) against the fitted users (poisson_mf_cavi.py:173-197)."""
+        cfg = self.config
+        return gamma_fold_in(self, ITEM, df, n_iter, (cfg.a0, cfg.b0, False, 0.0, 0.0))
 
     def predict(self, user_ids, item_ids):
         return self._need_ctx().predict(np.asarray(user_ids, dtype=int), np.asarray(item_ids, dtype=int))

@@ -100,6 +100,12 @@ class PoissonMFExtendedCAVI(DeviceModel):
             self._pull_state()
         return self
 
+    def fold_in_users(self, df, n_iter=10):
+        """Not available: `pmf_gamma_fold_in` does not cover the per-row scalar factors phi / psi of this model."""
+        raise NotImplementedError(f"{type(self).__name__} has no fold-in: the device fold-in does not cover the extended model's scalar factors")
+
+    fold_in_items = fold_in_users
+
     def predict(self, user_ids, item_ids):
         return self._need_ctx().predict(np.asarray(user_ids, dtype=int), np.asarray(item_ids, dtype=int),
                                         use_bias=PREDICT_SCALE)
