@@ -240,6 +240,64 @@ int pmf_gamma_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row
                       double *out_rate /* n_rows x K, may be NULL */, double *out_prior_rate /* n_rows, may be NULL */,
                       double *out_hyper_rate /* n_rows, may be NULL */);
 
+/* Evidence lower bound of the Poisson MF and HPF models: the per-row sums that do not depend on the hyperparameters.
+ * No reference counterpart (the reference never evaluates its objective).  q is defined by SHAPE and RATE alone:
+ * q(theta_rk) = Gamma(a_rk, b_rk) with a = SHAPE, b = RATE of `side`; FACTOR is not read -- E_rk = a/b and
+ * Elog_rk = psi(a) - log b are formed from the same two arrays -- and neither is PRIOR_RATE.  With hierarchical != 0,
+ * q(xi_r) = Gamma(kappa, h_r) with h_r = HYPER_RATE[r]; the shape kappa is the caller's (the host adds it).  The call
+ * returns for `side`, per row r and summed over all its rows (with or without ratings), over the ratings (o_j, x_j) of
+ * the row:
+ *     PMF_GAMMA_ELBO_SUM_FACTOR         sum_k a/b
+ *     PMF_GAMMA_ELBO_SUM_ELOG           sum_k psi(a) - log b
+ *     PMF_GAMMA_ELBO_ENTROPY            sum_k a - log b + lgamma(a) + (1 - a) psi(a)
+ *     PMF_GAMMA_ELBO_LOG_HYPER          log h_r
+ *     PMF_GAMMA_ELBO_INV_HYPER          1 / h_r
+ *     PMF_GAMMA_ELBO_FACTOR_OVER_HYPER  (sum_k a/b) / h_r                           (these three: 0 unless hierarchical)
+ *     PMF_GAMMA_ELBO_DATA               sum_j [ x_j lse_j - sum_k E_rk E_{o_j k} ],  lse_j = log sum_k exp(Elog_rk + Elog_{o_j k})
+ *     PMF_GAMMA_ELBO_LOGFACT            sum_j lgamma(x_j + 1)                       (these two: with_data != 0 only, else 0)
+ * lse_j is the data term at its optimal auxiliary multinomial, phi_jk proportional to exp(Elog_rk + Elog_{o_j k}).  The
+ * caller assembles, with DATA - LOGFACT taken from ONE side (either gives the same sum), R rows of a side and K factors:
+ *   Poisson MF, priors (a0, b0), per side:
+ *     R K (a0 log b0 - lgamma a0) + (a0 - 1) SUM_ELOG - b0 SUM_FACTOR + ENTROPY
+ *   HPF, per side, (s, s', r') = (a, a', b') for users and (c, c', d') for items, kappa = s' + K s:
+ *     K s (R psi(kappa) - LOG_HYPER) - R K lgamma(s) + (s - 1) SUM_ELOG - kappa FACTOR_OVER_HYPER + ENTROPY
+ *       + R (s' log r' - lgamma s') + (s' - 1)(R psi(kappa) - LOG_HYPER) - r' kappa INV_HYPER
+ *       + R (kappa + lgamma kappa + (1 - kappa) psi(kappa)) - LOG_HYPER
+ *   L = DATA - LOGFACT + the two sides' sums      (src/models/_gamma_elbo.py:elbo_from_gamma_terms is this formula).
+ * The reference's row update weights the factors with the arithmetic means E E / (E . E), not with exp(Elog); it is not
+ * exact coordinate ascent on L, so L need not rise from one of its iterations to the next.
+ * `totals[t]` is the sum of the per-row values in row order, in double: two calls give the same bits, whatever the task
+ * length.  `per_row` (rows x PMF_GAMMA_ELBO_TERMS, row-major) may be NULL.  psi and lgamma of the row terms are
+ * evaluated in double whatever the context's dtype (lgamma(a) + (1 - a) psi(a) cancels in fp32 once a shape reaches
+ * the thousands); the per-rating arithmetic and the per-task and per-row sums of DATA are in the context's dtype,
+ * LOGFACT is in double.  The data term runs over the side's GAMMA work list, the sweep's own cuts (read only); the
+ * partial sums of a split row are added in slot order.  LOGFACT comes from a Stirling series that equals
+ * lgamma(x + 1) for x >= 0; for a negative rating DATA and LOGFACT are undefined (finite-time, the values mean nothing; the
+ * model classes refuse one).  Reads the context only: model state, ratings, work lists and the stored
+ * validation set stay as they are; never a collective, with or without a communicator.  The row terms, the gathered
+ * tables ([rows][2][kpad] of each side in the context's dtype) and the partial sums live in the context's scratch
+ * buffer: pmf_ctx_device_bytes may grow on the first call and does not grow on the ones after it.  Launches are
+ * timed as PMF_KERNEL_GAMMA_FINAL (row pass) and PMF_KERNEL_GAMMA_SWEEP (data pass).
+ * Cost, measured at K = 64 fp32, 1M users, 50M ratings: the two kernels of a user call with data
+ * take 3.00 times a user half-sweep of pmf_gamma_sweep, the data pass alone 2.06 times it and 2.34 times
+ * pmf_prof_gather_ceiling; the whole call takes 5.1 times a full iteration by wall clock (1.27 times in kernel time: the
+ * rest is the download of the per-row terms and the host's sum).  The extended Poisson model (SCALE arrays) is not covered.
+ * PMF_EINVAL, with the missing thing named: null context, bad side, null totals, SHAPE or RATE of `side` not set;
+ * with_data: SHAPE or RATE of the other side not set, no ratings; hierarchical: HYPER_RATE of `side` not set.  An
+ * argument error writes nothing. */
+#define PMF_GAMMA_ELBO_SUM_FACTOR 0
+#define PMF_GAMMA_ELBO_SUM_ELOG 1
+#define PMF_GAMMA_ELBO_ENTROPY 2
+#define PMF_GAMMA_ELBO_LOG_HYPER 3
+#define PMF_GAMMA_ELBO_INV_HYPER 4
+#define PMF_GAMMA_ELBO_FACTOR_OVER_HYPER 5
+#define PMF_GAMMA_ELBO_DATA 6
+#define PMF_GAMMA_ELBO_LOGFACT 7
+#define PMF_GAMMA_ELBO_TERMS 8
+int pmf_gamma_elbo_terms(pmf_ctx *ctx, int side, int with_data, int hierarchical,
+                         double *totals /* [PMF_GAMMA_ELBO_TERMS] */,
+                         double *per_row /* rows x PMF_GAMMA_ELBO_TERMS, may be NULL */);
+
 /* Multi-GPU form of the same half-sweep (ratings sharded by user range,
  * SURVEY.md section 8e).  `accumulate` writes this rank's raw sums
  * [rows x 2 x Kpad] (shape sums, then rate sums; Kpad from pmf_ctx_kpad) into

@@ -848,6 +848,360 @@ extern "C" int pmf_gamma_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
     }
 }
 
+// ---------------------------------------------------------------------------
+// evidence lower bound (pmf_gamma_elbo_terms): the per-row sums that do not depend on the hyperparameters
+// ---------------------------------------------------------------------------
+// q(theta_rk) = Gamma(SHAPE, RATE) only (FACTOR is not read).  Two passes:
+//   row pass   a lane group per row in the sweep's layout; digamma and lgamma in DOUBLE whatever the context dtype -- it
+//              is rows x K evaluations, and lgamma(a) + (1 - a) psi(a) cancels in fp32 once a shape reaches the thousands
+//              (a = 1e4: two terms of 8e4 leave 6, fp32 keeps 7e-3 of it) -- and writes, in the context dtype, the table
+//              the data pass gathers from: [rows][2][kpad] = E log (pad elements -inf), then E (pad elements 0), so the
+//              two 16-byte pieces a lane needs of one rating lie in one 2 kpad block and exp of a pad adds 0.
+//   data pass  a lane group per task of the side's GAMMA list (read only); the row's own pair stays in registers; per
+//              rating the other row's pair is gathered and  x (m + log sum_k exp(s_k - m)) - sum_k E E  is formed with a
+//              DPP max and two DPP sums.  Log-sum-exp, not a dot product of exp(E log) tables: with a small prior shape
+//              psi(a) ~ -1/a and the product of two such entries underflows in fp32.  lgamma(x + 1) by the lane that
+//              loaded x, in double (gamma_log_factorial).  No atomics: the tasks of a split row leave partial sums that one thread adds in slot
+//              order.
+
+// psi(x), x > 0: psi(x) = psi(x + n) - sum_{j<n} 1/(x + j) up to x + n >= 10, then the asymptotic series
+//     ln x - 1/(2x) - sum_{n=1..6} B_2n / (2n x^2n).
+// The series' error is below its first omitted term, 1/(12 x^14) <= 8.4e-16 at x >= 10 -- under one ulp of
+// psi(10) = 2.25, so far below the 1e-11 relative bound of the tests that the shift needs no tuning; at most ten
+// recurrence steps (the loop is counted: a shape that is not positive gives a meaningless value, never a hang).
+__device__ __forceinline__ double gamma_digamma(double x) {
+    double shift = 0.0;
+    for (int n = 0; n < 10 && x < 10.0; ++n) {
+        shift += 1.0 / x;
+        x += 1.0;
+    }
+    const double r = 1.0 / x, r2 = r * r;
+    const double s = r2 * (1.0 / 12 - r2 * (1.0 / 120 - r2 * (1.0 / 252 - r2 * (1.0 / 240 - r2 * (1.0 / 132 - r2 * (691.0 / 32760))))));
+    return log(x) - 0.5 * r - s - shift;
+}
+
+// lgamma(x + 1) of a rating x >= 0, for the data pass: x + 1 is shifted up to y >= 10 (at most nine factors, their
+// product stays below 1e10), then Stirling's series (y - 1/2) ln y - y + ln(2 pi)/2 + sum_{n=1..6} B_2n / (2n (2n - 1) y^(2n-1)),
+// whose first omitted term is 1/(156 y^13) <= 6.4e-16.  Ratings 0 and 1 give exactly 0, as lgamma does.  The library's
+// lgamma stays out of this kernel: its coefficient tables are loop-invariant, the compiler keeps them in registers across
+// the rating loop and the fp32 kernel needs 204 VGPRs (2 waves per SIMD) instead of 68 (7 waves).
+__device__ __forceinline__ double gamma_log_factorial(double x) {
+    double y = x + 1.0;
+    if (y == 1.0 || y == 2.0) return 0.0;
+    double prod = 1.0;
+    for (int n = 0; n < 9 && y < 10.0; ++n) {
+        prod *= y;
+        y += 1.0;
+    }
+    const double r = 1.0 / y, r2 = r * r;
+    const double s = r * (1.0 / 12 - r2 * (1.0 / 360 - r2 * (1.0 / 1260 - r2 * (1.0 / 1680 - r2 * (1.0 / 1188 - r2 * (691.0 / 360360))))));
+    return (y - 0.5) * log(y) - y + 0.91893853320467274178 + s - log(prod);
+}
+
+// max over the lane group (group_sum's moves)
+template <int LANES, typename T>
+__device__ __forceinline__ T group_max(T x) {
+    if constexpr (LANES >= 2) x = vmax(x, dpp_move<0xB1>(x));
+    if constexpr (LANES >= 4) x = vmax(x, dpp_move<0x4E>(x));
+    if constexpr (LANES >= 8) x = vmax(x, dpp_move<0x141>(x));
+    if constexpr (LANES >= 16) x = vmax(x, dpp_move<0x140>(x));
+    if constexpr (LANES >= 32) x = vmax(x, __shfl_xor(x, 16, 64));
+    if constexpr (LANES >= 64) x = vmax(x, __shfl_xor(x, 32, 64));
+    return x;
+}
+
+template <typename T>
+struct GammaElboRowParams {
+    const T *shape, *rate;   // [rows][kpad]
+    const T *hyper_rate;     // [rows], or null: not hierarchical
+    T *table;                // [rows][2][kpad]
+    double *out;             // [rows][PMF_GAMMA_ELBO_TERMS], or null: the table only (the other side of a data call)
+    int64_t rows;
+    int K, kpad;
+};
+
+template <typename T, int LPR>
+__global__ __launch_bounds__(256) void gamma_elbo_row_kernel(GammaElboRowParams<T> p) {
+    constexpr int G = 256 / LPR;
+    const int c = threadIdx.x % LPR;
+    const int64_t row = (int64_t)blockIdx.x * G + threadIdx.x / LPR;
+    if (row >= p.rows) return;
+    const int koff = c * PMF_VEC;
+    const bool active = koff < p.kpad;
+    Vec4<T> a4 = zero4<T>(), b4 = zero4<T>();
+    if (active) {
+        a4 = load4(p.shape + row * p.kpad + koff);
+        b4 = load4(p.rate + row * p.kpad + koff);
+    }
+    Vec4<T> elog, ex;
+    double sum_e = 0.0, sum_elog = 0.0, entropy = 0.0;
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) {
+        elog.v[e] = (T)(-INFINITY);
+        ex.v[e] = (T)0;
+        if (active && koff + e < p.K) {
+            const double a = (double)a4.v[e], b = (double)b4.v[e];
+            const double lb = log(b), psi = gamma_digamma(a), x = a / b, el = psi - lb;
+            sum_e += x;
+            sum_elog += el;
+            if (p.out) entropy += a - lb + lgamma(a) + (1.0 - a) * psi;
+            elog.v[e] = (T)el;
+            ex.v[e] = (T)x;
+        }
+    }
+    if (active) {
+        T *dst = p.table + row * 2 * p.kpad + koff;
+        store4(dst, elog);
+        store4(dst + p.kpad, ex);
+    }
+    if (!p.out) return;   // (the same in every lane)
+    sum_e = group_sum<LPR>(sum_e);
+    sum_elog = group_sum<LPR>(sum_elog);
+    entropy = group_sum<LPR>(entropy);
+    if (c == 0) {
+        double *o = p.out + row * PMF_GAMMA_ELBO_TERMS;
+        o[PMF_GAMMA_ELBO_SUM_FACTOR] = sum_e;
+        o[PMF_GAMMA_ELBO_SUM_ELOG] = sum_elog;
+        o[PMF_GAMMA_ELBO_ENTROPY] = entropy;
+        const bool hier = p.hyper_rate != nullptr;
+        const double h = hier ? (double)p.hyper_rate[row] : 1.0;
+        o[PMF_GAMMA_ELBO_LOG_HYPER] = hier ? log(h) : 0.0;
+        o[PMF_GAMMA_ELBO_INV_HYPER] = hier ? 1.0 / h : 0.0;
+        o[PMF_GAMMA_ELBO_FACTOR_OVER_HYPER] = hier ? sum_e / h : 0.0;
+        o[PMF_GAMMA_ELBO_DATA] = 0.0;      // (the data pass writes over these two)
+        o[PMF_GAMMA_ELBO_LOGFACT] = 0.0;
+    }
+}
+
+template <typename T>
+struct GammaElboDataParams {
+    const PmfTask *tasks;
+    int64_t n_tasks;
+    const int32_t *other;
+    const T *val;
+    const T *table_self, *table_other;   // [rows][2][kpad]
+    T *part_data;                        // [n_slots]
+    double *part_logfact;                // [n_slots]
+    double *out;                         // [rows][PMF_GAMMA_ELBO_TERMS]
+    int kpad;
+};
+
+template <typename T, int LPR>
+__global__ __launch_bounds__(256) void gamma_elbo_data_kernel(GammaElboDataParams<T> p) {
+    constexpr int G = 256 / LPR;
+    constexpr int UN = LPR < 4 ? LPR : 4;
+    const int c = threadIdx.x % LPR;
+    const int64_t task_id = (int64_t)blockIdx.x * G + threadIdx.x / LPR;
+    if (task_id >= p.n_tasks) return;
+    const PmfTask t = p.tasks[task_id];
+    const int koff = c * PMF_VEC;
+    const int kpad = p.kpad;
+    const bool active = koff < kpad;
+    const T ninf = (T)(-INFINITY);
+
+    Vec4<T> sl, se = zero4<T>();   // the row's own E log and E; a lane past kpad holds pads
+    sl.v[0] = sl.v[1] = sl.v[2] = sl.v[3] = ninf;
+    if (active) {
+        const T *src = p.table_self + (int64_t)t.row * 2 * kpad + koff;
+        sl = load4(src);
+        se = load4(src + kpad);
+    }
+    T acc = (T)0;
+    double logfact = 0.0;
+    const int32_t *col = p.other + t.start;
+    const T *val = p.val + t.start;
+
+    for (int base = 0; base < t.len; base += LPR) {
+        const int n = min(LPR, t.len - base);
+        int my_o = 0;
+        T my_x = (T)0;
+        if (c < n) {
+            my_o = col[base + c];
+            my_x = val[base + c];
+            logfact += gamma_log_factorial((double)my_x);
+        }
+        for (int tt = 0; tt < n; tt += UN) {
+            int o[UN];
+            T xv[UN];
+            Vec4<T> bl[UN], be[UN];
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                o[q] = __shfl(my_o, tt + q, LPR);   // (lanes past the batch hold id 0: a valid row, loaded and not used)
+                xv[q] = __shfl(my_x, tt + q, LPR);
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                bl[q] = sl;   // (-inf in every element: what an inactive lane contributes)
+                be[q] = zero4<T>();
+                if (active) {
+                    const T *src = p.table_other + (int64_t)o[q] * 2 * kpad + koff;
+                    bl[q] = load4(src);
+                    be[q] = load4(src + kpad);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                if (tt + q < n) {
+                    T s[PMF_VEC];
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) s[e] = sl.v[e] + bl[q].v[e];
+                    const T m = group_max<LPR>(vmax(vmax(s[0], s[1]), vmax(s[2], s[3])));
+                    T z = exp(s[0] - m);   // (a pad is -inf: exp gives 0)
+                    z += exp(s[1] - m);
+                    z += exp(s[2] - m);
+                    z += exp(s[3] - m);
+                    T d = be[q].v[0] * se.v[0];
+                    d = fma(be[q].v[1], se.v[1], d);
+                    d = fma(be[q].v[2], se.v[2], d);
+                    d = fma(be[q].v[3], se.v[3], d);
+                    z = group_sum<LPR>(z);
+                    d = group_sum<LPR>(d);
+                    acc += xv[q] * (m + log(z)) - d;
+                }
+            }
+        }
+    }
+    logfact = group_sum<LPR>(logfact);
+    if (c != 0) return;
+    if (t.slot >= 0) {
+        p.part_data[t.slot] = acc;
+        p.part_logfact[t.slot] = logfact;
+    } else {
+        double *o = p.out + (int64_t)t.row * PMF_GAMMA_ELBO_TERMS;
+        o[PMF_GAMMA_ELBO_DATA] = (double)acc;
+        o[PMF_GAMMA_ELBO_LOGFACT] = logfact;
+    }
+}
+
+// one thread per split row: its partial sums in slot order
+template <typename T>
+__global__ void gamma_elbo_split_kernel(const PmfSplitRow *split, int64_t n_split, const T *part_data, const double *part_logfact,
+                                        double *out) {
+    const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (at >= n_split) return;
+    const PmfSplitRow sr = split[at];
+    T d = (T)0;
+    double lf = 0.0;
+    for (int s = 0; s < sr.n_slots; ++s) {
+        d += part_data[sr.first_slot + s];
+        lf += part_logfact[sr.first_slot + s];
+    }
+    double *o = out + (int64_t)sr.row * PMF_GAMMA_ELBO_TERMS;
+    o[PMF_GAMMA_ELBO_DATA] = (double)d;
+    o[PMF_GAMMA_ELBO_LOGFACT] = lf;
+}
+
+// Everything the call writes lives in the context's scratch buffer (grown once, kept): the per-row terms, both tables
+// and the split rows' partial sums.  The row pass is timed as PMF_KERNEL_GAMMA_FINAL (with the split rows' sums), the
+// data pass as PMF_KERNEL_GAMMA_SWEEP.
+template <typename T>
+static int run_gamma_elbo_terms(pmf_ctx *ctx, int side, bool with_data, bool hierarchical, double *totals, double *per_row) {
+    const int other = 1 - side, kpad = ctx->kpad;
+    const int64_t rows = ctx->rows[side], rows_o = ctx->rows[other];
+    const int lpr = pmf_lanes_per_row(kpad);
+    PMF_REQUIRE(lpr <= 64, PMF_ERANGE, "pmf_gamma_elbo_terms: unsupported n_factors %d", ctx->K);
+    PmfTaskView tl;
+    if (with_data) tl = pmf_task_view(ctx, side, ctx->index[side].gamma_tasks, false);
+    const auto aligned = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t out_bytes = aligned((size_t)rows * PMF_GAMMA_ELBO_TERMS * sizeof(double));
+    const size_t lf_bytes = aligned((size_t)tl.n_slots * sizeof(double));
+    const size_t pd_bytes = aligned((size_t)tl.n_slots * sizeof(T));
+    const size_t self_bytes = aligned((size_t)rows * 2 * kpad * sizeof(T));
+    const size_t other_bytes = with_data ? aligned((size_t)rows_o * 2 * kpad * sizeof(T)) : 0;
+    int rc;
+    if ((rc = pmf_ensure_scratch(ctx, out_bytes + lf_bytes + pd_bytes + self_bytes + other_bytes))) return rc;
+    char *base = ctx->d_scratch.as<char>();
+    double *d_out = reinterpret_cast<double *>(base);
+    double *d_lf = reinterpret_cast<double *>(base + out_bytes);
+    T *d_pd = reinterpret_cast<T *>(base + out_bytes + lf_bytes);
+    T *d_self = reinterpret_cast<T *>(base + out_bytes + lf_bytes + pd_bytes);
+    T *d_other = reinterpret_cast<T *>(base + out_bytes + lf_bytes + pd_bytes + self_bytes);
+
+    GammaElboRowParams<T> r;
+    r.shape = ctx->arr[side][PMF_ARR_SHAPE].as<const T>();
+    r.rate = ctx->arr[side][PMF_ARR_RATE].as<const T>();
+    r.hyper_rate = hierarchical ? ctx->arr[side][PMF_ARR_HYPER_RATE].as<const T>() : nullptr;
+    r.table = d_self;
+    r.out = d_out;
+    r.rows = rows;
+    r.K = ctx->K;
+    r.kpad = kpad;
+    GammaElboRowParams<T> ro = r;   // the other side: its table only
+    ro.shape = ctx->arr[other][PMF_ARR_SHAPE].as<const T>();
+    ro.rate = ctx->arr[other][PMF_ARR_RATE].as<const T>();
+    ro.hyper_rate = nullptr;
+    ro.table = d_other;
+    ro.out = nullptr;
+    ro.rows = rows_o;
+    GammaElboDataParams<T> d;
+    d.tasks = tl.d_tasks;
+    d.n_tasks = tl.n_tasks;
+    d.other = ctx->index[side].d_other.as<int32_t>();
+    d.val = ctx->index[side].d_val.as<const T>();
+    d.table_self = d_self;
+    d.table_other = d_other;
+    d.part_data = d_pd;
+    d.part_logfact = d_lf;
+    d.out = d_out;
+    d.kpad = kpad;
+    pmf_with_pow2<1>(lpr, [&](auto L) {
+        constexpr int G = 256 / L;
+        if (rows > 0) {
+            PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
+            hipLaunchKernelGGL((gamma_elbo_row_kernel<T, L>), dim3((unsigned)((rows + G - 1) / G)), dim3(256), 0, ctx->stream, r);
+            if (with_data && rows_o > 0)
+                hipLaunchKernelGGL((gamma_elbo_row_kernel<T, L>), dim3((unsigned)((rows_o + G - 1) / G)), dim3(256), 0, ctx->stream, ro);
+        }
+        if (with_data && tl.n_tasks > 0) {
+            PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
+            hipLaunchKernelGGL((gamma_elbo_data_kernel<T, L>), dim3((unsigned)((tl.n_tasks + G - 1) / G)), dim3(256), 0, ctx->stream, d);
+        }
+        if (with_data && tl.n_split > 0) {
+            PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
+            hipLaunchKernelGGL((gamma_elbo_split_kernel<T>), dim3((unsigned)((tl.n_split + 255) / 256)), dim3(256), 0, ctx->stream,
+                               tl.d_split, tl.n_split, d_pd, d_lf, d_out);
+        }
+    });
+    PMF_HIP_CHECK(hipGetLastError());
+    // per-row terms to the host; the totals are their sums in row order
+    std::vector<double> host;
+    double *dst = per_row;
+    if (!dst) {
+        host.resize((size_t)rows * PMF_GAMMA_ELBO_TERMS);
+        dst = host.data();
+    }
+    if (rows > 0)
+        PMF_HIP_CHECK(hipMemcpyAsync(dst, d_out, (size_t)rows * PMF_GAMMA_ELBO_TERMS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    double sum[PMF_GAMMA_ELBO_TERMS] = {};
+    for (int64_t row = 0; row < rows; ++row)
+        for (int t = 0; t < PMF_GAMMA_ELBO_TERMS; ++t) sum[t] += dst[row * PMF_GAMMA_ELBO_TERMS + t];
+    std::copy_n(sum, PMF_GAMMA_ELBO_TERMS, totals);
+    return PMF_OK;
+}
+
+extern "C" int pmf_gamma_elbo_terms(pmf_ctx *ctx, int side, int with_data, int hierarchical, double *totals, double *per_row) {
+    PMF_SIDE_ENTRY("pmf_gamma_elbo_terms");
+    PMF_REQUIRE(totals, PMF_EINVAL, "pmf_gamma_elbo_terms: null totals");
+    int rc;
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_SHAPE, "pmf_gamma_elbo_terms"))) return rc;
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_RATE, "pmf_gamma_elbo_terms"))) return rc;
+    if (with_data) {
+        if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_SHAPE, "pmf_gamma_elbo_terms"))) return rc;
+        if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_RATE, "pmf_gamma_elbo_terms"))) return rc;
+        PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gamma_elbo_terms: ratings have not been set");
+    }
+    if (hierarchical && (rc = pmf_require_array(ctx, side, PMF_ARR_HYPER_RATE, "pmf_gamma_elbo_terms (hierarchical)"))) return rc;
+    try {  // host containers may throw: nothing propagates across the C boundary
+        return pmf_with_dtype(ctx, [&](auto t) {
+            return run_gamma_elbo_terms<decltype(t)>(ctx, side, with_data != 0, hierarchical != 0, totals, per_row);
+        });
+    } catch (const std::bad_alloc &) {
+        pmf_set_error("pmf_gamma_elbo_terms: out of host memory");
+        return PMF_ENOMEM;
+    }
+}
+
 // Profiling aid (no reference counterpart): average device time of `repeats` launches of the
 // gather-only twin of the Poisson/HPF half-sweep of `side` -- the ceiling the cache hierarchy sets
 // for this context's gather pattern (bench.py reports the sweep kernel against it).

@@ -33,6 +33,9 @@ OP_SUM, OP_MAX = 0, 1
 EXCHANGE = {"auto": 0, "allreduce": 1, "scatter_gather": 2}
 MAX_LABELS = 32
 ELBO_SQNORM, ELBO_LOGDET, ELBO_BIAS_SQ, ELBO_ESS, ELBO_TERMS = 0, 1, 2, 3, 4      # columns of pmf_gauss_elbo_terms
+# columns of pmf_gamma_elbo_terms
+(GAMMA_ELBO_SUM_FACTOR, GAMMA_ELBO_SUM_ELOG, GAMMA_ELBO_ENTROPY, GAMMA_ELBO_LOG_HYPER, GAMMA_ELBO_INV_HYPER,
+ GAMMA_ELBO_FACTOR_OVER_HYPER, GAMMA_ELBO_DATA, GAMMA_ELBO_LOGFACT, GAMMA_ELBO_TERMS) = range(9)
 TASK_LISTS = {"gamma": 0, "gauss": 1, "bias": 2, "sgd": 3}
 
 
@@ -78,6 +81,7 @@ SIGNATURES = {
     "pmf_gamma_ext_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),
     "pmf_gamma_fold_in": (C.c_int, [_p, C.c_int, C.c_int64, _i64p, _i32p, _f64p, C.c_double, C.c_double, C.c_int, C.c_double,
                                     C.c_double, C.c_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
+    "pmf_gamma_elbo_terms": (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _f64p, _f64p]),
     "pmf_ctx_kpad": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "pmf_gamma_accumulate": (C.c_int, [_p, C.c_int, _p]),
     "pmf_gamma_finalize": (C.c_int, [_p, C.c_int, _p, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]),

@@ -10,13 +10,14 @@ import ctypes as C
 
 import numpy as np
 
-from . import (ARR_COV, ELBO_TERMS, EXCHANGE, F32, F64, ITEM, KERNEL_NAMES, MAX_LABELS, OP_MAX, OP_SUM, TASK_LISTS, TEST_LIB_PATH,
+from . import (ARR_COV, ELBO_TERMS, EXCHANGE, F32, F64, GAMMA_ELBO_TERMS, ITEM, KERNEL_NAMES, MAX_LABELS, OP_MAX, OP_SUM, TASK_LISTS, TEST_LIB_PATH,
                UNIQUE_ID_BYTES, USER, PmfError, PmfLibraryError, as_f64, as_i32, check, load, ptr)
 
 
 class Context:
-    def __init__(self, n_users, n_items, n_factors, dtype="f32", device=0):
-        self._lib = load()
+    def __init__(self, n_users, n_items, n_factors, dtype="f32", device=0, lib=None):
+        """`lib`: another build of the same ABI, already bound (tools/: a yardstick build beside the product's)."""
+        self._lib = lib if lib is not None else load()
         self._h = C.c_void_p()
         self.n_users, self.n_items, self.K = int(n_users), int(n_items), int(n_factors)
         self.dtype = {"f32": F32, "f64": F64, F32: F32, F64: F64}[dtype]
@@ -247,6 +248,17 @@ class Context:
                                           float(hyper_rate_prior), int(n_iter), opt(init_f), opt(init_r), ptr(factor, C.c_double),
                                           opt(shape), opt(rate), opt(prior_rate), opt(hyper_rate)), "pmf_gamma_fold_in")
         return factor, shape, rate, prior_rate, hyper_rate
+
+    def gamma_elbo_terms(self, side, with_data=False, hierarchical=False, per_row=False):
+        """The sums of `side` the Poisson MF / HPF ELBO is assembled from (`pmf_gamma_elbo_terms`; columns
+        `pmf_hip.GAMMA_ELBO_*`): the totals [GAMMA_ELBO_TERMS] as float64 and, when asked, the (rows, GAMMA_ELBO_TERMS)
+        per-row array as well.  DATA and LOGFACT are zero unless `with_data`, the three HYPER columns unless
+        `hierarchical`.  The context is only read."""
+        totals = np.zeros(GAMMA_ELBO_TERMS, dtype=np.float64)
+        rows = np.zeros((self.rows(side), GAMMA_ELBO_TERMS), dtype=np.float64) if per_row else None
+        check(self._lib.pmf_gamma_elbo_terms(self._h, side, int(bool(with_data)), int(bool(hierarchical)), ptr(totals, C.c_double),
+                                             ptr(rows, C.c_double) if per_row else None), "pmf_gamma_elbo_terms")
+        return (totals, rows) if per_row else totals
 
     def gamma_accumulate(self, side, stats_ptr):
         check(self._lib.pmf_gamma_accumulate(self._h, side, C.c_void_p(stats_ptr)), "pmf_gamma_accumulate")

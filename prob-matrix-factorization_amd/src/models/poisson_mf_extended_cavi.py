@@ -62,7 +62,10 @@ class PoissonMFExtendedCAVI(DeviceModel):
             setattr(self, f"b_{scalar}", ctx.get_array(side, ARR_SCALE_RATE))
             setattr(self, f"E_{scalar}", ctx.get_array(side, ARR_SCALE))
 
-    def fit(self, train_df, val_df=None):
+    def fit(self, train_df, val_df=None, *, track_elbo=False, elbo_tol=None):
+        """`track_elbo` / `elbo_tol` are refused: `pmf_gamma_elbo_terms` does not cover the scalar factors phi / psi."""
+        if track_elbo or elbo_tol is not None:
+            raise NotImplementedError(f"{type(self).__name__} has no ELBO: the device ELBO does not cover the extended model's scalar factors")
         cfg = self.config
         self._infer_dimensions(train_df)
         self._initialize_variational_params()
@@ -105,6 +108,10 @@ class PoissonMFExtendedCAVI(DeviceModel):
         raise NotImplementedError(f"{type(self).__name__} has no fold-in: the device fold-in does not cover the extended model's scalar factors")
 
     fold_in_items = fold_in_users
+
+    def elbo(self, parts=False):
+        """Not available: `pmf_gamma_elbo_terms` does not cover the per-row scalar factors phi / psi of this model."""
+        raise NotImplementedError(f"{type(self).__name__} has no ELBO: the device ELBO does not cover the extended model's scalar factors")
 
     def predict(self, user_ids, item_ids):
         return self._need_ctx().predict(np.asarray(user_ids, dtype=int), np.asarray(item_ids, dtype=int),
