@@ -542,6 +542,32 @@ int pmf_eval_run_var(pmf_ctx *ctx, int use_bias, double offset, double sigma2, d
 int pmf_topk_items(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias,
                    int32_t *out_items, double *out_scores);
 
+/* Ranks of held-out items (no reference counterpart: the reference evaluates point errors only).  Query row r is user
+ * user_ids[r] (repeats allowed) with the target items item_ids[row_ptr[r] .. row_ptr[r + 1]) (row_ptr[0] = 0,
+ * non-decreasing; a row without targets is legal).  With s_uj the score pmf_topk_items / pmf_predict define under
+ * `use_bias` (0, PMF_PREDICT_BIAS or PMF_PREDICT_SCALE; no offset, which does not change the order), the 0-based rank of
+ * target i of user u is
+ *     out_rank = #{ j in [0, n_items), j != i, j not excluded for u :  s_uj > s_ui  or  (s_uj == s_ui and j < i) }
+ * -- the order of pmf_topk_items: score descending, ties to the lower item id, -0.0 == +0.0, a NaN score never
+ * outranks anything; a target whose own score is NaN gets -1.  With `exclude_train` != 0 the excluded items of u are
+ * the DISTINCT items of u's training ratings (pmf_ctx_set_ratings keeps duplicate pairs; each item counts once).
+ * Exclusion applies to competitors only: a target that is itself a training item is ranked against the rest.
+ *     out_candidates[r] = #{ j : s_uj is not NaN, j not excluded for u }          (may be NULL)
+ * so that a percentile rank needs no second call.  s_ui is the very number the scan computes for item i of user u
+ * (exact score ties are common: every item without ratings keeps its prior row).
+ * Reads FACTOR of both sides (BIAS / SCALE under the flag) and, for `exclude_train`, the training ratings; model
+ * state, ratings, work lists and the stored validation set stay as they are (the first `exclude_train` call after
+ * pmf_ctx_set_ratings builds the distinct-item lists, which pmf_ctx_device_bytes then counts).  Never a collective.
+ * PMF_EINVAL (naming what is missing): null context or array, n_rows < 0, bad row_ptr, bad use_bias, a missing array,
+ * `exclude_train` without ratings; PMF_ERANGE: a user or item id outside the trained dimensions (or a context of more
+ * than 2^31 - 65 items: the kernels count items in 32-bit integers).  An argument error
+ * writes nothing; n_rows = 0 touches nothing.
+ * fp32 contexts with Kpad <= 128 scan Theta . Beta^T in score tiles on the matrix cores as pmf_topk_items does and
+ * count instead of keeping lists; no score matrix in HBM.  Timed under PMF_KERNEL_TOPK. */
+int pmf_rank_items(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_ids, const int64_t *row_ptr,
+                   const int32_t *item_ids, int use_bias, int exclude_train, int64_t *out_rank,
+                   int64_t *out_candidates);
+
 /* ---- profiling ----------------------------------------------------------
  * When enabled every kernel launch is bracketed by hipEvents on the context's
  * stream; pmf_prof_get synchronises and returns the accumulated device time

@@ -194,6 +194,7 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
     ctx->topk_two_phase = getenv("PMF_TOPK_TWO_PHASE") != nullptr;
     if (const char *nb = getenv("PMF_TOPK_STAGE_BUFFERS")) ctx->topk_stage_buffers = atoi(nb);
     if (const char *mb = getenv("PMF_TOPK_MAX_BLOCKS")) ctx->topk_max_blocks = atoi(mb);
+    if (const char *rt = getenv("PMF_RANK_TARGETS")) ctx->rank_targets = std::max(atoi(rt), 0);
     if (const char *tc = getenv("PMF_TASK_CHUNK")) {
         const int n = atoi(tc);
         if (n >= 32 && n <= 512 && (n & (n - 1)) == 0) ctx->task_chunk = n;   // anything else: the nnz rule

@@ -174,3 +174,83 @@ int pmf_index_device_finish(pmf_ctx *ctx, PmfIndexBuild *b, int64_t nnz) {
     }
     return PMF_OK;
 }
+
+// ---------------------------------------------------------------------------
+// distinct opposite-side ids per row (pmf_rank_items: "items the user has rated", each once)
+// ---------------------------------------------------------------------------
+namespace {
+
+// key[p] = row << 32 | other id, for entry p of the side's row order (the row by binary search in ptr)
+__global__ void pair_key_kernel(const int64_t *ptr, const int32_t *other, int64_t rows, int64_t nnz, uint64_t *key) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nnz) return;
+    int64_t lo = 0, hi = rows;   // last row with ptr[row] <= p
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ptr[mid] <= p) lo = mid;
+        else hi = mid;
+    }
+    key[p] = ((uint64_t)lo << 32) | (uint32_t)other[p];
+}
+
+__global__ void pair_split_kernel(const uint64_t *key, int64_t n, int32_t *other) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) other[p] = (int32_t)(uint32_t)key[p];
+}
+
+// ptr[r] = number of keys whose row is < r (r = 0 .. rows)
+__global__ void pair_ptr_kernel(const uint64_t *key, int64_t n, int64_t rows, int64_t *ptr) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r > rows) return;
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)(key[mid] >> 32) < r) lo = mid + 1;
+        else hi = mid;
+    }
+    ptr[r] = lo;
+}
+
+}  // namespace
+
+// Sort-unique of the (row, other id) pairs: one radix sort of 64-bit keys, rocPRIM's unique, and the row offsets by
+// binary search.  The temporaries belong to no context; the two result arrays do.
+int pmf_index_distinct(pmf_ctx *ctx, int side) {
+    PmfSideIndex &ix = ctx->index[side];
+    if (ix.d_distinct_ptr) return PMF_OK;
+    const int64_t rows = ctx->rows[side], nnz = ctx->nnz;
+    PmfBuf d_key, d_sorted, d_count, d_tmp, d_ptr, d_items;
+    int rc;
+    if ((rc = d_key.alloc(nullptr, (size_t)nnz * sizeof(uint64_t)))) return rc;
+    if ((rc = d_sorted.alloc(nullptr, (size_t)nnz * sizeof(uint64_t)))) return rc;
+    if ((rc = d_count.alloc(nullptr, sizeof(uint64_t)))) return rc;
+    if ((rc = d_ptr.alloc(ctx, (size_t)(rows + 1) * sizeof(int64_t)))) return rc;
+    uint64_t *key = d_key.as<uint64_t>(), *sorted = d_sorted.as<uint64_t>();
+    uint64_t n_distinct = 0;
+    if (nnz > 0) {
+        const unsigned bits = 32 + key_bits(rows);
+        size_t need_sort = 0, need_unique = 0;
+        PMF_HIP_CHECK(rocprim::radix_sort_keys(nullptr, need_sort, key, sorted, (size_t)nnz, 0u, bits, ctx->stream));
+        PMF_HIP_CHECK(rocprim::unique(nullptr, need_unique, sorted, key, d_count.as<uint64_t>(), (size_t)nnz,
+                                      rocprim::equal_to<uint64_t>(), ctx->stream));
+        if ((rc = d_tmp.alloc(nullptr, std::max(need_sort, need_unique)))) return rc;
+        hipLaunchKernelGGL(pair_key_kernel, dim3(grid_for(nnz)), dim3(256), 0, ctx->stream, ix.d_ptr.as<int64_t>(),
+                           ix.d_other.as<int32_t>(), rows, nnz, key);
+        PMF_HIP_CHECK(rocprim::radix_sort_keys(d_tmp.as(), need_sort, key, sorted, (size_t)nnz, 0u, bits, ctx->stream));
+        PMF_HIP_CHECK(rocprim::unique(d_tmp.as(), need_unique, sorted, key, d_count.as<uint64_t>(), (size_t)nnz,
+                                      rocprim::equal_to<uint64_t>(), ctx->stream));
+        PMF_HIP_CHECK(hipMemcpyAsync(&n_distinct, d_count.as(), sizeof(n_distinct), hipMemcpyDeviceToHost, ctx->stream));
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    if ((rc = d_items.alloc(ctx, (size_t)n_distinct * sizeof(int32_t)))) return rc;
+    if (n_distinct > 0)
+        hipLaunchKernelGGL(pair_split_kernel, dim3(grid_for((int64_t)n_distinct)), dim3(256), 0, ctx->stream, key,
+                           (int64_t)n_distinct, d_items.as<int32_t>());
+    hipLaunchKernelGGL(pair_ptr_kernel, dim3(grid_for(rows + 1)), dim3(256), 0, ctx->stream, key, (int64_t)n_distinct, rows,
+                       d_ptr.as<int64_t>());
+    PMF_HIP_CHECK(hipGetLastError());
+    PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // the keys go with this scope
+    ix.d_distinct_ptr = std::move(d_ptr);
+    ix.d_distinct = std::move(d_items);
+    return PMF_OK;
+}

@@ -141,6 +141,10 @@ struct PmfSideIndex {
     // elbo_bounds instead of the row chunks.  Built on the first call with a data term; goes with the ratings.
     PmfTaskList elbo_tasks;
     std::vector<int64_t> elbo_bounds;   // [n_windows + 1] first row of every window; empty = not built
+    // pmf_rank_items with exclude_train (USER side only): every row's DISTINCT ids on the opposite side, ascending --
+    // pmf_ctx_set_ratings keeps duplicate pairs.  Built on the first such call (pmf_index_distinct); goes with the ratings.
+    PmfBuf d_distinct_ptr;       // int64_t [rows + 1]; null = not built
+    PmfBuf d_distinct;           // int32_t [d_distinct_ptr[rows]]
     // Gaussian gather cache policy (PMF_GAUSS_HOT_MB; fp32, K <= 64): this side's most-rated rows, as many as fit
     // the budget, most-rated first (ties: lower id first) ...
     std::vector<int32_t> h_hot;
@@ -200,6 +204,7 @@ struct pmf_ctx {
     int topk_max_blocks = 0;       // PMF_TOPK_MAX_BLOCKS=n caps the fused kernel's persistent grid (tests: many tiles per block)
     int topk_stage_buffers = 0;    // PMF_TOPK_STAGE_BUFFERS=1|2 pins the fused kernel's stage buffering (0: by residency)
     bool topk_two_phase = false;   // PMF_TOPK_TWO_PHASE: score matrix in HBM + select instead of the fused kernel
+    int rank_targets = 0;          // PMF_RANK_TARGETS=n caps the target slots of a query row of pmf_rank_items (tests: the splitting path with few targets; 0: all RANK_SLOTS)
     int64_t fold_in_rows = 0;      // PMF_FOLD_IN_ROWS=n caps the rows of one block of pmf_gauss_fold_in and pmf_gamma_fold_in (tests: many blocks on a small batch; 0: by scratch size)
     int64_t gamma_fold_long = 0;   // PMF_GAMMA_FOLD_LONG=n: rows of pmf_gamma_fold_in with more than n ratings take the block-per-row kernel (tests: both kernels on small rows; 0: kGammaFoldLongRow)
     int64_t elbo_rows = 0;         // PMF_ELBO_ROWS=n caps the rows of one statistics window of pmf_gauss_elbo_terms (tests: many windows on a small problem; 0: by scratch size)
@@ -263,6 +268,8 @@ int pmf_index_device_begin(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, c
                            const double *ratings, PmfIndexBuild **out, int64_t *bad_position);
 void pmf_index_device_abort(PmfIndexBuild *b);
 int pmf_index_device_finish(pmf_ctx *ctx, PmfIndexBuild *b, int64_t nnz);
+// index[side].d_distinct_ptr / d_distinct from the side's d_ptr / d_other (no-op once built)
+int pmf_index_distinct(pmf_ctx *ctx, int side);
 
 // host <-> device layout helpers (pmf_ctx.hip)
 void pmf_array_shape(const pmf_ctx *ctx, int array, int *host_width, int *dev_stride);

@@ -252,6 +252,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const S *scores, int n
 // wave in parallel (lane e holds entry e: one compare, one ballot, one shift), in ascending item order, so
 // ties keep the lower item id.  With few query users the item range is cut into segments (gridDim.y) so
 // that the chip is filled; a merge kernel then picks the k best of the segments' lists.
+// (rank_fused_kernel below carries a copy of this kernel's staging and stage loop: keep the two in step.)
 #define TOPK_NEG_INF (-__builtin_inff())
 #ifndef PRIO_SLICE
 #define PRIO_SLICE 16      // stages between priority rotations (tools/probe_topk_stamps.py sweeps it: 1 .. 64 are equivalent)
@@ -894,4 +895,584 @@ extern "C" int pmf_topk_items(pmf_ctx *ctx, int64_t n_query, const int32_t *user
                     (long long)ctx->rows[PMF_SIDE_USER]);
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     return pmf_with_dtype(ctx, [&](auto t) { return run_topk<decltype(t)>(ctx, n_query, user_ids, k, use_bias, out_items, out_scores); });
+}
+
+// ---------------------------------------------------------------------------
+// pmf_rank_items: the rank of held-out items among a user's candidates
+// ---------------------------------------------------------------------------
+// A QUERY ROW is a user with up to RANK_SLOTS target items (the host cuts a user with more targets into several).  Per
+// query row the device keeps RANK_STRIDE int32 counters: per slot the number of items that rank before the target, the
+// number of NaN scores, the number of excluded (training) items with a non-NaN score, and a bit mask of the slots whose
+// own score is NaN.  rank = counter, candidates = n_items - NaN scores - excluded.
+//
+// fp32, Kpad <= 128 -- three launches, all of which produce a score with the SAME arithmetic: the KH
+// v_mfma_f32_32x32x2_f32 steps of topk_fused_kernel in its k order (an MFMA output element depends on its A row, its B
+// column and the k sequence only), then rank_score().  Exact ties are the normal case here (every item without ratings
+// keeps its prior row), so a threshold that differed from the scan's score of the same item in the last bit would move a
+// rank by the size of the tie group.
+//   rank_rows_kernel<.., false>  thresholds: one wavefront per query row, all 32 A rows the user's, B column t = the slot's
+//                                target item -> the target's own score
+//   rank_fused_kernel            the scan of topk_fused_kernel (same staging, same tiles); its epilogue counts, per slot,
+//                                the scores above the threshold (v_cmp + v_addc) and notes equal ones; only a tile that
+//                                holds a tie or a NaN takes the second pass that breaks ties by item id and counts NaNs
+//   rank_rows_kernel<.., true>   exclusion: one wavefront per query row, B columns = 32 of the user's distinct training
+//                                items at a time; what the scan counted for them is subtracted
+// fp64 contexts and Kpad > 128: rank_generic_kernel, fma chains, one wavefront per query row.
+#define RANK_SLOTS 4
+#define RANK_NAN (RANK_SLOTS)          // counter: NaN scores
+#define RANK_EXCL (RANK_SLOTS + 1)     // counter: excluded items with a non-NaN score
+#define RANK_MASK (RANK_SLOTS + 2)     // bit t: the score of slot t's target is NaN
+#define RANK_STRIDE (RANK_SLOTS + 3)
+
+template <int MODE, typename S>
+__device__ __forceinline__ S rank_score(S dot, S ucst, S ccst) {   // predict's arithmetic order, as the top-k kernels have it
+    if (MODE == PMF_PREDICT_BIAS) return ucst + ccst + dot;
+    if (MODE == PMF_PREDICT_SCALE) return dot * (ucst * ccst);
+    return dot;
+}
+
+// does a competitor (score s, item j) rank before the target (score th, item tg)?
+template <typename S>
+__device__ __forceinline__ bool rank_beats(S s, int j, S th, int tg) {
+    return (s > th || (s == th && j < tg)) && j != tg;
+}
+
+// sum over the 32 lanes of this lane's half-wave; every lane of the half receives it
+__device__ __forceinline__ int rank_half_sum(int x) {
+    x += __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, false);
+    x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, false);
+    return x + __shfl_xor(x, 16, 64);
+}
+
+struct RankParams {
+    const int32_t *tgt;   // [nq][RANK_SLOTS] target item of a slot, -1: unused
+    void *th;             // [nq][RANK_SLOTS] the targets' own scores (NaN in an unused slot); context dtype
+    int32_t *cnt;         // [nq][RANK_STRIDE]
+    const int64_t *ex_ptr;    // the users' distinct training items (exclusion), or null
+    const int32_t *ex_items;
+};
+
+// One wavefront per query row.  EXCLUDE = false: the targets' scores.  EXCLUDE = true: the training items' scores, and
+// what the scan counted for them taken off the counters.  (1 / 32 of the MFMA's rows is used: n_targets + n_ratings / 32
+// tiles per user against n_items / 32 per 32 users in the scan.)
+template <int KH, int MODE, bool EXCLUDE>
+__global__ __launch_bounds__(256) void rank_rows_kernel(TopkParams p, RankParams rp, const float *fu, const float *fi,
+                                                        const float *cu, const float *ci) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int h = lane >> 5, c = lane & 31;
+    const int q = blockIdx.x * 4 + wave;
+    if (q >= p.nq) return;
+    const int kpad = p.kpad, last_piece = kpad / 4 - 1;
+    const int user = p.users[q];
+    float a[KH];                                       // the scan's A layout: pieces 2 q + h of the row, zero past Kpad
+#pragma unroll
+    for (int t = 0; t < KH; t += 4) {
+        const int kk = 2 * t + 4 * h;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (kk < kpad) v = *reinterpret_cast<const float4 *>(fu + (int64_t)user * kpad + kk);
+        a[t] = v.x; a[t + 1] = v.y; a[t + 2] = v.z; a[t + 3] = v.w;
+    }
+    const float ucst = MODE != 0 ? cu[user] : 0.f;
+    // the user's score of this lane's column: item `item` (< 0: none, the result is not used)
+    auto column_score = [&](int item) __attribute__((always_inline)) -> float {
+        const float *row = fi + (int64_t)(item < 0 ? 0 : item) * kpad;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int t = 0; t < KH; t += 4) {
+            const int pc = t / 2 + h;                  // the scan's stage holds the last piece again past Kpad
+            const float4 b = *reinterpret_cast<const float4 *>(row + 4 * (pc < last_piece ? pc : last_piece));
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 1], b.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 2], b.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 3], b.w, acc, 0, 0, 0);
+        }
+        const float ccst = (MODE != 0 && item >= 0) ? ci[item] : 0.f;
+        return rank_score<MODE>(acc[0], ucst, ccst);   // (every row of the tile is this user's)
+    };
+    if (!EXCLUDE) {
+        const int item = c < RANK_SLOTS ? rp.tgt[(int64_t)q * RANK_SLOTS + c] : -1;
+        const float s = column_score(item);
+        const unsigned long long nan = __builtin_amdgcn_ballot_w64(item >= 0 && s != s);
+        if (h == 0 && c < RANK_SLOTS) static_cast<float *>(rp.th)[(int64_t)q * RANK_SLOTS + c] = item >= 0 ? s : __builtin_nanf("");
+        if (lane == 0) rp.cnt[(int64_t)q * RANK_STRIDE + RANK_MASK] = (int)(nan & ((1u << RANK_SLOTS) - 1u));
+    } else {
+        float th[RANK_SLOTS];
+        int tg[RANK_SLOTS], sub[RANK_SLOTS], n_ok = 0;
+#pragma unroll
+        for (int t = 0; t < RANK_SLOTS; ++t) {
+            th[t] = static_cast<const float *>(rp.th)[(int64_t)q * RANK_SLOTS + t];
+            tg[t] = rp.tgt[(int64_t)q * RANK_SLOTS + t];
+            sub[t] = 0;
+        }
+        const int64_t end = rp.ex_ptr[user + 1];
+        for (int64_t base = rp.ex_ptr[user]; base < end; base += 32) {
+            const int item = base + c < end ? rp.ex_items[base + c] : -1;   // (both half-waves: each holds half of the column's k)
+            const float s = column_score(item);
+            const bool mine = h == 0 && item >= 0;                          // ... and one of them counts it
+            n_ok += __popcll(__builtin_amdgcn_ballot_w64(mine && s == s));
+#pragma unroll
+            for (int t = 0; t < RANK_SLOTS; ++t)
+                sub[t] += __popcll(__builtin_amdgcn_ballot_w64(mine && rank_beats(s, item, th[t], tg[t])));
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int t = 0; t < RANK_SLOTS; ++t) rp.cnt[(int64_t)q * RANK_STRIDE + t] -= sub[t];
+            rp.cnt[(int64_t)q * RANK_STRIDE + RANK_EXCL] = n_ok;
+        }
+    }
+}
+
+// The scan.  Staging, A layout and tile arithmetic are topk_fused_kernel's (two stage buffers, persistent blocks in x,
+// item segments in y) -- a COPY of that kernel's fetch / stash / publish code and stage loop, because pmf_topk_items has to
+// stay what it is bit for bit: a change to either copy's staging or k order belongs in the other too (the thresholds of
+// rank_rows_kernel follow the same k order); TS = target slots held in registers (1 when no query row of the call has more than one target).
+// Per accumulator register r and slot t: one threshold, one counter.  Segments add their counts with integer atomics.
+// (waves per SIMD the register allocation leaves room for: the thresholds and counters take 32 TS registers, the A rows
+//  KH, the bias / scale modes 16 more -- at K = 64 those fit one step lower than the plain score does)
+template <int KH, int MODE, int TS>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(KH < 32 || (KH == 32 && MODE == 0) ? (TS == 1 ? (MODE == 0 ? 4 : 3) : 2) : (TS == 1 ? 2 : 1))))
+void rank_fused_kernel(TopkParams p, RankParams rp, const float *fu, const float *fi,
+                                                         const float *cu, const float *ci, int64_t seg_items) {
+    using S = TopkStage<KH>;
+    constexpr int ST = S::ST, PR = S::PR, PQ = S::PQ, LPT = S::LPT;
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int h = lane >> 5, c = lane & 31;
+    f32x4 *stage = reinterpret_cast<f32x4 *>(smem_raw);                                          // [2][ST][PQ]
+    const int i_begin = (int)((int64_t)blockIdx.y * seg_items);
+    const int i_end = (int)((int64_t)i_begin + seg_items < p.n_items ? (int64_t)i_begin + seg_items : p.n_items);
+    const int kpad = p.kpad;
+    const float *th_in = static_cast<const float *>(rp.th);
+    const int slot = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 3;   // HW_ID.WAVE_ID (time-sliced priority, as in the top-k scan)
+    auto slice_priority = [&](int stage_no) __attribute__((always_inline)) {
+        switch ((slot + stage_no / PRIO_SLICE) & 3) {
+            case 0: __builtin_amdgcn_s_setprio(0); break;
+            case 1: __builtin_amdgcn_s_setprio(1); break;
+            case 2: __builtin_amdgcn_s_setprio(2); break;
+            default: __builtin_amdgcn_s_setprio(3); break;
+        }
+    };
+
+    const int n_user_tiles = (p.nq + 127) / 128;
+    for (int ut = blockIdx.x; ut < n_user_tiles; ut += gridDim.x) {
+    const int q0 = (ut * 4 + wave) * 32;
+    const bool active = q0 < p.nq;                     // a wave without query rows still stages item rows
+    const int user = (q0 + c < p.nq) ? p.users[q0 + c] : -1;
+    float a[KH];
+#pragma unroll
+    for (int t = 0; t < KH; t += 4) {
+        const int kk = 2 * t + 4 * h;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (user >= 0 && kk < kpad) v = *reinterpret_cast<const float4 *>(fu + (int64_t)user * kpad + kk);
+        a[t] = v.x; a[t + 1] = v.y; a[t + 2] = v.z; a[t + 3] = v.w;
+    }
+    // per accumulator register r: the query row (r & 3) + 8 (r >> 2) + 4 h, its bias / scale, its thresholds and counters
+    // (a NaN threshold -- an unused slot, a row past the last query, a NaN target -- compares false both ways)
+    float ucst[16], th[TS][16];
+    int cnt[TS][16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int qq = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        ucst[r] = 0.f;
+        if (MODE != 0 && qq < p.nq) ucst[r] = cu[p.users[qq]];
+#pragma unroll
+        for (int t = 0; t < TS; ++t) {
+            th[t][r] = qq < p.nq ? th_in[(int64_t)qq * RANK_SLOTS + t] : __builtin_nanf("");
+            cnt[t][r] = 0;
+        }
+    }
+
+    // ---- staging: as in topk_fused_kernel -------------------------------------------------------------------------
+    f32x4 g[LPT];
+    const int last_piece = kpad / 4 - 1;
+    const char *next_stage = reinterpret_cast<const char *>(fi + (int64_t)i_begin * kpad);
+    const unsigned stage_bytes = (unsigned)ST * kpad * 4;
+    unsigned goff[LPT];
+#pragma unroll
+    for (int j = 0; j < LPT; ++j) {
+        const int idx = j * 256 + (int)threadIdx.x;
+        const int r = idx / PR, pc = idx % PR;
+        goff[j] = ((unsigned)r * kpad + 4u * (pc < last_piece ? pc : last_piece)) * 4u;
+    }
+    auto fetch_full = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < LPT; ++j) {
+            unsigned off = goff[j];
+            asm volatile("" : "+v"(off));             // (SGPR base + 32-bit VGPR offset)
+            g[j] = *reinterpret_cast<const f32x4 *>(next_stage + off);
+        }
+        next_stage += stage_bytes;
+    };
+    auto fetch_tail = [&](int i0) __attribute__((always_inline)) {    // the segment's last, partial stage: rows past the end re-read the last row
+        int tid = (int)threadIdx.x;
+        asm volatile("" : "+v"(tid));                 // (once per segment: its addresses are formed here, not kept in registers)
+#pragma unroll
+        for (int j = 0; j < LPT; ++j) {
+            const int idx = j * 256 + tid;
+            const int r = idx / PR, pc = idx % PR;
+            const int it = i0 + r < i_end ? i0 + r : i_end - 1;
+            g[j] = *reinterpret_cast<const f32x4 *>(fi + (int64_t)it * kpad + 4 * (pc < last_piece ? pc : last_piece));
+        }
+    };
+    auto stash = [&](int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < LPT; ++j) {
+            const int idx = j * 256 + (int)threadIdx.x;
+            stage[(size_t)buf * ST * PQ + (idx / PR) * PQ + idx % PR] = g[j];
+        }
+    };
+    // ---- one 32-item tile ----------------------------------------------------------------------------------------
+    auto tile = [&](auto TAIL, int i0, const f32x4 *rows) __attribute__((always_inline)) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        const f32x4 *mine = rows + c * PQ + h;
+#pragma unroll
+        for (int t = 0; t < KH; t += 4) {
+            const f32x4 b = mine[t / 2];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 1], b.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 2], b.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 3], b.w, acc, 0, 0, 0);
+        }
+        const int it = i0 + c;
+        const bool in_range = !decltype(TAIL)::value || it < i_end;
+        if (MODE != 0) {
+            const float ccst = in_range ? ci[it] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = rank_score<MODE>(acc[r], ucst[r], ccst);
+        }
+        if (decltype(TAIL)::value) {
+            // a column past the segment's end scores -inf: above no threshold, no NaN, and equal to a -inf threshold only
+            // with an item id above every target's
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = in_range ? acc[r] : TOPK_NEG_INF;
+        }
+        // first pass: what almost every tile needs -- scores above a threshold are counted, equal ones and NaNs noted
+        unsigned long long special = 0ull;
+#pragma unroll
+        for (int t = 0; t < TS; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                cnt[t][r] += acc[r] > th[t][r] ? 1 : 0;
+                special |= __builtin_amdgcn_ballot_w64(acc[r] == th[t][r]);
+            }
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) special |= __builtin_amdgcn_ballot_w64(__builtin_isunordered(acc[r], acc[r + 1]));
+        if (special == 0ull) return;
+        // second pass (rare): ties go to the lower item id -- the target itself is not its own competitor -- and NaN
+        // scores are counted.  (The empty asm makes the compiler compare again here instead of keeping the first pass's
+        // 16 TS lane masks alive across the branch, which it can only do by spilling scalars in the loop.)
+        // (this lane's rows are q0 + 4 h + a constant per register: one pointer each, immediate offsets -- formed here, behind
+        //  an empty asm, so that they hold no registers in the loop)
+        int first_row = q0 + 4 * h;
+        asm volatile("" : "+v"(first_row));
+        const int32_t *tgt_lane = rp.tgt + (int64_t)first_row * RANK_SLOTS;
+        int32_t *cnt_lane = rp.cnt + (int64_t)first_row * RANK_STRIDE;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2);
+            float s = acc[r];
+            asm volatile("" : "+v"(s));
+            const int nn = rank_half_sum(s != s ? 1 : 0);
+            if (c == 0 && nn && first_row + row < p.nq)   // (a NaN item row scores NaN in the rows past the last query too)
+                atomicAdd(cnt_lane + row * RANK_STRIDE + RANK_NAN, nn);
+#pragma unroll
+            for (int t = 0; t < TS; ++t)
+                if (in_range && s == th[t][r])        // (an equal threshold: the row is a query row)
+                    cnt[t][r] += it < tgt_lane[row * RANK_SLOTS + t] ? 1 : 0;
+        }
+    };
+    auto tiles = [&](auto TAIL, int i0, const f32x4 *rows) __attribute__((always_inline)) {
+        if (!active) return;
+        tile(TAIL, i0, rows);
+        if (ST == 64 && (!decltype(TAIL)::value || i0 + 32 < i_end)) tile(TAIL, i0 + 32, rows + 32 * PQ);
+    };
+    int buf = 0;
+    auto publish = [&]() __attribute__((always_inline)) {
+        stash(buf ^ 1);                               // last read there: the stage before this one, behind the barrier
+        __syncthreads();
+        buf ^= 1;
+    };
+    const int n_full = (i_end - i_begin) / ST;
+    const bool has_tail = (i_end - i_begin) % ST != 0;
+    const std::integral_constant<bool, false> FULL;
+    const std::integral_constant<bool, true> PARTIAL;
+    int i0 = i_begin;
+    if (n_full > 0) fetch_full(); else fetch_tail(i_begin);            // (segments are never empty)
+    stash(0);
+    __syncthreads();
+    const int n_steady = n_full > 0 ? n_full - 1 : 0;
+    for (int s0 = 0; s0 < n_steady; s0 += PRIO_SLICE) {
+        slice_priority(s0);
+        const int s1 = s0 + PRIO_SLICE < n_steady ? s0 + PRIO_SLICE : n_steady;
+        for (int st = s0; st < s1; ++st, i0 += ST) {
+            fetch_full();
+            tiles(FULL, i0, stage + (size_t)buf * ST * PQ);
+            publish();
+        }
+    }
+    if (n_full > 0) {
+        if (has_tail) fetch_tail(i0 + ST);
+        tiles(FULL, i0, stage + (size_t)buf * ST * PQ);
+        if (has_tail) publish();
+        i0 += ST;
+    }
+    if (has_tail) tiles(PARTIAL, i0, stage + (size_t)buf * ST * PQ);
+    __syncthreads();                                  // the next user tile's first stage goes where this one is read
+    // hand the counts over: sum over the 32 item columns of a half-wave, one atomic per (query row, counter) and segment
+    if (active) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int qq = q0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+#pragma unroll
+            for (int t = 0; t < TS; ++t) {
+                const int n = rank_half_sum(cnt[t][r]);
+                if (c == 0 && qq < p.nq && n) atomicAdd(rp.cnt + (int64_t)qq * RANK_STRIDE + t, n);
+            }
+        }
+    }
+    }   // user tiles
+    __builtin_amdgcn_s_setprio(0);
+}
+
+// fp64 contexts and Kpad > 128: one wavefront per query row, lanes stride the items; thresholds, competitors and excluded
+// items all come from the same fma chain.  Parity path.
+template <typename S>
+__global__ __launch_bounds__(256) void rank_generic_kernel(TopkParams p, RankParams rp, const S *fu, const S *fi, const S *bu,
+                                                           const S *bi, int mode) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int q = blockIdx.x * 4 + wave;
+    if (q >= p.nq) return;
+    const int user = p.users[q];
+    const S *arow = fu + (int64_t)user * p.kpad;
+    auto score = [&](int it) -> S {
+        const S *b = fi + (int64_t)it * p.kpad;
+        S s = (S)0;
+        for (int k = 0; k < p.K; ++k) s = fma(arow[k], b[k], s);
+        if (mode == PMF_PREDICT_BIAS) return rank_score<PMF_PREDICT_BIAS>(s, bu[user], bi[it]);
+        if (mode == PMF_PREDICT_SCALE) return rank_score<PMF_PREDICT_SCALE>(s, bu[user], bi[it]);
+        return s;
+    };
+    S th[RANK_SLOTS];
+    int tg[RANK_SLOTS], cnt[RANK_SLOTS], n_nan = 0, n_excl = 0, mask = 0;
+    // lane t scores slot t's target (the chain the competitors go through); the wave reads the results from it
+    const int my_tg = lane < RANK_SLOTS ? rp.tgt[(int64_t)q * RANK_SLOTS + lane] : -1;
+    const S my_th = my_tg >= 0 ? score(my_tg) : (S)__builtin_nanf("");
+#pragma unroll
+    for (int t = 0; t < RANK_SLOTS; ++t) {
+        tg[t] = __shfl(my_tg, t, 64);
+        th[t] = __shfl(my_th, t, 64);
+        if (tg[t] >= 0 && th[t] != th[t]) mask |= 1 << t;
+        cnt[t] = 0;
+    }
+    for (int it = lane; it < (int)p.n_items; it += 64) {
+        const S s = score(it);
+        n_nan += s != s ? 1 : 0;
+#pragma unroll
+        for (int t = 0; t < RANK_SLOTS; ++t) cnt[t] += rank_beats(s, it, th[t], tg[t]) ? 1 : 0;
+    }
+    if (rp.ex_ptr) {
+        const int64_t end = rp.ex_ptr[user + 1];
+        for (int64_t e = rp.ex_ptr[user] + lane; e < end; e += 64) {
+            const int it = rp.ex_items[e];
+            const S s = score(it);
+            n_excl += s == s ? 1 : 0;
+#pragma unroll
+            for (int t = 0; t < RANK_SLOTS; ++t) cnt[t] -= rank_beats(s, it, th[t], tg[t]) ? 1 : 0;
+        }
+    }
+    int32_t *out = rp.cnt + (int64_t)q * RANK_STRIDE;
+#pragma unroll
+    for (int t = 0; t < RANK_SLOTS; ++t) {
+        const int n = rank_half_sum(cnt[t]);
+        const int total = n + __shfl_xor(n, 32, 64);
+        if (lane == 0) out[t] = total;
+    }
+    n_nan = rank_half_sum(n_nan);
+    n_nan += __shfl_xor(n_nan, 32, 64);
+    n_excl = rank_half_sum(n_excl);
+    n_excl += __shfl_xor(n_excl, 32, 64);
+    if (lane == 0) {
+        out[RANK_NAN] = n_nan;
+        out[RANK_EXCL] = n_excl;
+        out[RANK_MASK] = mask;
+    }
+}
+
+template <int KH, int MODE, int TS>
+static hipError_t launch_rank_fused(pmf_ctx *ctx, const TopkParams &p, const RankParams &rp, dim3 grid, const float *fu,
+                                    const float *fi, const float *cu, const float *ci, int64_t seg_items) {
+    const void *fn = (const void *)rank_fused_kernel<KH, MODE, TS>;
+    const size_t smem = 2 * TopkStage<KH>::buffer_bytes;
+    int per_cu = 0, cus = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, smem);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    if (e != hipSuccess) return e;
+    if (grid.y == 1) {   // persistent in x, as the top-k scan
+        unsigned resident = (unsigned)std::max(1, per_cu) * (unsigned)std::max(1, cus);
+        if (ctx->topk_max_blocks > 0) resident = std::min(resident, (unsigned)ctx->topk_max_blocks);
+        if (grid.x > resident) grid.x = resident;
+    }
+    hipLaunchKernelGGL((rank_fused_kernel<KH, MODE, TS>), grid, dim3(256), smem, ctx->stream, p, rp, fu, fi, cu, ci, seg_items);
+    return hipSuccess;
+}
+
+// the launches of one batch of query rows (ids, targets and zeroed counters are on the device)
+template <typename T>
+static int launch_rank(pmf_ctx *ctx, const TopkParams &p, const RankParams &rp, int mode, bool one_slot) {
+    const int64_t I = p.n_items;
+    const int carr = mode == PMF_PREDICT_SCALE ? PMF_ARR_SCALE : PMF_ARR_BIAS;
+    const T *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const T>();
+    const T *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const T>();
+    const T *cu = mode ? ctx->arr[PMF_SIDE_USER][carr].as<const T>() : nullptr;
+    const T *ci = mode ? ctx->arr[PMF_SIDE_ITEM][carr].as<const T>() : nullptr;
+    const dim3 row_grid((unsigned)((p.nq + 3) / 4));
+    PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
+    if constexpr (std::is_same<T, float>::value) {
+        if (ctx->kpad <= 128) {   // (the item count fits the scan's ints: rank_items_impl)
+            // segments of the item range: the rule of run_topk_fused
+            const int64_t waves = ((int64_t)p.nq + 31) / 32;
+            int nseg = (int)std::min<int64_t>(64, std::max<int64_t>(1, 4096 / waves));
+            nseg = (int)std::min<int64_t>(nseg, std::max<int64_t>(1, I / 2048));
+            const int64_t seg_items = ((I + nseg - 1) / nseg + 31) / 32 * 32;
+            nseg = (int)((I + seg_items - 1) / seg_items);
+            const dim3 grid((unsigned)((p.nq + 127) / 128), (unsigned)nseg);
+            auto with_mode = [&](auto kh) {
+                auto launch = [&](auto m) {
+                    constexpr int KH = decltype(kh)::value, MODE = decltype(m)::value;
+                    hipLaunchKernelGGL((rank_rows_kernel<KH, MODE, false>), row_grid, dim3(256), 0, ctx->stream, p, rp, fu, fi, cu, ci);
+                    hipError_t e = one_slot ? launch_rank_fused<KH, MODE, 1>(ctx, p, rp, grid, fu, fi, cu, ci, seg_items)
+                                            : launch_rank_fused<KH, MODE, RANK_SLOTS>(ctx, p, rp, grid, fu, fi, cu, ci, seg_items);
+                    if (e == hipSuccess && rp.ex_ptr)
+                        hipLaunchKernelGGL((rank_rows_kernel<KH, MODE, true>), row_grid, dim3(256), 0, ctx->stream, p, rp, fu, fi, cu, ci);
+                    return e;
+                };
+                if (mode == PMF_PREDICT_BIAS) return launch(std::integral_constant<int, PMF_PREDICT_BIAS>());
+                if (mode == PMF_PREDICT_SCALE) return launch(std::integral_constant<int, PMF_PREDICT_SCALE>());
+                return launch(std::integral_constant<int, 0>());
+            };
+            PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, with_mode));
+            return PMF_OK;
+        }
+    }
+    hipLaunchKernelGGL((rank_generic_kernel<T>), row_grid, dim3(256), 0, ctx->stream, p, rp, fu, fi, cu, ci, mode);
+    return PMF_OK;
+}
+
+static int rank_items_impl(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_ids, const int64_t *row_ptr,
+                           const int32_t *item_ids, int use_bias, int exclude_train, int64_t *out_rank,
+                           int64_t *out_candidates) {
+    const int64_t U = ctx->rows[PMF_SIDE_USER], I = ctx->rows[PMF_SIDE_ITEM];
+    PMF_REQUIRE(user_ids && row_ptr, PMF_EINVAL, "pmf_rank_items: null user_ids or row_ptr");
+    PMF_REQUIRE(row_ptr[0] == 0, PMF_EINVAL, "pmf_rank_items: row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
+    for (int64_t n = 0; n < n_rows; ++n)
+        PMF_REQUIRE(row_ptr[n + 1] >= row_ptr[n], PMF_EINVAL, "pmf_rank_items: row_ptr decreases at row %lld", (long long)n);
+    const int64_t n_targets = row_ptr[n_rows];
+    PMF_REQUIRE(n_targets == 0 || (item_ids && out_rank), PMF_EINVAL, "pmf_rank_items: null item_ids or out_rank");
+    PMF_REQUIRE(use_bias == 0 || use_bias == PMF_PREDICT_BIAS || use_bias == PMF_PREDICT_SCALE, PMF_EINVAL,
+                "pmf_rank_items: use_bias must be 0, PMF_PREDICT_BIAS or PMF_PREDICT_SCALE (got %d)", use_bias);
+    int rc;
+    if ((rc = pmf_require_array(ctx, PMF_SIDE_USER, PMF_ARR_FACTOR, "pmf_rank_items"))) return rc;
+    if ((rc = pmf_require_array(ctx, PMF_SIDE_ITEM, PMF_ARR_FACTOR, "pmf_rank_items"))) return rc;
+    if (use_bias) {
+        const int carr = use_bias == PMF_PREDICT_SCALE ? PMF_ARR_SCALE : PMF_ARR_BIAS;
+        if ((rc = pmf_require_array(ctx, PMF_SIDE_USER, carr, "pmf_rank_items"))) return rc;
+        if ((rc = pmf_require_array(ctx, PMF_SIDE_ITEM, carr, "pmf_rank_items"))) return rc;
+    }
+    PMF_REQUIRE(I <= (int64_t)INT32_MAX - 64, PMF_ERANGE, "pmf_rank_items: %lld items; the kernels count items in 32-bit integers",
+                (long long)I);
+    PMF_REQUIRE(!exclude_train || ctx->index[PMF_SIDE_USER].d_ptr, PMF_EINVAL,
+                "pmf_rank_items: exclude_train needs the training ratings (pmf_ctx_set_ratings); the context holds none");
+    for (int64_t n = 0; n < n_rows; ++n)
+        PMF_REQUIRE(user_ids[n] >= 0 && user_ids[n] < U, PMF_ERANGE, "pmf_rank_items: user id %d at position %lld outside [0, %lld)",
+                    user_ids[n], (long long)n, (long long)U);
+    for (int64_t n = 0; n < n_targets; ++n)
+        PMF_REQUIRE(item_ids[n] >= 0 && item_ids[n] < I, PMF_ERANGE, "pmf_rank_items: item id %d at position %lld outside [0, %lld)",
+                    item_ids[n], (long long)n, (long long)I);
+    PMF_HIP_CHECK(hipSetDevice(ctx->device));
+    if (exclude_train && (rc = pmf_index_distinct(ctx, PMF_SIDE_USER))) return rc;
+
+    // query rows: a user's targets in runs of at most `slots`; a user without targets keeps one row (its candidates)
+    const int slots = ctx->rank_targets > 0 ? std::min(ctx->rank_targets, RANK_SLOTS) : RANK_SLOTS;
+    struct QueryRow {
+        int64_t row, first;   // the caller's row and the offset of the run's first target in item_ids
+        int n;
+    };
+    std::vector<QueryRow> qrows;
+    bool one_slot = true;
+    for (int64_t n = 0; n < n_rows; ++n) {
+        int64_t at = row_ptr[n];
+        do {
+            const int len = (int)std::min<int64_t>(slots, row_ptr[n + 1] - at);
+            qrows.push_back({n, at, len});
+            one_slot = one_slot && len <= 1;
+            at += len;
+        } while (at < row_ptr[n + 1]);
+    }
+    const int64_t n_query = (int64_t)qrows.size();
+    const int64_t Q = std::min<int64_t>(n_query, 1 << 20);   // query rows per launch
+    const size_t id_bytes = ((size_t)Q * sizeof(int32_t) + 15) / 16 * 16;
+    const size_t slot_bytes = (size_t)Q * RANK_SLOTS * 8;     // targets (int32) / thresholds (context dtype), 16-byte multiples
+    const size_t cnt_bytes = ((size_t)Q * RANK_STRIDE * sizeof(int32_t) + 15) / 16 * 16;
+    if ((rc = pmf_ensure_scratch(ctx, id_bytes + 2 * slot_bytes + cnt_bytes))) return rc;
+    char *base = ctx->d_scratch.as<char>();
+    int32_t *d_users = (int32_t *)base;
+    int32_t *d_tgt = (int32_t *)(base + id_bytes);
+    void *d_th = base + id_bytes + slot_bytes;
+    int32_t *d_cnt = (int32_t *)(base + id_bytes + 2 * slot_bytes);
+    std::vector<int32_t> h_users((size_t)Q), h_tgt((size_t)Q * RANK_SLOTS), h_cnt((size_t)Q * RANK_STRIDE);
+    for (int64_t at = 0; at < n_query; at += Q) {
+        const int nq = (int)std::min<int64_t>(Q, n_query - at);
+        for (int q = 0; q < nq; ++q) {
+            const QueryRow &qr = qrows[(size_t)(at + q)];
+            h_users[(size_t)q] = user_ids[qr.row];
+            for (int t = 0; t < RANK_SLOTS; ++t) h_tgt[(size_t)q * RANK_SLOTS + t] = t < qr.n ? item_ids[qr.first + t] : -1;
+        }
+        PMF_HIP_CHECK(hipMemcpyAsync(d_users, h_users.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        PMF_HIP_CHECK(hipMemcpyAsync(d_tgt, h_tgt.data(), (size_t)nq * RANK_SLOTS * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        PMF_HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)nq * RANK_STRIDE * sizeof(int32_t), ctx->stream));
+        TopkParams p;
+        p.users = d_users;
+        p.nq = nq;
+        p.n_items = I;
+        p.K = ctx->K;
+        p.kpad = ctx->kpad;
+        RankParams rp;
+        rp.tgt = d_tgt;
+        rp.th = d_th;
+        rp.cnt = d_cnt;
+        rp.ex_ptr = exclude_train ? ctx->index[PMF_SIDE_USER].d_distinct_ptr.as<const int64_t>() : nullptr;
+        rp.ex_items = exclude_train ? ctx->index[PMF_SIDE_USER].d_distinct.as<const int32_t>() : nullptr;
+        if ((rc = pmf_with_dtype(ctx, [&](auto t) { return launch_rank<decltype(t)>(ctx, p, rp, use_bias, one_slot); }))) return rc;
+        PMF_HIP_CHECK(hipGetLastError());
+        PMF_HIP_CHECK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)nq * RANK_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (int q = 0; q < nq; ++q) {
+            const QueryRow &qr = qrows[(size_t)(at + q)];
+            const int32_t *cnt = h_cnt.data() + (size_t)q * RANK_STRIDE;
+            for (int t = 0; t < qr.n; ++t) out_rank[qr.first + t] = (cnt[RANK_MASK] >> t) & 1 ? -1 : (int64_t)cnt[t];
+            if (out_candidates && qr.first == row_ptr[qr.row]) out_candidates[qr.row] = I - cnt[RANK_NAN] - cnt[RANK_EXCL];
+        }
+    }
+    return PMF_OK;
+}
+
+extern "C" int pmf_rank_items(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_ids, const int64_t *row_ptr,
+                              const int32_t *item_ids, int use_bias, int exclude_train, int64_t *out_rank,
+                              int64_t *out_candidates) {
+    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "pmf_rank_items: null context");
+    PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_rank_items: negative n_rows");
+    if (n_rows == 0) return PMF_OK;
+    try {
+        return rank_items_impl(ctx, n_rows, user_ids, row_ptr, item_ids, use_bias, exclude_train, out_rank, out_candidates);
+    } catch (const std::bad_alloc &) {
+        pmf_set_error("pmf_rank_items: out of host memory");
+        return PMF_ENOMEM;
+    }
 }

@@ -14,6 +14,19 @@ from . import (ARR_COV, ELBO_TERMS, EXCHANGE, F32, F64, GAMMA_ELBO_TERMS, ITEM, 
                UNIQUE_ID_BYTES, USER, PmfError, PmfLibraryError, as_f64, as_i32, check, load, ptr)
 
 
+def rank_batch(user_ids, item_ids):
+    """Flat (user, item) pairs -> the CSR batch `pmf_rank_items` takes: (users, row_ptr, items, order) with `users` the
+    sorted distinct user ids, row r holding items[row_ptr[r]:row_ptr[r + 1]] -- user r's items in input order -- and
+    `order` the input position of every batch entry: `out[order] = batch_result` undoes the grouping.  Pure NumPy."""
+    u, i = np.asarray(user_ids).reshape(-1), np.asarray(item_ids).reshape(-1)
+    if len(u) != len(i):
+        raise ValueError("user_ids and item_ids must have the same length")
+    users, row = np.unique(u, return_inverse=True)
+    order = np.argsort(row.reshape(-1), kind="stable")
+    row_ptr = np.concatenate([[0], np.cumsum(np.bincount(row.reshape(-1), minlength=len(users)))]).astype(np.int64)
+    return users, row_ptr, i[order], order
+
+
 class Context:
     def __init__(self, n_users, n_items, n_factors, dtype="f32", device=0, lib=None):
         """`lib`: another build of the same ABI, already bound (tools/: a yardstick build beside the product's)."""
@@ -434,6 +447,32 @@ class Context:
                                        ptr(items, C.c_int32), ptr(scores, C.c_double)), "pmf_topk_items")
         return items, scores
 
+    def rank_rows(self, user_ids, row_ptr, item_ids, use_bias=False, exclude_train=False):
+        """`pmf_rank_items` on a CSR batch: row r is user user_ids[r] (repeats allowed) with the targets
+        item_ids[row_ptr[r]:row_ptr[r + 1]].  Returns (ranks int64 [len(item_ids)], candidates int64 [len(user_ids)])."""
+        u, i = as_i32(user_ids, "user_ids"), as_i32(item_ids, "item_ids")
+        rp = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.int64).reshape(-1))
+        if len(rp) != len(u) + 1:
+            raise ValueError("row_ptr must hold len(user_ids) + 1 offsets")
+        ranks = np.empty(len(i), dtype=np.int64)
+        cand = np.empty(len(u), dtype=np.int64)
+        check(self._lib.pmf_rank_items(self._h, len(u), ptr(u, C.c_int32), ptr(rp, C.c_int64), ptr(i, C.c_int32), int(use_bias),
+                                       int(bool(exclude_train)), ptr(ranks, C.c_int64), ptr(cand, C.c_int64)), "pmf_rank_items")
+        return ranks, cand
+
+    def rank_items(self, user_ids, item_ids, use_bias=False, exclude_train=False):
+        """0-based rank of every pair's item among its user's candidate items under `predict`'s score (`use_bias` as for
+        `topk_items`; ties to the lower item id; -1 where the pair's own score is NaN) and the user's number of
+        candidates, both int64 and aligned with the input pairs.  `exclude_train`: the user's training items (each once)
+        are no competitors and no candidates."""
+        users, row_ptr, items, order = rank_batch(user_ids, item_ids)
+        r, c = self.rank_rows(users, row_ptr, items, use_bias, exclude_train)
+        ranks = np.empty(len(order), dtype=np.int64)
+        cand = np.empty(len(order), dtype=np.int64)
+        ranks[order] = r
+        cand[order] = np.repeat(c, np.diff(row_ptr))
+        return ranks, cand
+
     # ---- profiling ------------------------------------------------------
     def prof_enable(self, on=True):
         check(self._lib.pmf_prof_enable(self._h, int(bool(on))), "pmf_prof_enable")
@@ -457,4 +496,4 @@ class Context:
         return out
 
 
-__all__ = ["Context", "PmfError", "USER", "ITEM"]
+__all__ = ["Context", "PmfError", "USER", "ITEM", "rank_batch"]

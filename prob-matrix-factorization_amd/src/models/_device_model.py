@@ -318,6 +318,29 @@ class DeviceModel:
         (items [n, k] int32, scores [n, k] float64)."""
         return self._need_ctx().topk_items(np.asarray(user_ids, dtype=int), int(k), use_bias=self._uses_bias)
 
+    def heldout_ranks(self, df, exclude_train=True):
+        """Extension (no reference counterpart): where every row's item lands in its user's ranking of the items under
+        `predict`'s score -- (ranks, candidates), int64, aligned with the frame's rows (`Context.rank_items`).  Rows
+        whose user or item the fit has not seen get -1 in both.  `exclude_train`: the items of the user's training
+        ratings are left out of the ranking, as a recommender would."""
+        ctx = self._need_ctx()
+        if exclude_train and self._shard_ctx is not None:
+            raise NotImplementedError("after a sharded fit the full-size context holds the factors but no training ratings: "
+                                      "exclude_train=True is not available, pass exclude_train=False")
+        u, i = df["u"].to_numpy(dtype=int), df["i"].to_numpy(dtype=int)
+        seen = (u >= 0) & (u < self.n_users) & (i >= 0) & (i < self.n_items)
+        ranks = np.full(len(u), -1, dtype=np.int64)
+        cand = np.full(len(u), -1, dtype=np.int64)
+        ranks[seen], cand[seen] = ctx.rank_items(u[seen], i[seen], use_bias=self._uses_bias, exclude_train=exclude_train)
+        return ranks, cand
+
+    def evaluate_ranking(self, df, ks=(10,), exclude_train=True):
+        """recall / precision / hit rate / NDCG at every k of `ks`, MRR and mean percentile rank of the frame's pairs
+        (`src.evaluation.ranking.ranking_metrics`); rows with an unseen user or item count as skipped."""
+        from src.evaluation.ranking import ranking_metrics
+        ranks, cand = self.heldout_ranks(df, exclude_train=exclude_train)
+        return ranking_metrics(df["u"].to_numpy(dtype=int), ranks, cand, ks=ks)
+
     def close(self):
         """Release the device context(s) (predict is unavailable afterwards)."""
         for name in ("_ctx", "_shard_ctx"):
