@@ -348,16 +348,23 @@ __device__ __forceinline__ void pair_pad_chunk(Vec4<float> &v, int q, int kp, fl
 // rows 4 (l >> 4) + 0..3.  One step sweeps the pivot set Kb = {p .. p + 3}: with R = B[Kb, :] (4 x n, the pivot rows),
 // D = B[Kb, Kb] and U = R^T D^-1 (n x 4),
 //     B[i][j] -= U[i,:] R[:,j]  (i, j not in Kb),   B[i, Kb] = U[i,:],   B[Kb, j] = U[j,:]^T,   B[Kb, Kb] = -D^-1
-// -- four scalar sweeps in one.  All four cases come out of ONE MFMA per tile, without cancellation, when
+// -- four scalar sweeps in one.  D^-1 is never formed: with D = L diag(d) L^T (L unit lower triangular), W = L^-1 and
+// Y = W R (4 x n), U = Y^T diag(1/d) W and U R = Y^T diag(1/d) Y -- the four rank-1 updates of the scalar sweep, every
+// term as well scaled as there.  (Multiplying R by an explicit D^-1 loses cond(D) digits more than the scalar sweep: a
+// nearly singular pivot block whose rows couple to a row outside it -- three of four equicorrelated rows in one block,
+// the fourth in the next -- then misses the error bound of DESIGN.md section 4.3 by a factor of 25 .. 100.)  All four
+// cases come out of ONE MFMA per tile when
 //   * the accumulator entries in the pivot rows and pivot columns are zeroed first,
-//   * the A operand (lane: row i, pivot index c) is -U[i][c], but D^-1[c][i - p] for the pivot rows themselves,
-//   * the B operand (lane: pivot index c, column j) is R[c][j], but -delta(c, j - p) for the pivot columns themselves:
-// a pivot row then receives  sum_c D^-1[c][k'] R[c][j] = U[j][k'],  a pivot column  sum_c (-U[i][c]) (-delta) = U[i][c'],
-// and the pivot block  sum_c D^-1[c][k'] (-delta(c, c')) = -D^-1.  The only data exchanged per step is the pivot panel R
+//   * the B operand (lane: pivot index c, column j) is Y[c][j], with -e_(j - p) in the place of R[:, j] for the pivot
+//     columns themselves, i.e. -W[c][j - p],
+//   * the A operand (lane: row i, pivot index c) is -(1 / d[c]) times the B operand of column i:
+// a pivot row k' then receives  sum_c (W[c][k'] / d[c]) Y[c][j] = U[j][k'],  a pivot column c'  sum_c (-Y[c][i] / d[c])
+// (-W[c][c']) = U[i][c'],
+// and the pivot block  sum_c (W[c][k'] / d[c]) (-W[c][c']) = -D^-1.  The only data exchanged per step is the pivot panel R
 // (128 x 4 floats, double-buffered in LDS): its owner -- the 16 lanes that hold those four rows in their four
 // accumulator registers -- writes it as one float4 per column as soon as that tile row has been updated (the tile row
 // of the NEXT pivots is updated first), so the panel's write -> barrier -> read trip runs under the remaining MFMAs.
-// Every wave inverts the 4 x 4 pivot block itself (scalar sweep in registers, identical on all lanes).  Per step a
+// Every wave factors the 4 x 4 pivot block itself (in registers, identical on all lanes).  Per step a
 // wave issues TH x TT MFMAs (32 at K = 128: 1024 matrix-pipe cycles) and about 150 VALU instructions, against the
 // 128 LDS-broadcast-bound scalar pivots x 85 VALU instructions of the VALU splits it replaced.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -434,49 +441,50 @@ __device__ __forceinline__ void pair_solve_mfma_wave(float *img, float *rt, floa
         const int p = 4 * s, Ip = p >> 4, q = p & 15, qg = q >> 2;
         const float *rb = rt + (s & 1) * 512;
         __syncthreads();   // the panel of step s is visible; everybody has finished reading the other buffer
-        // D = B[Kb, Kb] (4 x 4, symmetric) -> -D^-1 by four scalar sweeps, identical on every lane
+        // D = B[Kb, Kb] (4 x 4, symmetric) = L diag(d) L^T, identical on every lane; W = L^-1 (unit lower triangular)
         float m[4][4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const float4 col = *reinterpret_cast<const float4 *>(rb + (p + c) * 4);
             m[0][c] = col.x; m[1][c] = col.y; m[2][c] = col.z; m[3][c] = col.w;
         }
+        float dinv[4], l[4][4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float pinv = rcp_nr(m[k][k]);
-            float u[4];
+            dinv[k] = rcp_nr(m[k][k]);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) u[i] = m[i][k] * pinv;
+            for (int i = k + 1; i < 4; ++i) l[i][k] = m[i][k] * dinv[k];
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = k + 1; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (i != k && j != k) m[i][j] = fmaf(-u[i], m[k][j], m[i][j]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i != k) m[i][k] = m[k][i] = u[i];
-            m[k][k] = -pinv;
+                for (int j = k + 1; j <= i; ++j) m[i][j] = fmaf(-l[i][k], m[j][k], m[i][j]);   // (the lower triangle)
         }
-        // dcol[k] = D^-1[k][lg] (this lane's pivot index as an A operand) = -m[k][lg]
-        float dcol[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dcol[k] = -(lg == 0 ? m[k][0] : lg == 1 ? m[k][1] : lg == 2 ? m[k][2] : m[k][3]);
+        const float w10 = -l[1][0];
+        const float w21 = -l[2][1], w20 = fmaf(-l[2][1], w10, -l[2][0]);
+        const float w32 = -l[3][2], w31 = fmaf(-l[3][2], w21, -l[3][1]);
+        const float w30 = fmaf(-l[3][2], w20, fmaf(-l[3][1], w10, -l[3][0]));
+        // this lane's pivot index is lg: row lg of W, and -1 / d[lg]
+        const float wr0 = lg == 0 ? 1.f : lg == 1 ? w10 : lg == 2 ? w20 : w30;
+        const float wr1 = lg == 0 ? 0.f : lg == 1 ? 1.f : lg == 2 ? w21 : w31;
+        const float wr2 = lg <= 1 ? 0.f : lg == 2 ? 1.f : w32;
+        const float wr3 = lg == 3 ? 1.f : 0.f;
+        const float ndinv = -(lg == 0 ? dinv[0] : lg == 1 ? dinv[1] : lg == 2 ? dinv[2] : dinv[3]);
         const int cq = lc - q;                      // 0..3 when this lane's row / column index is a pivot
         const bool piv = cq >= 0 && cq < 4;
-        const float apiv = cq == 0 ? dcol[0] : cq == 1 ? dcol[1] : cq == 2 ? dcol[2] : dcol[3];   // D^-1[lg][cq]
+        // y[c][j] = (W R)[c][j] for this lane's column j and c = lg, with -e_(j - p) in the place of R[:, j] for the pivot
+        // columns themselves: the B operand.  The A operand of row i is -y[c][i] / d[c] (update_row).
         float bop[TT];
 #pragma unroll
         for (int J = 0; J < TT; ++J) {
-            bop[J] = rb[(16 * J + lc) * 4 + lg];
-            if (J == Ip && piv) bop[J] = (lg == cq) ? -1.f : 0.f;
+            float4 x = *reinterpret_cast<const float4 *>(rb + (16 * J + lc) * 4);
+            if (J == Ip && piv) x = make_float4(cq == 0 ? -1.f : 0.f, cq == 1 ? -1.f : 0.f, cq == 2 ? -1.f : 0.f, cq == 3 ? -1.f : 0.f);
+            bop[J] = fmaf(wr3, x.w, fmaf(wr2, x.z, fmaf(wr1, x.y, wr0 * x.x)));
         }
         auto update_row = [&](auto ii_tag) {
             constexpr int ii = decltype(ii_tag)::value;
-            const int I = base + ii;
-            const float4 x = *reinterpret_cast<const float4 *>(rb + (16 * I + lc) * 4);
-            float a = -fmaf(x.w, dcol[3], fmaf(x.z, dcol[2], fmaf(x.y, dcol[1], x.x * dcol[0])));
+            constexpr int I = base + ii;
+            const float a = ndinv * bop[I < TT ? I : 0];   // (I >= TT: a tile row this wave does not have, never run)
             const bool prow = I == Ip;              // wave-uniform
-            if (prow && piv) a = apiv;
             // the accumulator entries of the pivot rows (tile row Ip) and pivot columns (tile column Ip) start from zero.
             // Wave-uniform BRANCHES around the selects (the empty asm keeps the compiler from turning them back into
             // selects on every tile): vector instructions take their issue cycles from the fp32 matrix pipe
@@ -586,7 +594,7 @@ __global__ __launch_bounds__(128, 2) void gauss_solve_pair_kernel(SolveParams<fl
 // Both waves fold their blocks into the shared LDS image; a complete row is then
 // solved in place by the same two waves (pair_solve_mfma).
 // NT = chunk columns per wave (host picks the smallest that covers ceil(chunks / 2) / 64):
-// 17 for K = 128 (1032 chunks per wave), 13 for K <= 112, 9 for K <= 92.
+// 17 for K = 128 (1032 chunks per wave), 13 for K <= 114, 9 for K <= 95.
 template <int NT, bool FUSE, int MT = 0>
 __global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams<float> p, float inv_sigma2, float inv_eta2,
                                                                      float *cov_self, float *factor_self) {
@@ -658,7 +666,7 @@ __global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams
         // load) instead of being kept live -- and spilled -- across the loop
         int qb = q_begin + lane;
         asm volatile("" : "+v"(qb));
-        // NT <= 9 (K <= 92) leaves registers for BOTH ratings of the pair in flight (2 x 36 load registers):
+        // NT <= 9 (K <= 95) leaves registers for BOTH ratings of the pair in flight (2 x 36 load registers):
         // more bytes outstanding per streaming wave, which matters while the CU's other blocks are solving
         constexpr bool BOTH = NT <= 9;
         float4 a[NT], a2[BOTH ? NT : 1];
@@ -1432,7 +1440,14 @@ static void launch_accum_mfma(pmf_ctx *ctx, const GaussParams<float> &p, dim3 gr
     }
 }
 
-// MT = 16-row tiles per dimension of the fused MFMA block sweep (ceil(K / 16): 5..8)
+// MT = 16-row tiles per dimension of the fused MFMA block sweep: ceil(K / 16), from K alone.  NT follows the chunk
+// count and its classes end elsewhere (NT = 9 reaches K = 95, NT = 13 K = 114), so NT = 13 meets MT = 8 at K = 113, 114.
+template <int NT, int MT>
+static void launch_accum_mfma128_fused(pmf_ctx *ctx, const GaussParams<float> &p, dim3 grid, size_t smem, float is2, float ie2,
+                                       float *cov, float *fac) {
+    hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, true, MT>), grid, dim3(128), smem, ctx->stream, p, is2, ie2, cov, fac);
+}
+
 template <int NT>
 static void launch_accum_mfma128(pmf_ctx *ctx, const GaussParams<float> &p, dim3 grid, size_t smem, bool fuse, float is2,
                                  float ie2, float *cov, float *fac) {
@@ -1441,15 +1456,16 @@ static void launch_accum_mfma128(pmf_ctx *ctx, const GaussParams<float> &p, dim3
                            (float *)nullptr, (float *)nullptr);
         return;
     }
-    const int mt = (ctx->K + 15) / 16;
-    if constexpr (NT == 9) {          // K <= 92
-        if (mt <= 5) hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, true, 5>), grid, dim3(128), smem, ctx->stream, p, is2, ie2, cov, fac);
-        else hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, true, 6>), grid, dim3(128), smem, ctx->stream, p, is2, ie2, cov, fac);
-    } else if constexpr (NT == 13) {  // K <= 112
-        if (mt <= 6) hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, true, 6>), grid, dim3(128), smem, ctx->stream, p, is2, ie2, cov, fac);
-        else hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, true, 7>), grid, dim3(128), smem, ctx->stream, p, is2, ie2, cov, fac);
-    } else {
-        hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, true, 8>), grid, dim3(128), smem, ctx->stream, p, is2, ie2, cov, fac);
+    const int mt = (ctx->K + 15) / 16;   // 5..8
+    if constexpr (NT == 9) {          // 64 < K <= 95: 5 or 6 tiles
+        if (mt <= 5) launch_accum_mfma128_fused<NT, 5>(ctx, p, grid, smem, is2, ie2, cov, fac);
+        else launch_accum_mfma128_fused<NT, 6>(ctx, p, grid, smem, is2, ie2, cov, fac);
+    } else if constexpr (NT == 13) {  // 96 <= K <= 114: 6, 7 or 8 tiles
+        if (mt <= 6) launch_accum_mfma128_fused<NT, 6>(ctx, p, grid, smem, is2, ie2, cov, fac);
+        else if (mt == 7) launch_accum_mfma128_fused<NT, 7>(ctx, p, grid, smem, is2, ie2, cov, fac);
+        else launch_accum_mfma128_fused<NT, 8>(ctx, p, grid, smem, is2, ie2, cov, fac);
+    } else {                          // 115 <= K <= 128: 8 tiles
+        launch_accum_mfma128_fused<NT, 8>(ctx, p, grid, smem, is2, ie2, cov, fac);
     }
 }
 
