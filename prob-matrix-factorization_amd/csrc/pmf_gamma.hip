@@ -572,7 +572,12 @@ template <typename T>
 static int run_gamma(pmf_ctx *ctx, int side, PmfPass pass, bool ext, void *stats, const GammaPriors &pr) {
     const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gamma_tasks, pass != PMF_PASS_FUSED);
     int rc;
-    if ((rc = check_gamma_inputs(ctx, side))) return rc;
+    if (pass == PMF_PASS_FINALIZE) {
+        // reads the statistics only, whichever accumulate wrote them: after pmf_gamma_exact_accumulate no FACTOR need exist
+        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_FACTOR))) return rc;
+    } else if ((rc = check_gamma_inputs(ctx, side))) {
+        return rc;
+    }
     if (pass != PMF_PASS_ACCUMULATE) {
         if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SHAPE))) return rc;
         if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_RATE))) return rc;
@@ -1200,6 +1205,222 @@ extern "C" int pmf_gamma_elbo_terms(pmf_ctx *ctx, int side, int with_data, int h
         pmf_set_error("pmf_gamma_elbo_terms: out of host memory");
         return PMF_ENOMEM;
     }
+}
+
+// ---------------------------------------------------------------------------
+// exact coordinate-ascent half-sweep (pmf_gamma_exact_sweep / pmf_gamma_exact_accumulate)
+// ---------------------------------------------------------------------------
+// The statistics of pmf_gamma_sweep with the weights of coordinate ascent on the bound: phi_jk = exp(s_jk - lse_j),
+// s_jk = Elog_side[r,k] + Elog_other[o_j,k], instead of E E / (E . E).  Both tables come from gamma_elbo_row_kernel
+// (psi in double) and are rebuilt by every call from SHAPE and RATE as they are, into a buffer of their own
+// (pmf_ctx::d_gamma_tables: pmf_gamma_elbo_terms writes the scratch buffer and cannot touch them).  The access shape is
+// gamma_elbo_data_kernel's: a lane group per task, the row's own E log in registers, the other row's (E log, E) pair
+// gathered from one 2 kpad block, UN gathers in flight.  Per rating one DPP max, one exp per element -- the same
+// e_k = exp(s_k - m) is the normaliser's addend and the weight's numerator -- one DPP sum and one division.
+// Log-sum-exp, not a dot product of exp(E log) tables, for the reason given at the ELBO data pass.  A pad is -inf in
+// the E log half and 0 in the E half: it adds 0 to both sums.  The epilogue is gamma_sweep_kernel's.
+template <typename T, int LPR, bool STATS>
+__global__ __launch_bounds__(256) void gamma_exact_kernel(GammaParams<T> p, const T *table_self, const T *table_other) {
+    constexpr int G = 256 / LPR;
+    constexpr int UN = LPR < 4 ? LPR : 4;
+    const int c = threadIdx.x % LPR;
+    const int64_t task_id = (int64_t)blockIdx.x * G + threadIdx.x / LPR;
+    if (task_id >= p.n_tasks) return;
+    const PmfTask t = p.tasks[task_id];
+    const int koff = c * PMF_VEC;
+    const int kpad = p.kpad;
+    const bool active = koff < kpad;
+    const T ninf = (T)(-INFINITY);
+
+    Vec4<T> sl;   // the row's own E log; a lane past kpad holds pads
+    sl.v[0] = sl.v[1] = sl.v[2] = sl.v[3] = ninf;
+    if (active) sl = load4(table_self + (int64_t)t.row * 2 * kpad + koff);
+    Vec4<T> acc_a = zero4<T>(), acc_b = zero4<T>();
+    const int32_t *col = p.other + t.start;
+    const T *val = p.val + t.start;
+
+    for (int base = 0; base < t.len; base += LPR) {
+        const int n = min(LPR, t.len - base);
+        int my_o = 0;
+        T my_x = (T)0;
+        if (c < n) {
+            my_o = col[base + c];
+            my_x = val[base + c];
+        }
+        for (int tt = 0; tt < n; tt += UN) {
+            int o[UN];
+            T xv[UN];
+            Vec4<T> bl[UN], be[UN];
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                o[q] = __shfl(my_o, tt + q, LPR);   // (lanes past the batch hold id 0: a valid row, loaded and not used)
+                xv[q] = __shfl(my_x, tt + q, LPR);
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                bl[q] = sl;   // (-inf in every element: what an inactive lane contributes)
+                be[q] = zero4<T>();
+                if (active) {
+                    const T *src = table_other + (int64_t)o[q] * 2 * kpad + koff;
+                    bl[q] = load4(src);
+                    be[q] = load4(src + kpad);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                if (tt + q < n) {
+                    T s[PMF_VEC], ex[PMF_VEC];
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) s[e] = sl.v[e] + bl[q].v[e];
+                    const T m = group_max<LPR>(vmax(vmax(s[0], s[1]), vmax(s[2], s[3])));
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) ex[e] = exp(s[e] - m);   // (a pad is -inf: exp gives 0)
+                    T z = ex[0];
+                    z += ex[1];
+                    z += ex[2];
+                    z += ex[3];
+                    z = group_sum<LPR>(z);   // >= 1: the largest element adds exp(0)
+                    const T w = xv[q] / z;
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) {
+                        acc_a.v[e] += w * ex[e];
+                        acc_b.v[e] += be[q].v[e];
+                    }
+                }
+            }
+        }
+    }
+
+    if (t.slot >= 0) {
+        if (active) {
+            T *slot = p.partial + (int64_t)t.slot * p.pw;
+            store4(slot + koff, acc_a);
+            store4(slot + kpad + koff, acc_b);
+        }
+    } else if (STATS) {
+        if (active) {
+            T *dst = p.stats + (int64_t)t.row * 2 * kpad + koff;
+            store4(dst, acc_a);
+            store4(dst + kpad, acc_b);
+        }
+    } else {
+        gamma_finalize_row<T, LPR, false>(p, t.row, c, active, acc_a, acc_b, (T)0, t.len == 0);
+    }
+}
+
+static int check_gamma_exact_inputs(pmf_ctx *ctx, int side, const char *what) {
+    int rc;
+    for (int s : {side, 1 - side}) {
+        if ((rc = pmf_require_array(ctx, s, PMF_ARR_SHAPE, what))) return rc;
+        if ((rc = pmf_require_array(ctx, s, PMF_ARR_RATE, what))) return rc;
+    }
+    PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "%s: ratings have not been set", what);
+    PMF_REQUIRE(pmf_lanes_per_row(ctx->kpad) <= 64, PMF_ERANGE, "%s: unsupported n_factors %d", what, ctx->K);
+    return PMF_OK;
+}
+
+// the user table, then the item table: the same bytes whichever side a call sweeps, so the buffer grows once
+template <typename T>
+static T *gamma_exact_table(const pmf_ctx *ctx, int side) {
+    return ctx->d_gamma_tables.as<T>() + (side == PMF_SIDE_USER ? 0 : (size_t)ctx->rows[PMF_SIDE_USER] * 2 * ctx->kpad);
+}
+
+// Both sides' (E log, E) tables from SHAPE and RATE as they are now, on the context's stream (timed as the row pass).
+template <typename T>
+static int gamma_exact_build_tables(pmf_ctx *ctx) {
+    const int kpad = ctx->kpad;
+    int rc;
+    if ((rc = ctx->d_gamma_tables.reserve(ctx, (size_t)(ctx->rows[0] + ctx->rows[1]) * 2 * kpad * sizeof(T), {ctx->stream}))) return rc;
+    PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
+    for (int s = 0; s < 2; ++s) {
+        GammaElboRowParams<T> r;
+        r.shape = ctx->arr[s][PMF_ARR_SHAPE].as<const T>();
+        r.rate = ctx->arr[s][PMF_ARR_RATE].as<const T>();
+        r.hyper_rate = nullptr;
+        r.table = gamma_exact_table<T>(ctx, s);
+        r.out = nullptr;
+        r.rows = ctx->rows[s];
+        r.K = ctx->K;
+        r.kpad = kpad;
+        if (r.rows > 0)
+            pmf_with_pow2<1>(pmf_lanes_per_row(kpad), [&](auto L) {
+                constexpr int G = 256 / L;
+                hipLaunchKernelGGL((gamma_elbo_row_kernel<T, L>), dim3((unsigned)((r.rows + G - 1) / G)), dim3(256), 0, ctx->stream, r);
+            });
+    }
+    PMF_HIP_CHECK(hipGetLastError());
+    return PMF_OK;
+}
+
+// the exact kernel over the tasks, then the reference sweep's split kernel over the rows cut into several tasks
+template <typename T, int LPR, bool STATS>
+static void launch_gamma_exact(pmf_ctx *ctx, const GammaParams<T> &p, const T *table_self, const T *table_other, const PmfTaskView &tl) {
+    constexpr int G = 256 / LPR;
+    if (tl.n_tasks > 0) {
+        PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
+        hipLaunchKernelGGL((gamma_exact_kernel<T, LPR, STATS>), dim3((unsigned)((tl.n_tasks + G - 1) / G)), dim3(256), 0, ctx->stream, p,
+                           table_self, table_other);
+    }
+    if (tl.n_split > 0) {
+        PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
+        size_t smem = (size_t)G * 2 * ctx->kpad * sizeof(T);
+        hipLaunchKernelGGL((gamma_split_kernel<T, LPR, STATS, false>), dim3((unsigned)tl.n_split), dim3(256), smem, ctx->stream, p);
+    }
+}
+
+// PMF_PASS_FUSED or PMF_PASS_ACCUMULATE (finalize is run_gamma's).  The caller has checked the inputs and, with
+// `tables` false, built the tables itself.
+template <typename T>
+static int run_gamma_exact(pmf_ctx *ctx, int side, PmfPass pass, bool tables, void *stats, const GammaPriors &pr) {
+    const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gamma_tasks, pass != PMF_PASS_FUSED);
+    int rc;
+    if (pass == PMF_PASS_FUSED) {
+        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_FACTOR))) return rc;   // (written, never read)
+        if (pr.hierarchical && (rc = pmf_alloc_array(ctx, side, PMF_ARR_HYPER_RATE))) return rc;
+    }
+    const int pw = 2 * ctx->kpad;
+    if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * pw * sizeof(T)))) return rc;
+    if (tables && (rc = gamma_exact_build_tables<T>(ctx))) return rc;
+    const GammaParams<T> p = gamma_params<T>(ctx, side, tl, stats, pr, pw);
+    const T *table_self = gamma_exact_table<T>(ctx, side), *table_other = gamma_exact_table<T>(ctx, 1 - side);
+    return gamma_launch(ctx, [&](auto L) {
+        if (pass == PMF_PASS_ACCUMULATE)
+            launch_gamma_exact<T, L, true>(ctx, p, table_self, table_other, tl);
+        else
+            launch_gamma_exact<T, L, false>(ctx, p, table_self, table_other, tl);
+    });
+}
+
+extern "C" int pmf_gamma_exact_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior,
+                                     int hierarchical, double hyper_shape, double hyper_rate_prior) {
+    PMF_SIDE_ENTRY("pmf_gamma_exact_sweep");
+    const GammaPriors pr = {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior};
+    int rc;
+    if ((rc = check_gamma_exact_inputs(ctx, side, "pmf_gamma_exact_sweep"))) return rc;
+    if (hierarchical && (rc = pmf_require_array(ctx, side, PMF_ARR_PRIOR_RATE, "pmf_gamma_exact_sweep (hierarchical)"))) return rc;
+    return pmf_with_dtype(ctx, [&](auto t) {
+        using T = decltype(t);
+        if (side != PMF_SIDE_ITEM || !pmf_comm_active(ctx)) return run_gamma_exact<T>(ctx, side, PMF_PASS_FUSED, true, nullptr, pr);
+        // several ranks: pmf_gamma_sweep's exchange with the exact accumulate; the tables are built once, on the compute
+        // stream, before the first chunk (finalize writes SHAPE and RATE of chunk c while later chunks still read the tables)
+        const PmfExchange ex = {false, pr.hierarchical ? 5 : 3,
+                                {PMF_ARR_FACTOR, PMF_ARR_SHAPE, PMF_ARR_RATE, PMF_ARR_PRIOR_RATE, PMF_ARR_HYPER_RATE}};
+        int rc;
+        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_FACTOR))) return rc;
+        if (pr.hierarchical && (rc = pmf_alloc_array(ctx, side, PMF_ARR_HYPER_RATE))) return rc;
+        if ((rc = gamma_exact_build_tables<T>(ctx))) return rc;
+        return pmf_comm_half_sweep(ctx, side, 0, (size_t)2 * ctx->kpad, true, ex,
+                                   [&](void *s) { return run_gamma_exact<T>(ctx, side, PMF_PASS_ACCUMULATE, false, s, GammaPriors()); },
+                                   [&](void *s) { return run_gamma<T>(ctx, side, PMF_PASS_FINALIZE, false, s, pr); });
+    });
+}
+
+extern "C" int pmf_gamma_exact_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
+    PMF_SIDE_ENTRY("pmf_gamma_exact_accumulate");
+    PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gamma_exact_accumulate: null stats buffer");
+    int rc;
+    if ((rc = check_gamma_exact_inputs(ctx, side, "pmf_gamma_exact_accumulate"))) return rc;
+    return pmf_with_dtype(ctx, [&](auto t) { return run_gamma_exact<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, true, stats_dev, {}); });
 }
 
 // Profiling aid (no reference counterpart): average device time of `repeats` launches of the

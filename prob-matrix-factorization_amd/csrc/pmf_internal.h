@@ -194,6 +194,9 @@ struct pmf_ctx {
 
     // scratch, grown on demand (pmf_ensure_*)
     PmfBuf d_partial, d_scratch;
+    // pmf_gamma_exact_sweep / _accumulate: the (E log, E) tables [rows][2][kpad] of the users, then of the items; rebuilt
+    // by every call, in storage of their own so that a pmf_gamma_elbo_terms call (d_scratch) cannot write over them
+    PmfBuf d_gamma_tables;
     PmfBuf h_pinned{PmfBuf::PINNED};
 
     // diagnostic switches, read from the environment once when the context is created

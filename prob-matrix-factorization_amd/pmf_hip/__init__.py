@@ -85,6 +85,8 @@ SIGNATURES = {
     "pmf_ctx_kpad": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "pmf_gamma_accumulate": (C.c_int, [_p, C.c_int, _p]),
     "pmf_gamma_finalize": (C.c_int, [_p, C.c_int, _p, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]),
+    "pmf_gamma_exact_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]),
+    "pmf_gamma_exact_accumulate": (C.c_int, [_p, C.c_int, _p]),
     "pmf_gauss_factor_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),
     "pmf_gauss_bias_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),
     "pmf_gauss_fold_in": (C.c_int, [_p, C.c_int, C.c_int64, _i64p, _i32p, _f64p, C.c_double, C.c_double, C.c_double, C.c_int,

@@ -276,16 +276,20 @@ def _fused_item(comm):
     return (not distributed(comm)) or getattr(comm, "in_library", False)
 
 
-def gamma_iteration(engine, comm, stats_item, user_prior, item_prior):
+def gamma_iteration(engine, comm, stats_item, user_prior, item_prior, exact=False):
     """Poisson MF / HPF.  `*_prior` = (shape_prior, rate_prior, hierarchical,
     hyper_shape, hyper_rate_prior) as taken by `gamma_sweep`.  `stats_item` is only used with an
-    external collective: the [I x 2 x Kpad] buffer object with `.ptr` and `.tensor`."""
-    engine.gamma_sweep(USER, *user_prior)
+    external collective: the [I x 2 x Kpad] buffer object with `.ptr` and `.tensor`.  `exact`: the
+    exact coordinate-ascent update (`gamma_exact_sweep` / `gamma_exact_accumulate`) instead of the
+    reference's."""
+    sweep = engine.gamma_exact_sweep if exact else engine.gamma_sweep
+    sweep(USER, *user_prior)
     if _fused_item(comm):
-        engine.gamma_sweep(ITEM, *item_prior)
+        sweep(ITEM, *item_prior)
         return
+    accumulate = engine.gamma_exact_accumulate if exact else engine.gamma_accumulate
     _item_half_sweep(engine, comm, stats_item, 2 * engine.kpad,
-                     lambda: engine.gamma_accumulate(ITEM, stats_item.ptr),
+                     lambda: accumulate(ITEM, stats_item.ptr),
                      lambda: engine.gamma_finalize(ITEM, stats_item.ptr, *item_prior))
 
 

@@ -283,6 +283,18 @@ class Context:
                                            float(hyper_shape), float(hyper_rate_prior)),
               "pmf_gamma_finalize")
 
+    def gamma_exact_sweep(self, side, shape_prior, rate_prior, hierarchical=False, hyper_shape=0.0,
+                          hyper_rate_prior=0.0):
+        """`gamma_sweep` with the weights of exact coordinate ascent on the bound (`pmf_gamma_exact_sweep`): reads SHAPE
+        and RATE of both sides, not FACTOR."""
+        check(self._lib.pmf_gamma_exact_sweep(self._h, side, float(shape_prior), float(rate_prior),
+                                              int(bool(hierarchical)), float(hyper_shape),
+                                              float(hyper_rate_prior)), "pmf_gamma_exact_sweep")
+
+    def gamma_exact_accumulate(self, side, stats_ptr):
+        """The raw sums of `gamma_exact_sweep` in `gamma_accumulate`'s layout; `gamma_finalize` finalises them."""
+        check(self._lib.pmf_gamma_exact_accumulate(self._h, side, C.c_void_p(stats_ptr)), "pmf_gamma_exact_accumulate")
+
     # ---- Gaussian -------------------------------------------------------
     def gauss_factor_sweep(self, side, sigma2, eta2):
         check(self._lib.pmf_gauss_factor_sweep(self._h, side, float(sigma2), float(eta2)),

@@ -53,6 +53,19 @@ def check_tracking(model, track_elbo, elbo_tol, train_df):
     return track
 
 
+def check_update(update, train_df):
+    """`fit`'s `update` argument -> whether the fit runs the exact coordinate-ascent row update; refuses an unknown mode
+    and, for the exact update, a negative rating (its weights multiply the rating: the Poisson likelihood is not defined
+    for one), before any device call.  The frame is looked at only under "exact"."""
+    if update not in ("reference", "exact"):
+        raise ValueError(f"update must be 'reference' or 'exact', not {update!r}")
+    if update == "exact":
+        ratings = train_df["rating"].to_numpy(dtype=float)
+        if len(ratings) and float(np.min(ratings)) < 0:
+            raise ValueError("update='exact': a training rating is negative; the Poisson likelihood is not defined for it")
+    return update == "exact"
+
+
 def model_elbo(model, ctx):
     """(value, parts) for the state `ctx` holds: the data term from the user side, whose gathers hit the smaller item
     table, and the item side without data."""

@@ -82,15 +82,21 @@ class HPF_CAVI(DeviceModel):
         cfg = self.config
         return (cfg.a, cfg.a_prime, cfg.b_prime), (cfg.c, cfg.c_prime, cfg.d_prime), True
 
-    def fit(self, train_df, val_df=None, *, track_elbo=False, elbo_tol=None):
+    def fit(self, train_df, val_df=None, *, track_elbo=False, elbo_tol=None, update="reference"):
         """`track_elbo`: evaluate the evidence lower bound after every iteration (`history_["elbo"]`, an `ELBO:` line
         when verbose; measured at K = 64 fp32, 1M users, 50M ratings: the user call's two kernels take 3.00 times a user
         half-sweep (the data pass 2.34 times the sweep's gather ceiling); an `elbo()` takes 5.27 times a whole iteration by wall
         clock, 1.30 times in kernel time -- the rest is the download and the host's sum of the per-row terms).  `elbo_tol` (implies `track_elbo`): stop when (L_t - L_{t-1}) / |L_{t-1}| falls below
         it -- an early stop that needs no `val_df`.  The rule also fires on a DECREASE, which can happen here: the
         reference's row update weights the factors with E[theta] E[beta] / (E[theta] . E[beta]) where exact CAVI uses
-        exp(E log theta + E log beta), so an iteration is not exact coordinate ascent on this bound."""
+        exp(E log theta + E log beta), so an iteration is not exact coordinate ascent on this bound.
+        `update`: "reference" (default) runs the reference's row update, which weights a rating's factors with
+        E[theta] E[beta] / (E[theta] . E[beta]); "exact" runs coordinate ascent on the bound (`pmf_gamma_exact_sweep`: weights
+        exp(E log theta + E log beta), normalised, formed from the shapes and rates), under which the bound cannot fall from
+        one half-sweep to the next, except by rounding.  `history_["update"]` records the mode.  A negative training rating
+        is refused under "exact".  Cost of an exact half-sweep: DESIGN.md section 4.12."""
         cfg = self.config
+        exact = _gamma_elbo.check_update(update, train_df)
         track_elbo = _gamma_elbo.check_tracking(self, track_elbo, elbo_tol, train_df)
         self._infer_dimensions(train_df)
         self._initialize()
@@ -103,6 +109,12 @@ class HPF_CAVI(DeviceModel):
         ctx.set_array(ITEM, ARR_FACTOR, self.E_beta)
         ctx.set_array(USER, ARR_PRIOR_RATE, self._mine(self.E_xi))
         ctx.set_array(ITEM, ARR_PRIOR_RATE, self.E_eta)
+        self.history_["update"] = update
+        if exact:      # q is its shapes and rates: the exact update reads them, not FACTOR
+            ctx.set_array(USER, ARR_SHAPE, self._mine(self.gamma_a_theta))
+            ctx.set_array(USER, ARR_RATE, self._mine(self.gamma_b_theta))
+            ctx.set_array(ITEM, ARR_SHAPE, self.gamma_a_beta)
+            ctx.set_array(ITEM, ARR_RATE, self.gamma_b_beta)
         user_prior = (cfg.a, 0.0, True, self.gamma_a_xi, cfg.b_prime)
         item_prior = (cfg.c, 0.0, True, self.gamma_a_eta, cfg.d_prime)
         monitor = self._monitor_setup(val_df)
@@ -111,7 +123,7 @@ class HPF_CAVI(DeviceModel):
             if cfg.verbose:
                 print(f"\nHPF_CAVI iteration {it}/{cfg.max_iter}")
             # theta then xi (hpf_cavi.py:126-159); beta then eta (hpf_cavi.py:162-193)
-            self._run_iteration(lambda: pdist.gamma_iteration(ctx, self._comm, None, user_prior, item_prior))
+            self._run_iteration(lambda: pdist.gamma_iteration(ctx, self._comm, None, user_prior, item_prior, exact=exact))
             self._tick(it)
             elbo_stop = track_elbo and _gamma_elbo.record_elbo(self, ctx, it, elbo_tol)
             if monitor is not None:    # (before the ELBO stop: every iteration that ran has its validation entries)
@@ -145,12 +157,13 @@ class HPF_CAVI(DeviceModel):
         u, i, rating; `u` holds arbitrary labels.  The item side stays frozen; each user gets `n_iter` theta / xi updates
         (hpf_cavi.py:126-159) from the prior mean, on the device (`pmf_gamma_fold_in`), without a refit.  Rows with an
         item id the fit has not seen are dropped; a user left without ratings runs the same updates on empty sums.
-        Returns a `GammaFoldIn`, one row per label in sorted order."""
+        The row update is the reference's even for a model fitted with `update="exact"`.  Returns a `GammaFoldIn`, one row per label in sorted order."""
         cfg = self.config
         return gamma_fold_in(self, USER, df, n_iter, (cfg.a, 0.0, True, cfg.a_prime + cfg.n_factors * cfg.a, cfg.b_prime))
 
     def fold_in_items(self, df, n_iter=10):
-        """The same for new items (labels in column `i`) against the fitted users (hpf_cavi.py:162-193)."""
+        """The same for new items (labels in column `i`) against the fitted users (hpf_cavi.py:162-193); the reference's
+        row update here too, whatever `update` the fit ran."""
         cfg = self.config
         return gamma_fold_in(self, ITEM, df, n_iter, (cfg.c, 0.0, True, cfg.c_prime + cfg.n_factors * cfg.c, cfg.d_prime))
 
