@@ -344,6 +344,65 @@ int pmf_gamma_exact_sweep(pmf_ctx *ctx, int side, double shape_prior, double rat
                           int hierarchical, double hyper_shape, double hyper_rate_prior);
 int pmf_gamma_exact_accumulate(pmf_ctx *ctx, int side, void *stats_dev);
 
+/* Posterior predictive of the Poisson MF and HPF models for n (user, item) pairs: mean and variance of the rate under
+ * q and, with ratings, three log densities of the count.  No reference counterpart beyond PLUGIN (the reference's
+ * PoissonLogPredictiveLikelihood, metrics.py:53-66, on the host).  q is defined by SHAPE and RATE alone, as for
+ * pmf_gamma_elbo_terms: FACTOR, PRIOR_RATE and HYPER_RATE are not read, so one call serves both models.  For pair
+ * (u, i) write a, b = SHAPE, RATE of user u and c, d = SHAPE, RATE of item i, k < K, x the pair's rating:
+ *     E_k      = (a_k / b_k)(c_k / d_k)
+ *     out_mean = mu = sum_k E_k                                       = E_q[theta_u . beta_i]
+ *     out_var  = v  = sum_k E_k^2 (1/a_k + 1/c_k + 1/(a_k c_k))       = Var_q[theta_u . beta_i]
+ *                                                  (E[theta^2] = (a/b)^2 (1 + 1/a); the factors are independent under q)
+ *     PLUGIN   x log lambda - lambda - lgamma(x + 1),   lambda = max(mu, 1e-10)
+ *                                                  (PoissonLogPredictiveLikelihood at E theta, E beta, clamp included)
+ *     BOUND    x lse_k(psi(a_k) - log b_k + psi(c_k) - log d_k) - mu - lgamma(x + 1)
+ *                                                  (the data term of pmf_gamma_elbo_terms on a held-out pair; <= PLUGIN
+ *                                                   for x >= 0 by Jensen's inequality)
+ *     NEGBIN   log NB(x; r, mu),  r = mu^2 / v:
+ *              lgamma(x + r) - lgamma(r) - lgamma(x + 1) + r log(r / (r + mu)) + x log(mu / (r + mu))
+ *                                                  (the rate moment-matched to a Gamma of mean mu and variance v; the
+ *                                                   count's predictive variance is mu + v)
+ * out_logp is n x PMF_GAMMA_PRED_KINDS, row-major.  totals[0] = sum of out_var, totals[1 + kind] = sum of that column.
+ * NEGBIN is evaluated as  x log mu - lgamma(x + 1) - (r + x) log1p(mu / r) + D,  D = lgamma(x + r) - lgamma(r) - x log r:
+ * the literal form loses every digit once r passes about 1e8 (terms of size r log r leave one of size x), and shapes in
+ * the thousands make such r ordinary.  For r >= 10, D = (x + r - 1/2) log1p(x / r) - x + S(x + r) - S(r) with S the tail
+ * of Stirling's series; below that both lgammas are shifted up.  It tends to the unclamped Poisson term
+ * x log mu - mu - lgamma(x + 1) as v -> 0, and IS that term when v == 0 or r is not finite (x log mu = 0 at x = 0).
+ * Precision: mu and v are summed in the context's dtype by a lane group per pair (the 16-byte row gathers of
+ * pmf_predict); everything after them -- logs, lgamma terms -- is formed in double from the (mu, v) the call returns, so
+ * out_mean and out_var are the very bits out_logp was formed from.  BOUND's lse is a max-subtracted log-sum-exp in the
+ * context's dtype over (E log, E) tables whose psi is evaluated in double; it is never a product of exp tables.
+ * With with_bound != 0 both sides' tables ([rows][2][Kpad], context dtype) are rebuilt by every call from SHAPE and RATE
+ * as they are then, in the storage pmf_gamma_exact_sweep rebuilds its own tables in: every call of either kind writes
+ * them before it reads them, pmf_gamma_elbo_terms never touches them, so interleaved calls do not disturb each other;
+ * pmf_ctx_device_bytes may grow on the first call and does not grow after it.  With with_bound == 0 no table is built
+ * and no psi is evaluated; the BOUND column and total are then quiet NaN.
+ * Ratings need not be integers; for a negative rating the three densities are undefined (finite-time, the values mean
+ * nothing; the model classes refuse one).  With ratings == NULL only out_mean / out_var / totals[0] are produced:
+ * out_logp must be NULL, totals[1..3] are NaN and with_bound is ignored.
+ * totals are per-block partial sums in double, added in block order, staging round after staging round: no atomics, two
+ * calls give the same bits.  Pairs are staged in rounds of bounded scratch (2^20 pairs; PMF_GAMMA_PRED_PAIRS=n, read
+ * when the context is created, caps them), so n is unbounded.  The pair pass is timed as PMF_KERNEL_EVAL when ratings
+ * are given and PMF_KERNEL_PREDICT otherwise, the table pass as PMF_KERNEL_GAMMA_FINAL.  Reads the context only: model
+ * state, ratings, work lists and the stored validation set stay as they are; never a collective, with or without a
+ * communicator.  The extended Poisson model (SCALE arrays) is not covered.
+ * PMF_EINVAL, naming what is missing: null context (whatever n is), n < 0, a null id array, all four outputs null,
+ * out_logp without ratings, SHAPE or RATE of either side not set.  PMF_ERANGE: an id outside the trained dimensions (id
+ * and position named; unlike pmf_predict, which scores such a pair as 0), unsupported n_factors.  An argument error
+ * writes nothing; n = 0 touches nothing and returns 0.
+ * Cost: DESIGN.md section 4.13. */
+#define PMF_GAMMA_PRED_PLUGIN 0
+#define PMF_GAMMA_PRED_BOUND  1
+#define PMF_GAMMA_PRED_NEGBIN 2
+#define PMF_GAMMA_PRED_KINDS  3
+/* totals: [0] = sum of out_var, [1 + kind] = sum of out_logp[:, kind] */
+#define PMF_GAMMA_PRED_TOTALS 4
+int pmf_gamma_predictive(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, const int32_t *item_ids,
+                         const double *ratings /* n, may be NULL */, int with_bound,
+                         double *out_mean /* n, may be NULL */, double *out_var /* n, may be NULL */,
+                         double *out_logp /* n x PMF_GAMMA_PRED_KINDS, may be NULL */,
+                         double *totals /* [PMF_GAMMA_PRED_TOTALS], may be NULL */);
+
 /* ---- Gaussian MF half-sweeps -------------------------------------------
  * Factor half-sweep (gaussian_mf_cavi_bias.py:132-165 users, :170-201 items;
  * bias-free twin gaussian_mf_cavi.py:121-147 / :152-178 when no BIAS array is

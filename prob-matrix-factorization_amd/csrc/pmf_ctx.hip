@@ -202,6 +202,7 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
     if (const char *fr = getenv("PMF_FOLD_IN_ROWS")) ctx->fold_in_rows = std::max(atoll(fr), 0LL);
     if (const char *fl = getenv("PMF_GAMMA_FOLD_LONG")) ctx->gamma_fold_long = std::max(atoll(fl), 0LL);
     if (const char *er = getenv("PMF_ELBO_ROWS")) ctx->elbo_rows = std::max(atoll(er), 0LL);
+    if (const char *pp = getenv("PMF_GAMMA_PRED_PAIRS")) ctx->gamma_pred_pairs = std::max(atoll(pp), 0LL);
     if (const char *ex = getenv("PMF_COMM_EXCHANGE")) {
         if (!strcmp(ex, "allreduce")) ctx->exchange = PMF_EXCHANGE_ALLREDUCE;
         else if (!strcmp(ex, "scatter_gather")) ctx->exchange = PMF_EXCHANGE_SCATTER_GATHER;

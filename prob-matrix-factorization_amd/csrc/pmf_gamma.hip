@@ -1423,6 +1423,361 @@ extern "C" int pmf_gamma_exact_accumulate(pmf_ctx *ctx, int side, void *stats_de
     return pmf_with_dtype(ctx, [&](auto t) { return run_gamma_exact<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, true, stats_dev, {}); });
 }
 
+// ---------------------------------------------------------------------------
+// posterior predictive of a pair (pmf_gamma_predictive): mean, variance and three log densities of a count
+// ---------------------------------------------------------------------------
+// q is SHAPE and RATE of both sides (FACTOR is not read).  A lane group owns a batch of LPR consecutive pairs: lane j
+// loads pair j's ids (one coalesced read) and hands them out by __shfl, as the sweeps hand out a task's ratings.  Per
+// pair the whole group works in predict_pair's layout: lane c owns elements [4c, 4c + 4) of the four gathered rows (a, b
+// of the user, c, d of the item; UN pairs' gathers in flight), forms E_k = (a/b)(c/d) and E_k^2 (1/a + 1/c + 1/(a c)) for
+// its elements in the context dtype, and two DPP sums give the pair's mean and variance.  Under BOUND the E log halves
+// of the two table rows (gamma_elbo_row_kernel's, psi in double) are gathered as well and lse_k(E log + E log) is a DPP
+// max, one exp per element and a DPP sum, as in the ELBO's data pass.  Lane j keeps pair j's three numbers; after the
+// batch every lane converts ITS pair's (mean, var) to double and forms every log and lgamma term from those two numbers
+// -- what the call returns as mean and var are the bits the densities were formed from -- so the double arithmetic (seven
+// logarithms a pair) runs on all lanes of the wavefront instead of on one lane in LPR, and the ratings are read and the
+// outputs written one pair per lane, coalesced.  A lane's sums over its pairs, a DPP sum over the group, the groups of a
+// block in group order through LDS, the blocks in block order on the host: no atomics, the same bits every time.
+
+// S(y) = sum_{n=1..6} B_2n / (2n (2n - 1) y^(2n-1)), the tail of Stirling's series (gamma_log_factorial's); y >= 10
+__device__ __forceinline__ double gamma_stirling_tail(double y) {
+    const double r = 1.0 / y, r2 = r * r;
+    return r * (1.0 / 12 - r2 * (1.0 / 360 - r2 * (1.0 / 1260 - r2 * (1.0 / 1680 - r2 * (1.0 / 1188 - r2 * (691.0 / 360360))))));
+}
+
+// log(1 + t), t > -1, from log alone: with u = fl(1 + t), log(u) t / (u - 1) -- the quotient puts back what the rounding
+// of 1 + t lost (t itself where u == 1).  A few ulp.  The library's log1p stays out of the kernel for the reason its
+// lgamma does: a second table of coefficients that the compiler keeps in registers across the pair loop.
+__device__ __forceinline__ double gamma_log1p(double t) {
+    const double u = 1.0 + t;
+    return u == 1.0 ? t : log(u) * (t / (u - 1.0));
+}
+
+// D(x, r) = lgamma(x + r) - lgamma(r) - x log r, the part of the negative binomial's log density that vanishes as
+// r -> inf.  Its three terms are of size r log r and leave x^2 / (2 r): past r ~ 1e8 nothing of D survives in double.
+// Stirling's series of both lgammas with the x log r and the r log r parts cancelled by hand gives, for r >= 10,
+//     D(x, r) = (x + r - 1/2) log1p(x / r) - x + S(x + r) - S(r),
+// whose terms are of size x.  Below 10 both arguments are shifted up by the same n <= 10 steps to s = r + n:
+//     D(x, r) = D(x, s) + x log(s / r) - log prod_{j<n} (x + r + j) / (r + j).
+__device__ __forceinline__ double gamma_negbin_excess(double x, double r) {
+    double s = r, num = 1.0, den = 1.0;
+    for (int n = 0; n < 10 && s < 10.0; ++n) {
+        num *= x + s;
+        den *= s;
+        s += 1.0;
+    }
+    const double d = (x + s - 0.5) * gamma_log1p(x / s) - x + gamma_stirling_tail(x + s) - gamma_stirling_tail(s);
+    return s == r ? d : d + x * log(s / r) - log(num / den);
+}
+
+template <typename T>
+struct GammaPredParams {
+    const int32_t *u, *i;   // [n] ids inside the trained dimensions (the host has checked them)
+    int64_t n;
+    const T *shape_u, *rate_u, *shape_i, *rate_i;   // [rows][kpad]
+    const T *table_u, *table_i;                     // [rows][2][kpad], BOUND only
+    const double *x;        // [n] ratings, or null: the moments only
+    double *mean, *var;     // [n], or null
+    double *logp;           // [n][PMF_GAMMA_PRED_KINDS], or null
+    double *block_out;      // [grid][PMF_GAMMA_PRED_TOTALS]
+    int K, kpad;
+};
+
+// this lane's share of the mean and the variance of theta_u . beta_i from its elements of the four rows, in the context
+// dtype.  Every operation is rounded on its own (no contraction): the two instantiations of the kernel give the same
+// bits, and the tests count the roundings.
+template <typename T>
+__device__ __forceinline__ void gamma_pred_moments(const Vec4<T> &a, const Vec4<T> &b, const Vec4<T> &s, const Vec4<T> &d, int koff, int K,
+                                                   T &m, T &v) {
+#pragma clang fp contract(off)
+    m = (T)0;
+    v = (T)0;
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) {
+        if (koff + e < K) {   // (a pad element holds 0 / 0)
+            const T ex = (a.v[e] / b.v[e]) * (s.v[e] / d.v[e]);
+            const T w = ((T)1 / a.v[e] + (T)1 / s.v[e]) + (T)1 / (a.v[e] * s.v[e]);
+            m += ex;
+            v += (ex * ex) * w;
+        }
+    }
+}
+
+// PLUGIN and NEGBIN of one pair from its rating and the (mean, variance) the call returns, all in double; `rest` is
+// -mu - lgamma(x + 1), what BOUND adds to x lse.  A function of its own, not inlined: its seven logarithms' coefficients
+// (64-bit constants sit in scalar register pairs on this target) then live for the length of one call instead of across
+// the kernel's pair loop, where the scalar registers are taken by the call's twelve base pointers.
+struct GammaPredDensities {
+    double plugin, negbin, rest;
+};
+__device__ __noinline__ GammaPredDensities gamma_pred_densities(double x, double mu, double vv) {
+    double plugin, negbin;
+    const double lf = gamma_log_factorial(x);
+    const double lmu = log(mu);
+    const bool floored = mu < PMF_RATE_FLOOR;
+    plugin = floored ? x * -23.025850929940457 - PMF_RATE_FLOOR - lf : x * lmu - mu - lf;   // (log 1e-10)
+    const double xlm = x == 0.0 ? 0.0 : x * lmu;   // 0 log 0 = 0: a count of 0 has density exp(-mu)
+    // the rate moment-matched to Gamma(r, r / mu): the count is negative binomial; the unclamped Poisson term where the
+    // variance is 0 or r leaves double's range
+    const double rr = mu * mu / vv;
+    negbin = xlm - mu - lf;
+    if (vv != 0.0 && isfinite(rr)) negbin = xlm - lf - (rr + x) * gamma_log1p(mu / rr) + gamma_negbin_excess(x, rr);
+    return {plugin, negbin, -mu - lf};
+}
+
+// sum_k exp(e_k - mx) of a lane's four elements and the logarithm of the group's sum: inline in fp32, calls in fp64 (for
+// the reason above: exp and log in double bring some forty scalar registers of coefficients)
+__device__ __forceinline__ float gamma_pred_exp_sum(float e0, float e1, float e2, float e3, float mx) {
+    float z = exp(e0 - mx);   // (a pad is -inf: exp gives 0)
+    z += exp(e1 - mx);
+    z += exp(e2 - mx);
+    z += exp(e3 - mx);
+    return z;
+}
+__device__ __noinline__ double gamma_pred_exp_sum(double e0, double e1, double e2, double e3, double mx) {
+    double z = exp(e0 - mx);
+    z += exp(e1 - mx);
+    z += exp(e2 - mx);
+    z += exp(e3 - mx);
+    return z;
+}
+__device__ __forceinline__ float gamma_pred_log(float z) { return log(z); }
+__device__ __noinline__ double gamma_pred_log(double z) { return log(z); }
+
+template <typename T, int LPR, bool BOUND>
+__global__ __launch_bounds__(256) void gamma_pred_kernel(GammaPredParams<T> p) {
+    constexpr int G = 256 / LPR;
+    constexpr int UN = sizeof(T) == 4 ? 4 : 2;   // pairs whose gathers are in flight (LPR >= 4)
+    __shared__ double s_part[G][PMF_GAMMA_PRED_TOTALS];
+    const int c = threadIdx.x % LPR;
+    const int g = threadIdx.x / LPR;
+    const int koff = c * PMF_VEC;
+    const int kpad = p.kpad;
+    const bool active = koff < kpad;
+    const T ninf = (T)(-INFINITY);
+    const int64_t batches = (p.n + LPR - 1) / LPR;
+    const int64_t stride = (int64_t)gridDim.x * G;
+    // all groups of a wavefront iterate the same number of times (DPP inside)
+    const int64_t rounds = (batches + stride - 1) / stride;
+    int64_t batch = (int64_t)blockIdx.x * G + g;
+    double sum_v = 0.0, sum_plugin = 0.0, sum_bound = 0.0, sum_negbin = 0.0;
+    for (int64_t r = 0; r < rounds; ++r, batch += stride) {
+        if (batch < batches) {
+            const int64_t base = batch * LPR;
+            const int cnt = (int)min((int64_t)LPR, p.n - base);
+            int my_u = 0, my_i = 0;   // (lanes past the batch hold id 0: a valid row, loaded and not used)
+            if (c < cnt) {
+                my_u = p.u[base + c];
+                my_i = p.i[base + c];
+            }
+            T my_m = (T)0, my_v = (T)0, my_lse = (T)0;
+            for (int tt = 0; tt < cnt; tt += UN) {
+                int64_t au[UN], ai[UN];
+                Vec4<T> a[UN], b[UN], s[UN], d[UN], lu[UN], li[UN];
+#pragma unroll
+                for (int q = 0; q < UN; ++q) {
+                    au[q] = (int64_t)__shfl(my_u, tt + q, LPR) * kpad + koff;
+                    ai[q] = (int64_t)__shfl(my_i, tt + q, LPR) * kpad + koff;
+                }
+#pragma unroll
+                for (int q = 0; q < UN; ++q) {
+                    a[q] = b[q] = s[q] = d[q] = zero4<T>();
+                    if (active) {
+                        a[q] = load4(p.shape_u + au[q]);
+                        b[q] = load4(p.rate_u + au[q]);
+                        s[q] = load4(p.shape_i + ai[q]);
+                        d[q] = load4(p.rate_i + ai[q]);
+                    }
+                    if constexpr (BOUND) {
+                        // (-inf in every element: what a lane past kpad contributes; a pad of the tables is -inf too)
+                        lu[q].v[0] = lu[q].v[1] = lu[q].v[2] = lu[q].v[3] = ninf;
+                        li[q] = lu[q];
+                        if (active) {
+                            lu[q] = load4(p.table_u + 2 * au[q] - koff);   // row * 2 kpad + koff
+                            li[q] = load4(p.table_i + 2 * ai[q] - koff);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < UN; ++q) {
+                    if (tt + q < cnt) {
+                        T m, v, lse = (T)0;
+                        gamma_pred_moments<T>(a[q], b[q], s[q], d[q], koff, active ? p.K : 0, m, v);
+                        m = group_sum<LPR>(m);
+                        v = group_sum<LPR>(v);
+                        if constexpr (BOUND) {
+                            T e[PMF_VEC];
+#pragma unroll
+                            for (int k = 0; k < PMF_VEC; ++k) e[k] = lu[q].v[k] + li[q].v[k];
+                            const T mx = group_max<LPR>(vmax(vmax(e[0], e[1]), vmax(e[2], e[3])));
+                            const T z = group_sum<LPR>(gamma_pred_exp_sum(e[0], e[1], e[2], e[3], mx));   // >= 1: the largest element adds exp(0)
+                            lse = mx + gamma_pred_log(z);
+                        }
+                        if (c == tt + q) {
+                            my_m = m;
+                            my_v = v;
+                            my_lse = lse;
+                        }
+                    }
+                }
+            }
+            if (c < cnt) {   // this lane's pair of the batch
+                const int64_t idx = base + c;
+                const double mu = (double)my_m, vv = (double)my_v;
+                if (p.mean) p.mean[idx] = mu;
+                if (p.var) p.var[idx] = vv;
+                sum_v += vv;
+                if (p.x) {
+                    const double x = p.x[idx];
+                    const GammaPredDensities t = gamma_pred_densities(x, mu, vv);
+                    const double plugin = t.plugin, negbin = t.negbin;
+                    double bound = __builtin_nan("");
+                    if constexpr (BOUND) {
+                        bound = x * (double)my_lse + t.rest;
+                        sum_bound += bound;
+                    }
+                    sum_plugin += plugin;
+                    sum_negbin += negbin;
+                    if (p.logp) {
+                        double *o = p.logp + idx * PMF_GAMMA_PRED_KINDS;
+                        o[PMF_GAMMA_PRED_PLUGIN] = plugin;
+                        o[PMF_GAMMA_PRED_BOUND] = bound;
+                        o[PMF_GAMMA_PRED_NEGBIN] = negbin;
+                    }
+                }
+            }
+        }
+    }
+    // (every lane of the block arrives: the rounds are the same for all)
+    sum_v = group_sum<LPR>(sum_v);
+    sum_plugin = group_sum<LPR>(sum_plugin);
+    sum_bound = group_sum<LPR>(sum_bound);
+    sum_negbin = group_sum<LPR>(sum_negbin);
+    if (c == 0) {
+        s_part[g][0] = sum_v;
+        s_part[g][1 + PMF_GAMMA_PRED_PLUGIN] = sum_plugin;
+        s_part[g][1 + PMF_GAMMA_PRED_BOUND] = sum_bound;
+        s_part[g][1 + PMF_GAMMA_PRED_NEGBIN] = sum_negbin;
+    }
+    __syncthreads();
+    if (threadIdx.x < PMF_GAMMA_PRED_TOTALS) {
+        double s = 0.0;
+        for (int k = 0; k < G; ++k) s += s_part[k][threadIdx.x];
+        p.block_out[(int64_t)blockIdx.x * PMF_GAMMA_PRED_TOTALS + threadIdx.x] = s;
+    }
+}
+
+static const int64_t kGammaPredPairs = 1 << 20;   // pairs per staging round (PMF_GAMMA_PRED_PAIRS=n overrides it): 56 MB of scratch
+static const int kGammaPredMaxGrid = 1024;
+
+// Pairs in staging rounds: ids (and ratings) up, one launch, the per-pair outputs and the block partial sums down; the
+// totals are the partial sums in block order, round after round.  The scratch layout does not depend on what was
+// asked for, so a call never grows what an earlier call of the same n left.
+template <typename T>
+static int run_gamma_predictive(pmf_ctx *ctx, int64_t n, const int32_t *u, const int32_t *i, const double *x, bool bound,
+                                double *out_mean, double *out_var, double *out_logp, double *totals) {
+    const int kpad = ctx->kpad;
+    const int64_t step = ctx->gamma_pred_pairs > 0 ? ctx->gamma_pred_pairs : kGammaPredPairs;
+    const int64_t m = std::min(n, step);
+    const size_t part_bytes = (size_t)kGammaPredMaxGrid * PMF_GAMMA_PRED_TOTALS * sizeof(double);
+    int rc;
+    if ((rc = pmf_ensure_scratch(ctx, part_bytes + (size_t)m * ((3 + PMF_GAMMA_PRED_KINDS) * sizeof(double) + 2 * sizeof(int32_t))))) return rc;
+    if ((rc = pmf_ensure_pinned(ctx, part_bytes))) return rc;
+    double *d_part = ctx->d_scratch.as<double>();
+    double *d_x = d_part + (size_t)kGammaPredMaxGrid * PMF_GAMMA_PRED_TOTALS;
+    double *d_mean = d_x + m, *d_var = d_mean + m, *d_logp = d_var + m;
+    int32_t *d_u = reinterpret_cast<int32_t *>(d_logp + (size_t)m * PMF_GAMMA_PRED_KINDS);
+    int32_t *d_i = d_u + m;
+    if (bound && (rc = gamma_exact_build_tables<T>(ctx))) return rc;
+
+    GammaPredParams<T> p;
+    p.u = d_u;
+    p.i = d_i;
+    p.shape_u = ctx->arr[PMF_SIDE_USER][PMF_ARR_SHAPE].as<const T>();
+    p.rate_u = ctx->arr[PMF_SIDE_USER][PMF_ARR_RATE].as<const T>();
+    p.shape_i = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_SHAPE].as<const T>();
+    p.rate_i = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_RATE].as<const T>();
+    p.table_u = bound ? gamma_exact_table<T>(ctx, PMF_SIDE_USER) : nullptr;
+    p.table_i = bound ? gamma_exact_table<T>(ctx, PMF_SIDE_ITEM) : nullptr;
+    p.x = x ? d_x : nullptr;
+    p.mean = out_mean ? d_mean : nullptr;
+    p.var = out_var ? d_var : nullptr;
+    p.logp = out_logp ? d_logp : nullptr;
+    p.block_out = d_part;
+    p.K = ctx->K;
+    p.kpad = kpad;
+    double sum[PMF_GAMMA_PRED_TOTALS] = {};
+    for (int64_t at = 0; at < n; at += step) {
+        const int64_t cnt = std::min(step, n - at);
+        PMF_HIP_CHECK(hipMemcpyAsync(d_u, u + at, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        PMF_HIP_CHECK(hipMemcpyAsync(d_i, i + at, (size_t)cnt * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        if (x) PMF_HIP_CHECK(hipMemcpyAsync(d_x, x + at, (size_t)cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        p.n = cnt;
+        int grid = 0;
+        {
+            PmfProfScope prof(ctx, x ? PMF_KERNEL_EVAL : PMF_KERNEL_PREDICT);
+            pmf_with_pow2<4>(pmf_lanes_per_row(kpad), [&](auto L) {
+                grid = (int)std::min<int64_t>((cnt + 255) / 256, kGammaPredMaxGrid);   // a block's 256 / L groups take L pairs each
+                if (bound)
+                    hipLaunchKernelGGL((gamma_pred_kernel<T, L, true>), dim3(grid), dim3(256), 0, ctx->stream, p);
+                else
+                    hipLaunchKernelGGL((gamma_pred_kernel<T, L, false>), dim3(grid), dim3(256), 0, ctx->stream, p);
+            });
+        }
+        PMF_HIP_CHECK(hipGetLastError());
+        if (out_mean) PMF_HIP_CHECK(hipMemcpyAsync(out_mean + at, d_mean, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_var) PMF_HIP_CHECK(hipMemcpyAsync(out_var + at, d_var, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_logp)
+            PMF_HIP_CHECK(hipMemcpyAsync(out_logp + at * PMF_GAMMA_PRED_KINDS, d_logp, (size_t)cnt * PMF_GAMMA_PRED_KINDS * sizeof(double),
+                                         hipMemcpyDeviceToHost, ctx->stream));
+        PMF_HIP_CHECK(hipMemcpyAsync(ctx->h_pinned.as(), d_part, (size_t)grid * PMF_GAMMA_PRED_TOTALS * sizeof(double), hipMemcpyDeviceToHost,
+                                     ctx->stream));
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        const double *h = ctx->h_pinned.as<const double>();
+        for (int b = 0; b < grid; ++b)
+            for (int t = 0; t < PMF_GAMMA_PRED_TOTALS; ++t) sum[t] += h[(size_t)b * PMF_GAMMA_PRED_TOTALS + t];
+    }
+    if (totals) {
+        const double nan = __builtin_nan("");
+        totals[0] = sum[0];
+        totals[1 + PMF_GAMMA_PRED_PLUGIN] = x ? sum[1 + PMF_GAMMA_PRED_PLUGIN] : nan;
+        totals[1 + PMF_GAMMA_PRED_BOUND] = x && bound ? sum[1 + PMF_GAMMA_PRED_BOUND] : nan;
+        totals[1 + PMF_GAMMA_PRED_NEGBIN] = x ? sum[1 + PMF_GAMMA_PRED_NEGBIN] : nan;
+    }
+    return PMF_OK;
+}
+
+extern "C" int pmf_gamma_predictive(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, const int32_t *item_ids, const double *ratings,
+                                    int with_bound, double *out_mean, double *out_var, double *out_logp, double *totals) {
+    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "pmf_gamma_predictive: null context");
+    PMF_REQUIRE(n >= 0, PMF_EINVAL, "pmf_gamma_predictive: negative n");
+    if (n == 0) return PMF_OK;
+    PMF_REQUIRE(user_ids != nullptr, PMF_EINVAL, "pmf_gamma_predictive: null user_ids");
+    PMF_REQUIRE(item_ids != nullptr, PMF_EINVAL, "pmf_gamma_predictive: null item_ids");
+    PMF_REQUIRE(out_mean || out_var || out_logp || totals, PMF_EINVAL, "pmf_gamma_predictive: no output (out_mean, out_var, out_logp and totals are all null)");
+    PMF_REQUIRE(ratings || !out_logp, PMF_EINVAL, "pmf_gamma_predictive: out_logp without ratings");
+    int rc;
+    for (int s : {PMF_SIDE_USER, PMF_SIDE_ITEM}) {
+        if ((rc = pmf_require_array(ctx, s, PMF_ARR_SHAPE, "pmf_gamma_predictive"))) return rc;
+        if ((rc = pmf_require_array(ctx, s, PMF_ARR_RATE, "pmf_gamma_predictive"))) return rc;
+    }
+    PMF_REQUIRE(pmf_lanes_per_row(ctx->kpad) <= 64, PMF_ERANGE, "pmf_gamma_predictive: unsupported n_factors %d", ctx->K);
+    for (int64_t k = 0; k < n; ++k) {
+        PMF_REQUIRE(user_ids[k] >= 0 && user_ids[k] < ctx->rows[PMF_SIDE_USER], PMF_ERANGE,
+                    "pmf_gamma_predictive: user id %d at position %lld outside [0, %lld)", user_ids[k], (long long)k,
+                    (long long)ctx->rows[PMF_SIDE_USER]);
+        PMF_REQUIRE(item_ids[k] >= 0 && item_ids[k] < ctx->rows[PMF_SIDE_ITEM], PMF_ERANGE,
+                    "pmf_gamma_predictive: item id %d at position %lld outside [0, %lld)", item_ids[k], (long long)k,
+                    (long long)ctx->rows[PMF_SIDE_ITEM]);
+    }
+    PMF_HIP_CHECK(hipSetDevice(ctx->device));
+    return pmf_with_dtype(ctx, [&](auto t) {
+        // (without ratings there is no BOUND to form: no table is built)
+        return run_gamma_predictive<decltype(t)>(ctx, n, user_ids, item_ids, ratings, with_bound != 0 && ratings, out_mean, out_var, out_logp,
+                                                 totals);
+    });
+}
+
 // Profiling aid (no reference counterpart): average device time of `repeats` launches of the
 // gather-only twin of the Poisson/HPF half-sweep of `side` -- the ceiling the cache hierarchy sets
 // for this context's gather pattern (bench.py reports the sweep kernel against it).

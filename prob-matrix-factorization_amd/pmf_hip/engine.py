@@ -6,11 +6,12 @@ lifetime management only.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
 
-from . import (ARR_COV, ELBO_TERMS, EXCHANGE, F32, F64, GAMMA_ELBO_TERMS, ITEM, KERNEL_NAMES, MAX_LABELS, OP_MAX, OP_SUM, TASK_LISTS, TEST_LIB_PATH,
+from . import (ARR_COV, ELBO_TERMS, EXCHANGE, F32, F64, GAMMA_ELBO_TERMS, GAMMA_PRED_KINDS, GAMMA_PRED_TOTALS, ITEM, KERNEL_NAMES, MAX_LABELS, OP_MAX, OP_SUM, TASK_LISTS, TEST_LIB_PATH,
                UNIQUE_ID_BYTES, USER, PmfError, PmfLibraryError, as_f64, as_i32, check, load, ptr)
 
 
@@ -25,6 +26,11 @@ def rank_batch(user_ids, item_ids):
     order = np.argsort(row.reshape(-1), kind="stable")
     row_ptr = np.concatenate([[0], np.cumsum(np.bincount(row.reshape(-1), minlength=len(users)))]).astype(np.int64)
     return users, row_ptr, i[order], order
+
+
+# what `Context.gamma_predictive` returns: `mean`, `var` [n] and `logp` [n, GAMMA_PRED_KINDS] (None where not asked for or
+# not defined), `totals` [GAMMA_PRED_TOTALS]
+GammaPredictive = collections.namedtuple("GammaPredictive", "mean var logp totals")
 
 
 class Context:
@@ -295,6 +301,35 @@ class Context:
         """The raw sums of `gamma_exact_sweep` in `gamma_accumulate`'s layout; `gamma_finalize` finalises them."""
         check(self._lib.pmf_gamma_exact_accumulate(self._h, side, C.c_void_p(stats_ptr)), "pmf_gamma_exact_accumulate")
 
+    def gamma_predictive(self, user_ids, item_ids, ratings=None, with_bound=True, per_pair=True):
+        """Posterior predictive of the Poisson MF / HPF models for the pairs (`pmf_gamma_predictive`; q is SHAPE and RATE
+        of both sides): a `GammaPredictive` with `mean` = E[theta_u . beta_i] and `var` = Var[theta_u . beta_i] (float64
+        [n]), `logp` [n, GAMMA_PRED_KINDS] -- the PLUGIN, BOUND and NEGBIN log densities of `ratings`, columns
+        `pmf_hip.GAMMA_PRED_*`; None without ratings -- and `totals` [GAMMA_PRED_TOTALS] = sum of var, then of every
+        column (NaN where there is none).  Without `with_bound` no table is built and the BOUND column and total are NaN;
+        without `per_pair` only `totals` is formed (`mean`, `var`, `logp` are None).  Every id must lie inside the trained
+        dimensions.  The context is only read."""
+        u, i = as_i32(user_ids, "user_ids"), as_i32(item_ids, "item_ids")
+        if len(u) != len(i):
+            raise ValueError("user_ids and item_ids must have the same length")
+        x = None if ratings is None else as_f64(ratings)
+        if x is not None and x.shape != (len(u),):
+            raise ValueError("ratings must have the length of user_ids")
+        n = len(u)
+        mean = np.zeros(n, dtype=np.float64) if per_pair else None
+        var = np.zeros(n, dtype=np.float64) if per_pair else None
+        logp = np.zeros((n, GAMMA_PRED_KINDS), dtype=np.float64) if per_pair and x is not None else None
+        totals = np.full(GAMMA_PRED_TOTALS, np.nan, dtype=np.float64)
+        totals[0] = 0.0
+        if x is not None:
+            totals[1:] = 0.0
+            if not with_bound:
+                totals[2] = np.nan
+        opt = lambda a: None if a is None else ptr(a, C.c_double)
+        check(self._lib.pmf_gamma_predictive(self._h, n, ptr(u, C.c_int32), ptr(i, C.c_int32), opt(x), int(bool(with_bound)),
+                                             opt(mean), opt(var), opt(logp), ptr(totals, C.c_double)), "pmf_gamma_predictive")
+        return GammaPredictive(mean, var, logp, totals)
+
     # ---- Gaussian -------------------------------------------------------
     def gauss_factor_sweep(self, side, sigma2, eta2):
         check(self._lib.pmf_gauss_factor_sweep(self._h, side, float(sigma2), float(eta2)),
@@ -508,4 +543,4 @@ class Context:
         return out
 
 
-__all__ = ["Context", "PmfError", "USER", "ITEM", "rank_batch"]
+__all__ = ["Context", "GammaPredictive", "PmfError", "USER", "ITEM", "rank_batch"]

@@ -12,7 +12,7 @@ import numpy as np
 
 from src.evaluation.metrics import macro_mae, rmse
 from src.models._device_model import ITEM, USER, DeviceModel, frame_arrays
-from src.models import _gamma_elbo
+from src.models import _gamma_elbo, _gamma_predictive
 from src.models._gamma_fold_in import gamma_fold_in
 from pmf_hip import ARR_FACTOR, ARR_HYPER_RATE, ARR_PRIOR_RATE, ARR_RATE, ARR_SHAPE, dist as pdist
 
@@ -82,7 +82,8 @@ class HPF_CAVI(DeviceModel):
         cfg = self.config
         return (cfg.a, cfg.a_prime, cfg.b_prime), (cfg.c, cfg.c_prime, cfg.d_prime), True
 
-    def fit(self, train_df, val_df=None, *, track_elbo=False, elbo_tol=None, update="reference"):
+    def fit(self, train_df, val_df=None, *, track_elbo=False, elbo_tol=None, update="reference", track_loglik=False, loglik_tol=None,
+            loglik_kind="plugin"):
         """`track_elbo`: evaluate the evidence lower bound after every iteration (`history_["elbo"]`, an `ELBO:` line
         when verbose; measured at K = 64 fp32, 1M users, 50M ratings: the user call's two kernels take 3.00 times a user
         half-sweep (the data pass 2.34 times the sweep's gather ceiling); an `elbo()` takes 5.27 times a whole iteration by wall
@@ -94,10 +95,18 @@ class HPF_CAVI(DeviceModel):
         E[theta] E[beta] / (E[theta] . E[beta]); "exact" runs coordinate ascent on the bound (`pmf_gamma_exact_sweep`: weights
         exp(E log theta + E log beta), normalised, formed from the shapes and rates), under which the bound cannot fall from
         one half-sweep to the next, except by rounding.  `history_["update"]` records the mode.  A negative training rating
-        is refused under "exact".  Cost of an exact half-sweep: DESIGN.md section 4.12."""
+        is refused under "exact".  Cost of an exact half-sweep: DESIGN.md section 4.12.
+        `track_loglik` (needs `val_df`): after every iteration the total held-out log-likelihood of the validation rows
+        with seen ids goes to `history_["val_loglik"]` (a `Validation log-likelihood:` line when verbose), formed on the
+        device from the shapes and rates (`pmf_gamma_predictive`), for any number of distinct ratings.  `loglik_kind`:
+        "plugin" (default: the reference's PoissonLogPredictiveLikelihood at the factor means), "bound" or "negbin", as
+        for `log_predictive_density`.  `loglik_tol` (implies `track_loglik`): stop when (L_t - L_{t-1}) / |L_{t-1}| falls
+        below it -- the stopping rule of the HPF paper; it fires on a decrease too.  It is independent of, and checked after,
+        the RMSE rule and `elbo_tol`.  Cost: DESIGN.md section 4.13."""
         cfg = self.config
         exact = _gamma_elbo.check_update(update, train_df)
         track_elbo = _gamma_elbo.check_tracking(self, track_elbo, elbo_tol, train_df)
+        track_loglik = _gamma_predictive.check_tracking(self, track_loglik, loglik_tol, loglik_kind, val_df)
         self._infer_dimensions(train_df)
         self._initialize()
         u, i, x = frame_arrays(train_df)
@@ -105,6 +114,9 @@ class HPF_CAVI(DeviceModel):
         self.history_.pop("elbo", None)
         if track_elbo:
             self.history_["elbo"] = []
+        self.history_.pop("val_loglik", None)
+        if track_loglik:
+            self.history_["val_loglik"] = []
         ctx.set_array(USER, ARR_FACTOR, self._mine(self.E_theta))
         ctx.set_array(ITEM, ARR_FACTOR, self.E_beta)
         ctx.set_array(USER, ARR_PRIOR_RATE, self._mine(self.E_xi))
@@ -118,6 +130,7 @@ class HPF_CAVI(DeviceModel):
         user_prior = (cfg.a, 0.0, True, self.gamma_a_xi, cfg.b_prime)
         item_prior = (cfg.c, 0.0, True, self.gamma_a_eta, cfg.d_prime)
         monitor = self._monitor_setup(val_df)
+        loglik = _gamma_predictive.monitor_setup(self, ctx, val_df, loglik_kind) if track_loglik else None
         previous = None
         for it in range(1, cfg.max_iter + 1):
             if cfg.verbose:
@@ -126,6 +139,7 @@ class HPF_CAVI(DeviceModel):
             self._run_iteration(lambda: pdist.gamma_iteration(ctx, self._comm, None, user_prior, item_prior, exact=exact))
             self._tick(it)
             elbo_stop = track_elbo and _gamma_elbo.record_elbo(self, ctx, it, elbo_tol)
+            loglik_stop = track_loglik and _gamma_predictive.record_loglik(self, loglik, it, loglik_tol)
             if monitor is not None:    # (before the ELBO stop: every iteration that ran has its validation entries)
                 val_rmse, val_macro_mae = monitor()
                 self._record(val_rmse, val_macro_mae)
@@ -148,6 +162,11 @@ class HPF_CAVI(DeviceModel):
                     self.history_["stopped_early"] = True
                     break
             previous = val_rmse
+            if loglik_stop:    # (after the other two rules: every iteration that ran has all its entries)
+                if cfg.verbose:
+                    print("Early stopping: validation log-likelihood change below loglik_tol.")
+                self.history_["stopped_early"] = True
+                break
         if self.history_["iterations"] > 0:
             self._pull_state()
         return self
@@ -176,6 +195,24 @@ class HPF_CAVI(DeviceModel):
         clock, 1.30 times in kernel time -- the rest is the download and the host's sum of the per-row terms); `parts=True` also returns the dict of
         `elbo_from_gamma_terms`."""
         return _gamma_elbo.fitted_elbo(self, parts)
+
+    def predict_variance(self, user_ids, item_ids, include_noise=True):
+        """Var[theta_u . beta_i] under the fitted q(theta_uk) = Gamma(shape, rate) (items alike; the factors are
+        independent): sum_k E_k^2 (1/a_k + 1/c_k + 1/(a_k c_k)) with E_k the product of the two means and a, c the two
+        shapes (float64), plus the mean itself when `include_noise`: a count's own variance is E[rate] + Var[rate].  0 for
+        ids the fit has not seen, which `predict` treats as the point 0.  Formed on the device (`pmf_gamma_predictive`)."""
+        return _gamma_predictive.predict_variance(self, user_ids, item_ids, include_noise)
+
+    def log_predictive_density(self, df, kind="negbin", per_row=False):
+        """TOTAL over the rows of `df` with seen ids (as the reference's PoissonLogPredictiveLikelihood returns a total) of
+        the log density of the rating under the fitted q; rows with an unseen id are skipped, nan (with the warning) when
+        none is left, a negative rating is a ValueError.  `kind`: "plugin" -- Poisson at the factor means,
+        max(mean, 1e-10), the reference's metric; "bound" -- the ELBO's data term on the held-out pair, a lower bound on
+        the log density of the exact predictive; "negbin" (default) -- the negative binomial whose rate is the Gamma with the mean and
+        variance of theta_u . beta_i under q, which is as wide as q is unsure.  `per_row=True` also returns the terms of the kept rows,
+        in frame order.  Formed on the device (`pmf_gamma_predictive`: the densities in double from the mean and variance
+        it returns); the context is only read."""
+        return _gamma_predictive.log_predictive_density(self, df, kind, per_row)
 
     def predict(self, user_ids, item_ids):
         return self._need_ctx().predict(np.asarray(user_ids, dtype=int), np.asarray(item_ids, dtype=int))
