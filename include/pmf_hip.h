@@ -337,8 +337,7 @@ int pmf_gamma_finalize(pmf_ctx *ctx, int side, const void *stats_dev, double sha
  * pmf_gamma_exact_accumulate writes the raw sums [rows x 2 x Kpad] (shape sums, then rate sums: the layout of
  * pmf_gamma_accumulate) of the selected chunk into `stats_dev`; pmf_gamma_finalize finalises either kind.
  * PMF_EINVAL, with the missing thing named: null context, bad side, SHAPE or RATE of either side not set, no ratings,
- * hierarchical and PRIOR_RATE of `side` not set, null stats buffer.  PMF_ERANGE: unsupported n_factors.  An argument
- * error writes nothing.
+ * hierarchical and PRIOR_RATE of `side` not set, null stats buffer.  An argument error writes nothing.
  * Cost, measured at K = 64 fp32, 1M users, 50M ratings: DESIGN.md section 4.12. */
 int pmf_gamma_exact_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior,
                           int hierarchical, double hyper_shape, double hyper_rate_prior);
@@ -388,8 +387,8 @@ int pmf_gamma_exact_accumulate(pmf_ctx *ctx, int side, void *stats_dev);
  * communicator.  The extended Poisson model (SCALE arrays) is not covered.
  * PMF_EINVAL, naming what is missing: null context (whatever n is), n < 0, a null id array, all four outputs null,
  * out_logp without ratings, SHAPE or RATE of either side not set.  PMF_ERANGE: an id outside the trained dimensions (id
- * and position named; unlike pmf_predict, which scores such a pair as 0), unsupported n_factors.  An argument error
- * writes nothing; n = 0 touches nothing and returns 0.
+ * and position named; unlike pmf_predict, which scores such a pair as 0).  An argument error writes nothing; n = 0
+ * touches nothing and returns 0.
  * Cost: DESIGN.md section 4.13. */
 #define PMF_GAMMA_PRED_PLUGIN 0
 #define PMF_GAMMA_PRED_BOUND  1

@@ -652,12 +652,7 @@ static int set_row_chunks_impl(pmf_ctx *ctx, int side, int n_chunks) {
 }
 
 extern "C" int pmf_ctx_set_row_chunks(pmf_ctx *ctx, int side, int n_chunks) {
-    try {
-        return set_row_chunks_impl(ctx, side, n_chunks);
-    } catch (const std::bad_alloc &) {
-        pmf_set_error("pmf_ctx_set_row_chunks: out of host memory");
-        return PMF_ENOMEM;
-    }
+    return pmf_no_throw("pmf_ctx_set_row_chunks", [&] { return set_row_chunks_impl(ctx, side, n_chunks); });
 }
 
 extern "C" int pmf_ctx_chunk_rows(pmf_ctx *ctx, int side, int chunk, int64_t *row_begin, int64_t *row_end) {

@@ -498,13 +498,14 @@ __global__ __launch_bounds__(256) void gamma_fold_kernel(GammaFoldParams<T> p) {
 // ---------------------------------------------------------------------------
 struct GammaPriors { double shape = 0, rate = 0; int hierarchical = 0; double hyper_shape = 0, hyper_rate = 0; };
 
-// the sweep kernel over the tasks, then the split kernel over the rows cut into several tasks
-template <typename T, int LPR, bool STATS, bool EXT>
-static void launch_gamma(pmf_ctx *ctx, const GammaParams<T> &p, const PmfTaskView &tl) {
+// SWEEP (gamma_sweep_kernel, or gamma_exact_kernel with its two tables in `more`) over the tasks, then the split
+// kernel over the rows cut into several tasks
+template <typename T, int LPR, bool STATS, bool EXT, auto SWEEP, typename... A>
+static void launch_gamma(pmf_ctx *ctx, const GammaParams<T> &p, const PmfTaskView &tl, A... more) {
     constexpr int G = 256 / LPR;
     if (tl.n_tasks > 0) {
         PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
-        hipLaunchKernelGGL((gamma_sweep_kernel<T, LPR, STATS, EXT>), dim3((unsigned)((tl.n_tasks + G - 1) / G)), dim3(256), 0, ctx->stream, p);
+        hipLaunchKernelGGL(SWEEP, dim3((unsigned)((tl.n_tasks + G - 1) / G)), dim3(256), 0, ctx->stream, p, more...);
     }
     if (tl.n_split > 0) {
         PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
@@ -513,12 +514,11 @@ static void launch_gamma(pmf_ctx *ctx, const GammaParams<T> &p, const PmfTaskVie
     }
 }
 
-// f(std::integral_constant<int, LPR>()) for the context's lanes per row, then the launch error check
+// f(std::integral_constant<int, LPR>()) for the context's lanes per row (at most 64: pmf_ctx_create caps n_factors),
+// then the launch error check
 template <typename F>
 static int gamma_launch(pmf_ctx *ctx, F &&f) {
-    const int lpr = pmf_lanes_per_row(ctx->kpad);
-    PMF_REQUIRE(lpr <= 64, PMF_ERANGE, "pmf_gamma_sweep: unsupported n_factors %d", ctx->K);
-    pmf_with_pow2<1>(lpr, f);
+    pmf_with_pow2<1>(pmf_lanes_per_row(ctx->kpad), f);
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
 }
@@ -529,6 +529,16 @@ static int check_gamma_inputs(pmf_ctx *ctx, int side) {
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gamma_sweep"))) return rc;
     if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_FACTOR, "pmf_gamma_sweep"))) return rc;
     PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gamma_sweep: ratings have not been set");
+    return PMF_OK;
+}
+
+// SHAPE and RATE of the sides listed are set: q itself, which the ELBO, the exact update and the predictive read
+static int require_gamma_q(pmf_ctx *ctx, std::initializer_list<int> sides, const char *what) {
+    int rc;
+    for (int s : sides) {
+        if ((rc = pmf_require_array(ctx, s, PMF_ARR_SHAPE, what))) return rc;
+        if ((rc = pmf_require_array(ctx, s, PMF_ARR_RATE, what))) return rc;
+    }
     return PMF_OK;
 }
 
@@ -603,11 +613,11 @@ static int run_gamma(pmf_ctx *ctx, int side, PmfPass pass, bool ext, void *stats
                 hipLaunchKernelGGL((gamma_finalize_all_kernel<T, L>), dim3((unsigned)((p.rows - p.row0 + G - 1) / G)), dim3(256), 0,
                                    ctx->stream, p);
         } else if (pass == PMF_PASS_ACCUMULATE) {
-            launch_gamma<T, L, true, false>(ctx, p, tl);
+            launch_gamma<T, L, true, false, gamma_sweep_kernel<T, L, true, false>>(ctx, p, tl);
         } else if (ext) {
-            launch_gamma<T, L, false, true>(ctx, p, tl);
+            launch_gamma<T, L, false, true, gamma_sweep_kernel<T, L, false, true>>(ctx, p, tl);
         } else {
-            launch_gamma<T, L, false, false>(ctx, p, tl);
+            launch_gamma<T, L, false, false, gamma_sweep_kernel<T, L, false, false>>(ctx, p, tl);
         }
     });
 }
@@ -627,6 +637,22 @@ static int run_gather_probe(pmf_ctx *ctx, int side) {
     });
 }
 
+// The item half-sweep on several ranks (pmf_comm.hip): `accumulate` per chunk, the exchange, run_gamma's finalize.
+// Finalize is element-wise (cheap) and writes 3 Kpad + 2 values per row for 2 Kpad of statistics, so the plain
+// all-reduce is the default exchange here.  `alloc`: the arrays of the side the call creates first, in this order
+// (HYPER_RATE only when hierarchical).
+template <typename T>
+static int gamma_comm_half_sweep(pmf_ctx *ctx, int side, const GammaPriors &pr, std::initializer_list<int> alloc,
+                                 const std::function<int(void *)> &accumulate) {
+    const PmfExchange ex = {false, pr.hierarchical ? 5 : 3,
+                            {PMF_ARR_FACTOR, PMF_ARR_SHAPE, PMF_ARR_RATE, PMF_ARR_PRIOR_RATE, PMF_ARR_HYPER_RATE}};
+    int rc;
+    for (int array : alloc)
+        if ((array != PMF_ARR_HYPER_RATE || pr.hierarchical) && (rc = pmf_alloc_array(ctx, side, array))) return rc;
+    return pmf_comm_half_sweep(ctx, side, 0, (size_t)2 * ctx->kpad, true, ex, accumulate,
+                               [&](void *s) { return run_gamma<T>(ctx, side, PMF_PASS_FINALIZE, false, s, pr); });
+}
+
 extern "C" int pmf_gamma_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior,
                                int hierarchical, double hyper_shape, double hyper_rate_prior) {
     PMF_SIDE_ENTRY("pmf_gamma_sweep");
@@ -634,17 +660,10 @@ extern "C" int pmf_gamma_sweep(pmf_ctx *ctx, int side, double shape_prior, doubl
     return pmf_with_dtype(ctx, [&](auto t) {
         using T = decltype(t);
         if (side != PMF_SIDE_ITEM || !pmf_comm_active(ctx)) return run_gamma<T>(ctx, side, PMF_PASS_FUSED, false, nullptr, pr);
-        // several ranks (pmf_comm.hip): finalize is element-wise (cheap) and writes 3 Kpad + 2 values per row for 2 Kpad of
-        // statistics, so the plain all-reduce is the default exchange here
-        const PmfExchange ex = {false, pr.hierarchical ? 5 : 3,
-                                {PMF_ARR_FACTOR, PMF_ARR_SHAPE, PMF_ARR_RATE, PMF_ARR_PRIOR_RATE, PMF_ARR_HYPER_RATE}};
-        int rc;
-        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SHAPE))) return rc;   // (the gathers address them before finalize runs)
-        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_RATE))) return rc;
-        if (pr.hierarchical && (rc = pmf_alloc_array(ctx, side, PMF_ARR_HYPER_RATE))) return rc;
-        return pmf_comm_half_sweep(ctx, side, 0, (size_t)2 * ctx->kpad, true, ex,
-                                   [&](void *s) { return run_gamma<T>(ctx, side, PMF_PASS_ACCUMULATE, false, s, GammaPriors()); },
-                                   [&](void *s) { return run_gamma<T>(ctx, side, PMF_PASS_FINALIZE, false, s, pr); });
+        // (SHAPE and RATE: the gathers address them before finalize runs)
+        return gamma_comm_half_sweep<T>(ctx, side, pr, {PMF_ARR_SHAPE, PMF_ARR_RATE, PMF_ARR_HYPER_RATE}, [&](void *s) {
+            return run_gamma<T>(ctx, side, PMF_PASS_ACCUMULATE, false, s, GammaPriors());
+        });
     });
 }
 
@@ -705,7 +724,6 @@ template <typename T>
 static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
     const int K = ctx->K, kpad = ctx->kpad;
     const int lpr = pmf_lanes_per_row(kpad);
-    PMF_REQUIRE(lpr <= 64, PMF_ERANGE, "pmf_gamma_fold_in: unsupported n_factors %d", K);
     const int64_t long_row = ctx->gamma_fold_long > 0 ? ctx->gamma_fold_long : kGammaFoldLongRow;
     const int64_t by_bytes = std::max<int64_t>(1, kGammaFoldRowBytes / ((int64_t)kpad * (int64_t)sizeof(T)));
     const int64_t max_rows = std::min(by_bytes, ctx->fold_in_rows > 0 ? ctx->fold_in_rows : (int64_t)INT32_MAX);
@@ -839,18 +857,12 @@ extern "C" int pmf_gamma_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
     const int other = 1 - side;
     int rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gamma_fold_in"))) return rc;
-    for (int64_t k = 0; k < nnz; ++k)
-        PMF_REQUIRE(other_ids[k] >= 0 && other_ids[k] < ctx->rows[other], PMF_ERANGE,
-                    "pmf_gamma_fold_in: id %d at position %lld outside [0, %lld)", other_ids[k], (long long)k,
-                    (long long)ctx->rows[other]);
+    if ((rc = pmf_check_ids(other_ids, nnz, ctx->rows[other], "pmf_gamma_fold_in", "id"))) return rc;
     const GammaFoldBatch a = {n_rows, row_ptr, other_ids, ratings, {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior},
                               n_iter, init_factor, init_prior_rate, out_factor, out_shape, out_rate, out_prior_rate, out_hyper_rate};
-    try {  // host containers may throw: nothing propagates across the C boundary
+    return pmf_no_throw("pmf_gamma_fold_in", [&] {
         return pmf_with_dtype(ctx, [&](auto t) { return run_gamma_fold_in<decltype(t)>(ctx, side, a); });
-    } catch (const std::bad_alloc &) {
-        pmf_set_error("pmf_gamma_fold_in: out of host memory");
-        return PMF_ENOMEM;
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1096,6 +1108,24 @@ __global__ void gamma_elbo_split_kernel(const PmfSplitRow *split, int64_t n_spli
     o[PMF_GAMMA_ELBO_LOGFACT] = lf;
 }
 
+// gamma_elbo_row_kernel over the rows of side `s`: their (E log, E) table into `table` and, with `out`, the per-row
+// terms (`hierarchical`: those of HYPER_RATE among them).  The caller holds the profile bracket and checks the launch.
+template <typename T, int LPR>
+static void launch_gamma_row_table(pmf_ctx *ctx, int s, T *table, double *out, bool hierarchical) {
+    constexpr int G = 256 / LPR;
+    GammaElboRowParams<T> r;
+    r.shape = ctx->arr[s][PMF_ARR_SHAPE].as<const T>();
+    r.rate = ctx->arr[s][PMF_ARR_RATE].as<const T>();
+    r.hyper_rate = hierarchical ? ctx->arr[s][PMF_ARR_HYPER_RATE].as<const T>() : nullptr;
+    r.table = table;
+    r.out = out;
+    r.rows = ctx->rows[s];
+    r.K = ctx->K;
+    r.kpad = ctx->kpad;
+    if (r.rows > 0)
+        hipLaunchKernelGGL((gamma_elbo_row_kernel<T, LPR>), dim3((unsigned)((r.rows + G - 1) / G)), dim3(256), 0, ctx->stream, r);
+}
+
 // Everything the call writes lives in the context's scratch buffer (grown once, kept): the per-row terms, both tables
 // and the split rows' partial sums.  The row pass is timed as PMF_KERNEL_GAMMA_FINAL (with the split rows' sums), the
 // data pass as PMF_KERNEL_GAMMA_SWEEP.
@@ -1104,7 +1134,6 @@ static int run_gamma_elbo_terms(pmf_ctx *ctx, int side, bool with_data, bool hie
     const int other = 1 - side, kpad = ctx->kpad;
     const int64_t rows = ctx->rows[side], rows_o = ctx->rows[other];
     const int lpr = pmf_lanes_per_row(kpad);
-    PMF_REQUIRE(lpr <= 64, PMF_ERANGE, "pmf_gamma_elbo_terms: unsupported n_factors %d", ctx->K);
     PmfTaskView tl;
     if (with_data) tl = pmf_task_view(ctx, side, ctx->index[side].gamma_tasks, false);
     const auto aligned = [](size_t n) { return (n + 255) & ~(size_t)255; };
@@ -1122,22 +1151,6 @@ static int run_gamma_elbo_terms(pmf_ctx *ctx, int side, bool with_data, bool hie
     T *d_self = reinterpret_cast<T *>(base + out_bytes + lf_bytes + pd_bytes);
     T *d_other = reinterpret_cast<T *>(base + out_bytes + lf_bytes + pd_bytes + self_bytes);
 
-    GammaElboRowParams<T> r;
-    r.shape = ctx->arr[side][PMF_ARR_SHAPE].as<const T>();
-    r.rate = ctx->arr[side][PMF_ARR_RATE].as<const T>();
-    r.hyper_rate = hierarchical ? ctx->arr[side][PMF_ARR_HYPER_RATE].as<const T>() : nullptr;
-    r.table = d_self;
-    r.out = d_out;
-    r.rows = rows;
-    r.K = ctx->K;
-    r.kpad = kpad;
-    GammaElboRowParams<T> ro = r;   // the other side: its table only
-    ro.shape = ctx->arr[other][PMF_ARR_SHAPE].as<const T>();
-    ro.rate = ctx->arr[other][PMF_ARR_RATE].as<const T>();
-    ro.hyper_rate = nullptr;
-    ro.table = d_other;
-    ro.out = nullptr;
-    ro.rows = rows_o;
     GammaElboDataParams<T> d;
     d.tasks = tl.d_tasks;
     d.n_tasks = tl.n_tasks;
@@ -1153,9 +1166,8 @@ static int run_gamma_elbo_terms(pmf_ctx *ctx, int side, bool with_data, bool hie
         constexpr int G = 256 / L;
         if (rows > 0) {
             PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
-            hipLaunchKernelGGL((gamma_elbo_row_kernel<T, L>), dim3((unsigned)((rows + G - 1) / G)), dim3(256), 0, ctx->stream, r);
-            if (with_data && rows_o > 0)
-                hipLaunchKernelGGL((gamma_elbo_row_kernel<T, L>), dim3((unsigned)((rows_o + G - 1) / G)), dim3(256), 0, ctx->stream, ro);
+            launch_gamma_row_table<T, L>(ctx, side, d_self, d_out, hierarchical);
+            if (with_data) launch_gamma_row_table<T, L>(ctx, other, d_other, nullptr, false);   // the other side: its table only
         }
         if (with_data && tl.n_tasks > 0) {
             PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
@@ -1189,22 +1201,17 @@ extern "C" int pmf_gamma_elbo_terms(pmf_ctx *ctx, int side, int with_data, int h
     PMF_SIDE_ENTRY("pmf_gamma_elbo_terms");
     PMF_REQUIRE(totals, PMF_EINVAL, "pmf_gamma_elbo_terms: null totals");
     int rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_SHAPE, "pmf_gamma_elbo_terms"))) return rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_RATE, "pmf_gamma_elbo_terms"))) return rc;
+    if ((rc = require_gamma_q(ctx, {side}, "pmf_gamma_elbo_terms"))) return rc;
     if (with_data) {
-        if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_SHAPE, "pmf_gamma_elbo_terms"))) return rc;
-        if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_RATE, "pmf_gamma_elbo_terms"))) return rc;
+        if ((rc = require_gamma_q(ctx, {1 - side}, "pmf_gamma_elbo_terms"))) return rc;
         PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gamma_elbo_terms: ratings have not been set");
     }
     if (hierarchical && (rc = pmf_require_array(ctx, side, PMF_ARR_HYPER_RATE, "pmf_gamma_elbo_terms (hierarchical)"))) return rc;
-    try {  // host containers may throw: nothing propagates across the C boundary
+    return pmf_no_throw("pmf_gamma_elbo_terms", [&] {
         return pmf_with_dtype(ctx, [&](auto t) {
             return run_gamma_elbo_terms<decltype(t)>(ctx, side, with_data != 0, hierarchical != 0, totals, per_row);
         });
-    } catch (const std::bad_alloc &) {
-        pmf_set_error("pmf_gamma_elbo_terms: out of host memory");
-        return PMF_ENOMEM;
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1310,12 +1317,8 @@ __global__ __launch_bounds__(256) void gamma_exact_kernel(GammaParams<T> p, cons
 
 static int check_gamma_exact_inputs(pmf_ctx *ctx, int side, const char *what) {
     int rc;
-    for (int s : {side, 1 - side}) {
-        if ((rc = pmf_require_array(ctx, s, PMF_ARR_SHAPE, what))) return rc;
-        if ((rc = pmf_require_array(ctx, s, PMF_ARR_RATE, what))) return rc;
-    }
+    if ((rc = require_gamma_q(ctx, {side, 1 - side}, what))) return rc;
     PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "%s: ratings have not been set", what);
-    PMF_REQUIRE(pmf_lanes_per_row(ctx->kpad) <= 64, PMF_ERANGE, "%s: unsupported n_factors %d", what, ctx->K);
     return PMF_OK;
 }
 
@@ -1328,44 +1331,14 @@ static T *gamma_exact_table(const pmf_ctx *ctx, int side) {
 // Both sides' (E log, E) tables from SHAPE and RATE as they are now, on the context's stream (timed as the row pass).
 template <typename T>
 static int gamma_exact_build_tables(pmf_ctx *ctx) {
-    const int kpad = ctx->kpad;
     int rc;
-    if ((rc = ctx->d_gamma_tables.reserve(ctx, (size_t)(ctx->rows[0] + ctx->rows[1]) * 2 * kpad * sizeof(T), {ctx->stream}))) return rc;
+    if ((rc = ctx->d_gamma_tables.reserve(ctx, (size_t)(ctx->rows[0] + ctx->rows[1]) * 2 * ctx->kpad * sizeof(T), {ctx->stream}))) return rc;
     PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
-    for (int s = 0; s < 2; ++s) {
-        GammaElboRowParams<T> r;
-        r.shape = ctx->arr[s][PMF_ARR_SHAPE].as<const T>();
-        r.rate = ctx->arr[s][PMF_ARR_RATE].as<const T>();
-        r.hyper_rate = nullptr;
-        r.table = gamma_exact_table<T>(ctx, s);
-        r.out = nullptr;
-        r.rows = ctx->rows[s];
-        r.K = ctx->K;
-        r.kpad = kpad;
-        if (r.rows > 0)
-            pmf_with_pow2<1>(pmf_lanes_per_row(kpad), [&](auto L) {
-                constexpr int G = 256 / L;
-                hipLaunchKernelGGL((gamma_elbo_row_kernel<T, L>), dim3((unsigned)((r.rows + G - 1) / G)), dim3(256), 0, ctx->stream, r);
-            });
-    }
+    pmf_with_pow2<1>(pmf_lanes_per_row(ctx->kpad), [&](auto L) {
+        for (int s = 0; s < 2; ++s) launch_gamma_row_table<T, L>(ctx, s, gamma_exact_table<T>(ctx, s), nullptr, false);
+    });
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
-}
-
-// the exact kernel over the tasks, then the reference sweep's split kernel over the rows cut into several tasks
-template <typename T, int LPR, bool STATS>
-static void launch_gamma_exact(pmf_ctx *ctx, const GammaParams<T> &p, const T *table_self, const T *table_other, const PmfTaskView &tl) {
-    constexpr int G = 256 / LPR;
-    if (tl.n_tasks > 0) {
-        PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
-        hipLaunchKernelGGL((gamma_exact_kernel<T, LPR, STATS>), dim3((unsigned)((tl.n_tasks + G - 1) / G)), dim3(256), 0, ctx->stream, p,
-                           table_self, table_other);
-    }
-    if (tl.n_split > 0) {
-        PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
-        size_t smem = (size_t)G * 2 * ctx->kpad * sizeof(T);
-        hipLaunchKernelGGL((gamma_split_kernel<T, LPR, STATS, false>), dim3((unsigned)tl.n_split), dim3(256), smem, ctx->stream, p);
-    }
 }
 
 // PMF_PASS_FUSED or PMF_PASS_ACCUMULATE (finalize is run_gamma's).  The caller has checked the inputs and, with
@@ -1384,10 +1357,10 @@ static int run_gamma_exact(pmf_ctx *ctx, int side, PmfPass pass, bool tables, vo
     const GammaParams<T> p = gamma_params<T>(ctx, side, tl, stats, pr, pw);
     const T *table_self = gamma_exact_table<T>(ctx, side), *table_other = gamma_exact_table<T>(ctx, 1 - side);
     return gamma_launch(ctx, [&](auto L) {
-        if (pass == PMF_PASS_ACCUMULATE)
-            launch_gamma_exact<T, L, true>(ctx, p, table_self, table_other, tl);
+        if (pass == PMF_PASS_ACCUMULATE)   // (the split kernel is the reference sweep's)
+            launch_gamma<T, L, true, false, gamma_exact_kernel<T, L, true>>(ctx, p, tl, table_self, table_other);
         else
-            launch_gamma_exact<T, L, false>(ctx, p, table_self, table_other, tl);
+            launch_gamma<T, L, false, false, gamma_exact_kernel<T, L, false>>(ctx, p, tl, table_self, table_other);
     });
 }
 
@@ -1403,15 +1376,11 @@ extern "C" int pmf_gamma_exact_sweep(pmf_ctx *ctx, int side, double shape_prior,
         if (side != PMF_SIDE_ITEM || !pmf_comm_active(ctx)) return run_gamma_exact<T>(ctx, side, PMF_PASS_FUSED, true, nullptr, pr);
         // several ranks: pmf_gamma_sweep's exchange with the exact accumulate; the tables are built once, on the compute
         // stream, before the first chunk (finalize writes SHAPE and RATE of chunk c while later chunks still read the tables)
-        const PmfExchange ex = {false, pr.hierarchical ? 5 : 3,
-                                {PMF_ARR_FACTOR, PMF_ARR_SHAPE, PMF_ARR_RATE, PMF_ARR_PRIOR_RATE, PMF_ARR_HYPER_RATE}};
         int rc;
-        if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_FACTOR))) return rc;
-        if (pr.hierarchical && (rc = pmf_alloc_array(ctx, side, PMF_ARR_HYPER_RATE))) return rc;
         if ((rc = gamma_exact_build_tables<T>(ctx))) return rc;
-        return pmf_comm_half_sweep(ctx, side, 0, (size_t)2 * ctx->kpad, true, ex,
-                                   [&](void *s) { return run_gamma_exact<T>(ctx, side, PMF_PASS_ACCUMULATE, false, s, GammaPriors()); },
-                                   [&](void *s) { return run_gamma<T>(ctx, side, PMF_PASS_FINALIZE, false, s, pr); });
+        return gamma_comm_half_sweep<T>(ctx, side, pr, {PMF_ARR_FACTOR, PMF_ARR_HYPER_RATE}, [&](void *s) {
+            return run_gamma_exact<T>(ctx, side, PMF_PASS_ACCUMULATE, false, s, GammaPriors());
+        });
     });
 }
 
@@ -1757,11 +1726,7 @@ extern "C" int pmf_gamma_predictive(pmf_ctx *ctx, int64_t n, const int32_t *user
     PMF_REQUIRE(out_mean || out_var || out_logp || totals, PMF_EINVAL, "pmf_gamma_predictive: no output (out_mean, out_var, out_logp and totals are all null)");
     PMF_REQUIRE(ratings || !out_logp, PMF_EINVAL, "pmf_gamma_predictive: out_logp without ratings");
     int rc;
-    for (int s : {PMF_SIDE_USER, PMF_SIDE_ITEM}) {
-        if ((rc = pmf_require_array(ctx, s, PMF_ARR_SHAPE, "pmf_gamma_predictive"))) return rc;
-        if ((rc = pmf_require_array(ctx, s, PMF_ARR_RATE, "pmf_gamma_predictive"))) return rc;
-    }
-    PMF_REQUIRE(pmf_lanes_per_row(ctx->kpad) <= 64, PMF_ERANGE, "pmf_gamma_predictive: unsupported n_factors %d", ctx->K);
+    if ((rc = require_gamma_q(ctx, {PMF_SIDE_USER, PMF_SIDE_ITEM}, "pmf_gamma_predictive"))) return rc;
     for (int64_t k = 0; k < n; ++k) {
         PMF_REQUIRE(user_ids[k] >= 0 && user_ids[k] < ctx->rows[PMF_SIDE_USER], PMF_ERANGE,
                     "pmf_gamma_predictive: user id %d at position %lld outside [0, %lld)", user_ids[k], (long long)k,

@@ -1934,17 +1934,11 @@ extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
     int rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_fold_in"))) return rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_COV, "pmf_gauss_fold_in"))) return rc;
-    for (int64_t k = 0; k < nnz; ++k)
-        PMF_REQUIRE(other_ids[k] >= 0 && other_ids[k] < ctx->rows[other], PMF_ERANGE,
-                    "pmf_gauss_fold_in: id %d at position %lld outside [0, %lld)", other_ids[k], (long long)k,
-                    (long long)ctx->rows[other]);
+    if ((rc = pmf_check_ids(other_ids, nnz, ctx->rows[other], "pmf_gauss_fold_in", "id"))) return rc;
     const FoldInBatch a = {n_rows, row_ptr, other_ids, ratings, sigma2, eta2, eta_bias2, n_iter, out_factor, out_cov, out_bias};
-    try {  // host containers may throw: nothing propagates across the C boundary
+    return pmf_no_throw("pmf_gauss_fold_in", [&] {
         return pmf_with_dtype(ctx, [&](auto t) { return run_fold_in<decltype(t)>(ctx, side, a); });
-    } catch (const std::bad_alloc &) {
-        pmf_set_error("pmf_gauss_fold_in: out of host memory");
-        return PMF_ENOMEM;
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2387,10 +2381,7 @@ extern "C" int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, doubl
         if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_COV, "pmf_gauss_elbo_terms"))) return rc;
         PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gauss_elbo_terms: ratings have not been set");
     }
-    try {  // host containers may throw: nothing propagates across the C boundary
+    return pmf_no_throw("pmf_gauss_elbo_terms", [&] {
         return pmf_with_dtype(ctx, [&](auto t) { return run_elbo_terms<decltype(t)>(ctx, side, with_data != 0, totals, per_row); });
-    } catch (const std::bad_alloc &) {
-        pmf_set_error("pmf_gauss_elbo_terms: out of host memory");
-        return PMF_ENOMEM;
-    }
+    });
 }

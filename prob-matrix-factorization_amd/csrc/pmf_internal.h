@@ -7,6 +7,7 @@
 
 #include <functional>
 #include <initializer_list>
+#include <new>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -42,6 +43,25 @@ void pmf_set_error(const char *fmt, ...);
             return (code);                \
         }                                 \
     } while (0)
+
+// every ids[k] lies in [0, rows), or PMF_ERANGE naming the first that does not ("user id", "item id", "id")
+static inline int pmf_check_ids(const int32_t *ids, int64_t n, int64_t rows, const char *fn, const char *noun) {
+    for (int64_t k = 0; k < n; ++k)
+        PMF_REQUIRE(ids[k] >= 0 && ids[k] < rows, PMF_ERANGE, "%s: %s %d at position %lld outside [0, %lld)", fn, noun, ids[k],
+                    (long long)k, (long long)rows);
+    return PMF_OK;
+}
+
+// f(), with std::bad_alloc turned into PMF_ENOMEM: host containers may throw, and nothing propagates across the C boundary
+template <typename F>
+static inline int pmf_no_throw(const char *fn, F &&f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc &) {
+        pmf_set_error("%s: out of host memory", fn);
+        return PMF_ENOMEM;
+    }
+}
 
 // prologue of the per-side entry points (`ctx` and `side` are their arguments)
 #define PMF_SIDE_ENTRY(fn)                                                                             \

@@ -889,10 +889,7 @@ extern "C" int pmf_topk_items(pmf_ctx *ctx, int64_t n_query, const int32_t *user
     PMF_REQUIRE(user_ids && out_items && out_scores, PMF_EINVAL, "pmf_topk_items: null argument");
     PMF_REQUIRE(k >= 1 && k <= 1024 && k <= ctx->rows[PMF_SIDE_ITEM], PMF_ERANGE,
                 "pmf_topk_items: k=%d outside [1, min(1024, n_items)]", k);
-    for (int64_t n = 0; n < n_query; ++n)
-        PMF_REQUIRE(user_ids[n] >= 0 && user_ids[n] < ctx->rows[PMF_SIDE_USER], PMF_ERANGE,
-                    "pmf_topk_items: user id %d at position %lld outside [0, %lld)", user_ids[n], (long long)n,
-                    (long long)ctx->rows[PMF_SIDE_USER]);
+    if (int rc = pmf_check_ids(user_ids, n_query, ctx->rows[PMF_SIDE_USER], "pmf_topk_items", "user id")) return rc;
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     return pmf_with_dtype(ctx, [&](auto t) { return run_topk<decltype(t)>(ctx, n_query, user_ids, k, use_bias, out_items, out_scores); });
 }
@@ -1389,12 +1386,8 @@ static int rank_items_impl(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_ids
                 (long long)I);
     PMF_REQUIRE(!exclude_train || ctx->index[PMF_SIDE_USER].d_ptr, PMF_EINVAL,
                 "pmf_rank_items: exclude_train needs the training ratings (pmf_ctx_set_ratings); the context holds none");
-    for (int64_t n = 0; n < n_rows; ++n)
-        PMF_REQUIRE(user_ids[n] >= 0 && user_ids[n] < U, PMF_ERANGE, "pmf_rank_items: user id %d at position %lld outside [0, %lld)",
-                    user_ids[n], (long long)n, (long long)U);
-    for (int64_t n = 0; n < n_targets; ++n)
-        PMF_REQUIRE(item_ids[n] >= 0 && item_ids[n] < I, PMF_ERANGE, "pmf_rank_items: item id %d at position %lld outside [0, %lld)",
-                    item_ids[n], (long long)n, (long long)I);
+    if ((rc = pmf_check_ids(user_ids, n_rows, U, "pmf_rank_items", "user id"))) return rc;
+    if ((rc = pmf_check_ids(item_ids, n_targets, I, "pmf_rank_items", "item id"))) return rc;
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     if (exclude_train && (rc = pmf_index_distinct(ctx, PMF_SIDE_USER))) return rc;
 
@@ -1469,10 +1462,7 @@ extern "C" int pmf_rank_items(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_
     PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "pmf_rank_items: null context");
     PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_rank_items: negative n_rows");
     if (n_rows == 0) return PMF_OK;
-    try {
+    return pmf_no_throw("pmf_rank_items", [&] {
         return rank_items_impl(ctx, n_rows, user_ids, row_ptr, item_ids, use_bias, exclude_train, out_rank, out_candidates);
-    } catch (const std::bad_alloc &) {
-        pmf_set_error("pmf_rank_items: out of host memory");
-        return PMF_ENOMEM;
-    }
+    });
 }
