@@ -514,6 +514,7 @@ int pmf_comm_half_sweep(pmf_ctx *ctx, int side, int which, size_t width, bool ch
                         const std::function<int(void *)> &accumulate, const std::function<int(void *)> &finalize) {
     PmfComm *cm = ctx->comm;
     const int n = chunked ? ctx->n_chunks[side] : 1;
+    pmf_factor_written(ctx);   // (the finalize or the all-gather of a half-sweep may write FACTOR)
     int rc = ctx->d_stats[which].reserve(ctx, (size_t)ctx->rows[side] * width * ctx->elem,
                                          {ctx->stream, cm->stream, cm->fin_stream});
     if (!rc) rc = ensure_events(cm, (size_t)n);

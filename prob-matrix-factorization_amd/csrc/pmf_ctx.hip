@@ -189,6 +189,7 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
     ctx->gauss_generic = getenv("PMF_GAUSS_GENERIC") != nullptr;
     ctx->gauss_unfused = getenv("PMF_GAUSS_UNFUSED") != nullptr;
     ctx->gauss_lds_solve = getenv("PMF_GAUSS_LDS_SOLVE") != nullptr;
+    ctx->gauss_bias_gather = getenv("PMF_GAUSS_BIAS_GATHER") != nullptr;
     const char *hot_mb = getenv("PMF_GAUSS_HOT_MB");
     ctx->gauss_hot_bytes = (hot_mb ? std::max(atoll(hot_mb), 0LL) : (long long)PMF_GAUSS_HOT_MB_DEFAULT) << 20;
     ctx->topk_two_phase = getenv("PMF_TOPK_TWO_PHASE") != nullptr;
@@ -213,6 +214,7 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
 
 // Drop the ratings: both sides' index, work lists and hot-row flags.  The sweeps refuse a context in this state.
 static void drop_ratings(pmf_ctx *ctx) {
+    pmf_factor_written(ctx);
     ctx->index[0] = PmfSideIndex();
     ctx->index[1] = PmfSideIndex();
     ctx->nnz = 0;
@@ -644,6 +646,7 @@ static int set_row_chunks_impl(pmf_ctx *ctx, int side, int n_chunks) {
     if ((int64_t)n_chunks > ctx->rows[side]) n_chunks = (int)(ctx->rows[side] > 0 ? ctx->rows[side] : 1);
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    pmf_factor_written(ctx);
     ctx->n_chunks[side] = n_chunks;
     ctx->cur_chunk[side] = -1;
     if (!ctx->index[side].d_ptr) return PMF_OK;
@@ -760,6 +763,7 @@ extern "C" int pmf_set_array(pmf_ctx *ctx, int side, int array, const double *ho
     PMF_REQUIRE(array >= 0 && array < PMF_ARR_COUNT, PMF_EINVAL, "pmf_set_array: bad array id %d", array);
     PMF_REQUIRE(host, PMF_EINVAL, "pmf_set_array: null host pointer");
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
+    if (array == PMF_ARR_FACTOR) pmf_factor_written(ctx);
     int rc = pmf_alloc_array(ctx, side, array);
     if (rc) return rc;
     int width, stride;
@@ -869,6 +873,7 @@ static int array_rows_impl(pmf_ctx *ctx, int side, int array, int64_t n, const i
         PMF_REQUIRE(rows[k] >= 0 && rows[k] < ctx->rows[side], PMF_ERANGE, "%s: row %lld at position %lld outside [0, %lld)",
                     fn, (long long)rows[k], (long long)k, (long long)ctx->rows[side]);
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
+    if (host_in && array == PMF_ARR_FACTOR) pmf_factor_written(ctx);
     int rc = host_in ? pmf_alloc_array(ctx, side, array) : pmf_require_array(ctx, side, array, fn);
     if (rc) return rc;
     int width, stride;

@@ -582,6 +582,7 @@ template <typename T>
 static int run_gamma(pmf_ctx *ctx, int side, PmfPass pass, bool ext, void *stats, const GammaPriors &pr) {
     const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gamma_tasks, pass != PMF_PASS_FUSED);
     int rc;
+    pmf_factor_written(ctx);
     if (pass == PMF_PASS_FINALIZE) {
         // reads the statistics only, whichever accumulate wrote them: after pmf_gamma_exact_accumulate no FACTOR need exist
         if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_FACTOR))) return rc;
@@ -1347,6 +1348,7 @@ template <typename T>
 static int run_gamma_exact(pmf_ctx *ctx, int side, PmfPass pass, bool tables, void *stats, const GammaPriors &pr) {
     const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gamma_tasks, pass != PMF_PASS_FUSED);
     int rc;
+    pmf_factor_written(ctx);
     if (pass == PMF_PASS_FUSED) {
         if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_FACTOR))) return rc;   // (written, never read)
         if (pr.hierarchical && (rc = pmf_alloc_array(ctx, side, PMF_ARR_HYPER_RATE))) return rc;

@@ -47,6 +47,13 @@ struct GaussParams {
     // [nnz] per rating of `other`: 1 if that row of the opposite side is hot (PMF_GAUSS_HOT_MB), null = all hot.
     // Read by the fp32 K <= 64 accumulate only: cold rows are gathered with non-temporal loads.
     const uint8_t *hot = nullptr;
+    // Mean sums for the bias sweep, H_r = sum_j m_j over the ratings of row r (fused fp32 K <= 64 factor sweep only;
+    // all null everywhere else): a whole-row task stores m_r . H_r, with m_r the mean it has just solved, to mdot[r];
+    // a split task stores its part of H to partial_h[slot], the combine sums the parts in slot order into
+    // hsplit[position in `split`], and the split rows' solve forms the dot.
+    T *mdot = nullptr;        // [rows]
+    T *partial_h = nullptr;   // [n_slots][kpad]
+    T *hsplit = nullptr;      // [n_split][kpad]
 };
 
 __device__ __forceinline__ void wave_lds_fence() {
@@ -88,8 +95,8 @@ __device__ __forceinline__ void tri_rc(int p, int &r, int &c) {
 // chunks are loaded as 16/32-byte accesses (2 x CH in flight per lane) and
 // acc += V + m[r] m[c].  The (r, c) of a lane's entries are pass constants.
 template <typename T, int KR>
-__device__ __forceinline__ void solve_from_image(const T *img, T wj, int K, int kpad, T inv_sigma2, T inv_eta2,
-                                                 T *vout, T *mout, int lane);
+__device__ __forceinline__ T solve_from_image(const T *img, T wj, int K, int kpad, T inv_sigma2, T inv_eta2,
+                                              T *vout, T *mout, int lane);
 
 // KS > 0 (K <= 64): a task that is a whole row keeps its sums in an LDS image and is solved on the spot by the
 // same wavefront (the KS-row register sweep), as in the MFMA kernels -- this is how fp64 contexts (parity mode)
@@ -212,6 +219,10 @@ struct SolveParams {
     T *factor;
     T inv_sigma2, inv_eta2;
     int K, kpad, kp, cov_stride;
+    // K <= 64, both or neither: hsum[k] = the mean sums of rows[k] ([n][kpad], GaussParams::hsplit), mdot[row] receives
+    // the new mean's dot product with them
+    const T *hsum = nullptr;
+    T *mdot = nullptr;
 };
 
 __device__ __forceinline__ float readlane_dyn(float x, int lane) {
@@ -232,10 +243,10 @@ __device__ __forceinline__ double readlane_dyn(double x, int lane) {
 // cancellation).  The pivot row is always register 0 because every update
 // writes row i into register i-1; after KR steps the rows are back in place
 // and B = -inverse.  `img` is the packed lower triangle of S in LDS, `wj` lane
-// j's right-hand side; writes the packed inverse and the mean.
+// j's right-hand side; writes the packed inverse and the mean, and returns lane j's element of the mean as stored.
 template <typename T, int KR>
-__device__ __forceinline__ void solve_from_image(const T *img, T wj, int K, int kpad, T inv_sigma2, T inv_eta2,
-                                                 T *vout, T *mout, int lane) {
+__device__ __forceinline__ T solve_from_image(const T *img, T wj, int K, int kpad, T inv_sigma2, T inv_eta2,
+                                              T *vout, T *mout, int lane) {
     const int j = lane;
     T B[KR];
     const int jc = j < K ? j : 0;
@@ -291,7 +302,9 @@ __device__ __forceinline__ void solve_from_image(const T *img, T wj, int K, int 
         mj = fma(vij, readlane_dyn(wj, i), mj);
         if (i < K && j <= i) vout[i * (i + 1) / 2 + j] = vij;
     }
-    if (j < kpad) mout[j] = (j < K) ? mj * inv_sigma2 : (T)0;
+    const T mean = (j < K) ? mj * inv_sigma2 : (T)0;
+    if (j < kpad) mout[j] = mean;
+    return mean;
 }
 
 template <typename T, int KR>
@@ -307,8 +320,13 @@ __global__ __launch_bounds__(256) void gauss_solve_reg_kernel(SolveParams<T> p) 
     for (int q = lane * PMF_VEC; q < p.cov_stride; q += 64 * PMF_VEC) store4(img + q, load4(S + q));
     wave_lds_fence();
     const T wj = (lane < p.K) ? p.src_w[(int64_t)row * p.src_w_stride + lane] : (T)0;
-    solve_from_image<T, KR>(img, wj, p.K, p.kpad, p.inv_sigma2, p.inv_eta2,
-                            p.cov + (int64_t)row * p.cov_stride, p.factor + (int64_t)row * p.kpad, lane);
+    const T mean = solve_from_image<T, KR>(img, wj, p.K, p.kpad, p.inv_sigma2, p.inv_eta2,
+                                           p.cov + (int64_t)row * p.cov_stride, p.factor + (int64_t)row * p.kpad, lane);
+    if (p.hsum) {   // (uniform; lanes >= K hold a zero mean.  The position is formed again, as a scalar: nothing of it stays live across the sweep)
+        const int64_t k = (int64_t)blockIdx.x * 4 + rfl(threadIdx.x >> 6);
+        const T dot = group_sum<64>(mean * p.hsum[k * p.kpad + min((int)(threadIdx.x & 63), p.kpad - 1)]);
+        if ((threadIdx.x & 63) == 0) p.mdot[rfl(p.rows[k])] = dot;   // (hsum comes with a row list)
+    }
 }
 
 // 64 < K <= 128, fp32: a row is handled by the TWO wavefronts of a 128-thread block.
@@ -876,6 +894,7 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
 #pragma unroll
     for (int s = 0; s < NT; ++s) acc[s] = make_float4(0.f, 0.f, 0.f, 0.f);
     float wlo = 0.f, whi = 0.f;
+    float hlo = 0.f, hhi = 0.f;   // FUSE: the sum of the gathered mean rows themselves (GaussParams::mdot), two adds per pair
 
     // one loop trip = PU pairs of ratings; FULL trips carry no validity tests
     // The task's row ids and ratings come 64 at a time (one coalesced load each per 64 ratings) and
@@ -943,6 +962,10 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
         for (int u = 0; u < PU; ++u) {
             wlo = fmaf(mlo[u], res[u], wlo);
             whi = fmaf(mhi[u], res[u], whi);
+            if constexpr (FUSE) {
+                hlo += mlo[u];
+                if constexpr (KB == 64) hhi += mhi[u];
+            }
             d[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(mlo[u], mlo[u], d[0], 0, 0, 0);
             if constexpr (KB == 64) {
                 d[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(mhi[u], mlo[u], d[1], 0, 0, 0);
@@ -996,6 +1019,10 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
     wave_lds_fence();
     wlo += __shfl_xor(wlo, 32, 64);
     whi += __shfl_xor(whi, 32, 64);
+    if constexpr (FUSE) {
+        hlo += __shfl_xor(hlo, 32, 64);
+        if constexpr (KB == 64) hhi += __shfl_xor(hhi, 32, 64);
+    }
     if (FUSE && t.slot < 0) {
         // the row is complete: finish it here (S = image + covariance sums stays in
         // LDS) while the other wavefronts of the CU keep streaming
@@ -1012,14 +1039,25 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
             }
         }
         wave_lds_fence();
-        solve_from_image<float, KS>(img, h ? whi : wlo, K, kpad, inv_sigma2, inv_eta2,
-                                    cov_self + (int64_t)t.row * stride, factor_self + (int64_t)t.row * kpad, lane);
+        const float mean = solve_from_image<float, KS>(img, h ? whi : wlo, K, kpad, inv_sigma2, inv_eta2,
+                                                       cov_self + (int64_t)t.row * stride, factor_self + (int64_t)t.row * kpad, lane);
+        if (p.mdot) {   // (uniform; lanes >= K hold a zero mean)
+            const float dot = group_sum<64>(mean * (h ? hhi : hlo));
+            if (lane == 0) p.mdot[t.row] = dot;
+        }
         return;
     }
     float *out_s, *out_w;
     if (t.slot >= 0) {
         out_s = p.partial + (int64_t)t.slot * (stride + kpad);
         out_w = out_s + stride;
+        if constexpr (FUSE) {
+            if (p.partial_h && h == 0) {   // (lanes >= K summed zeros: the row padding is written as such)
+                float *out_h = p.partial_h + (int64_t)t.slot * kpad;
+                if (c < kpad) out_h[c] = hlo;
+                if (KB == 64 && 32 + c < kpad) out_h[32 + c] = hhi;
+            }
+        }
     } else {
         out_s = p.dst_s + (int64_t)t.row * p.dst_s_stride;
         out_w = p.dst_w + (int64_t)t.row * p.dst_w_stride;
@@ -1053,26 +1091,32 @@ __global__ __launch_bounds__(256) void gauss_combine_kernel(GaussParams<T> p) {
     const int width = p.cov_stride + p.kpad;  // multiple of PMF_VEC
     T *out_s = p.dst_s + (int64_t)sr.row * p.dst_s_stride;
     T *out_w = p.dst_w + (int64_t)sr.row * p.dst_w_stride;
-    const T *base = p.partial + (int64_t)sr.first_slot * width;
-    for (int e = threadIdx.x * PMF_VEC; e < width; e += 256 * PMF_VEC) {
+    // with p.partial_h the row's mean sums are kpad more elements behind the slot's width, in a slot array of their own
+    const int total = width + (p.partial_h ? p.kpad : 0);
+    for (int e = threadIdx.x * PMF_VEC; e < total; e += 256 * PMF_VEC) {
+        const bool hpart = e >= width;
+        const T *base = hpart ? p.partial_h + (int64_t)sr.first_slot * p.kpad + (e - width)
+                              : p.partial + (int64_t)sr.first_slot * width + e;
+        const int64_t step = hpart ? p.kpad : width;
         Vec4<T> acc = zero4<T>();
         int k = 0;
         for (; k + UN <= sr.n_slots; k += UN) {
             Vec4<T> v[UN];
 #pragma unroll
-            for (int q = 0; q < UN; ++q) v[q] = load4(base + (int64_t)(k + q) * width + e);
+            for (int q = 0; q < UN; ++q) v[q] = load4(base + (int64_t)(k + q) * step);
 #pragma unroll
             for (int q = 0; q < UN; ++q)
 #pragma unroll
                 for (int c = 0; c < PMF_VEC; ++c) acc.v[c] += v[q].v[c];
         }
         for (; k < sr.n_slots; ++k) {
-            Vec4<T> v = load4(base + (int64_t)k * width + e);
+            Vec4<T> v = load4(base + (int64_t)k * step);
 #pragma unroll
             for (int c = 0; c < PMF_VEC; ++c) acc.v[c] += v.v[c];
         }
         if (e < p.cov_stride) store4(out_s + e, acc);
-        else store4(out_w + (e - p.cov_stride), acc);
+        else if (!hpart) store4(out_w + (e - p.cov_stride), acc);
+        else store4(p.hsplit + (int64_t)blockIdx.x * p.kpad + (e - width), acc);
     }
 }
 
@@ -1237,13 +1281,53 @@ __global__ __launch_bounds__(256) void gauss_bias_kernel(BiasParams<T> p) {
     }
 }
 
+// The same sums without the gather, for a side whose fused factor sweep has left mdot[r] = m_r . H_r, H_r = the sum
+// of the mean rows of r's ratings (GaussParams::mdot; valid while neither side's means nor the ratings have changed):
+//     sum_j (x_j - b_o(j) - m_r . m_o(j)) = sum_j (x_j - b_o(j)) - m_r . H_r
+// What is left is a stream of 8 bytes per rating (id and rating, coalesced over the LPR lanes of the task's group)
+// and one 4-byte gather from the other side's bias table; LPR follows the task length, not K.  A split task leaves
+// its part of the first sum in its slot and gauss_bias_split_kernel subtracts the dot product once per row.
+template <typename T, int LPR>
+__global__ __launch_bounds__(256) void gauss_bias_sums_kernel(BiasParams<T> p, const T *mdot) {
+    constexpr int G = 256 / LPR;
+    constexpr int UN = 4;
+    const int c = threadIdx.x % LPR;
+    const int64_t task_id = (int64_t)blockIdx.x * G + threadIdx.x / LPR;
+    if (task_id >= p.n_tasks) return;
+    const PmfTask t = p.tasks[task_id];
+    const int32_t *col = p.other + t.start;
+    const T *val = p.val + t.start;
+    T sum = (T)0;
+    for (int base = c; base < t.len; base += UN * LPR) {
+        int o[UN];
+        T x[UN], b[UN];
+#pragma unroll
+        for (int q = 0; q < UN; ++q) {   // (past the task: its last rating again, not added)
+            const int j = min(base + q * LPR, t.len - 1);
+            o[q] = col[j];
+            x[q] = val[j];
+        }
+#pragma unroll
+        for (int q = 0; q < UN; ++q) b[q] = p.bias_other[o[q]];
+#pragma unroll
+        for (int q = 0; q < UN; ++q)
+            if (base + q * LPR < t.len) sum += x[q] - b[q];
+    }
+    sum = group_sum<LPR>(sum);
+    if (c != 0) return;
+    if (t.slot >= 0) p.partial[t.slot] = sum;
+    else p.bias_self[t.row] = bias_from_sum(p, sum - mdot[t.row], (T)t.len);
+}
+
+// `mdot` (may be null): subtracted from a split row's sum, see gauss_bias_sums_kernel
 template <typename T, bool STATS>
-__global__ void gauss_bias_split_kernel(BiasParams<T> p, int64_t n_split, const int64_t *ptr) {
+__global__ void gauss_bias_split_kernel(BiasParams<T> p, int64_t n_split, const int64_t *ptr, const T *mdot) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_split) return;
     const PmfSplitRow sr = p.split[s];
     T sum = (T)0;
     for (int k = 0; k < sr.n_slots; ++k) sum += p.partial[sr.first_slot + k];
+    if (mdot) sum -= mdot[sr.row];
     const T cnt = (T)(ptr[sr.row + 1] - ptr[sr.row]);
     if (STATS) {
         p.stats[(int64_t)sr.row * 2] = sum;
@@ -1553,11 +1637,19 @@ static int launch_accumulate(pmf_ctx *ctx, const GaussParams<T> &p, int64_t n_sp
     return PMF_OK;
 }
 
+// GaussParams::partial_h of the fused factor sweep: behind the partial slots, and behind it GaussParams::hsplit
+template <typename T>
+static T *gauss_partial_h(const pmf_ctx *ctx, const PmfTaskView &tl) {
+    return ctx->d_partial.as<T>() + tl.n_slots * (ctx->cov_stride + ctx->kpad);
+}
+
 // The fused pass sums in place into COV / FACTOR, the accumulate pass into `stats`.  *fused (fused pass): the kernel
-// also solved every single-task row, so the caller only solves the split rows.
+// also solved every single-task row, so the caller only solves the split rows.  *sums (fused pass): the kernel also
+// emits the mean sums of the bias sweep (GaussParams::mdot) -- only the fused fp32 K <= 64 kernel of a context with
+// biases and without a communicator does.
 template <typename T>
 static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double sigma2, double eta2,
-                                 bool *fused = nullptr) {
+                                 bool *fused = nullptr, bool *sums = nullptr) {
     const int other = 1 - side;
     const PmfSideIndex &ix = ctx->index[side];
     const bool acc = pass == PMF_PASS_ACCUMULATE;
@@ -1569,18 +1661,29 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *sta
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_factor_sweep"))) return rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_COV, "pmf_gauss_factor_sweep"))) return rc;
     const int width = ctx->cov_stride + ctx->kpad;
-    if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * width * sizeof(T)))) return rc;
+    const bool fuse = !acc && !ctx->gauss_unfused;
+    const bool emit = sums && fuse && std::is_same<T, float>::value && !ctx->gauss_generic && ctx->K <= 64 &&
+                      !ctx->gauss_bias_gather && pmf_has_bias(ctx) && !pmf_comm_active(ctx);
+    const size_t h_elems = emit ? (size_t)(tl.n_slots + tl.n_split) * ctx->kpad : 0;
+    if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, ((size_t)tl.n_slots * width + h_elems) * sizeof(T)))) return rc;
+    if (emit && (rc = ctx->d_mdot[side].reserve(ctx, (size_t)ctx->rows[side] * sizeof(T), {ctx->stream}))) return rc;
     if (acc && tl.row1 > tl.row0)  // rows without ratings on this rank contribute zeros
         PMF_HIP_CHECK(hipMemsetAsync((T *)stats + tl.row0 * width, 0, (size_t)(tl.row1 - tl.row0) * width * sizeof(T), ctx->stream));
     GaussParams<T> p = gauss_params<T>(ctx, side);
     p.tasks = tl.d_tasks;
     p.n_tasks = tl.n_tasks;
     p.split = tl.d_split;
+    if (emit) {
+        p.mdot = ctx->d_mdot[side].as<T>();
+        p.partial_h = gauss_partial_h<T>(ctx, tl);
+        p.hsplit = p.partial_h + tl.n_slots * ctx->kpad;
+    }
+    if (sums) *sums = emit;
     p.dst_s = acc ? (T *)stats : ctx->arr[side][PMF_ARR_COV].as<T>();
     p.dst_s_stride = acc ? width : ctx->cov_stride;
     p.dst_w = acc ? (T *)stats + ctx->cov_stride : ctx->arr[side][PMF_ARR_FACTOR].as<T>();
     p.dst_w_stride = acc ? width : ctx->kpad;
-    return launch_accumulate<T>(ctx, p, tl.n_split, !acc && !ctx->gauss_unfused, sigma2, eta2, fused);
+    return launch_accumulate<T>(ctx, p, tl.n_split, fuse, sigma2, eta2, fused);
 }
 
 // the row solver for the context's K and dtype over the rows `sp` names
@@ -1636,10 +1739,11 @@ static SolveParams<T> solve_params(const pmf_ctx *ctx, double sigma2, double eta
 }
 
 // finalize pass: every row of the selected range from `stats`; fused pass: the rows with ratings (the split rows only
-// when the accumulate kernel solved the others) from the sums in COV / FACTOR
+// when the accumulate kernel solved the others) from the sums in COV / FACTOR.  `sums` (with split_rows_only): the
+// accumulate emitted the mean sums, so the split rows' solve completes ctx->d_mdot[side].
 template <typename T>
 static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *stats, double sigma2, double eta2,
-                            bool split_rows_only = false) {
+                            bool split_rows_only = false, bool sums = false) {
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0, PMF_EINVAL, "pmf_gauss_factor_sweep: variances must be positive");
     int rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_factor_finalize"))) return rc;
@@ -1657,12 +1761,17 @@ static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *st
     sp.src_w_stride = fin ? width : ctx->kpad;
     sp.cov = ctx->arr[side][PMF_ARR_COV].as<T>();
     sp.factor = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
+    if (sums && split_rows_only && sp.n > 0) {
+        sp.hsum = gauss_partial_h<T>(ctx, tl) + tl.n_slots * ctx->kpad;
+        sp.mdot = ctx->d_mdot[side].as<T>();
+    }
     return launch_solve<T>(ctx, sp);
 }
 
 extern "C" int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
     PMF_SIDE_ENTRY("pmf_gauss_factor_sweep");
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0, PMF_EINVAL, "pmf_gauss_factor_sweep: variances must be positive");
+    pmf_factor_written(ctx);   // the other side's mean sums were taken against this side's old means
     return pmf_with_dtype(ctx, [&](auto t) {
         using T = decltype(t);
         if (side == PMF_SIDE_ITEM && pmf_comm_active(ctx)) {
@@ -1673,9 +1782,12 @@ extern "C" int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, dou
                                        [&](void *s) { return run_factor_accumulate<T>(ctx, side, PMF_PASS_ACCUMULATE, s, 1.0, 1.0); },
                                        [&](void *s) { return run_factor_solve<T>(ctx, side, PMF_PASS_FINALIZE, s, sigma2, eta2); });
         }
-        bool fused = false;
-        int rc = run_factor_accumulate<T>(ctx, side, PMF_PASS_FUSED, nullptr, sigma2, eta2, &fused);
-        return rc ? rc : run_factor_solve<T>(ctx, side, PMF_PASS_FUSED, nullptr, sigma2, eta2, fused);
+        bool fused = false, sums = false;
+        int rc = run_factor_accumulate<T>(ctx, side, PMF_PASS_FUSED, nullptr, sigma2, eta2, &fused, &sums);
+        if (!rc) rc = run_factor_solve<T>(ctx, side, PMF_PASS_FUSED, nullptr, sigma2, eta2, fused, fused && sums);
+        // every row with ratings was solved with its mean sums at hand: by the accumulate kernel or as a split row
+        if (!rc && fused && sums) ctx->gauss_mdot_valid[side] = true;
+        return rc;
     });
 }
 
@@ -1689,6 +1801,7 @@ extern "C" int pmf_gauss_factor_finalize(pmf_ctx *ctx, int side, const void *sta
                                          double eta2) {
     PMF_SIDE_ENTRY("pmf_gauss_factor_finalize");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_factor_finalize: null stats buffer");
+    pmf_factor_written(ctx);
     return pmf_with_dtype(ctx, [&](auto t) { return run_factor_solve<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, stats_dev, sigma2, eta2); });
 }
 
@@ -1724,6 +1837,10 @@ static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double si
     p.kpad = ctx->kpad;
     p.row0 = tl.row0;
     p.rows = tl.row1;
+    // fused single-rank fp32 pass after this side's fused factor sweep, nothing written since: the sums form
+    const bool from_sums = pass == PMF_PASS_FUSED && std::is_same<T, float>::value && ctx->gauss_mdot_valid[side] &&
+                           !ctx->gauss_bias_gather && !pmf_comm_active(ctx);
+    const T *mdot = from_sums ? ctx->d_mdot[side].as<const T>() : nullptr;
     PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_BIAS);   // (the statistics memset included)
     if (pass == PMF_PASS_FINALIZE) {
         if (p.rows > p.row0)
@@ -1732,7 +1849,13 @@ static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double si
     } else {
         if (acc && p.rows > p.row0)
             PMF_HIP_CHECK(hipMemsetAsync((T *)stats + p.row0 * 2, 0, (size_t)(p.rows - p.row0) * 2 * sizeof(T), ctx->stream));
-        if (tl.n_tasks > 0)
+        if (tl.n_tasks > 0 && from_sums) {
+            // a wavefront per task where the tasks are long (the benchmark's item side: 512), 16 lanes otherwise
+            if (ctx->nnz / tl.n_tasks >= 64)
+                hipLaunchKernelGGL((gauss_bias_sums_kernel<T, 64>), dim3((unsigned)((p.n_tasks + 3) / 4)), dim3(256), 0, ctx->stream, p, mdot);
+            else
+                hipLaunchKernelGGL((gauss_bias_sums_kernel<T, 16>), dim3((unsigned)((p.n_tasks + 15) / 16)), dim3(256), 0, ctx->stream, p, mdot);
+        } else if (tl.n_tasks > 0)
             pmf_with_pow2<1>(pmf_lanes_per_row(ctx->kpad), [&](auto L) {
                 dim3 grid((unsigned)((p.n_tasks + 256 / L - 1) / (256 / L)));
                 if (acc) hipLaunchKernelGGL((gauss_bias_kernel<T, L, true>), grid, dim3(256), 0, ctx->stream, p);
@@ -1740,8 +1863,8 @@ static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double si
             });
         if (tl.n_split > 0) {
             dim3 grid((unsigned)((tl.n_split + 255) / 256));
-            if (acc) hipLaunchKernelGGL((gauss_bias_split_kernel<T, true>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr.as<int64_t>());
-            else hipLaunchKernelGGL((gauss_bias_split_kernel<T, false>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr.as<int64_t>());
+            if (acc) hipLaunchKernelGGL((gauss_bias_split_kernel<T, true>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr.as<int64_t>(), mdot);
+            else hipLaunchKernelGGL((gauss_bias_split_kernel<T, false>), grid, dim3(256), 0, ctx->stream, p, tl.n_split, ix.d_ptr.as<int64_t>(), mdot);
         }
     }
     PMF_HIP_CHECK(hipGetLastError());

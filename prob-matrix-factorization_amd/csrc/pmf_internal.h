@@ -214,6 +214,12 @@ struct pmf_ctx {
 
     // scratch, grown on demand (pmf_ensure_*)
     PmfBuf d_partial, d_scratch;
+    // Gaussian bias sweep from the factor sweep's mean sums (pmf_gauss.hip): d_mdot[side][r] = m_r . H_r, with m_r the
+    // mean the fused factor sweep of `side` has just written and H_r the sum of the mean rows of the other side it
+    // gathered for row r (a pair rated twice counts twice).  gauss_mdot_valid[side] holds while the FACTOR arrays of
+    // BOTH sides and the ratings are what that sweep saw: everything that may write either calls pmf_factor_written.
+    PmfBuf d_mdot[2];
+    bool gauss_mdot_valid[2] = {false, false};
     // pmf_gamma_exact_sweep / _accumulate: the (E log, E) tables [rows][2][kpad] of the users, then of the items; rebuilt
     // by every call, in storage of their own so that a pmf_gamma_elbo_terms call (d_scratch) cannot write over them
     PmfBuf d_gamma_tables;
@@ -223,6 +229,7 @@ struct pmf_ctx {
     bool gauss_generic = false;    // PMF_GAUSS_GENERIC: the generic accumulate kernel instead of the MFMA ones
     bool gauss_unfused = false;    // PMF_GAUSS_UNFUSED: accumulate and solve as separate launches
     bool gauss_lds_solve = false;  // PMF_GAUSS_LDS_SOLVE: the block-per-row LDS solve for 64 < K <= 128
+    bool gauss_bias_gather = false;  // PMF_GAUSS_BIAS_GATHER: the bias sweep always gathers the mean rows (never the factor sweep's mean sums)
     int64_t gauss_hot_bytes = 0;   // PMF_GAUSS_HOT_MB: budget of the hot gathered rows per side (0: policy off)
     int topk_max_blocks = 0;       // PMF_TOPK_MAX_BLOCKS=n caps the fused kernel's persistent grid (tests: many tiles per block)
     int topk_stage_buffers = 0;    // PMF_TOPK_STAGE_BUFFERS=1|2 pins the fused kernel's stage buffering (0: by residency)
@@ -354,5 +361,8 @@ static inline auto pmf_with_pow2(int n, F &&f) {
     if (MIN == 64 || n <= MIN) return f(std::integral_constant<int, MIN>());
     return pmf_with_pow2<MIN < 64 ? 2 * MIN : 64>(n, f);
 }
+
+// a FACTOR array or the ratings are about to change: the mean sums of the last factor sweeps no longer describe them
+static inline void pmf_factor_written(pmf_ctx *ctx) { ctx->gauss_mdot_valid[0] = ctx->gauss_mdot_valid[1] = false; }
 
 static inline bool pmf_has_bias(const pmf_ctx *ctx) { return ctx->arr[0][PMF_ARR_BIAS] && ctx->arr[1][PMF_ARR_BIAS]; }

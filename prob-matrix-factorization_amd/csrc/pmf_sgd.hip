@@ -164,6 +164,7 @@ int run_sgd(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double lr, double
     const int other = 1 - side;
     const PmfSideIndex &ix = ctx->index[side];
     PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_gauss_sgd_sweep: ratings have not been set");
+    pmf_factor_written(ctx);
     int rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_sgd_sweep"))) return rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_sgd_sweep"))) return rc;
