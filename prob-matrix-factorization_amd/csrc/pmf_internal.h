@@ -362,6 +362,14 @@ static inline auto pmf_with_pow2(int n, F &&f) {
     return pmf_with_pow2<MIN < 64 ? 2 * MIN : 64>(n, f);
 }
 
+// f(std::integral_constant<int, MODE>()) for predict's mode: 0, PMF_PREDICT_BIAS or PMF_PREDICT_SCALE (checked by the caller)
+template <typename F>
+static inline auto pmf_with_predict_mode(int mode, F &&f) {
+    if (mode == PMF_PREDICT_BIAS) return f(std::integral_constant<int, PMF_PREDICT_BIAS>());
+    if (mode == PMF_PREDICT_SCALE) return f(std::integral_constant<int, PMF_PREDICT_SCALE>());
+    return f(std::integral_constant<int, 0>());
+}
+
 // a FACTOR array or the ratings are about to change: the mean sums of the last factor sweeps no longer describe them
 static inline void pmf_factor_written(pmf_ctx *ctx) { ctx->gauss_mdot_valid[0] = ctx->gauss_mdot_valid[1] = false; }
 

@@ -107,6 +107,45 @@ __device__ __forceinline__ void wave_best(S &bv, int &bidx, bool &found) {
     }
 }
 
+// A wavefront writes one user's k best candidates, best first, to out_items / out_scores (the user's k entries): k passes,
+// each the wave arg-best of the candidates that rank after the previous pick -- deterministic, no sorting network.
+// scan(visit) calls visit(value, index) for every candidate of this lane (no NaN among them).  Fewer than k candidates:
+// the rest is item -1, score 0.0.
+template <typename S, typename Scan>
+__device__ __forceinline__ void topk_select_passes(int lane, int k, int32_t *out_items, double *out_scores, Scan &&scan) {
+    bool have_prev = false;
+    S pv = (S)0;
+    int pi = -1;
+    for (int t = 0; t < k; ++t) {
+        bool found = false;
+        S bv = (S)0;
+        int bidx = 0x7fffffff;
+        scan([&](S v, int i) __attribute__((always_inline)) {
+            if (have_prev && !ranks_before(pv, pi, v, i)) return;
+            if (!found || ranks_before(v, i, bv, bidx)) {
+                bv = v;
+                bidx = i;
+                found = true;
+            }
+        });
+        wave_best(bv, bidx, found);
+        if (lane == 0) {
+            out_items[t] = found ? bidx : -1;
+            out_scores[t] = found ? (double)bv : 0.0;
+        }
+        if (!found) {  // fewer than k rankable items: fill the rest
+            for (int r = t + 1; r < k && lane == 0; ++r) {
+                out_items[r] = -1;
+                out_scores[r] = 0.0;
+            }
+            break;
+        }
+        have_prev = true;
+        pv = bv;
+        pi = bidx;
+    }
+}
+
 // One wavefront per user, k <= 64.  Two passes over the user's score row instead of k:
 //  (1) per-lane maxima; the k-th largest of the 64 lane maxima is a lower bound tau of the
 //      k-th best score (the k best lane maxima are k distinct entries >= tau);
@@ -184,54 +223,17 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const S *scores, int n
             __builtin_amdgcn_wave_barrier();
         }
     }
-    bool have_prev = false;
-    S pv = (S)0;
-    int pi = -1;
-    for (int t = 0; t < k; ++t) {
-        bool found = false;
-        S bv = (S)0;
-        int bidx = 0x7fffffff;
+    topk_select_passes<S>(lane, k, out_items + (int64_t)q * k, out_scores + (int64_t)q * k, [&](auto visit) __attribute__((always_inline)) {
         if (count >= 0) {
-            for (int e = lane; e < count; e += 64) {
-                const S v = cv[e];
-                const int i = ci[e];
-                if (have_prev && !ranks_before(pv, pi, v, i)) continue;
-                if (!found || ranks_before(v, i, bv, bidx)) {
-                    bv = v;
-                    bidx = i;
-                    found = true;
-                }
-            }
+            for (int e = lane; e < count; e += 64) visit(cv[e], ci[e]);
         } else {
             for (int64_t i = lane; i < n_items; i += 64) {
                 const S v = row[i];
-                if (!(v == v)) continue;  // NaN never ranks
-                if (have_prev && !ranks_before(pv, pi, v, (int)i)) continue;
-                if (!found || ranks_before(v, (int)i, bv, bidx)) {
-                    bv = v;
-                    bidx = (int)i;
-                    found = true;
-                }
+                if (v == v) visit(v, (int)i);         // NaN never ranks
             }
         }
-        wave_best(bv, bidx, found);
-        if (lane == 0) {
-            out_items[(int64_t)q * k + t] = found ? bidx : -1;
-            out_scores[(int64_t)q * k + t] = found ? (double)bv : 0.0;
-        }
-        if (!found) {  // fewer than k rankable items: fill the rest
-            for (int r = t + 1; r < k && lane == 0; ++r) {
-                out_items[(int64_t)q * k + r] = -1;
-                out_scores[(int64_t)q * k + r] = 0.0;
-            }
-            break;
-        }
-        have_prev = true;
-        pv = bv;
-        pi = bidx;
-    }
+    });
 }
-
 
 // ---------------------------------------------------------------------------
 // fused score + select, fp32, Kpad <= 128, k <= 64: scores never touch HBM
@@ -252,7 +254,11 @@ __global__ __launch_bounds__(256) void topk_select_kernel(const S *scores, int n
 // wave in parallel (lane e holds entry e: one compare, one ballot, one shift), in ascending item order, so
 // ties keep the lower item id.  With few query users the item range is cut into segments (gridDim.y) so
 // that the chip is filled; a merge kernel then picks the k best of the segments' lists.
-// (rank_fused_kernel below carries a copy of this kernel's staging and stage loop: keep the two in step.)
+// (The A pieces, the MFMA chain, the score and the priority slices are functions that rank_fused_kernel uses too.  Its
+//  staging lambdas, publish and stage loop are still a COPY of this kernel's, less the one-buffer publish and the priority
+//  rotation before the last full stage: as a shared function or struct, in nine spellings, they changed the register
+//  allocation of rank_fused_kernel<32, 0, 1> into one with VGPR spills.  A change to the staging or the stage loop of
+//  either kernel belongs in the other too.)
 #define TOPK_NEG_INF (-__builtin_inff())
 #ifndef PRIO_SLICE
 #define PRIO_SLICE 16      // stages between priority rotations (tools/probe_topk_stamps.py sweeps it: 1 .. 64 are equivalent)
@@ -291,6 +297,62 @@ struct TopkStage {
     static constexpr size_t buffer_bytes = (size_t)ST * PQ * 16;   // the kernel takes one or two of these (nbuf)
 };
 
+// The score arithmetic of the fused kernels -- topk_fused_kernel, rank_fused_kernel and rank_rows_kernel -- is the three
+// functions below and nothing else: pmf_rank_items is right only if all three give a score with the same bits (an MFMA
+// output element depends on its A row, its B column and the k sequence only).
+
+// A operand: lane (c = l & 31, h = l >> 5) holds the 16-byte pieces 2 q + h, q = 0 .. KH / 4 - 1, of the row of `user`
+// in a[4 q .. 4 q + 3]; this is the piece of t = 4 q (zero past Kpad, and for user < 0: no user).
+// (The caller keeps the loop over t: the same loop inside a function of its own changes the register allocation of every
+//  fused kernel -- topk_fused_kernel<16, 0, 2> goes from 87 to 99 VGPRs, five waves per SIMD to four;
+//  tools/kernel_asm_table.py shows it.)
+__device__ __forceinline__ float4 topk_a_piece(const float *fu, int user, int kpad, int h, int t) {
+    const int kk = 2 * t + 4 * h;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (user >= 0 && kk < kpad) v = *reinterpret_cast<const float4 *>(fu + (int64_t)user * kpad + kk);
+    return v;
+}
+
+// the KH MFMA steps of one 32-item tile; piece(t), t = 0, 4, .., KH - 4, is piece t / 2 + h of this lane's item (column c)
+// -- past Kpad the last piece again, as the stage holds it (the A operand is zero there)
+template <int KH, typename Piece>
+__device__ __forceinline__ void topk_mfma_tile(const float (&a)[KH], f32x16 &acc, Piece &&piece) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int t = 0; t < KH; t += 4) {
+        const f32x4 b = piece(t);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 1], b.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 2], b.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 3], b.w, acc, 0, 0, 0);
+    }
+}
+
+// dot product -> score: predict's arithmetic order (ucst / ccst: the user's and the item's bias or scale)
+template <int MODE, typename S>
+__device__ __forceinline__ S rank_score(S dot, S ucst, S ccst) {
+    if (MODE == PMF_PREDICT_BIAS) return ucst + ccst + dot;
+    if (MODE == PMF_PREDICT_SCALE) return dot * (ucst * ccst);
+    return dot;
+}
+
+// Time-sliced priority.  Left alone, the SIMD's arbitration favours the same resident wave for a whole scan: the
+// four blocks of a CU then finish one after the other (9.4 .. 16.5 ms for the same work) and the last quarter of
+// the launch runs at 3, 2, 1 blocks per CU.  Rotating s_setprio over the SIMD's wave slots every PRIO_SLICE stages
+// makes them finish together (12.3 .. 12.7 ms): profiles/r03_topk_wave_stamps.jsonl.
+__device__ __forceinline__ int topk_wave_slot() {   // HW_ID.WAVE_ID: this wave's slot on its SIMD
+    return __builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 3;
+}
+__device__ __forceinline__ void topk_slice_priority(int slot, int stage_no) {
+    switch ((slot + stage_no / PRIO_SLICE) & 3) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
+
 // (waves per SIMD the register allocation must leave room for: four for the plain K <= 64 scan, whose lists leave room for
 //  four blocks per CU; the bias / scale modes and K > 64 need more registers than that)
 template <int KH, int MODE, int NBUF>
@@ -325,19 +387,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? 
 #ifdef PMF_TOPK_STAMPS
     const long long st_begin = __builtin_amdgcn_s_memrealtime();
     long long st_drain = 0, st_barrier = 0, st_cand = 0, st_tiles = 0;
-#define STAMP_BARRIER() do { const long long t_ = __builtin_amdgcn_s_memtime(); __syncthreads(); st_barrier += __builtin_amdgcn_s_memtime() - t_; } while (0)
-#else
-#define STAMP_BARRIER() __syncthreads()
 #endif
+    auto barrier = [&]() __attribute__((always_inline)) {   // the scan's block barrier (the stamped build times the wait)
+#ifdef PMF_TOPK_STAMPS
+        const long long t_ = __builtin_amdgcn_s_memtime();
+#endif
+        __syncthreads();
+#ifdef PMF_TOPK_STAMPS
+        st_barrier += __builtin_amdgcn_s_memtime() - t_;
+#endif
+    };
 
     // A operand: this lane's pieces of user (q0 + c)'s row, resident for the whole scan
     const int user = (q0 + c < p.nq) ? p.users[q0 + c] : -1;
     float a[KH];
 #pragma unroll
     for (int t = 0; t < KH; t += 4) {
-        const int kk = 2 * t + 4 * h;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (user >= 0 && kk < kpad) v = *reinterpret_cast<const float4 *>(fu + (int64_t)user * kpad + kk);
+        const float4 v = topk_a_piece(fu, user, kpad, h, t);
         a[t] = v.x; a[t + 1] = v.y; a[t + 2] = v.z; a[t + 3] = v.w;
     }
     // per accumulator register r: the user of row (r & 3) + 8 (r >> 2) + 4 h, its bias / scale, its k-th best
@@ -440,31 +506,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? 
         return topk_key_score_bits(kth);
     };
 
-    // the KH MFMA steps of one 32-item tile, B operand from the staged rows
-    auto mfma_all = [&](const f32x4 *rows, f32x16 &acc) __attribute__((always_inline)) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        const f32x4 *mine = rows + c * PQ + h;
-#pragma unroll
-        for (int t = 0; t < KH; t += 4) {
-            const f32x4 b = mine[t / 2];             // piece 2 (t / 4) + h of item (i0 + c)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 1], b.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 2], b.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 3], b.w, acc, 0, 0, 0);
-        }
-    };
-    // dot products -> scores (predict's arithmetic order); TAIL: the stage holds rows past the segment's end
+    // dot products -> scores; TAIL: the stage holds rows past the segment's end
     auto scores = [&](auto TAIL, int i0, f32x16 &acc) __attribute__((always_inline)) {
         if (MODE == 0) return;
         const int it = i0 + c;
         float ccst = MODE == PMF_PREDICT_SCALE ? 1.f : 0.f;
         if (!decltype(TAIL)::value || it < i_end) ccst = ci[it];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if (MODE == PMF_PREDICT_BIAS) acc[r] = ucst[r] + ccst + acc[r];  // b_u + b_i + dot
-            if (MODE == PMF_PREDICT_SCALE) acc[r] = acc[r] * (ucst[r] * ccst);
-        }
+        for (int r = 0; r < 16; ++r) acc[r] = rank_score<MODE>(acc[r], ucst[r], ccst);
     };
     // Does any score of the tile reach its user's list?  Almost never (a list changes ~k ln(N / k) times in N items), so
     // the test itself is what a tile pays: 16 v_cmpx narrow EXEC to the lanes whose rows are ALL below their thresholds
@@ -540,26 +589,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? 
             }
         }
     };
-    // Time-sliced priority.  Left alone, the SIMD's arbitration favours the same resident wave for a whole scan: the
-    // four blocks of a CU then finish one after the other (9.4 .. 16.5 ms for the same work) and the last quarter of
-    // the launch runs at 3, 2, 1 blocks per CU.  Rotating s_setprio over the SIMD's wave slots every PRIO_SLICE stages
-    // makes them finish together (12.3 .. 12.7 ms): profiles/r03_topk_wave_stamps.jsonl.
-    const int slot = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 3;   // HW_ID.WAVE_ID: this wave's slot on its SIMD
-    auto slice_priority = [&](int stage_no) __attribute__((always_inline)) {
-        switch ((slot + stage_no / PRIO_SLICE) & 3) {
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
-    };
+    const int slot = topk_wave_slot();
+    auto slice_priority = [&](int stage_no) __attribute__((always_inline)) { topk_slice_priority(slot, stage_no); };
     auto rotate_priority = [&](int stage_no) __attribute__((always_inline)) {
         if ((stage_no & (PRIO_SLICE - 1)) == 0) slice_priority(stage_no);
     };
     auto tile = [&](auto TAIL, int i0, const f32x4 *rows, int stage_no) __attribute__((always_inline)) {
         f32x16 acc;
         unsigned long long mk[16], okm;
-        mfma_all(rows, acc);
+        const f32x4 *mine = rows + c * PQ + h;
+        topk_mfma_tile<KH>(a, acc, [&](int t) __attribute__((always_inline)) { return mine[t / 2]; });
         scores(TAIL, i0, acc);
         // which half of the rows holds a candidate (the v_cmpx blocks' lane masks); a partial tile takes both
         unsigned long long m1 = 0ull, m2 = 0ull;
@@ -597,12 +636,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? 
     auto publish = [&]() __attribute__((always_inline)) {
         if (nbuf == 2) {
             stash(buf ^ 1);                           // last read there: the stage before this one, behind the barrier
-            STAMP_BARRIER();
+            barrier();
             buf ^= 1;
         } else {                                      // one buffer (long lists: the LDS saved keeps another block resident)
-            STAMP_BARRIER();                          // every wave has read this stage
+            barrier();                                // every wave has read this stage
             stash(0);
-            STAMP_BARRIER();
+            barrier();
         }
     };
     // The loop proper has no case to tell apart: it runs while the stage after the current one is a full one; the
@@ -635,7 +674,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? 
         i0 += ST;
     }
     if (has_tail) tiles(PARTIAL, i0, stage + (size_t)buf * ST * PQ, stage_no);
-    STAMP_BARRIER();                                  // the next user tile's first stage goes where this one is read
+    barrier();                                        // the next user tile's first stage goes where this one is read
     // hand the lists over: final result when the item range was not segmented, else this segment's candidates
     for (int e = lane; e < 32 * k; e += 64) {
         const int ul = e / k, t = e % k;
@@ -679,40 +718,36 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *cand_val, 
     if (q >= nq) return;
     const float *cv = cand_val + (int64_t)q * n_cand;
     const int32_t *ci = cand_idx + (int64_t)q * n_cand;
-    bool have_prev = false;
-    float pv = 0.f;
-    int pi = -1;
-    for (int t = 0; t < k; ++t) {
-        bool found = false;
-        float bv = 0.f;
-        int bidx = 0x7fffffff;
+    topk_select_passes<float>(lane, k, out_items + (int64_t)q * k, out_scores + (int64_t)q * k, [&](auto visit) __attribute__((always_inline)) {
         for (int e = lane; e < n_cand; e += 64) {
             const float v = cv[e];
             const int i = ci[e];
-            if (i == 0x7fffffff) continue;   // an unused list slot
-            if (have_prev && !ranks_before(pv, pi, v, i)) continue;
-            if (!found || ranks_before(v, i, bv, bidx)) {
-                bv = v;
-                bidx = i;
-                found = true;
-            }
+            if (i != 0x7fffffff) visit(v, i);         // (0x7fffffff: an unused list slot)
         }
-        wave_best(bv, bidx, found);
-        if (lane == 0) {
-            out_items[(int64_t)q * k + t] = found ? bidx : -1;
-            out_scores[(int64_t)q * k + t] = found ? (double)bv : 0.0;
-        }
-        if (!found) {
-            for (int r = t + 1; r < k && lane == 0; ++r) {
-                out_items[(int64_t)q * k + r] = -1;
-                out_scores[(int64_t)q * k + r] = 0.0;
-            }
-            break;
-        }
-        have_prev = true;
-        pv = bv;
-        pi = bidx;
-    }
+    });
+}
+
+// Segments of the item range of a fused scan (gridDim.y).  Few query rows: cut the range so that the grid still has a few
+// thousand wavefronts.  Returns the number of segments; *seg_items = items per segment, a multiple of 32.
+static int topk_segments(int64_t n_rows, int64_t I, int64_t *seg_items) {
+    const int64_t waves = (n_rows + 31) / 32;
+    int nseg = (int)std::min<int64_t>(64, std::max<int64_t>(1, 4096 / waves));
+    nseg = (int)std::min<int64_t>(nseg, std::max<int64_t>(1, I / 2048));
+    *seg_items = ((I + nseg - 1) / nseg + 31) / 32 * 32;
+    return (int)((I + *seg_items - 1) / *seg_items);
+}
+
+// The fused scans are persistent in x: at most as many blocks as are resident at once (per_cu, the occupancy query, x CUs),
+// each walking its share of the 128-user tiles; with a segmented item range (few users) every (tile, segment) keeps its own
+// block.
+static hipError_t topk_persistent_grid(const pmf_ctx *ctx, int per_cu, dim3 *grid) {
+    int cus = 0;
+    const hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    if (e != hipSuccess || grid->y != 1) return e;
+    unsigned resident = (unsigned)std::max(1, per_cu) * (unsigned)std::max(1, cus);
+    if (ctx->topk_max_blocks > 0) resident = std::min(resident, (unsigned)ctx->topk_max_blocks);   // (tests: few blocks, many tiles each)
+    if (grid->x > resident) grid->x = resident;
+    return hipSuccess;
 }
 
 template <int KH, int MODE>
@@ -731,22 +766,14 @@ static hipError_t launch_topk_fused_mode(pmf_ctx *ctx, const TopkParams &p, dim3
         if (e == hipSuccess) e = hipFuncSetAttribute(fn1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
         if (e != hipSuccess) return e;
     }
-    int per_cu2 = 0, per_cu1 = 0, dev = 0, cus = 0;
+    int per_cu2 = 0, per_cu1 = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu2, fn2, 256, smem2);
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu1, fn1, 256, smem1);
-    if (e == hipSuccess) e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     if (e != hipSuccess) return e;
     int nbuf = per_cu1 > per_cu2 ? 1 : 2;
     if (ctx->topk_stage_buffers == 1 || ctx->topk_stage_buffers == 2) nbuf = ctx->topk_stage_buffers;
     const size_t smem = nbuf == 2 ? smem2 : smem1;
-    // persistent in x: at most as many blocks as are resident at once (the occupancy query x CUs), each walking its
-    // share of the 128-user tiles; with a segmented item range (few users) every (tile, segment) keeps its own block
-    if (grid.y == 1) {
-        unsigned resident = (unsigned)std::max(1, nbuf == 2 ? per_cu2 : per_cu1) * (unsigned)std::max(1, cus);
-        if (ctx->topk_max_blocks > 0) resident = std::min(resident, (unsigned)ctx->topk_max_blocks);   // (tests: few blocks, many tiles each)
-        if (grid.x > resident) grid.x = resident;
-    }
+    if ((e = topk_persistent_grid(ctx, nbuf == 2 ? per_cu2 : per_cu1, &grid)) != hipSuccess) return e;
     if (nbuf == 2)
         hipLaunchKernelGGL((topk_fused_kernel<KH, MODE, 2>), grid, dim3(256), smem, ctx->stream, p, fu, fi, cu, ci, k, seg_items,
                            nseg, cand_val, cand_idx, out_items, out_scores);
@@ -763,12 +790,8 @@ static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids
     const float *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const float>();
     const float *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const float>();
     const int64_t Q = std::min<int64_t>(n_query, 1 << 20);   // query users per launch
-    // few users: cut the item range so that the grid still has a few thousand wavefronts
-    const int64_t waves = (Q + 31) / 32;
-    int nseg = (int)std::min<int64_t>(64, std::max<int64_t>(1, 4096 / waves));
-    nseg = (int)std::min<int64_t>(nseg, std::max<int64_t>(1, I / 2048));
-    int64_t seg_items = ((I + nseg - 1) / nseg + 31) / 32 * 32;
-    nseg = (int)((I + seg_items - 1) / seg_items);
+    int64_t seg_items;
+    const int nseg = topk_segments(Q, I, &seg_items);
     const size_t n_cand = nseg > 1 ? (size_t)nseg * k : 0;
     const size_t id_bytes = ((size_t)Q * sizeof(int32_t) + 15) / 16 * 16;
     const size_t out_i = ((size_t)Q * k * sizeof(int32_t) + 15) / 16 * 16, out_s = (size_t)Q * k * sizeof(double);
@@ -795,16 +818,12 @@ static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids
             PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
             dim3 grid((unsigned)((nq + 127) / 128), (unsigned)nseg);
             // the instantiation for the K class KH and the bias mode
-            auto launch = [&](auto kh, auto m) {
-                return launch_topk_fused_mode<kh, m>(ctx, p, grid, list_bytes, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci,
-                                                     d_out_items, d_out_scores);
-            };
-            auto with_mode = [&](auto kh) {
-                if (mode == PMF_PREDICT_BIAS) return launch(kh, std::integral_constant<int, PMF_PREDICT_BIAS>());
-                if (mode == PMF_PREDICT_SCALE) return launch(kh, std::integral_constant<int, PMF_PREDICT_SCALE>());
-                return launch(kh, std::integral_constant<int, 0>());
-            };
-            PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, with_mode));   // KH: kpad / 2 rounded up to 8, 16, 32 or 64
+            PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, [&](auto kh) {   // KH: kpad / 2 rounded up to 8, 16, 32 or 64
+                return pmf_with_predict_mode(mode, [&](auto m) {
+                    return launch_topk_fused_mode<kh, m>(ctx, p, grid, list_bytes, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci,
+                                                         d_out_items, d_out_scores);
+                });
+            }));
             if (nseg > 1)
                 hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, d_cv, d_ci, nq,
                                    (int)n_cand, k, d_out_items, d_out_scores);
@@ -902,9 +921,8 @@ extern "C" int pmf_topk_items(pmf_ctx *ctx, int64_t n_query, const int32_t *user
 // number of NaN scores, the number of excluded (training) items with a non-NaN score, and a bit mask of the slots whose
 // own score is NaN.  rank = counter, candidates = n_items - NaN scores - excluded.
 //
-// fp32, Kpad <= 128 -- three launches, all of which produce a score with the SAME arithmetic: the KH
-// v_mfma_f32_32x32x2_f32 steps of topk_fused_kernel in its k order (an MFMA output element depends on its A row, its B
-// column and the k sequence only), then rank_score().  Exact ties are the normal case here (every item without ratings
+// fp32, Kpad <= 128 -- three launches, all of which produce a score with the SAME arithmetic, that of topk_fused_kernel:
+// topk_load_a(), topk_mfma_tile(), then rank_score().  Exact ties are the normal case here (every item without ratings
 // keeps its prior row), so a threshold that differed from the scan's score of the same item in the last bit would move a
 // rank by the size of the tie group.
 //   rank_rows_kernel<.., false>  thresholds: one wavefront per query row, all 32 A rows the user's, B column t = the slot's
@@ -920,13 +938,6 @@ extern "C" int pmf_topk_items(pmf_ctx *ctx, int64_t n_query, const int32_t *user
 #define RANK_EXCL (RANK_SLOTS + 1)     // counter: excluded items with a non-NaN score
 #define RANK_MASK (RANK_SLOTS + 2)     // bit t: the score of slot t's target is NaN
 #define RANK_STRIDE (RANK_SLOTS + 3)
-
-template <int MODE, typename S>
-__device__ __forceinline__ S rank_score(S dot, S ucst, S ccst) {   // predict's arithmetic order, as the top-k kernels have it
-    if (MODE == PMF_PREDICT_BIAS) return ucst + ccst + dot;
-    if (MODE == PMF_PREDICT_SCALE) return dot * (ucst * ccst);
-    return dot;
-}
 
 // does a competitor (score s, item j) rank before the target (score th, item tg)?
 template <typename S>
@@ -963,12 +974,10 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(TopkParams p, RankParams
     if (q >= p.nq) return;
     const int kpad = p.kpad, last_piece = kpad / 4 - 1;
     const int user = p.users[q];
-    float a[KH];                                       // the scan's A layout: pieces 2 q + h of the row, zero past Kpad
+    float a[KH];
 #pragma unroll
     for (int t = 0; t < KH; t += 4) {
-        const int kk = 2 * t + 4 * h;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (kk < kpad) v = *reinterpret_cast<const float4 *>(fu + (int64_t)user * kpad + kk);
+        const float4 v = topk_a_piece(fu, user, kpad, h, t);
         a[t] = v.x; a[t + 1] = v.y; a[t + 2] = v.z; a[t + 3] = v.w;
     }
     const float ucst = MODE != 0 ? cu[user] : 0.f;
@@ -976,17 +985,10 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(TopkParams p, RankParams
     auto column_score = [&](int item) __attribute__((always_inline)) -> float {
         const float *row = fi + (int64_t)(item < 0 ? 0 : item) * kpad;
         f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-        for (int t = 0; t < KH; t += 4) {
-            const int pc = t / 2 + h;                  // the scan's stage holds the last piece again past Kpad
-            const float4 b = *reinterpret_cast<const float4 *>(row + 4 * (pc < last_piece ? pc : last_piece));
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 1], b.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 2], b.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 3], b.w, acc, 0, 0, 0);
-        }
+        topk_mfma_tile<KH>(a, acc, [&](int t) __attribute__((always_inline)) {
+            const int pc = t / 2 + h;
+            return *reinterpret_cast<const f32x4 *>(row + 4 * (pc < last_piece ? pc : last_piece));
+        });
         const float ccst = (MODE != 0 && item >= 0) ? ci[item] : 0.f;
         return rank_score<MODE>(acc[0], ucst, ccst);   // (every row of the tile is this user's)
     };
@@ -1023,10 +1025,10 @@ __global__ __launch_bounds__(256) void rank_rows_kernel(TopkParams p, RankParams
     }
 }
 
-// The scan.  Staging, A layout and tile arithmetic are topk_fused_kernel's (two stage buffers, persistent blocks in x,
-// item segments in y) -- a COPY of that kernel's fetch / stash / publish code and stage loop, because pmf_topk_items has to
-// stay what it is bit for bit: a change to either copy's staging or k order belongs in the other too (the thresholds of
-// rank_rows_kernel follow the same k order); TS = target slots held in registers (1 when no query row of the call has more than one target).
+// The scan.  Two stage buffers, persistent blocks in x and item segments in y, as in topk_fused_kernel; the score comes
+// from the functions that kernel uses, while the staging lambdas, publish and the stage loop are a COPY of its code (the
+// comment above that kernel says why, and what the copy leaves out): a change to either copy belongs in the other too.
+// TS = target slots held in registers (1 when no query row of the call has more than one target).
 // Per accumulator register r and slot t: one threshold, one counter.  Segments add their counts with integer atomics.
 // (waves per SIMD the register allocation leaves room for: the thresholds and counters take 32 TS registers, the A rows
 //  KH, the bias / scale modes 16 more -- at K = 64 those fit one step lower than the plain score does)
@@ -1045,15 +1047,8 @@ void rank_fused_kernel(TopkParams p, RankParams rp, const float *fu, const float
     const int i_end = (int)((int64_t)i_begin + seg_items < p.n_items ? (int64_t)i_begin + seg_items : p.n_items);
     const int kpad = p.kpad;
     const float *th_in = static_cast<const float *>(rp.th);
-    const int slot = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 3;   // HW_ID.WAVE_ID (time-sliced priority, as in the top-k scan)
-    auto slice_priority = [&](int stage_no) __attribute__((always_inline)) {
-        switch ((slot + stage_no / PRIO_SLICE) & 3) {
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
-    };
+    const int slot = topk_wave_slot();
+    auto slice_priority = [&](int stage_no) __attribute__((always_inline)) { topk_slice_priority(slot, stage_no); };
 
     const int n_user_tiles = (p.nq + 127) / 128;
     for (int ut = blockIdx.x; ut < n_user_tiles; ut += gridDim.x) {
@@ -1063,9 +1058,7 @@ void rank_fused_kernel(TopkParams p, RankParams rp, const float *fu, const float
     float a[KH];
 #pragma unroll
     for (int t = 0; t < KH; t += 4) {
-        const int kk = 2 * t + 4 * h;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (user >= 0 && kk < kpad) v = *reinterpret_cast<const float4 *>(fu + (int64_t)user * kpad + kk);
+        const float4 v = topk_a_piece(fu, user, kpad, h, t);
         a[t] = v.x; a[t + 1] = v.y; a[t + 2] = v.z; a[t + 3] = v.w;
     }
     // per accumulator register r: the query row (r & 3) + 8 (r >> 2) + 4 h, its bias / scale, its thresholds and counters
@@ -1126,17 +1119,8 @@ void rank_fused_kernel(TopkParams p, RankParams rp, const float *fu, const float
     // ---- one 32-item tile ----------------------------------------------------------------------------------------
     auto tile = [&](auto TAIL, int i0, const f32x4 *rows) __attribute__((always_inline)) {
         f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         const f32x4 *mine = rows + c * PQ + h;
-#pragma unroll
-        for (int t = 0; t < KH; t += 4) {
-            const f32x4 b = mine[t / 2];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t], b.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 1], b.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 2], b.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t + 3], b.w, acc, 0, 0, 0);
-        }
+        topk_mfma_tile<KH>(a, acc, [&](int t) __attribute__((always_inline)) { return mine[t / 2]; });
         const int it = i0 + c;
         const bool in_range = !decltype(TAIL)::value || it < i_end;
         if (MODE != 0) {
@@ -1307,15 +1291,10 @@ static hipError_t launch_rank_fused(pmf_ctx *ctx, const TopkParams &p, const Ran
                                     const float *fi, const float *cu, const float *ci, int64_t seg_items) {
     const void *fn = (const void *)rank_fused_kernel<KH, MODE, TS>;
     const size_t smem = 2 * TopkStage<KH>::buffer_bytes;
-    int per_cu = 0, cus = 0;
+    int per_cu = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, smem);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+    if (e == hipSuccess) e = topk_persistent_grid(ctx, per_cu, &grid);
     if (e != hipSuccess) return e;
-    if (grid.y == 1) {   // persistent in x, as the top-k scan
-        unsigned resident = (unsigned)std::max(1, per_cu) * (unsigned)std::max(1, cus);
-        if (ctx->topk_max_blocks > 0) resident = std::min(resident, (unsigned)ctx->topk_max_blocks);
-        if (grid.x > resident) grid.x = resident;
-    }
     hipLaunchKernelGGL((rank_fused_kernel<KH, MODE, TS>), grid, dim3(256), smem, ctx->stream, p, rp, fu, fi, cu, ci, seg_items);
     return hipSuccess;
 }
@@ -1333,15 +1312,11 @@ static int launch_rank(pmf_ctx *ctx, const TopkParams &p, const RankParams &rp, 
     PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
     if constexpr (std::is_same<T, float>::value) {
         if (ctx->kpad <= 128) {   // (the item count fits the scan's ints: rank_items_impl)
-            // segments of the item range: the rule of run_topk_fused
-            const int64_t waves = ((int64_t)p.nq + 31) / 32;
-            int nseg = (int)std::min<int64_t>(64, std::max<int64_t>(1, 4096 / waves));
-            nseg = (int)std::min<int64_t>(nseg, std::max<int64_t>(1, I / 2048));
-            const int64_t seg_items = ((I + nseg - 1) / nseg + 31) / 32 * 32;
-            nseg = (int)((I + seg_items - 1) / seg_items);
+            int64_t seg_items;
+            const int nseg = topk_segments(p.nq, I, &seg_items);
             const dim3 grid((unsigned)((p.nq + 127) / 128), (unsigned)nseg);
-            auto with_mode = [&](auto kh) {
-                auto launch = [&](auto m) {
+            PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, [&](auto kh) {
+                return pmf_with_predict_mode(mode, [&](auto m) {
                     constexpr int KH = decltype(kh)::value, MODE = decltype(m)::value;
                     hipLaunchKernelGGL((rank_rows_kernel<KH, MODE, false>), row_grid, dim3(256), 0, ctx->stream, p, rp, fu, fi, cu, ci);
                     hipError_t e = one_slot ? launch_rank_fused<KH, MODE, 1>(ctx, p, rp, grid, fu, fi, cu, ci, seg_items)
@@ -1349,12 +1324,8 @@ static int launch_rank(pmf_ctx *ctx, const TopkParams &p, const RankParams &rp, 
                     if (e == hipSuccess && rp.ex_ptr)
                         hipLaunchKernelGGL((rank_rows_kernel<KH, MODE, true>), row_grid, dim3(256), 0, ctx->stream, p, rp, fu, fi, cu, ci);
                     return e;
-                };
-                if (mode == PMF_PREDICT_BIAS) return launch(std::integral_constant<int, PMF_PREDICT_BIAS>());
-                if (mode == PMF_PREDICT_SCALE) return launch(std::integral_constant<int, PMF_PREDICT_SCALE>());
-                return launch(std::integral_constant<int, 0>());
-            };
-            PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, with_mode));
+                });
+            }));
             return PMF_OK;
         }
     }

@@ -187,10 +187,26 @@ def test_fused_topk_edge_shapes_rank_like_numpy(U, I, K, k, max_blocks, monkeypa
     stage), exactly one tile, one item past a tile, k = the item count, k = 1 and k = 64, one user, user counts around the
     32 / 128 tile edges; Gaussian factors (scores of both signs).  `max_blocks` = 2 makes two blocks walk all user tiles
     (the persistent loop with many tiles per block).  Checked against a NumPy ranking of the device's own fp32 tables."""
-    import pmf_hip
-    from pmf_hip import ARR_FACTOR, ITEM, USER
     if max_blocks:
         monkeypatch.setenv("PMF_TOPK_MAX_BLOCKS", str(max_blocks))
+    _check_fused_edge_shape(U, I, K, k)
+
+
+@pytest.mark.parametrize("buffers", [1, 2])
+@pytest.mark.parametrize("U,I,K,k,max_blocks", [(5, 7, 3, 7, 0), (257, 1000, 100, 64, 0), (515, 97, 40, 24, 2)])
+def test_fused_topk_edge_shapes_with_either_stage_buffering(U, I, K, k, max_blocks, buffers, monkeypatch):
+    """PMF_TOPK_STAGE_BUFFERS pins the fused kernel's stage buffering: one buffer (two barriers per stage) and two give the
+    same ranking.  Three of the edge shapes: fewer items than a stage, a partial last stage behind full ones, and two
+    blocks that share five user tiles."""
+    monkeypatch.setenv("PMF_TOPK_STAGE_BUFFERS", str(buffers))
+    if max_blocks:
+        monkeypatch.setenv("PMF_TOPK_MAX_BLOCKS", str(max_blocks))
+    _check_fused_edge_shape(U, I, K, k)
+
+
+def _check_fused_edge_shape(U, I, K, k):
+    import pmf_hip
+    from pmf_hip import ARR_FACTOR, ITEM, USER
     rng = np.random.default_rng(U * 1000 + I)
     A, B = rng.standard_normal((U, K)), rng.standard_normal((I, K))
     if I > 8:
