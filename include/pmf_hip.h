@@ -634,6 +634,27 @@ int pmf_eval_run_var(pmf_ctx *ctx, int use_bias, double offset, double sigma2, d
  * (v_mfma_f32_32x32x2_f32), the running k best per user in LDS, no score matrix in HBM. */
 int pmf_topk_items(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias,
                    int32_t *out_items, double *out_scores);
+/* pmf_topk_items over the items a user has not rated: what a recommender serves, and the list whose recall@k
+ * pmf_rank_items(.., exclude_train = 1) measures.  With `exclude_train` == 0 the call IS pmf_topk_items (same code
+ * path, same bits).  With `exclude_train` != 0 the candidates of query user u are the items j that are not among the
+ * DISTINCT items of u's training ratings (pmf_ctx_set_ratings keeps duplicate pairs; each item counts once; a user
+ * without ratings excludes nothing).  Order, ties (lower item id), -0.0 == +0.0 and "a NaN score never ranks" are
+ * those of pmf_topk_items, and the item at position p of u's row is the candidate whose
+ * pmf_rank_items(.., exclude_train = 1) rank is p -- to the bit, tie groups included: both calls take the score of a
+ * pair from the same three functions.  A user with fewer than k rankable candidates gets -1 / 0.0 in the rest of the
+ * row: min(k, out_candidates of pmf_rank_items) entries are valid, none for a user who rated every item.  Repeated
+ * query users are allowed; k in [1, min(1024, n_items)].
+ * Reads the context only: model state, ratings, work lists and the stored validation set stay as they are (the first
+ * excluding call after pmf_ctx_set_ratings builds the distinct-item lists unless pmf_rank_items already has, and
+ * pmf_ctx_device_bytes then counts them; later calls of either kind add nothing; new ratings rebuild them).  Never a
+ * collective; two calls give the same bits.
+ * Errors (naming what is missing): those of pmf_topk_items, and PMF_EINVAL for `exclude_train` without ratings.  An
+ * argument error writes nothing; n_query = 0 touches nothing.
+ * The fused kernel drops an excluded item where a score has already passed its user's threshold, so the scan's steady
+ * state is that of pmf_topk_items; the two-phase path overwrites the excluded pairs' scores with NaN before the
+ * select (DESIGN.md 4.14 has the mechanism and what it costs).  Timed under PMF_KERNEL_TOPK. */
+int pmf_topk_items_excluding(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias,
+                             int exclude_train, int32_t *out_items, double *out_scores);
 
 /* Ranks of held-out items (no reference counterpart: the reference evaluates point errors only).  Query row r is user
  * user_ids[r] (repeats allowed) with the target items item_ids[row_ptr[r] .. row_ptr[r + 1]) (row_ptr[0] = 0,

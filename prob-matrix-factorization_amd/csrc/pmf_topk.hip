@@ -23,6 +23,14 @@ struct TopkParams {
     int K, kpad;
 };
 
+// TopkParams of an excluding call (pmf_topk_items_excluding): item j is no candidate of user u when it is among
+// ex_items[ex_ptr[u] .. ex_ptr[u + 1]), ascending item ids, each once -- the context's distinct training items
+// (pmf_index_distinct), as in RankParams; a caller's own CSR would fit the same two pointers.
+struct TopkExcludeParams : TopkParams {
+    const int64_t *ex_ptr;
+    const int32_t *ex_items;
+};
+
 // 32 users x 32 items per wavefront, 4 item tiles per block.
 // (bu / bi: BIAS arrays when mode == PMF_PREDICT_BIAS, SCALE arrays when mode == PMF_PREDICT_SCALE, else null)
 __global__ __launch_bounds__(256) void topk_scores_f32_kernel(TopkParams p, const float *fu, const float *fi,
@@ -82,6 +90,19 @@ __global__ void topk_scores_f64_kernel(TopkParams p, const double *fu, const dou
         for (int k = 0; k < p.K; ++k) s = fma(a[k], b[k], s);
         if (bu) s = mode == PMF_PREDICT_SCALE ? s * (bu[user] * bi[it]) : bu[user] + bi[it] + s;
         scores[e] = s;
+    }
+}
+
+// Exclusion on the two-phase path, between the score kernel and the select: the score of every excluded (query row, item)
+// pair becomes NaN, which the select never ranks.  One block per query row at a time, one thread per list entry (a user
+// repeated in the batch has a row of its own per repeat).
+template <typename S>
+__global__ __launch_bounds__(256) void topk_exclude_scores_kernel(TopkExcludeParams p, S *scores) {
+    for (int q = blockIdx.x; q < p.nq; q += gridDim.x) {
+        const int user = p.users[q];
+        const int64_t end = p.ex_ptr[user + 1];
+        for (int64_t e = p.ex_ptr[user] + threadIdx.x; e < end; e += blockDim.x)
+            scores[(int64_t)q * p.n_items + p.ex_items[e]] = (S)__builtin_nanf("");
     }
 }
 
@@ -297,6 +318,11 @@ struct TopkStage {
     static constexpr size_t buffer_bytes = (size_t)ST * PQ * 16;   // the kernel takes one or two of these (nbuf)
 };
 
+// LDS of topk_fused_kernel behind its stage buffers: the block's 4 x 32 lists of k 8-byte keys, + 64 entries (insert()
+// reads a full wave's width), then -- excluding scans only -- 20 bytes per wave and local user (the kernel says what)
+__host__ __device__ constexpr size_t topk_list_bytes(int k) { return (size_t)4 * 32 * k * 8 + 512; }
+#define TOPK_EXCLUDE_LDS_BYTES (4 * 32 * 20)
+
 // The score arithmetic of the fused kernels -- topk_fused_kernel, rank_fused_kernel and rank_rows_kernel -- is the three
 // functions below and nothing else: pmf_rank_items is right only if all three give a score with the same bits (an MFMA
 // output element depends on its A row, its B column and the k sequence only).
@@ -355,8 +381,12 @@ __device__ __forceinline__ void topk_slice_priority(int slot, int stage_no) {
 
 // (waves per SIMD the register allocation must leave room for: four for the plain K <= 64 scan, whose lists leave room for
 //  four blocks per CU; the bias / scale modes and K > 64 need more registers than that)
-template <int KH, int MODE, int NBUF>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? (MODE == 0 ? 4 : 3) : 2))) void topk_fused_kernel(TopkParams p, const float *fu, const float *fi, const float *cu,
+// EXCLUDE: the epilogue policy of pmf_topk_items_excluding -- a score that passed its user's threshold is dropped in
+// drain() when its item is on the user's exclusion list, before it reaches insert(); the tile test and the stage loop are
+// those of the plain scan.  (The exclusion pointers ride in the first argument, whose type depends on EXCLUDE: the plain
+// instantiations keep their argument layout, and with it their code.)
+template <int KH, int MODE, int NBUF, bool EXCLUDE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? (MODE == 0 ? 4 : 3) : 2))) void topk_fused_kernel(std::conditional_t<EXCLUDE, TopkExcludeParams, TopkParams> p, const float *fu, const float *fi, const float *cu,
                                                          const float *ci, int k, int64_t seg_items, int nseg,
                                                          float *cand_val, int32_t *cand_idx, int32_t *out_items,
                                                          double *out_scores) {
@@ -371,6 +401,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? 
     f32x4 *stage = reinterpret_cast<f32x4 *>(smem_raw);                                          // [nbuf][ST][PQ]
     // [32][k] list entries of this wave's users, best first: 64-bit keys (insert() below)
     unsigned long long *le = reinterpret_cast<unsigned long long *>(smem_raw + nbuf * S::buffer_bytes) + (size_t)wave * 32 * k;
+    // EXCLUDE: behind the lists and their padding (topk_list_bytes), per wave and local user, where the user's exclusion
+    // list begins in ex_items, (position of the first entry not yet passed, length) relative to that -- 32-bit, so
+    // that drain() compares them on the scalar unit -- and the item id AT that position (past the end: INT_MAX), which
+    // clears most candidates without a look at the list
+    unsigned char *ex_lds = smem_raw + nbuf * S::buffer_bytes + topk_list_bytes(k) + (size_t)wave * (TOPK_EXCLUDE_LDS_BYTES / 4);
+    long long *ex_start = reinterpret_cast<long long *>(ex_lds);          // [32]
+    int2 *ex_at = reinterpret_cast<int2 *>(ex_lds + 32 * sizeof(long long));   // [32] (x: position, y: length)
+    int *ex_next = reinterpret_cast<int *>(ex_lds + 32 * (sizeof(long long) + sizeof(int2)));   // [32]
     const int seg = blockIdx.y;
     // (item indices are ints in here -- the host sends more than 2^31 - 64 items to the two-phase path: 64-bit compares
     //  have no scalar form, and every instruction of this loop is paid for)
@@ -416,6 +454,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? 
         if (MODE != 0 && qq < p.nq) ucst[r] = cu[p.users[qq]];
     }
     for (int e = lane; e < 32 * k; e += 64) le[e] = TOPK_EMPTY_KEY;
+    if constexpr (EXCLUDE) {
+        // lane c: user (q0 + c)'s list, and where this segment's part of it begins (the first entry >= i_begin) -- the
+        // scan only ever moves on from there
+        long long first = 0;
+        int at = 0, n = 0;
+        if (user >= 0) {
+            first = p.ex_ptr[user];
+            n = (int)(p.ex_ptr[user + 1] - first);     // (distinct items of one user: fewer than n_items)
+            int hi = n;
+            while (i_begin > 0 && at < hi) {
+                const int mid = at + ((hi - at) >> 1);
+                if (p.ex_items[first + mid] < i_begin) at = mid + 1; else hi = mid;
+            }
+        }
+        if (h == 0) {
+            ex_start[c] = first;
+            ex_at[c] = make_int2(at, n);
+            ex_next[c] = at < n ? p.ex_items[first + at] : INT_MAX;
+        }
+    }
 
     // Loads are unconditional (no branch, nothing for the loop's wait counters to merge): a row past the
     // segment's end re-reads the last row (its scores are never ranked), a piece past Kpad re-reads the
@@ -550,6 +608,44 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? 
         for (int r = 0; r < 16; ++r)
             if (r >= r0 && r < r1) mk[r] = __builtin_amdgcn_ballot_w64(acc[r] >= tau[r]);
     };
+    // EXCLUDE: is `item` on the exclusion list of local user `ul`?  Everything here is wave-uniform.  A user's candidates
+    // reach drain() in ascending item order (tiles ascend, the lanes of a row ascend) and the list is sorted the same
+    // way, so one cursor per user only moves forward.  A candidate below the item id at the cursor is cleared by one LDS
+    // read and a scalar compare -- a load from the list here would be waited for behind the stage prefetch by the whole
+    // block, on every candidate.  Otherwise the cursor has to move (at most twice per list entry): the 64 lanes load the
+    // 64 entries at the cursor (past the end: an id above every item's), one ballot of `< item` advances the cursor, one
+    // of `== item` answers, and the entry now at the cursor is read from the loaded ones; the loop repeats only when all
+    // 64 entries were below.  The load is unconditional (the index is clamped) and the branches are scalar: EXEC stays
+    // all ones for insert().
+    auto excluded = [&](int ul, int item) __attribute__((always_inline)) -> bool {
+        if constexpr (EXCLUDE) {
+            if (item < __builtin_amdgcn_readfirstlane(ex_next[ul])) return false;
+            const int2 pn = ex_at[ul];
+            const int n = __builtin_amdgcn_readfirstlane(pn.y);      // (the cursor is inside the list: its entry is <= item)
+            const long long st = ex_start[ul];
+            const int32_t *list = p.ex_items + (((long long)__builtin_amdgcn_readfirstlane((int)(st >> 32)) << 32) |
+                                                (unsigned)__builtin_amdgcn_readfirstlane((int)st));
+            int pos = __builtin_amdgcn_readfirstlane(pn.x), next = INT_MAX;
+            bool hit = false;
+            do {
+                const int at = pos + lane;
+                const int v = list[at < n ? at : n - 1];
+                const int w = at < n ? v : INT_MAX;
+                int below = __popcll(__builtin_amdgcn_ballot_w64(w < item));   // (sorted: a prefix of the lanes)
+                hit = __builtin_amdgcn_ballot_w64(w == item) != 0ull;
+                if (hit && below < 63) ++below;       // (step over the entry that excludes this item: no candidate meets it again)
+                pos += below;
+                if (below < 64) {
+                    next = __builtin_amdgcn_readlane(w, below);
+                    break;
+                }
+            } while (pos < n);
+            ex_at[ul].x = pos;
+            ex_next[ul] = next;
+            return hit;
+        }
+        return false;
+    };
     // the tile's candidates go into their lists in ascending item order (lane order within the tile), so equal scores
     // keep the lower item id in front
     auto drain = [&](int r0, int r1, int i0, const f32x16 &acc, const unsigned long long (&mk)[16], unsigned long long okm)
@@ -569,6 +665,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KH <= 32 ? 
                 // (a row past the last query user never gets here: its threshold is +inf -- and if an infinite score did
                 //  bring it here, the list it lands in exists in LDS and is never handed over)
                 const int ul = (r & 3) + 8 * (r >> 2) + 4 * hh;
+                if (EXCLUDE && excluded(ul, i0 + (L & 31))) continue;   // dropped: never in the list, never moves tau
                 const unsigned vb = (unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(acc[r]), L);
 #ifdef PMF_TOPK_PAD_SCALAR   // (diagnostic: what an extra scalar / vector instruction per candidate costs the launch --
 #pragma unroll                // profiles/r03_topk_instruction_cost.log: about five cycles of SIMD time each, either kind)
@@ -750,16 +847,20 @@ static hipError_t topk_persistent_grid(const pmf_ctx *ctx, int per_cu, dim3 *gri
     return hipSuccess;
 }
 
-template <int KH, int MODE>
-static hipError_t launch_topk_fused_mode(pmf_ctx *ctx, const TopkParams &p, dim3 grid, size_t list_bytes, const float *fu,
+// (P: TopkParams, or TopkExcludeParams for the excluding kernels, whose lists are followed by the cursor words: the
+//  occupancy queries below are asked about the kernel and the LDS size that are launched)
+template <int KH, int MODE, typename P>
+static hipError_t launch_topk_fused_mode(pmf_ctx *ctx, const P &p, dim3 grid, const float *fu,
                                          const float *fi, const float *cu, const float *ci, int k, int64_t seg_items,
                                          int nseg, float *cand_val, int32_t *cand_idx, int32_t *out_items,
                                          double *out_scores) {
+    constexpr bool EXCLUDE = std::is_same<P, TopkExcludeParams>::value;
+    const size_t list_bytes = topk_list_bytes(k) + (EXCLUDE ? TOPK_EXCLUDE_LDS_BYTES : 0);
     // One stage buffer or two.  Two (one barrier per stage) is the faster loop at equal residency, but the lists take
     // 1 KB of LDS per k and block: from k = 23 at K = 64 the second buffer costs the CU a resident block
     // (profiles/r03_topk_long_lists.jsonl: 34.3 -> 30.8 ms at k = 24, 72.9 -> 49.3 ms at k = 64).  Take one buffer where
     // it keeps more blocks on the CU.  (ctx->topk_stage_buffers pins it: PMF_TOPK_STAGE_BUFFERS, for the probes.)
-    const void *fn2 = (const void *)topk_fused_kernel<KH, MODE, 2>, *fn1 = (const void *)topk_fused_kernel<KH, MODE, 1>;
+    const void *fn2 = (const void *)topk_fused_kernel<KH, MODE, 2, EXCLUDE>, *fn1 = (const void *)topk_fused_kernel<KH, MODE, 1, EXCLUDE>;
     const size_t smem2 = 2 * TopkStage<KH>::buffer_bytes + list_bytes, smem1 = TopkStage<KH>::buffer_bytes + list_bytes;
     if (smem2 > (64u << 10)) {   // long lists at K > 64: past the default dynamic-LDS limit
         hipError_t e = hipFuncSetAttribute(fn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
@@ -775,17 +876,19 @@ static hipError_t launch_topk_fused_mode(pmf_ctx *ctx, const TopkParams &p, dim3
     const size_t smem = nbuf == 2 ? smem2 : smem1;
     if ((e = topk_persistent_grid(ctx, nbuf == 2 ? per_cu2 : per_cu1, &grid)) != hipSuccess) return e;
     if (nbuf == 2)
-        hipLaunchKernelGGL((topk_fused_kernel<KH, MODE, 2>), grid, dim3(256), smem, ctx->stream, p, fu, fi, cu, ci, k, seg_items,
+        hipLaunchKernelGGL((topk_fused_kernel<KH, MODE, 2, EXCLUDE>), grid, dim3(256), smem, ctx->stream, p, fu, fi, cu, ci, k, seg_items,
                            nseg, cand_val, cand_idx, out_items, out_scores);
     else
-        hipLaunchKernelGGL((topk_fused_kernel<KH, MODE, 1>), grid, dim3(256), smem, ctx->stream, p, fu, fi, cu, ci, k, seg_items,
+        hipLaunchKernelGGL((topk_fused_kernel<KH, MODE, 1, EXCLUDE>), grid, dim3(256), smem, ctx->stream, p, fu, fi, cu, ci, k, seg_items,
                            nseg, cand_val, cand_idx, out_items, out_scores);
     return hipSuccess;
 }
 
 // fp32, Kpad <= 128, k <= 64
+// (ex_ptr / ex_items: the exclusion lists of an excluding call, else null)
 static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int mode, const float *cu,
-                          const float *ci, int32_t *out_items, double *out_scores) {
+                          const float *ci, const int64_t *ex_ptr, const int32_t *ex_items, int32_t *out_items,
+                          double *out_scores) {
     const int64_t I = ctx->rows[PMF_SIDE_ITEM];
     const float *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const float>();
     const float *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const float>();
@@ -804,24 +907,28 @@ static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids
     int32_t *d_users = (int32_t *)(base + out_s + out_i);
     float *d_cv = (float *)(base + out_s + out_i + id_bytes);
     int32_t *d_ci = (int32_t *)(base + out_s + out_i + id_bytes + cv_bytes);
-    const size_t list_bytes = (size_t)8 * 32 * k * sizeof(float) + 512;   // + 64 entries: insert() reads a full wave's width
     for (int64_t at = 0; at < n_query; at += Q) {
         const int nq = (int)std::min<int64_t>(Q, n_query - at);
         PMF_HIP_CHECK(hipMemcpyAsync(d_users, user_ids + at, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        TopkParams p;
+        TopkExcludeParams p;
         p.users = d_users;
         p.nq = nq;
         p.n_items = I;
         p.K = ctx->K;
         p.kpad = ctx->kpad;
+        p.ex_ptr = ex_ptr;
+        p.ex_items = ex_items;
         {
             PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
             dim3 grid((unsigned)((nq + 127) / 128), (unsigned)nseg);
             // the instantiation for the K class KH and the bias mode
             PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, [&](auto kh) {   // KH: kpad / 2 rounded up to 8, 16, 32 or 64
                 return pmf_with_predict_mode(mode, [&](auto m) {
-                    return launch_topk_fused_mode<kh, m>(ctx, p, grid, list_bytes, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci,
-                                                         d_out_items, d_out_scores);
+                    if (ex_ptr)
+                        return launch_topk_fused_mode<kh, m>(ctx, p, grid, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci,
+                                                             d_out_items, d_out_scores);
+                    return launch_topk_fused_mode<kh, m>(ctx, static_cast<const TopkParams &>(p), grid, fu, fi, cu, ci, k, seg_items,
+                                                         nseg, d_cv, d_ci, d_out_items, d_out_scores);
                 });
             }));
             if (nseg > 1)
@@ -836,27 +943,20 @@ static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids
     return PMF_OK;
 }
 
+// (arguments, arrays and flag are checked: topk_items_impl)
 template <typename T>
-static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias,
-                    int32_t *out_items, double *out_scores) {
+static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias, const int64_t *ex_ptr,
+                    const int32_t *ex_items, int32_t *out_items, double *out_scores) {
     const int64_t I = ctx->rows[PMF_SIDE_ITEM];
     int rc;
-    if ((rc = pmf_require_array(ctx, PMF_SIDE_USER, PMF_ARR_FACTOR, "pmf_topk_items"))) return rc;
-    if ((rc = pmf_require_array(ctx, PMF_SIDE_ITEM, PMF_ARR_FACTOR, "pmf_topk_items"))) return rc;
-    PMF_REQUIRE(use_bias == 0 || use_bias == PMF_PREDICT_BIAS || use_bias == PMF_PREDICT_SCALE, PMF_EINVAL,
-                "pmf_topk_items: use_bias must be 0, PMF_PREDICT_BIAS or PMF_PREDICT_SCALE (got %d)", use_bias);
     const int carr = use_bias == PMF_PREDICT_SCALE ? PMF_ARR_SCALE : PMF_ARR_BIAS;
-    if (use_bias) {
-        if ((rc = pmf_require_array(ctx, PMF_SIDE_USER, carr, "pmf_topk_items"))) return rc;
-        if ((rc = pmf_require_array(ctx, PMF_SIDE_ITEM, carr, "pmf_topk_items"))) return rc;
-    }
     const T *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const T>();
     const T *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const T>();
     const T *bu = use_bias ? ctx->arr[PMF_SIDE_USER][carr].as<const T>() : nullptr;
     const T *bi = use_bias ? ctx->arr[PMF_SIDE_ITEM][carr].as<const T>() : nullptr;
     if constexpr (std::is_same<T, float>::value) {
         if (ctx->kpad <= 128 && k <= 64 && I <= (int64_t)INT32_MAX - 64 && !ctx->topk_two_phase)   // (the fused scan counts items in ints)
-            return run_topk_fused(ctx, n_query, user_ids, k, use_bias, bu, bi, out_items, out_scores);
+            return run_topk_fused(ctx, n_query, user_ids, k, use_bias, bu, bi, ex_ptr, ex_items, out_items, out_scores);
     }
     // batch size: scores buffer of at most ~512 MB
     int64_t Q = std::max<int64_t>(32, (512ll << 20) / (I * (int64_t)sizeof(T)));
@@ -873,12 +973,14 @@ static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int 
     for (int64_t at = 0; at < n_query; at += Q) {
         const int nq = (int)std::min<int64_t>(Q, n_query - at);
         PMF_HIP_CHECK(hipMemcpyAsync(d_users, user_ids + at, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        TopkParams p;
+        TopkExcludeParams p;
         p.users = d_users;
         p.nq = nq;
         p.n_items = I;
         p.K = ctx->K;
         p.kpad = ctx->kpad;
+        p.ex_ptr = ex_ptr;
+        p.ex_items = ex_items;
         {
             PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
             if constexpr (std::is_same<T, float>::value) {
@@ -889,6 +991,9 @@ static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int 
                 hipLaunchKernelGGL(topk_scores_f64_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65535)),
                                    dim3(256), 0, ctx->stream, p, fu, fi, bu, bi, use_bias, d_scores);
             }
+            if (ex_ptr)   // excluded pairs score NaN from here on: the select never ranks them
+                hipLaunchKernelGGL((topk_exclude_scores_kernel<T>), dim3((unsigned)std::min(nq, 65535)), dim3(256), 0, ctx->stream,
+                                   p, d_scores);
             hipLaunchKernelGGL((topk_select_kernel<T>), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream,
                                d_scores, nq, I, k, d_out_items, d_out_scores);
         }
@@ -900,17 +1005,51 @@ static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int 
     return PMF_OK;
 }
 
+// pmf_topk_items (`fn` names the entry point in a refusal), and with `exclude_train` pmf_topk_items_excluding
+static int topk_items_impl(const char *fn, pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias,
+                           int exclude_train, int32_t *out_items, double *out_scores) {
+    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "%s: null context", fn);
+    PMF_REQUIRE(n_query >= 0, PMF_EINVAL, "%s: negative n_query", fn);
+    if (n_query == 0) return PMF_OK;
+    PMF_REQUIRE(user_ids && out_items && out_scores, PMF_EINVAL, "%s: null argument", fn);
+    PMF_REQUIRE(k >= 1 && k <= 1024 && k <= ctx->rows[PMF_SIDE_ITEM], PMF_ERANGE, "%s: k=%d outside [1, min(1024, n_items)]", fn, k);
+    if (int rc = pmf_check_ids(user_ids, n_query, ctx->rows[PMF_SIDE_USER], fn, "user id")) return rc;
+    // (every refusal comes before the first write: an argument error leaves the outputs and the context as they were)
+    int rc;
+    if ((rc = pmf_require_array(ctx, PMF_SIDE_USER, PMF_ARR_FACTOR, fn))) return rc;
+    if ((rc = pmf_require_array(ctx, PMF_SIDE_ITEM, PMF_ARR_FACTOR, fn))) return rc;
+    PMF_REQUIRE(use_bias == 0 || use_bias == PMF_PREDICT_BIAS || use_bias == PMF_PREDICT_SCALE, PMF_EINVAL,
+                "%s: use_bias must be 0, PMF_PREDICT_BIAS or PMF_PREDICT_SCALE (got %d)", fn, use_bias);
+    if (use_bias) {
+        const int carr = use_bias == PMF_PREDICT_SCALE ? PMF_ARR_SCALE : PMF_ARR_BIAS;
+        if ((rc = pmf_require_array(ctx, PMF_SIDE_USER, carr, fn))) return rc;
+        if ((rc = pmf_require_array(ctx, PMF_SIDE_ITEM, carr, fn))) return rc;
+    }
+    PMF_REQUIRE(!exclude_train || ctx->index[PMF_SIDE_USER].d_ptr, PMF_EINVAL,
+                "%s: exclude_train needs the training ratings (pmf_ctx_set_ratings); the context holds none", fn);
+    PMF_HIP_CHECK(hipSetDevice(ctx->device));
+    const int64_t *ex_ptr = nullptr;
+    const int32_t *ex_items = nullptr;
+    if (exclude_train) {
+        if ((rc = pmf_index_distinct(ctx, PMF_SIDE_USER))) return rc;   // (built once per set of ratings)
+        ex_ptr = ctx->index[PMF_SIDE_USER].d_distinct_ptr.as<const int64_t>();
+        ex_items = ctx->index[PMF_SIDE_USER].d_distinct.as<const int32_t>();
+    }
+    return pmf_with_dtype(ctx, [&](auto t) {
+        return run_topk<decltype(t)>(ctx, n_query, user_ids, k, use_bias, ex_ptr, ex_items, out_items, out_scores);
+    });
+}
+
 extern "C" int pmf_topk_items(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias,
                               int32_t *out_items, double *out_scores) {
-    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "pmf_topk_items: null context");
-    PMF_REQUIRE(n_query >= 0, PMF_EINVAL, "pmf_topk_items: negative n_query");
-    if (n_query == 0) return PMF_OK;
-    PMF_REQUIRE(user_ids && out_items && out_scores, PMF_EINVAL, "pmf_topk_items: null argument");
-    PMF_REQUIRE(k >= 1 && k <= 1024 && k <= ctx->rows[PMF_SIDE_ITEM], PMF_ERANGE,
-                "pmf_topk_items: k=%d outside [1, min(1024, n_items)]", k);
-    if (int rc = pmf_check_ids(user_ids, n_query, ctx->rows[PMF_SIDE_USER], "pmf_topk_items", "user id")) return rc;
-    PMF_HIP_CHECK(hipSetDevice(ctx->device));
-    return pmf_with_dtype(ctx, [&](auto t) { return run_topk<decltype(t)>(ctx, n_query, user_ids, k, use_bias, out_items, out_scores); });
+    return topk_items_impl("pmf_topk_items", ctx, n_query, user_ids, k, use_bias, 0, out_items, out_scores);
+}
+
+extern "C" int pmf_topk_items_excluding(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias,
+                                        int exclude_train, int32_t *out_items, double *out_scores) {
+    return pmf_no_throw("pmf_topk_items_excluding", [&] {
+        return topk_items_impl("pmf_topk_items_excluding", ctx, n_query, user_ids, k, use_bias, exclude_train, out_items, out_scores);
+    });
 }
 
 // ---------------------------------------------------------------------------

@@ -106,6 +106,7 @@ SIGNATURES = {
     "pmf_predict_var": (C.c_int, [_p, C.c_int64, _i32p, _i32p, _f64p]),
     "pmf_eval_run_var": (C.c_int, [_p, C.c_int, C.c_double, C.c_double, _f64p, _f64p]),
     "pmf_topk_items": (C.c_int, [_p, C.c_int64, _i32p, C.c_int, C.c_int, _i32p, _f64p]),
+    "pmf_topk_items_excluding": (C.c_int, [_p, C.c_int64, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _f64p]),
     "pmf_rank_items": (C.c_int, [_p, C.c_int64, _i32p, _i64p, _i32p, C.c_int, C.c_int, _i64p, _i64p]),
     "pmf_prof_enable": (C.c_int, [_p, C.c_int]),
     "pmf_prof_reset": (C.c_int, [_p]),

@@ -484,14 +484,21 @@ class Context:
               "pmf_eval_run_var")
         return getattr(self, "_eval_n", 0), sv.value, sl.value
 
-    def topk_items(self, user_ids, k, use_bias=False):
+    def topk_items(self, user_ids, k, use_bias=False, exclude_train=False):
         """`use_bias`: False / 0, PREDICT_BIAS (scores + b_u + b_i) or PREDICT_SCALE (scores * s_u * s_i):
-        the same flag `predict` takes, so the ranking follows the model's own score."""
+        the same flag `predict` takes, so the ranking follows the model's own score.  Returns (items int32 [n, k],
+        scores float64 [n, k]), best first, -1 / 0.0 where fewer than k items rank.  `exclude_train`: the user's training
+        items (each once) are no candidates (`pmf_topk_items_excluding`): column p holds the item whose
+        `rank_items(.., exclude_train=True)` rank is p."""
         u = as_i32(user_ids, "user_ids")
         items = np.empty((len(u), k), dtype=np.int32)
         scores = np.empty((len(u), k), dtype=np.float64)
-        check(self._lib.pmf_topk_items(self._h, len(u), ptr(u, C.c_int32), int(k), int(use_bias),
-                                       ptr(items, C.c_int32), ptr(scores, C.c_double)), "pmf_topk_items")
+        if exclude_train:
+            check(self._lib.pmf_topk_items_excluding(self._h, len(u), ptr(u, C.c_int32), int(k), int(use_bias), 1,
+                                                     ptr(items, C.c_int32), ptr(scores, C.c_double)), "pmf_topk_items_excluding")
+        else:
+            check(self._lib.pmf_topk_items(self._h, len(u), ptr(u, C.c_int32), int(k), int(use_bias),
+                                           ptr(items, C.c_int32), ptr(scores, C.c_double)), "pmf_topk_items")
         return items, scores
 
     def rank_rows(self, user_ids, row_ptr, item_ids, use_bias=False, exclude_train=False):

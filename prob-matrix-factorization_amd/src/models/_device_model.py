@@ -312,11 +312,21 @@ class DeviceModel:
         self.history_["val_rmse"].append(rmse_v)
         self.history_["val_macro_mae"].append(mae_v)
 
-    def top_k_items(self, user_ids, k=10):
+    def _need_train_ratings(self):
+        """`exclude_train=True` reads the training ratings of the context that serves the ranking calls."""
+        if self._shard_ctx is not None:
+            raise NotImplementedError("after a sharded fit the full-size context holds the factors but no training ratings: "
+                                      "exclude_train=True is not available, pass exclude_train=False")
+
+    def top_k_items(self, user_ids, k=10, exclude_train=False):
         """Extension (no reference counterpart): the k highest-scoring items per
         user under `predict`'s score, ties to the lower item id.  Returns
-        (items [n, k] int32, scores [n, k] float64)."""
-        return self._need_ctx().topk_items(np.asarray(user_ids, dtype=int), int(k), use_bias=self._uses_bias)
+        (items [n, k] int32, scores [n, k] float64).  `exclude_train`: the items of the user's training ratings are
+        left out, as a recommender would (the list `evaluate_ranking` measures); -1 / 0.0 where fewer than k remain."""
+        ctx = self._need_ctx()
+        if exclude_train:
+            self._need_train_ratings()
+        return ctx.topk_items(np.asarray(user_ids, dtype=int), int(k), use_bias=self._uses_bias, exclude_train=exclude_train)
 
     def heldout_ranks(self, df, exclude_train=True):
         """Extension (no reference counterpart): where every row's item lands in its user's ranking of the items under
@@ -324,9 +334,8 @@ class DeviceModel:
         whose user or item the fit has not seen get -1 in both.  `exclude_train`: the items of the user's training
         ratings are left out of the ranking, as a recommender would."""
         ctx = self._need_ctx()
-        if exclude_train and self._shard_ctx is not None:
-            raise NotImplementedError("after a sharded fit the full-size context holds the factors but no training ratings: "
-                                      "exclude_train=True is not available, pass exclude_train=False")
+        if exclude_train:
+            self._need_train_ratings()
         u, i = df["u"].to_numpy(dtype=int), df["i"].to_numpy(dtype=int)
         seen = (u >= 0) & (u < self.n_users) & (i >= 0) & (i < self.n_items)
         ranks = np.full(len(u), -1, dtype=np.int64)

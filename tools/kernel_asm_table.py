@@ -2,6 +2,10 @@
 the command line): is a kernel's body -- label to s_endpgm, the __hip_cuid_ symbol aside -- byte-equal, and what do the
 two builds' metadata say about registers, spills, LDS and the waves per SIMD that follow from them.
     python tools/kernel_asm_table.py PARENT.s BRANCH.s [--csv FILE] [--loop SUBSTRING ...]
+A kernel is matched by its demangled name, and its body is compared with the symbol and the function's number in the
+local labels (BB<n>_) and the comments taken out, so that kernels added to the unit do not make every later body differ.  --drop-last ARG:
+a branch kernel `name<.., ARG>` that the parent lacks is compared with the parent's `name<..>` (a template parameter added
+with ARG as the value that keeps the old kernel); branch kernels without a parent kernel are listed with empty parent columns.
 --loop: for the kernels whose demangled name contains SUBSTRING, also count the instructions of the steady-state stage
 loop of the fused item scan: the innermost loop that holds both MFMAs and a barrier, from its head to its last s_barrier.
 Exit status 1 when a kernel that is not byte-equal loses waves per SIMD, spills, or differs in LDS (or a --loop grows)."""
@@ -32,7 +36,8 @@ def kernels(path):
     out = {}
     for sym, m in meta.items():
         at = re.search(r"^" + re.escape(sym) + r":", text, re.M).start()
-        out[sym] = (text[at:text.index("s_endpgm", at)], m)
+        body = text[at:text.index("s_endpgm", at)].replace(sym, "KERNEL")
+        out[demangle(sym)] = (re.sub(r"[ \t]*;.*", "", re.sub(r"BB\d+_", "BB_", body)), m)
     return out
 
 
@@ -85,13 +90,33 @@ def main():
     ap.add_argument("branch")
     ap.add_argument("--csv")
     ap.add_argument("--loop", action="append", default=[])
+    ap.add_argument("--drop-last")
     args = ap.parse_args()
     a, b = kernels(args.parent), kernels(args.branch)
-    assert set(a) == set(b), sorted(set(a) ^ set(b))
+    twin = {}
+    for name in b:
+        old = name
+        if name not in a and args.drop_last and name.endswith(", " + args.drop_last + ">"):
+            old = name[:-len(", " + args.drop_last + ">")] + ">"
+        if old in a:
+            twin[name] = old
+    assert set(twin.values()) == set(a), sorted(set(a) - set(twin.values()))
     rows, bad, equal = [], [], 0
-    for sym in sorted(a):
-        name = demangle(sym)
-        (ba, ma), (bb, mb) = a[sym], b[sym]
+    for name in sorted(b):
+        bb, mb = b[name]
+        if name not in twin:   # new in the branch
+            row = {"kernel": name, "body_equal": "", "waves_parent": "", "waves_branch": waves(mb)}
+            for f in FIELDS:
+                row[f + "_parent"], row[f + "_branch"] = "", mb[f]
+            row["instructions_parent"], row["instructions_branch"] = "", len(instructions(bb.splitlines()))
+            row["stage_loop_parent"], row["stage_loop_branch"] = "", stage_loop(bb) if any(s in name for s in args.loop) else ""
+            if mb["vgpr_spill_count"] or mb["private_segment_fixed_size"]:
+                bad.append((name, "spill / scratch", mb["vgpr_spill_count"], mb["private_segment_fixed_size"]))
+            print(f"new: {name}: vgpr {mb['vgpr_count']}, sgpr spills {mb['sgpr_spill_count']}, waves {waves(mb)}, "
+                  f"instructions {row['instructions_branch']}, stage loop {row['stage_loop_branch']}")
+            rows.append(row)
+            continue
+        ba, ma = a[twin[name]]
         same = ba == bb
         equal += same
         row = {"kernel": name, "body_equal": int(same), "waves_parent": waves(ma), "waves_branch": waves(mb)}
@@ -116,7 +141,7 @@ def main():
                   f"{mb['sgpr_spill_count']}, waves {waves(ma)} -> {waves(mb)}, instructions {row['instructions_parent']} -> "
                   f"{row['instructions_branch']}, stage loop {row['stage_loop_parent']} -> {row['stage_loop_branch']}")
         rows.append(row)
-    print(f"{equal} of {len(rows)} kernel bodies byte-equal")
+    print(f"{equal} of {len(twin)} kernel bodies byte-equal, {len(rows) - len(twin)} new kernels")
     if args.csv:
         with open(args.csv, "w", newline="") as f:
             w = csv.DictWriter(f, fieldnames=list(rows[0]))
