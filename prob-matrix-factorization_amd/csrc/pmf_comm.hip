@@ -747,7 +747,7 @@ extern "C" int pmf_comm_gather_user_rows(pmf_ctx *ctx, int array, const int64_t 
     int width, stride;
     pmf_array_shape(ctx, array, &width, &stride);
     const int64_t row_bytes = (int64_t)stride * (int64_t)ctx->elem;
-    const int64_t step = std::max<int64_t>(1, (64ll << 20) / row_bytes);
+    const int64_t step = std::max<int64_t>(1, ctx->stage_bytes / row_bytes);
     int64_t longest = 0;
     for (int r = 0; r < cm->nranks; ++r) longest = std::max(longest, bounds[r + 1] - bounds[r]);
     const size_t block = (size_t)(std::min(step, std::max<int64_t>(longest, 1)) * row_bytes);

@@ -204,6 +204,14 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
     if (const char *fl = getenv("PMF_GAMMA_FOLD_LONG")) ctx->gamma_fold_long = std::max(atoll(fl), 0LL);
     if (const char *er = getenv("PMF_ELBO_ROWS")) ctx->elbo_rows = std::max(atoll(er), 0LL);
     if (const char *pp = getenv("PMF_GAMMA_PRED_PAIRS")) ctx->gamma_pred_pairs = std::max(atoll(pp), 0LL);
+    if (const char *qr = getenv("PMF_TOPK_QUERY_ROWS")) {
+        const long long n = atoll(qr);
+        ctx->topk_query_rows = n > 0 ? std::max(n / 32 * 32, 32LL) : 0;
+    }
+    if (const char *sb = getenv("PMF_STAGE_BYTES")) {
+        const long long n = atoll(sb);
+        if (n > 0) ctx->stage_bytes = n;
+    }
     if (const char *ex = getenv("PMF_COMM_EXCHANGE")) {
         if (!strcmp(ex, "allreduce")) ctx->exchange = PMF_EXCHANGE_ALLREDUCE;
         else if (!strcmp(ex, "scatter_gather")) ctx->exchange = PMF_EXCHANGE_SCATTER_GATHER;
@@ -430,7 +438,8 @@ int pmf_upload_tasks(pmf_ctx *ctx, const std::vector<int64_t> &ptr, int64_t rows
     out.n_tasks = (int64_t)tasks.size();
     out.n_split = (int64_t)split.size();
     out.n_slots = n_slots;
-    out.max_len = tasks.empty() ? 0 : tasks.front().len;
+    out.max_len = 0;   // (with row chunks the list is longest-first inside each chunk's group only: not tasks.front())
+    for (const PmfTask &t : tasks) out.max_len = std::max(out.max_len, t.len);
     int rc = out.d_tasks.alloc(ctx, tasks.size() * sizeof(PmfTask));
     if (rc) return rc;
     rc = out.d_split.alloc(ctx, split.size() * sizeof(PmfSplitRow));
@@ -755,8 +764,6 @@ void pmf_unpack_rows(const pmf_ctx *ctx, int array, const void *src, double *dst
     });
 }
 
-static const int64_t kStageBytes = 64ll << 20;
-
 extern "C" int pmf_set_array(pmf_ctx *ctx, int side, int array, const double *host) {
     CHECK_CTX(ctx, "pmf_set_array");
     CHECK_SIDE(side, "pmf_set_array");
@@ -770,7 +777,7 @@ extern "C" int pmf_set_array(pmf_ctx *ctx, int side, int array, const double *ho
     pmf_array_shape(ctx, array, &width, &stride);
     const int64_t rows = ctx->rows[side];
     const int64_t row_bytes = (int64_t)stride * (int64_t)ctx->elem;
-    const int64_t step = std::max<int64_t>(1, kStageBytes / row_bytes);
+    const int64_t step = std::max<int64_t>(1, ctx->stage_bytes / row_bytes);
     if ((rc = pmf_ensure_pinned(ctx, (size_t)(std::min(step, rows) * row_bytes)))) return rc;
     for (int64_t r0 = 0; r0 < rows; r0 += step) {
         int64_t nr = std::min(step, rows - r0);
@@ -798,7 +805,7 @@ extern "C" int pmf_get_array(pmf_ctx *ctx, int side, int array, double *host) {
     pmf_array_shape(ctx, array, &width, &stride);
     const int64_t rows = ctx->rows[side];
     const int64_t row_bytes = (int64_t)stride * (int64_t)ctx->elem;
-    const int64_t step = std::max<int64_t>(1, kStageBytes / row_bytes);
+    const int64_t step = std::max<int64_t>(1, ctx->stage_bytes / row_bytes);
     if ((rc = pmf_ensure_pinned(ctx, (size_t)(std::min(step, rows) * row_bytes)))) return rc;
     for (int64_t r0 = 0; r0 < rows; r0 += step) {
         int64_t nr = std::min(step, rows - r0);
@@ -815,7 +822,7 @@ int pmf_fold_in_download(pmf_ctx *ctx, int array, const void *dev, double *host,
     int width, stride, rc;
     pmf_array_shape(ctx, array, &width, &stride);
     const int64_t row_bytes = (int64_t)stride * (int64_t)ctx->elem;
-    const int64_t step = std::max<int64_t>(1, kStageBytes / row_bytes);
+    const int64_t step = std::max<int64_t>(1, ctx->stage_bytes / row_bytes);
     if ((rc = pmf_ensure_pinned(ctx, (size_t)(std::min(step, rows) * row_bytes)))) return rc;
     for (int64_t r0 = 0; r0 < rows; r0 += step) {
         const int64_t nr = std::min(step, rows - r0);
@@ -879,7 +886,7 @@ static int array_rows_impl(pmf_ctx *ctx, int side, int array, int64_t n, const i
     int width, stride;
     pmf_array_shape(ctx, array, &width, &stride);
     const int64_t row_bytes = (int64_t)stride * (int64_t)ctx->elem;
-    const int64_t step = std::min(n, std::max<int64_t>(1, kStageBytes / row_bytes));
+    const int64_t step = std::min(n, std::max<int64_t>(1, ctx->stage_bytes / row_bytes));
     // device staging: [step rows of the array's layout][step row ids]; the host side of it is the pinned buffer
     const size_t data_bytes = (size_t)((step * row_bytes + 15) / 16 * 16);
     if ((rc = pmf_ensure_scratch(ctx, data_bytes + (size_t)step * sizeof(int64_t)))) return rc;

@@ -824,6 +824,9 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float *cand_val, 
     });
 }
 
+// query rows of one round of the fused top-k and of pmf_rank_items (ctx->topk_query_rows: PMF_TOPK_QUERY_ROWS, for the tests)
+static int64_t topk_round_rows(const pmf_ctx *ctx) { return ctx->topk_query_rows > 0 ? ctx->topk_query_rows : (int64_t)1 << 20; }
+
 // Segments of the item range of a fused scan (gridDim.y).  Few query rows: cut the range so that the grid still has a few
 // thousand wavefronts.  Returns the number of segments; *seg_items = items per segment, a multiple of 32.
 static int topk_segments(int64_t n_rows, int64_t I, int64_t *seg_items) {
@@ -892,7 +895,7 @@ static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids
     const int64_t I = ctx->rows[PMF_SIDE_ITEM];
     const float *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const float>();
     const float *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const float>();
-    const int64_t Q = std::min<int64_t>(n_query, 1 << 20);   // query users per launch
+    const int64_t Q = std::min<int64_t>(n_query, topk_round_rows(ctx));   // query users per launch
     int64_t seg_items;
     const int nseg = topk_segments(Q, I, &seg_items);
     const size_t n_cand = nseg > 1 ? (size_t)nseg * k : 0;
@@ -961,6 +964,7 @@ static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int 
     // batch size: scores buffer of at most ~512 MB
     int64_t Q = std::max<int64_t>(32, (512ll << 20) / (I * (int64_t)sizeof(T)));
     Q = std::min<int64_t>(Q / 32 * 32, (n_query + 31) / 32 * 32);
+    if (ctx->topk_query_rows > 0) Q = std::min(Q, ctx->topk_query_rows);
     const size_t score_bytes = (size_t)Q * I * sizeof(T);
     const size_t id_bytes = (size_t)Q * sizeof(int32_t);
     const size_t out_bytes = (size_t)Q * k * (sizeof(int32_t) + sizeof(double));
@@ -1519,7 +1523,7 @@ static int rank_items_impl(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_ids
         } while (at < row_ptr[n + 1]);
     }
     const int64_t n_query = (int64_t)qrows.size();
-    const int64_t Q = std::min<int64_t>(n_query, 1 << 20);   // query rows per launch
+    const int64_t Q = std::min<int64_t>(n_query, topk_round_rows(ctx));   // query rows per launch
     const size_t id_bytes = ((size_t)Q * sizeof(int32_t) + 15) / 16 * 16;
     const size_t slot_bytes = (size_t)Q * RANK_SLOTS * 8;     // targets (int32) / thresholds (context dtype), 16-byte multiples
     const size_t cnt_bytes = ((size_t)Q * RANK_STRIDE * sizeof(int32_t) + 15) / 16 * 16;

@@ -208,3 +208,34 @@ def test_gaussian_item_row_chunks_do_not_change_the_result(K, dtype):
     for other in out[1:]:
         for a, b in zip(out[0], other):
             assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("order", ["chunks_first", "ratings_first"])
+def test_task_max_len_is_the_longest_task_of_all_row_chunks(order, monkeypatch):
+    """With row chunks the work lists are grouped by chunk and longest-first only inside a group: the longest task of the
+    list is not its first.  Items 6 and 7 (the last of four chunks) have 40 and 100 ratings, every other item one or two;
+    at this size a task holds at most 32 ratings (256 in the gradient list), so the 100-rating row is cut into four
+    pieces of 25 (`oracle.cavi_oracle.sgd_pieces`, the builder's rule).  The same value with 1 and with 4 chunks."""
+    import pmf_hip
+    from oracle.cavi_oracle import sgd_pieces
+    from pmf_hip import ITEM
+    monkeypatch.delenv("PMF_TASK_CHUNK", raising=False)
+    U, I = 120, 8
+    counts = [1, 2, 2, 1, 1, 2, 40, 100]
+    i = np.repeat(np.arange(I), counts)
+    u = np.concatenate([np.arange(n) for n in counts])
+    x = np.ones(len(i))
+    want = {kind: max(max(sgd_pieces(n, chunk)) for n in counts)
+            for kind, chunk in (("gamma", 32), ("gauss", 32), ("bias", 32), ("sgd", 256))}
+    assert want == {"gamma": 25, "gauss": 25, "bias": 25, "sgd": 100}
+    for chunks in (1, 4):
+        with pmf_hip.Context(U, I, 8, dtype="f32") as c:
+            if order == "chunks_first":
+                c.set_row_chunks(ITEM, chunks)
+                c.set_ratings(u, i, x)
+            else:
+                c.set_ratings(u, i, x)
+                c.set_row_chunks(ITEM, chunks)                   # the lists are rebuilt
+            assert c.n_chunks[ITEM] == chunks and c.chunk_rows(ITEM, chunks - 1) == (I - I // chunks, I)
+            got = {kind: c.task_max_len(ITEM, kind) for kind in want}
+        assert got == want, (chunks, got)
