@@ -682,6 +682,58 @@ int pmf_rank_items(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_ids, const 
                    const int32_t *item_ids, int use_bias, int exclude_train, int64_t *out_rank,
                    int64_t *out_candidates);
 
+/* Top-k and ranks for ANY query rows against all rows of one side: recommendations for rows the fit has not seen (the
+ * factors pmf_gauss_fold_in / pmf_gamma_fold_in return), similar items and similar users (one side against itself), the
+ * audience of an item (users as candidates).  The scans are those of pmf_topk_items / pmf_rank_items; what differs is
+ * where their operands come from.
+ * Candidates are all rows of `cand_side` (either side); k in [1, min(1024, rows(cand_side))].  Exactly one of `query_ids`
+ * and `query_factor` is non-null:
+ *   ids mode     query row q is row query_ids[q] of `query_side`'s FACTOR (repeats allowed); under PMF_PREDICT_BIAS its
+ *                coefficient is BIAS[query_ids[q]], under PMF_PREDICT_SCALE SCALE[query_ids[q]].  query_side == cand_side
+ *                is allowed with `score` 0 or PMF_SCORE_COSINE only: a bias or scale of two rows of one side is no model
+ *                score (PMF_EINVAL).
+ *   vector mode  query row q is the caller's K doubles query_factor[q K .. q K + K), converted to the context's dtype as
+ *                pmf_set_array_rows converts; `query_side` is ignored; query_coef[q] is the row's bias or scale, required
+ *                under PMF_PREDICT_BIAS / PMF_PREDICT_SCALE and ignored otherwise.
+ * Score: that of pmf_topk_items under `score` = 0, PMF_PREDICT_BIAS or PMF_PREDICT_SCALE, from the same arithmetic.
+ * PMF_SCORE_COSINE is dot * (inv_q * inv_c) with inv = 1 / sqrt(sum_k f_k^2) in the context's dtype (correctly rounded
+ * square root and division), formed per call from the staged query rows and from cand_side's FACTOR as it is then; it runs
+ * as PMF_PREDICT_SCALE on those inverse norms.  A zero row needs no special case: 0 * inf is NaN and a NaN never ranks, so
+ * a zero candidate never appears and a zero query row gets a row of -1 / 0.0.
+ * Order, ties (lower candidate id first), -0.0 == +0.0 and the NaN rule are those of pmf_topk_items.
+ * Exclusion (ex_ptr may be NULL: none): ex_ids[ex_ptr[q] .. ex_ptr[q + 1]) are candidate ids that are no candidates of
+ * query ROW q -- the list belongs to the row, not to the id: two rows with the same id may carry different lists.  The
+ * lists may be in any order and hold repeats (the library sorts each and drops repeats before the upload).  In
+ * pmf_rank_query exclusion applies to competitors only, as in pmf_rank_items.  Leaving the query itself out (similar
+ * items) is the caller's one-entry list; there is no flag for it.
+ * pmf_rank_query: the targets of row q are tgt_ids[tgt_ptr[q] .. tgt_ptr[q + 1]); out_rank (one per target) and
+ * out_candidates (one per row, may be NULL) are defined as in pmf_rank_items with "item" read as "row of cand_side".
+ * Position equals rank: the id at position p of row q in pmf_topk_query is the candidate whose pmf_rank_query rank is p,
+ * to the bit, tie groups included (both calls stage the rows, the coefficients and the inverse norms with the same code);
+ * min(k, out_candidates) entries of a row are valid.
+ * pmf_topk_query(PMF_SIDE_ITEM, n, PMF_SIDE_USER, ids, NULL, NULL, score, NULL, NULL, k, ..) gives the bytes of
+ * pmf_topk_items(n, ids, k, score), and with every row's list set to that user's training items those of
+ * pmf_topk_items_excluding(.., 1, ..); the same holds for pmf_rank_query and pmf_rank_items.
+ * Reads the context only: model state, ratings, work lists and the stored validation set stay as they are (the staging
+ * buffers grow on the first call, pmf_ctx_device_bytes counts them, and a later call of the same size adds nothing).
+ * Never a collective; two calls give the same bits.
+ * PMF_EINVAL (naming what is wrong): null context, bad side, both or neither query source, a missing query_coef, a bad
+ * score, a bad ex_ptr / tgt_ptr ([0] != 0 or decreasing), a null argument, a missing array (FACTOR of cand_side always,
+ * FACTOR of query_side in ids mode, BIAS / SCALE as the score needs them).  PMF_ERANGE: k, a query id, a target id or an
+ * excluded id out of range (naming the id and its position); for pmf_rank_query also more than 2^31 - 65 candidates
+ * (pmf_topk_query sends that case to the two-phase path).  An argument error writes nothing; n_query = 0 touches nothing.
+ * fp32 contexts with Kpad <= 128 (and k <= 64) run the fused scans, everything else the two-phase path / the generic
+ * ranking kernel, as the item calls do; the diagnostic switches of those calls act here too.  Timed under
+ * PMF_KERNEL_TOPK. */
+#define PMF_SCORE_COSINE 4     /* `score` of the two query calls only; 0, PMF_PREDICT_BIAS, PMF_PREDICT_SCALE as elsewhere */
+int pmf_topk_query(pmf_ctx *ctx, int cand_side, int64_t n_query, int query_side, const int32_t *query_ids,
+                   const double *query_factor, const double *query_coef, int score, const int64_t *ex_ptr,
+                   const int32_t *ex_ids, int k, int32_t *out_ids, double *out_scores);
+int pmf_rank_query(pmf_ctx *ctx, int cand_side, int64_t n_query, int query_side, const int32_t *query_ids,
+                   const double *query_factor, const double *query_coef, int score, const int64_t *ex_ptr,
+                   const int32_t *ex_ids, const int64_t *tgt_ptr, const int32_t *tgt_ids, int64_t *out_rank,
+                   int64_t *out_candidates);
+
 /* ---- profiling ----------------------------------------------------------
  * When enabled every kernel launch is bracketed by hipEvents on the context's
  * stream; pmf_prof_get synchronises and returns the accumulated device time

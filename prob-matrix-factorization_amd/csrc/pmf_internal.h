@@ -223,6 +223,10 @@ struct pmf_ctx {
     // pmf_gamma_exact_sweep / _accumulate: the (E log, E) tables [rows][2][kpad] of the users, then of the items; rebuilt
     // by every call, in storage of their own so that a pmf_gamma_elbo_terms call (d_scratch) cannot write over them
     PmfBuf d_gamma_tables;
+    // pmf_topk_query / pmf_rank_query (pmf_topk.hip): what a call keeps for all its rounds -- the sorted exclusion CSR and
+    // the candidates' inverse norms -- and the staged query rows of one round (table, coefficients, gather ids).  Grown on
+    // demand, in storage of their own: the scans' outputs and score matrix live in d_scratch.
+    PmfBuf d_query_call, d_query_rows;
     PmfBuf h_pinned{PmfBuf::PINNED};
 
     // diagnostic switches, read from the environment once when the context is created
@@ -238,7 +242,7 @@ struct pmf_ctx {
     int64_t fold_in_rows = 0;      // PMF_FOLD_IN_ROWS=n caps the rows of one block of pmf_gauss_fold_in and pmf_gamma_fold_in (tests: many blocks on a small batch; 0: by scratch size)
     int64_t gamma_fold_long = 0;   // PMF_GAMMA_FOLD_LONG=n: rows of pmf_gamma_fold_in with more than n ratings take the block-per-row kernel (tests: both kernels on small rows; 0: kGammaFoldLongRow)
     int64_t gamma_pred_pairs = 0;  // PMF_GAMMA_PRED_PAIRS=n caps the pairs of one staging round of pmf_gamma_predictive (tests: many rounds on a small batch; 0: kGammaPredPairs)
-    int64_t topk_query_rows = 0;   // PMF_TOPK_QUERY_ROWS=n caps the query rows of one round of pmf_topk_items* and pmf_rank_items, rounded down to a multiple of 32 and at least 32 (tests: many rounds on a small batch; 0: 1 << 20 rows, or 512 MB of scores on the two-phase path)
+    int64_t topk_query_rows = 0;   // PMF_TOPK_QUERY_ROWS=n caps the query rows of one round of pmf_topk_items*, pmf_rank_items and the two query calls, rounded down to a multiple of 32 and at least 32 (tests: many rounds on a small batch; 0: 1 << 20 rows, or 512 MB of scores on the two-phase path)
     int64_t stage_bytes = 64ll << 20;   // PMF_STAGE_BYTES=n: bytes of one staging round of pmf_set_array / pmf_get_array, the row exchanges, the fold-ins' downloads and pmf_comm_gather_user_rows, at least one row (tests: many rounds on a few rows; 0 / unset: 64 MiB)
     int64_t elbo_rows = 0;         // PMF_ELBO_ROWS=n caps the rows of one statistics window of pmf_gauss_elbo_terms (tests: many windows on a small problem; 0: by scratch size)
     size_t elbo_lds_bytes = 0;     // dynamic LDS size the ELBO row kernel of this context's K and dtype has been allowed (0: not yet asked)

@@ -25,7 +25,8 @@ struct TopkParams {
 
 // TopkParams of an excluding call (pmf_topk_items_excluding): item j is no candidate of user u when it is among
 // ex_items[ex_ptr[u] .. ex_ptr[u + 1]), ascending item ids, each once -- the context's distinct training items
-// (pmf_index_distinct), as in RankParams; a caller's own CSR would fit the same two pointers.
+// (pmf_index_distinct), as in RankParams; pmf_topk_query hands a caller's own CSR, indexed by the staged row, to the same
+// two pointers.
 struct TopkExcludeParams : TopkParams {
     const int64_t *ex_ptr;
     const int32_t *ex_items;
@@ -887,14 +888,33 @@ static hipError_t launch_topk_fused_mode(pmf_ctx *ctx, const P &p, dim3 grid, co
     return hipSuccess;
 }
 
+// ---------------------------------------------------------------------------
+// what a scan reads: the query source
+// ---------------------------------------------------------------------------
+// The A side (the query rows: a table addressed by the ids in p.users, and their bias / scale), the B side (the
+// candidates: all n_cand rows of a table, and theirs) and the exclusion CSR, which is indexed by the A ids.  The item
+// calls (pmf_topk_items*, pmf_rank_items) pass the context's USER arrays against its ITEM arrays with the callers' user
+// ids; the query calls (pmf_topk_query, pmf_rank_query) stage the rows of every round into a dense table first.
+struct QueryStage;
+struct TopkSource {
+    const void *fa = nullptr, *ca = nullptr;   // A: FACTOR-shaped table [.. x kpad] and coefficients (null under score 0); context dtype
+    const void *fb = nullptr, *cb = nullptr;   // B: the same for the candidates
+    int64_t n_cand = 0;                        // rows of the B table
+    const int64_t *ex_ptr = nullptr;           // device: ex_ids[ex_ptr[a] .. ex_ptr[a + 1]) are no candidates of A id a (ascending, distinct), or null
+    const int32_t *ex_ids = nullptr;
+    const int32_t *ids = nullptr;              // host: the A id of the caller's row n -- or null with `staged`:
+    const QueryStage *staged = nullptr;        // the rows are staged per round, and row n of a round that begins at row n0 has A id n - n0
+};
+// the source of one round, rows [row0, row0 + n): `src` itself, or with fa / ca / ex_ptr those of the rows staged here
+static int topk_round_source(pmf_ctx *ctx, const TopkSource &src, int64_t row0, int64_t n, TopkSource *round);
+// ... and the round's A ids on the device, one per row
+static int topk_round_ids(pmf_ctx *ctx, const TopkSource &src, int64_t row0, int n, int32_t *d_ids);
+
 // fp32, Kpad <= 128, k <= 64
-// (ex_ptr / ex_items: the exclusion lists of an excluding call, else null)
-static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int mode, const float *cu,
-                          const float *ci, const int64_t *ex_ptr, const int32_t *ex_items, int32_t *out_items,
+// (cu / ci / the exclusion lists: src's, per round)
+static int run_topk_fused(pmf_ctx *ctx, const TopkSource &src, int64_t n_query, int k, int mode, int32_t *out_items,
                           double *out_scores) {
-    const int64_t I = ctx->rows[PMF_SIDE_ITEM];
-    const float *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const float>();
-    const float *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const float>();
+    const int64_t I = src.n_cand;
     const int64_t Q = std::min<int64_t>(n_query, topk_round_rows(ctx));   // query users per launch
     int64_t seg_items;
     const int nseg = topk_segments(Q, I, &seg_items);
@@ -912,22 +932,25 @@ static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids
     int32_t *d_ci = (int32_t *)(base + out_s + out_i + id_bytes + cv_bytes);
     for (int64_t at = 0; at < n_query; at += Q) {
         const int nq = (int)std::min<int64_t>(Q, n_query - at);
-        PMF_HIP_CHECK(hipMemcpyAsync(d_users, user_ids + at, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        TopkSource r;
+        if ((rc = topk_round_source(ctx, src, at, nq, &r)) || (rc = topk_round_ids(ctx, src, at, nq, d_users))) return rc;
+        const float *fu = static_cast<const float *>(r.fa), *fi = static_cast<const float *>(r.fb);
+        const float *cu = static_cast<const float *>(r.ca), *ci = static_cast<const float *>(r.cb);
         TopkExcludeParams p;
         p.users = d_users;
         p.nq = nq;
         p.n_items = I;
         p.K = ctx->K;
         p.kpad = ctx->kpad;
-        p.ex_ptr = ex_ptr;
-        p.ex_items = ex_items;
+        p.ex_ptr = r.ex_ptr;
+        p.ex_items = r.ex_ids;
         {
             PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
             dim3 grid((unsigned)((nq + 127) / 128), (unsigned)nseg);
             // the instantiation for the K class KH and the bias mode
             PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, [&](auto kh) {   // KH: kpad / 2 rounded up to 8, 16, 32 or 64
                 return pmf_with_predict_mode(mode, [&](auto m) {
-                    if (ex_ptr)
+                    if (p.ex_ptr)
                         return launch_topk_fused_mode<kh, m>(ctx, p, grid, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci,
                                                              d_out_items, d_out_scores);
                     return launch_topk_fused_mode<kh, m>(ctx, static_cast<const TopkParams &>(p), grid, fu, fi, cu, ci, k, seg_items,
@@ -948,18 +971,13 @@ static int run_topk_fused(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids
 
 // (arguments, arrays and flag are checked: topk_items_impl)
 template <typename T>
-static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias, const int64_t *ex_ptr,
-                    const int32_t *ex_items, int32_t *out_items, double *out_scores) {
-    const int64_t I = ctx->rows[PMF_SIDE_ITEM];
+static int run_topk(pmf_ctx *ctx, const TopkSource &src, int64_t n_query, int k, int use_bias, int32_t *out_items,
+                    double *out_scores) {
+    const int64_t I = src.n_cand;
     int rc;
-    const int carr = use_bias == PMF_PREDICT_SCALE ? PMF_ARR_SCALE : PMF_ARR_BIAS;
-    const T *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const T>();
-    const T *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const T>();
-    const T *bu = use_bias ? ctx->arr[PMF_SIDE_USER][carr].as<const T>() : nullptr;
-    const T *bi = use_bias ? ctx->arr[PMF_SIDE_ITEM][carr].as<const T>() : nullptr;
     if constexpr (std::is_same<T, float>::value) {
         if (ctx->kpad <= 128 && k <= 64 && I <= (int64_t)INT32_MAX - 64 && !ctx->topk_two_phase)   // (the fused scan counts items in ints)
-            return run_topk_fused(ctx, n_query, user_ids, k, use_bias, bu, bi, ex_ptr, ex_items, out_items, out_scores);
+            return run_topk_fused(ctx, src, n_query, k, use_bias, out_items, out_scores);
     }
     // batch size: scores buffer of at most ~512 MB
     int64_t Q = std::max<int64_t>(32, (512ll << 20) / (I * (int64_t)sizeof(T)));
@@ -976,15 +994,18 @@ static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int 
     int32_t *d_users = d_out_items + (size_t)Q * k;
     for (int64_t at = 0; at < n_query; at += Q) {
         const int nq = (int)std::min<int64_t>(Q, n_query - at);
-        PMF_HIP_CHECK(hipMemcpyAsync(d_users, user_ids + at, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        TopkSource r;
+        if ((rc = topk_round_source(ctx, src, at, nq, &r)) || (rc = topk_round_ids(ctx, src, at, nq, d_users))) return rc;
+        const T *fu = static_cast<const T *>(r.fa), *fi = static_cast<const T *>(r.fb);
+        const T *bu = static_cast<const T *>(r.ca), *bi = static_cast<const T *>(r.cb);
         TopkExcludeParams p;
         p.users = d_users;
         p.nq = nq;
         p.n_items = I;
         p.K = ctx->K;
         p.kpad = ctx->kpad;
-        p.ex_ptr = ex_ptr;
-        p.ex_items = ex_items;
+        p.ex_ptr = r.ex_ptr;
+        p.ex_items = r.ex_ids;
         {
             PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
             if constexpr (std::is_same<T, float>::value) {
@@ -995,7 +1016,7 @@ static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int 
                 hipLaunchKernelGGL(topk_scores_f64_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65535)),
                                    dim3(256), 0, ctx->stream, p, fu, fi, bu, bi, use_bias, d_scores);
             }
-            if (ex_ptr)   // excluded pairs score NaN from here on: the select never ranks them
+            if (p.ex_ptr)   // excluded pairs score NaN from here on: the select never ranks them
                 hipLaunchKernelGGL((topk_exclude_scores_kernel<T>), dim3((unsigned)std::min(nq, 65535)), dim3(256), 0, ctx->stream,
                                    p, d_scores);
             hipLaunchKernelGGL((topk_select_kernel<T>), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream,
@@ -1007,6 +1028,24 @@ static int run_topk(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int 
         PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     return PMF_OK;
+}
+
+// the source of the item calls: the context's users (by the caller's ids) against its items under `mode`, with the users'
+// distinct training items excluded (built: pmf_index_distinct) or nothing
+static TopkSource topk_items_source(const pmf_ctx *ctx, const int32_t *user_ids, int mode, bool exclude_train) {
+    const int carr = mode == PMF_PREDICT_SCALE ? PMF_ARR_SCALE : PMF_ARR_BIAS;
+    TopkSource src;
+    src.fa = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as();
+    src.fb = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as();
+    src.ca = mode ? ctx->arr[PMF_SIDE_USER][carr].as() : nullptr;
+    src.cb = mode ? ctx->arr[PMF_SIDE_ITEM][carr].as() : nullptr;
+    src.n_cand = ctx->rows[PMF_SIDE_ITEM];
+    if (exclude_train) {
+        src.ex_ptr = ctx->index[PMF_SIDE_USER].d_distinct_ptr.as<const int64_t>();
+        src.ex_ids = ctx->index[PMF_SIDE_USER].d_distinct.as<const int32_t>();
+    }
+    src.ids = user_ids;
+    return src;
 }
 
 // pmf_topk_items (`fn` names the entry point in a refusal), and with `exclude_train` pmf_topk_items_excluding
@@ -1032,16 +1071,9 @@ static int topk_items_impl(const char *fn, pmf_ctx *ctx, int64_t n_query, const 
     PMF_REQUIRE(!exclude_train || ctx->index[PMF_SIDE_USER].d_ptr, PMF_EINVAL,
                 "%s: exclude_train needs the training ratings (pmf_ctx_set_ratings); the context holds none", fn);
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
-    const int64_t *ex_ptr = nullptr;
-    const int32_t *ex_items = nullptr;
-    if (exclude_train) {
-        if ((rc = pmf_index_distinct(ctx, PMF_SIDE_USER))) return rc;   // (built once per set of ratings)
-        ex_ptr = ctx->index[PMF_SIDE_USER].d_distinct_ptr.as<const int64_t>();
-        ex_items = ctx->index[PMF_SIDE_USER].d_distinct.as<const int32_t>();
-    }
-    return pmf_with_dtype(ctx, [&](auto t) {
-        return run_topk<decltype(t)>(ctx, n_query, user_ids, k, use_bias, ex_ptr, ex_items, out_items, out_scores);
-    });
+    if (exclude_train && (rc = pmf_index_distinct(ctx, PMF_SIDE_USER))) return rc;   // (built once per set of ratings)
+    const TopkSource src = topk_items_source(ctx, user_ids, use_bias, exclude_train != 0);
+    return pmf_with_dtype(ctx, [&](auto t) { return run_topk<decltype(t)>(ctx, src, n_query, k, use_bias, out_items, out_scores); });
 }
 
 extern "C" int pmf_topk_items(pmf_ctx *ctx, int64_t n_query, const int32_t *user_ids, int k, int use_bias,
@@ -1444,13 +1476,10 @@ static hipError_t launch_rank_fused(pmf_ctx *ctx, const TopkParams &p, const Ran
 
 // the launches of one batch of query rows (ids, targets and zeroed counters are on the device)
 template <typename T>
-static int launch_rank(pmf_ctx *ctx, const TopkParams &p, const RankParams &rp, int mode, bool one_slot) {
+static int launch_rank(pmf_ctx *ctx, const TopkSource &src, const TopkParams &p, const RankParams &rp, int mode, bool one_slot) {
     const int64_t I = p.n_items;
-    const int carr = mode == PMF_PREDICT_SCALE ? PMF_ARR_SCALE : PMF_ARR_BIAS;
-    const T *fu = ctx->arr[PMF_SIDE_USER][PMF_ARR_FACTOR].as<const T>();
-    const T *fi = ctx->arr[PMF_SIDE_ITEM][PMF_ARR_FACTOR].as<const T>();
-    const T *cu = mode ? ctx->arr[PMF_SIDE_USER][carr].as<const T>() : nullptr;
-    const T *ci = mode ? ctx->arr[PMF_SIDE_ITEM][carr].as<const T>() : nullptr;
+    const T *fu = static_cast<const T *>(src.fa), *fi = static_cast<const T *>(src.fb);
+    const T *cu = static_cast<const T *>(src.ca), *ci = static_cast<const T *>(src.cb);
     const dim3 row_grid((unsigned)((p.nq + 3) / 4));
     PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
     if constexpr (std::is_same<T, float>::value) {
@@ -1473,6 +1502,81 @@ static int launch_rank(pmf_ctx *ctx, const TopkParams &p, const RankParams &rp, 
         }
     }
     hipLaunchKernelGGL((rank_generic_kernel<T>), row_grid, dim3(256), 0, ctx->stream, p, rp, fu, fi, cu, ci, mode);
+    return PMF_OK;
+}
+
+// The ranks of the targets item_ids[row_ptr[n] .. row_ptr[n + 1]) of every row n of `src` among its candidates (arguments
+// and arrays are checked, the device is current: rank_items_impl, pmf_rank_query).
+static int run_rank(pmf_ctx *ctx, const TopkSource &src, int64_t n_rows, const int64_t *row_ptr, const int32_t *item_ids,
+                    int use_bias, int64_t *out_rank, int64_t *out_candidates) {
+    const int64_t I = src.n_cand;
+    int rc;
+    // query rows: a user's targets in runs of at most `slots`; a user without targets keeps one row (its candidates)
+    const int slots = ctx->rank_targets > 0 ? std::min(ctx->rank_targets, RANK_SLOTS) : RANK_SLOTS;
+    struct QueryRow {
+        int64_t row, first;   // the caller's row and the offset of the run's first target in item_ids
+        int n;
+    };
+    std::vector<QueryRow> qrows;
+    bool one_slot = true;
+    for (int64_t n = 0; n < n_rows; ++n) {
+        int64_t at = row_ptr[n];
+        do {
+            const int len = (int)std::min<int64_t>(slots, row_ptr[n + 1] - at);
+            qrows.push_back({n, at, len});
+            one_slot = one_slot && len <= 1;
+            at += len;
+        } while (at < row_ptr[n + 1]);
+    }
+    const int64_t n_query = (int64_t)qrows.size();
+    const int64_t Q = std::min<int64_t>(n_query, topk_round_rows(ctx));   // query rows per launch
+    const size_t id_bytes = ((size_t)Q * sizeof(int32_t) + 15) / 16 * 16;
+    const size_t slot_bytes = (size_t)Q * RANK_SLOTS * 8;     // targets (int32) / thresholds (context dtype), 16-byte multiples
+    const size_t cnt_bytes = ((size_t)Q * RANK_STRIDE * sizeof(int32_t) + 15) / 16 * 16;
+    if ((rc = pmf_ensure_scratch(ctx, id_bytes + 2 * slot_bytes + cnt_bytes))) return rc;
+    char *base = ctx->d_scratch.as<char>();
+    int32_t *d_users = (int32_t *)base;
+    int32_t *d_tgt = (int32_t *)(base + id_bytes);
+    void *d_th = base + id_bytes + slot_bytes;
+    int32_t *d_cnt = (int32_t *)(base + id_bytes + 2 * slot_bytes);
+    std::vector<int32_t> h_users((size_t)Q), h_tgt((size_t)Q * RANK_SLOTS), h_cnt((size_t)Q * RANK_STRIDE);
+    for (int64_t at = 0; at < n_query; at += Q) {
+        const int nq = (int)std::min<int64_t>(Q, n_query - at);
+        // (a staged source: the round's query rows belong to the caller's rows row0 .. row1, which are what is staged)
+        const int64_t row0 = qrows[(size_t)at].row, row1 = qrows[(size_t)(at + nq - 1)].row;
+        TopkSource r;
+        if ((rc = topk_round_source(ctx, src, row0, row1 - row0 + 1, &r))) return rc;
+        for (int q = 0; q < nq; ++q) {
+            const QueryRow &qr = qrows[(size_t)(at + q)];
+            h_users[(size_t)q] = src.ids ? src.ids[qr.row] : (int32_t)(qr.row - row0);
+            for (int t = 0; t < RANK_SLOTS; ++t) h_tgt[(size_t)q * RANK_SLOTS + t] = t < qr.n ? item_ids[qr.first + t] : -1;
+        }
+        PMF_HIP_CHECK(hipMemcpyAsync(d_users, h_users.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        PMF_HIP_CHECK(hipMemcpyAsync(d_tgt, h_tgt.data(), (size_t)nq * RANK_SLOTS * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        PMF_HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)nq * RANK_STRIDE * sizeof(int32_t), ctx->stream));
+        TopkParams p;
+        p.users = d_users;
+        p.nq = nq;
+        p.n_items = I;
+        p.K = ctx->K;
+        p.kpad = ctx->kpad;
+        RankParams rp;
+        rp.tgt = d_tgt;
+        rp.th = d_th;
+        rp.cnt = d_cnt;
+        rp.ex_ptr = r.ex_ptr;
+        rp.ex_items = r.ex_ids;
+        if ((rc = pmf_with_dtype(ctx, [&](auto t) { return launch_rank<decltype(t)>(ctx, r, p, rp, use_bias, one_slot); }))) return rc;
+        PMF_HIP_CHECK(hipGetLastError());
+        PMF_HIP_CHECK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)nq * RANK_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (int q = 0; q < nq; ++q) {
+            const QueryRow &qr = qrows[(size_t)(at + q)];
+            const int32_t *cnt = h_cnt.data() + (size_t)q * RANK_STRIDE;
+            for (int t = 0; t < qr.n; ++t) out_rank[qr.first + t] = (cnt[RANK_MASK] >> t) & 1 ? -1 : (int64_t)cnt[t];
+            if (out_candidates && qr.first == row_ptr[qr.row]) out_candidates[qr.row] = I - cnt[RANK_NAN] - cnt[RANK_EXCL];
+        }
+    }
     return PMF_OK;
 }
 
@@ -1505,69 +1609,8 @@ static int rank_items_impl(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_ids
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     if (exclude_train && (rc = pmf_index_distinct(ctx, PMF_SIDE_USER))) return rc;
 
-    // query rows: a user's targets in runs of at most `slots`; a user without targets keeps one row (its candidates)
-    const int slots = ctx->rank_targets > 0 ? std::min(ctx->rank_targets, RANK_SLOTS) : RANK_SLOTS;
-    struct QueryRow {
-        int64_t row, first;   // the caller's row and the offset of the run's first target in item_ids
-        int n;
-    };
-    std::vector<QueryRow> qrows;
-    bool one_slot = true;
-    for (int64_t n = 0; n < n_rows; ++n) {
-        int64_t at = row_ptr[n];
-        do {
-            const int len = (int)std::min<int64_t>(slots, row_ptr[n + 1] - at);
-            qrows.push_back({n, at, len});
-            one_slot = one_slot && len <= 1;
-            at += len;
-        } while (at < row_ptr[n + 1]);
-    }
-    const int64_t n_query = (int64_t)qrows.size();
-    const int64_t Q = std::min<int64_t>(n_query, topk_round_rows(ctx));   // query rows per launch
-    const size_t id_bytes = ((size_t)Q * sizeof(int32_t) + 15) / 16 * 16;
-    const size_t slot_bytes = (size_t)Q * RANK_SLOTS * 8;     // targets (int32) / thresholds (context dtype), 16-byte multiples
-    const size_t cnt_bytes = ((size_t)Q * RANK_STRIDE * sizeof(int32_t) + 15) / 16 * 16;
-    if ((rc = pmf_ensure_scratch(ctx, id_bytes + 2 * slot_bytes + cnt_bytes))) return rc;
-    char *base = ctx->d_scratch.as<char>();
-    int32_t *d_users = (int32_t *)base;
-    int32_t *d_tgt = (int32_t *)(base + id_bytes);
-    void *d_th = base + id_bytes + slot_bytes;
-    int32_t *d_cnt = (int32_t *)(base + id_bytes + 2 * slot_bytes);
-    std::vector<int32_t> h_users((size_t)Q), h_tgt((size_t)Q * RANK_SLOTS), h_cnt((size_t)Q * RANK_STRIDE);
-    for (int64_t at = 0; at < n_query; at += Q) {
-        const int nq = (int)std::min<int64_t>(Q, n_query - at);
-        for (int q = 0; q < nq; ++q) {
-            const QueryRow &qr = qrows[(size_t)(at + q)];
-            h_users[(size_t)q] = user_ids[qr.row];
-            for (int t = 0; t < RANK_SLOTS; ++t) h_tgt[(size_t)q * RANK_SLOTS + t] = t < qr.n ? item_ids[qr.first + t] : -1;
-        }
-        PMF_HIP_CHECK(hipMemcpyAsync(d_users, h_users.data(), (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        PMF_HIP_CHECK(hipMemcpyAsync(d_tgt, h_tgt.data(), (size_t)nq * RANK_SLOTS * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        PMF_HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)nq * RANK_STRIDE * sizeof(int32_t), ctx->stream));
-        TopkParams p;
-        p.users = d_users;
-        p.nq = nq;
-        p.n_items = I;
-        p.K = ctx->K;
-        p.kpad = ctx->kpad;
-        RankParams rp;
-        rp.tgt = d_tgt;
-        rp.th = d_th;
-        rp.cnt = d_cnt;
-        rp.ex_ptr = exclude_train ? ctx->index[PMF_SIDE_USER].d_distinct_ptr.as<const int64_t>() : nullptr;
-        rp.ex_items = exclude_train ? ctx->index[PMF_SIDE_USER].d_distinct.as<const int32_t>() : nullptr;
-        if ((rc = pmf_with_dtype(ctx, [&](auto t) { return launch_rank<decltype(t)>(ctx, p, rp, use_bias, one_slot); }))) return rc;
-        PMF_HIP_CHECK(hipGetLastError());
-        PMF_HIP_CHECK(hipMemcpyAsync(h_cnt.data(), d_cnt, (size_t)nq * RANK_STRIDE * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (int q = 0; q < nq; ++q) {
-            const QueryRow &qr = qrows[(size_t)(at + q)];
-            const int32_t *cnt = h_cnt.data() + (size_t)q * RANK_STRIDE;
-            for (int t = 0; t < qr.n; ++t) out_rank[qr.first + t] = (cnt[RANK_MASK] >> t) & 1 ? -1 : (int64_t)cnt[t];
-            if (out_candidates && qr.first == row_ptr[qr.row]) out_candidates[qr.row] = I - cnt[RANK_NAN] - cnt[RANK_EXCL];
-        }
-    }
-    return PMF_OK;
+    const TopkSource src = topk_items_source(ctx, user_ids, use_bias, exclude_train != 0);
+    return run_rank(ctx, src, n_rows, row_ptr, item_ids, use_bias, out_rank, out_candidates);
 }
 
 extern "C" int pmf_rank_items(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_ids, const int64_t *row_ptr,
@@ -1578,5 +1621,293 @@ extern "C" int pmf_rank_items(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_
     if (n_rows == 0) return PMF_OK;
     return pmf_no_throw("pmf_rank_items", [&] {
         return rank_items_impl(ctx, n_rows, user_ids, row_ptr, item_ids, use_bias, exclude_train, out_rank, out_candidates);
+    });
+}
+
+// ---------------------------------------------------------------------------
+// pmf_topk_query / pmf_rank_query: any rows against all rows of one side
+// ---------------------------------------------------------------------------
+// No scan of their own: the query rows of a round are STAGED into a dense [n x Kpad] table of the context's dtype with
+// their coefficients in a dense [n] array, the scan's ids are 0 .. n - 1, and the kernels above run on that source as they
+// run on the context's users.  Cosine is the PMF_PREDICT_SCALE arithmetic, dot * (c_q * c_c), on inverse row norms.
+// Both calls prepare their source with the same functions (query_check, query_begin, query_stage_rows): a pair has one
+// score, whichever call asks.
+
+// staged row q = row ids[q] of `table`, its coefficient = coef_table[ids[q]] (null: none); one 16-byte piece per lane,
+// consecutive lanes on consecutive pieces of a row
+template <typename T>
+__global__ __launch_bounds__(256) void query_gather_kernel(const T *table, const T *coef_table, const int32_t *ids, int n,
+                                                           int kpad, T *rows, T *coef) {
+    const int pr = kpad * (int)sizeof(T) / 16;        // pieces per row (Kpad is a multiple of 4)
+    const int64_t total = (int64_t)n * pr;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        const int q = (int)(e / pr), pc = (int)(e % pr);
+        const int id = ids[q];
+        reinterpret_cast<f32x4 *>(rows)[e] = reinterpret_cast<const f32x4 *>(table + (int64_t)id * kpad)[pc];
+        if (coef_table && pc == 0) coef[q] = coef_table[id];
+    }
+}
+
+// ids[q] = q: the scan's ids of a staged round
+__global__ __launch_bounds__(256) void query_iota_kernel(int32_t *ids, int n) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n) ids[q] = q;
+}
+
+// inv[r] = 1 / sqrt(sum_k rows[r][k]^2) in T, correctly rounded square root and division (a zero row gives +inf, a row
+// with a NaN gives NaN).  16 lanes per row, 16-byte pieces, a fixed order of additions: two calls give the same bits.
+template <typename T>
+__global__ __launch_bounds__(256) void query_inv_norm_kernel(const T *rows, int64_t n, int kpad, T *inv) {
+    constexpr int PE = 16 / (int)sizeof(T);           // elements per piece
+    const int sub = threadIdx.x & 15;
+    for (int64_t base = (int64_t)blockIdx.x * 16; base < n; base += (int64_t)gridDim.x * 16) {   // (uniform trips: the shuffles)
+        const int64_t r = base + (threadIdx.x >> 4);
+        T s = (T)0;
+        if (r < n) {
+            const T *row = rows + r * kpad;
+            for (int k = sub * PE; k < kpad; k += 16 * PE) {
+                const f32x4 piece = *reinterpret_cast<const f32x4 *>(row + k);
+                T v[PE];
+                __builtin_memcpy(v, &piece, 16);
+#pragma unroll
+                for (int j = 0; j < PE; ++j) s = fma(v[j], v[j], s);
+            }
+        }
+        s += __shfl_xor(s, 8, 64);
+        s += __shfl_xor(s, 4, 64);
+        s += __shfl_xor(s, 2, 64);
+        s += __shfl_xor(s, 1, 64);
+        if (sub == 0 && r < n) inv[r] = (T)1 / sqrt(s);
+    }
+}
+
+template <typename T>
+static void launch_inv_norm(pmf_ctx *ctx, const T *rows, int64_t n, T *inv) {
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + 15) / 16, 1 << 20);
+    hipLaunchKernelGGL((query_inv_norm_kernel<T>), dim3(blocks), dim3(256), 0, ctx->stream, rows, n, ctx->kpad, inv);
+}
+
+// where the query rows come from (pmf_topk_query documents the two modes)
+struct QueryStage {
+    const int32_t *ids = nullptr;                         // ids mode: host [n_query] rows of ...
+    const void *table = nullptr, *coef_table = nullptr;   // ... this device table, with this coefficient array (null: none)
+    const double *factor = nullptr, *coef = nullptr;      // vector mode: host [n_query x K] and [n_query] (null: none)
+    bool cosine = false;                                  // the coefficient is the staged row's inverse norm
+    const int64_t *d_ex_ptr = nullptr;                    // device [n_query + 1]: the rows' exclusion lists, or null
+};
+
+// rows [row0, row0 + n) of `st` into ctx->d_query_rows; round->fa / ca / ex_ptr are theirs
+template <typename T>
+static int query_stage_rows(pmf_ctx *ctx, const QueryStage &st, int64_t row0, int64_t n, TopkSource *round) {
+    const int K = ctx->K, kpad = ctx->kpad;
+    const size_t row_bytes = (size_t)kpad * sizeof(T);
+    const size_t table_bytes = (size_t)n * row_bytes, coef_bytes = ((size_t)n * sizeof(T) + 15) / 16 * 16;
+    const size_t id_bytes = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16;
+    int rc;
+    if ((rc = ctx->d_query_rows.reserve(ctx, table_bytes + coef_bytes + id_bytes, {ctx->stream}))) return rc;
+    char *base = ctx->d_query_rows.as<char>();
+    T *d_rows = (T *)base, *d_coef = (T *)(base + table_bytes);
+    int32_t *d_ids = (int32_t *)(base + table_bytes + coef_bytes);
+    if (st.ids) {
+        PMF_HIP_CHECK(hipMemcpyAsync(d_ids, st.ids + row0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
+        const int64_t pieces = n * (int64_t)(row_bytes / 16);
+        hipLaunchKernelGGL((query_gather_kernel<T>), dim3((unsigned)std::min<int64_t>((pieces + 255) / 256, 1 << 20)), dim3(256), 0,
+                           ctx->stream, static_cast<const T *>(st.table), static_cast<const T *>(st.coef_table), d_ids, (int)n, kpad,
+                           d_rows, d_coef);
+    } else {
+        // the caller's float64 rows -> T, zero-padded to Kpad (the conversion of pmf_set_array_rows), through pinned steps
+        const int64_t step = std::max<int64_t>(1, ctx->stage_bytes / (int64_t)row_bytes);
+        if ((rc = pmf_ensure_pinned(ctx, (size_t)std::min(step, n) * row_bytes))) return rc;
+        T *pin = ctx->h_pinned.as<T>();
+        for (int64_t r0 = 0; r0 < n; r0 += step) {
+            const int64_t nr = std::min(step, n - r0);
+            for (int64_t r = 0; r < nr; ++r) {
+                const double *s = st.factor + (row0 + r0 + r) * K;
+                T *d = pin + r * kpad;
+                for (int k = 0; k < K; ++k) d[k] = (T)s[k];
+                for (int k = K; k < kpad; ++k) d[k] = (T)0;
+            }
+            PMF_HIP_CHECK(hipMemcpyAsync(d_rows + r0 * kpad, pin, (size_t)nr * row_bytes, hipMemcpyHostToDevice, ctx->stream));
+            PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        }
+        for (int64_t r0 = 0; st.coef && r0 < n; r0 += step * kpad) {
+            const int64_t nr = std::min(step * kpad, n - r0);
+            for (int64_t r = 0; r < nr; ++r) pin[r] = (T)st.coef[row0 + r0 + r];
+            PMF_HIP_CHECK(hipMemcpyAsync(d_coef + r0, pin, (size_t)nr * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+            PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    if (st.cosine) {
+        PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
+        launch_inv_norm<T>(ctx, d_rows, n, d_coef);
+    }
+    PMF_HIP_CHECK(hipGetLastError());
+    round->fa = d_rows;
+    round->ca = (st.cosine || st.coef_table || st.coef) ? d_coef : nullptr;
+    round->ex_ptr = st.d_ex_ptr ? st.d_ex_ptr + row0 : nullptr;
+    return PMF_OK;
+}
+
+static int topk_round_source(pmf_ctx *ctx, const TopkSource &src, int64_t row0, int64_t n, TopkSource *round) {
+    *round = src;
+    if (!src.staged) return PMF_OK;
+    return pmf_with_dtype(ctx, [&](auto t) { return query_stage_rows<decltype(t)>(ctx, *src.staged, row0, n, round); });
+}
+
+static int topk_round_ids(pmf_ctx *ctx, const TopkSource &src, int64_t row0, int n, int32_t *d_ids) {
+    if (src.ids) {
+        PMF_HIP_CHECK(hipMemcpyAsync(d_ids, src.ids + row0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        hipLaunchKernelGGL(query_iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_ids, n);
+    }
+    return PMF_OK;
+}
+
+// a call's source, and what it points into
+struct QueryCall {
+    int mode = 0;                      // the kernels' mode: `score`, with PMF_PREDICT_SCALE for cosine
+    QueryStage stage;
+    TopkSource src;
+    std::vector<int64_t> ex_ptr;       // the exclusion lists, each sorted and without repeats
+    std::vector<int32_t> ex_ids;
+};
+
+// The checks the two query calls share, and the host side of their source.  Nothing is written anywhere else.
+static int query_check(const char *fn, pmf_ctx *ctx, int cand_side, int64_t n_query, int query_side, const int32_t *query_ids,
+                       const double *query_factor, const double *query_coef, int score, const int64_t *ex_ptr,
+                       const int32_t *ex_ids, QueryCall *qc) {
+    PMF_REQUIRE(cand_side == PMF_SIDE_USER || cand_side == PMF_SIDE_ITEM, PMF_EINVAL, "%s: bad cand_side %d", fn, cand_side);
+    PMF_REQUIRE(!(query_ids && query_factor), PMF_EINVAL, "%s: both query_ids and query_factor given; exactly one names the query rows", fn);
+    PMF_REQUIRE(query_ids || query_factor, PMF_EINVAL, "%s: neither query_ids nor query_factor given; exactly one names the query rows", fn);
+    PMF_REQUIRE(score == 0 || score == PMF_PREDICT_BIAS || score == PMF_PREDICT_SCALE || score == PMF_SCORE_COSINE, PMF_EINVAL,
+                "%s: score must be 0, PMF_PREDICT_BIAS, PMF_PREDICT_SCALE or PMF_SCORE_COSINE (got %d)", fn, score);
+    const bool model_coef = score == PMF_PREDICT_BIAS || score == PMF_PREDICT_SCALE;
+    const int carr = score == PMF_PREDICT_SCALE ? PMF_ARR_SCALE : PMF_ARR_BIAS;
+    const int64_t C = ctx->rows[cand_side];
+    int rc;
+    if (query_ids) {
+        PMF_REQUIRE(query_side == PMF_SIDE_USER || query_side == PMF_SIDE_ITEM, PMF_EINVAL, "%s: bad query_side %d", fn, query_side);
+        PMF_REQUIRE(query_side != cand_side || !model_coef, PMF_EINVAL,
+                    "%s: query_side == cand_side needs score 0 or PMF_SCORE_COSINE: a bias or scale of two rows of one side is no model score (got %d)",
+                    fn, score);
+        if ((rc = pmf_check_ids(query_ids, n_query, ctx->rows[query_side], fn, "query id"))) return rc;
+        if ((rc = pmf_require_array(ctx, query_side, PMF_ARR_FACTOR, fn))) return rc;
+        if (model_coef && (rc = pmf_require_array(ctx, query_side, carr, fn))) return rc;
+    } else {
+        PMF_REQUIRE(!model_coef || query_coef, PMF_EINVAL, "%s: null query_coef: the caller's rows need their bias / scale under score %d", fn,
+                    score);
+    }
+    if ((rc = pmf_require_array(ctx, cand_side, PMF_ARR_FACTOR, fn))) return rc;
+    if (model_coef && (rc = pmf_require_array(ctx, cand_side, carr, fn))) return rc;
+    if (ex_ptr) {
+        PMF_REQUIRE(ex_ptr[0] == 0, PMF_EINVAL, "%s: ex_ptr[0] = %lld, not 0", fn, (long long)ex_ptr[0]);
+        for (int64_t n = 0; n < n_query; ++n)
+            PMF_REQUIRE(ex_ptr[n + 1] >= ex_ptr[n], PMF_EINVAL, "%s: ex_ptr decreases at row %lld", fn, (long long)n);
+        PMF_REQUIRE(ex_ptr[n_query] == 0 || ex_ids, PMF_EINVAL, "%s: null ex_ids", fn);
+        if ((rc = pmf_check_ids(ex_ids, ex_ptr[n_query], C, fn, "excluded id"))) return rc;
+        // the fused scan's cursor and the counts of the ranking need ascending distinct ids
+        qc->ex_ptr.assign((size_t)n_query + 1, 0);
+        qc->ex_ids.reserve((size_t)ex_ptr[n_query]);
+        for (int64_t n = 0; n < n_query; ++n) {
+            const size_t first = qc->ex_ids.size();
+            qc->ex_ids.insert(qc->ex_ids.end(), ex_ids + ex_ptr[n], ex_ids + ex_ptr[n + 1]);
+            std::sort(qc->ex_ids.begin() + first, qc->ex_ids.end());
+            qc->ex_ids.erase(std::unique(qc->ex_ids.begin() + first, qc->ex_ids.end()), qc->ex_ids.end());
+            qc->ex_ptr[(size_t)n + 1] = (int64_t)qc->ex_ids.size();
+        }
+    }
+    qc->mode = score == PMF_SCORE_COSINE ? PMF_PREDICT_SCALE : score;
+    qc->stage.cosine = score == PMF_SCORE_COSINE;
+    if (query_ids) {
+        qc->stage.ids = query_ids;
+        qc->stage.table = ctx->arr[query_side][PMF_ARR_FACTOR].as();
+        qc->stage.coef_table = model_coef ? ctx->arr[query_side][carr].as() : nullptr;
+    } else {
+        qc->stage.factor = query_factor;
+        qc->stage.coef = model_coef ? query_coef : nullptr;
+    }
+    qc->src.fb = ctx->arr[cand_side][PMF_ARR_FACTOR].as();
+    qc->src.cb = model_coef ? ctx->arr[cand_side][carr].as() : nullptr;
+    qc->src.n_cand = C;
+    qc->src.staged = &qc->stage;
+    return PMF_OK;
+}
+
+// The device side of a call's source, once per call into ctx->d_query_call: the exclusion CSR, and for cosine the
+// candidates' inverse norms from cand_side's FACTOR as it is now.
+template <typename T>
+static int query_begin(pmf_ctx *ctx, QueryCall *qc) {
+    const size_t ptr_bytes = qc->ex_ptr.size() * sizeof(int64_t);
+    // (16-byte multiples; the id part is never empty when there are lists, so that its pointer lies inside the buffer)
+    const size_t ptr_pad = (ptr_bytes + 15) / 16 * 16, ids_pad = ptr_bytes ? (qc->ex_ids.size() * sizeof(int32_t) + 16) / 16 * 16 : 0;
+    const size_t norm_bytes = qc->stage.cosine ? (size_t)qc->src.n_cand * sizeof(T) : 0;
+    if (ptr_pad + ids_pad + norm_bytes == 0) return PMF_OK;
+    int rc;
+    if ((rc = ctx->d_query_call.reserve(ctx, ptr_pad + ids_pad + norm_bytes, {ctx->stream}))) return rc;
+    char *base = ctx->d_query_call.as<char>();
+    if (!qc->ex_ptr.empty()) {
+        PMF_HIP_CHECK(hipMemcpyAsync(base, qc->ex_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (!qc->ex_ids.empty())
+            PMF_HIP_CHECK(hipMemcpyAsync(base + ptr_pad, qc->ex_ids.data(), qc->ex_ids.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                                         ctx->stream));
+        qc->stage.d_ex_ptr = (const int64_t *)base;
+        qc->src.ex_ids = (const int32_t *)(base + ptr_pad);
+    }
+    if (qc->stage.cosine) {
+        T *inv = (T *)(base + ptr_pad + ids_pad);
+        PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
+        launch_inv_norm<T>(ctx, static_cast<const T *>(qc->src.fb), qc->src.n_cand, inv);
+        qc->src.cb = inv;
+    }
+    PMF_HIP_CHECK(hipGetLastError());
+    return PMF_OK;
+}
+
+extern "C" int pmf_topk_query(pmf_ctx *ctx, int cand_side, int64_t n_query, int query_side, const int32_t *query_ids,
+                              const double *query_factor, const double *query_coef, int score, const int64_t *ex_ptr,
+                              const int32_t *ex_ids, int k, int32_t *out_ids, double *out_scores) {
+    const char *fn = "pmf_topk_query";
+    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "%s: null context", fn);
+    PMF_REQUIRE(n_query >= 0, PMF_EINVAL, "%s: negative n_query", fn);
+    if (n_query == 0) return PMF_OK;
+    return pmf_no_throw(fn, [&] {
+        QueryCall qc;
+        PMF_REQUIRE(out_ids && out_scores, PMF_EINVAL, "%s: null out_ids or out_scores", fn);
+        if (int rc = query_check(fn, ctx, cand_side, n_query, query_side, query_ids, query_factor, query_coef, score, ex_ptr, ex_ids, &qc))
+            return rc;
+        PMF_REQUIRE(k >= 1 && k <= 1024 && k <= qc.src.n_cand, PMF_ERANGE, "%s: k=%d outside [1, min(1024, rows of cand_side)]", fn, k);
+        // (every refusal comes before the first write)
+        PMF_HIP_CHECK(hipSetDevice(ctx->device));
+        return pmf_with_dtype(ctx, [&](auto t) {
+            if (int rc = query_begin<decltype(t)>(ctx, &qc)) return rc;
+            return run_topk<decltype(t)>(ctx, qc.src, n_query, k, qc.mode, out_ids, out_scores);
+        });
+    });
+}
+
+extern "C" int pmf_rank_query(pmf_ctx *ctx, int cand_side, int64_t n_query, int query_side, const int32_t *query_ids,
+                              const double *query_factor, const double *query_coef, int score, const int64_t *ex_ptr,
+                              const int32_t *ex_ids, const int64_t *tgt_ptr, const int32_t *tgt_ids, int64_t *out_rank,
+                              int64_t *out_candidates) {
+    const char *fn = "pmf_rank_query";
+    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "%s: null context", fn);
+    PMF_REQUIRE(n_query >= 0, PMF_EINVAL, "%s: negative n_query", fn);
+    if (n_query == 0) return PMF_OK;
+    return pmf_no_throw(fn, [&] {
+        QueryCall qc;
+        PMF_REQUIRE(tgt_ptr, PMF_EINVAL, "%s: null tgt_ptr", fn);
+        PMF_REQUIRE(tgt_ptr[0] == 0, PMF_EINVAL, "%s: tgt_ptr[0] = %lld, not 0", fn, (long long)tgt_ptr[0]);
+        for (int64_t n = 0; n < n_query; ++n)
+            PMF_REQUIRE(tgt_ptr[n + 1] >= tgt_ptr[n], PMF_EINVAL, "%s: tgt_ptr decreases at row %lld", fn, (long long)n);
+        PMF_REQUIRE(tgt_ptr[n_query] == 0 || (tgt_ids && out_rank), PMF_EINVAL, "%s: null tgt_ids or out_rank", fn);
+        if (int rc = query_check(fn, ctx, cand_side, n_query, query_side, query_ids, query_factor, query_coef, score, ex_ptr, ex_ids, &qc))
+            return rc;
+        PMF_REQUIRE(qc.src.n_cand <= (int64_t)INT32_MAX - 64, PMF_ERANGE, "%s: %lld candidates; the kernels count them in 32-bit integers", fn,
+                    (long long)qc.src.n_cand);
+        if (int rc = pmf_check_ids(tgt_ids, tgt_ptr[n_query], qc.src.n_cand, fn, "target id")) return rc;
+        PMF_HIP_CHECK(hipSetDevice(ctx->device));
+        if (int rc = pmf_with_dtype(ctx, [&](auto t) { return query_begin<decltype(t)>(ctx, &qc); })) return rc;
+        return run_rank(ctx, qc.src, n_query, tgt_ptr, tgt_ids, qc.mode, out_rank, out_candidates);
     });
 }

@@ -25,6 +25,7 @@ USER, ITEM = 0, 1
 (ARR_FACTOR, ARR_SHAPE, ARR_RATE, ARR_PRIOR_RATE, ARR_HYPER_RATE, ARR_COV, ARR_BIAS, ARR_SCALE, ARR_SCALE_SHAPE,
  ARR_SCALE_RATE) = range(10)
 PREDICT_BIAS, PREDICT_SCALE = 1, 2
+SCORE_COSINE = 4          # `score` of topk_query / rank_query only
 KERNEL_NAMES = ("gamma_sweep", "gamma_final", "gauss_accum", "gauss_solve", "gauss_bias",
                 "eval", "predict", "topk", "gauss_combine", "gauss_sgd", "comm_allreduce", "comm_wait", "predict_var")
 UNIQUE_ID_BYTES = 128
@@ -108,6 +109,9 @@ SIGNATURES = {
     "pmf_topk_items": (C.c_int, [_p, C.c_int64, _i32p, C.c_int, C.c_int, _i32p, _f64p]),
     "pmf_topk_items_excluding": (C.c_int, [_p, C.c_int64, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _f64p]),
     "pmf_rank_items": (C.c_int, [_p, C.c_int64, _i32p, _i64p, _i32p, C.c_int, C.c_int, _i64p, _i64p]),
+    "pmf_topk_query": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, _i32p, _f64p, _f64p, C.c_int, _i64p, _i32p, C.c_int, _i32p, _f64p]),
+    "pmf_rank_query": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, _i32p, _f64p, _f64p, C.c_int, _i64p, _i32p, _i64p, _i32p, _i64p,
+                                 _i64p]),
     "pmf_prof_enable": (C.c_int, [_p, C.c_int]),
     "pmf_prof_reset": (C.c_int, [_p]),
     "pmf_prof_get": (C.c_int, [_p, C.c_int, _f64p, _i64p]),

@@ -527,6 +527,86 @@ class Context:
         cand[order] = np.repeat(c, np.diff(row_ptr))
         return ranks, cand
 
+    # ---- any query rows against one side --------------------------------
+    def _query_args(self, cand_side, ids, query_side, factor, coef, exclude):
+        """The arguments `pmf_topk_query` and `pmf_rank_query` share (the arrays are returned too: ctypes keeps no
+        reference to them)."""
+        if (ids is None) == (factor is None):
+            raise ValueError("exactly one of `ids` (rows of the context) and `factor` (the caller's rows) names the query rows")
+        keep = []
+        if ids is not None:
+            q = as_i32(np.asarray(ids).reshape(-1), "ids")
+            n, side = len(q), (1 - cand_side) if query_side is None else int(query_side)
+            q_ids, q_factor, q_coef = ptr(q, C.c_int32), None, None
+            keep.append(q)
+        else:
+            f = as_f64(factor)
+            if f.ndim != 2 or f.shape[1] != self.K:
+                raise ValueError(f"factor must be [n, {self.K}], got {f.shape}")
+            n, side, q_ids, q_factor, q_coef = len(f), 0, None, ptr(f, C.c_double), None
+            keep.append(f)
+            if coef is not None:
+                c = as_f64(np.asarray(coef).reshape(-1))
+                if len(c) != n:
+                    raise ValueError("coef must hold one value per row of factor")
+                q_coef = ptr(c, C.c_double)
+                keep.append(c)
+        ex_ptr = ex_ids = None
+        if exclude is not None:
+            ep = np.ascontiguousarray(np.asarray(exclude[0], dtype=np.int64).reshape(-1))
+            ei = as_i32(np.asarray(exclude[1]).reshape(-1), "exclude ids")
+            if len(ep) != n + 1 or (n and ep[-1] != len(ei)):
+                raise ValueError("exclude must be (row_ptr, ids): one offset per query row and one more, ending at len(ids)")
+            ex_ptr, ex_ids = ptr(ep, C.c_int64), ptr(ei, C.c_int32)
+            keep += [ep, ei]
+        return n, (int(cand_side), n, side, q_ids, q_factor, q_coef), (ex_ptr, ex_ids), keep
+
+    def topk_query(self, cand_side, k, *, ids=None, query_side=None, factor=None, coef=None, score=0, exclude=None):
+        """The k best rows of `cand_side` for every query row (`pmf_topk_query`): (ids int32 [n, k], scores float64 [n, k]),
+        best first, -1 / 0.0 where fewer than k rank.  The query rows are rows `ids` of `query_side` (default: the side
+        opposite to `cand_side`) or the caller's `factor` [n, K] with `coef` [n] as their bias / scale.  `score`: 0,
+        PREDICT_BIAS, PREDICT_SCALE or SCORE_COSINE.  `exclude` = (row_ptr, ids): candidate ids that are no candidates of
+        query ROW q, in any order."""
+        n, query, ex, keep = self._query_args(cand_side, ids, query_side, factor, coef, exclude)
+        out_ids = np.empty((n, k), dtype=np.int32)
+        out_scores = np.empty((n, k), dtype=np.float64)
+        check(self._lib.pmf_topk_query(self._h, *query, int(score), *ex, int(k), ptr(out_ids, C.c_int32),
+                                       ptr(out_scores, C.c_double)), "pmf_topk_query")
+        return out_ids, out_scores
+
+    def rank_query(self, cand_side, targets, *, ids=None, query_side=None, factor=None, coef=None, score=0, exclude=None):
+        """`pmf_rank_query`: `targets` = (row_ptr, ids), the rows of `cand_side` whose ranks query row q asks for.  Returns
+        (ranks int64 [len(target ids)], candidates int64 [n]); the other arguments are those of `topk_query`."""
+        n, query, ex, keep = self._query_args(cand_side, ids, query_side, factor, coef, exclude)
+        tp = np.ascontiguousarray(np.asarray(targets[0], dtype=np.int64).reshape(-1))
+        ti = as_i32(np.asarray(targets[1]).reshape(-1), "target ids")
+        if len(tp) != n + 1 or (n and tp[-1] != len(ti)):
+            raise ValueError("targets must be (row_ptr, ids): one offset per query row and one more, ending at len(ids)")
+        ranks = np.empty(len(ti), dtype=np.int64)
+        cand = np.empty(n, dtype=np.int64)
+        check(self._lib.pmf_rank_query(self._h, *query, int(score), *ex, ptr(tp, C.c_int64), ptr(ti, C.c_int32),
+                                       ptr(ranks, C.c_int64), ptr(cand, C.c_int64)), "pmf_rank_query")
+        return ranks, cand
+
+    def rank_query_pairs(self, cand_side, rows, target_ids, *, ids=None, query_side=None, factor=None, coef=None, score=0,
+                         exclude=None):
+        """`rank_query` on flat pairs, in the manner of `rank_items`: pair p asks for the rank of candidate target_ids[p]
+        for query row rows[p] (an index into `ids` / `factor`).  Returns (ranks, candidates), int64, aligned with the pairs."""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        tgt = np.asarray(target_ids).reshape(-1)
+        if len(rows) != len(tgt):
+            raise ValueError("rows and target_ids must have the same length")
+        n = len(ids) if ids is not None else len(factor)
+        if len(rows) and (rows.min() < 0 or rows.max() >= n):
+            raise ValueError("rows must index the query rows")
+        order = np.argsort(rows, kind="stable")
+        row_ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int64)
+        r, c = self.rank_query(cand_side, (row_ptr, tgt[order]), ids=ids, query_side=query_side, factor=factor, coef=coef,
+                               score=score, exclude=exclude)
+        ranks = np.empty(len(rows), dtype=np.int64)
+        ranks[order] = r
+        return ranks, c[rows]
+
     # ---- profiling ------------------------------------------------------
     def prof_enable(self, on=True):
         check(self._lib.pmf_prof_enable(self._h, int(bool(on))), "pmf_prof_enable")

@@ -350,6 +350,79 @@ class DeviceModel:
         ranks, cand = self.heldout_ranks(df, exclude_train=exclude_train)
         return ranking_metrics(df["u"].to_numpy(dtype=int), ranks, cand, ks=ks)
 
+    # ---- any query rows: similar rows, the audience of an item, folded-in rows (`Context.topk_query` / `rank_query`) ----
+    def _similar(self, side, ids, k, metric):
+        if metric not in ("cosine", "dot"):
+            raise ValueError(f"metric must be 'cosine' or 'dot', got {metric!r}")
+        q = np.asarray(ids, dtype=int).reshape(-1)
+        return self._need_ctx().topk_query(side, int(k), ids=q, query_side=side,
+                                           score=pmf_hip.SCORE_COSINE if metric == "cosine" else 0,
+                                           exclude=(np.arange(len(q) + 1), q))       # every row leaves itself out
+
+    def similar_items(self, item_ids, k=10, metric="cosine"):
+        """Extension (no reference counterpart as an operation): the k nearest items of every item in factor space, by
+        cosine or dot product of the FACTOR rows, the item itself left out; ties to the lower id.  Returns
+        (items [n, k] int32, scores [n, k] float64).  Needs the factors only: available after a sharded fit."""
+        return self._similar(ITEM, item_ids, k, metric)
+
+    def similar_users(self, user_ids, k=10, metric="cosine"):
+        """The same for users against users."""
+        return self._similar(USER, user_ids, k, metric)
+
+    def top_k_users(self, item_ids, k=10):
+        """The audience of an item: the k users with the highest `predict` score for it, ties to the lower user id.
+        Returns (users [n, k] int32, scores [n, k] float64)."""
+        return self._need_ctx().topk_query(USER, int(k), ids=np.asarray(item_ids, dtype=int).reshape(-1), query_side=ITEM,
+                                           score=int(self._uses_bias))
+
+    def _fold_query(self, fold, exclude_seen):
+        """(candidate side, keyword arguments of `topk_query` / `rank_query`) for the rows of a fold-in record: the
+        caller's rows (vector mode) under `predict`'s score, against the side opposite to the fold's."""
+        score = int(self._uses_bias)
+        if score == pmf_hip.PREDICT_SCALE:
+            raise NotImplementedError("folded-in rows carry no scale factor: the extended Poisson model has no fold-in")
+        kw = {"factor": fold.mean if hasattr(fold, "mean") else fold.E, "score": score}
+        if score == pmf_hip.PREDICT_BIAS:
+            kw["coef"] = fold.bias
+        if exclude_seen:
+            if fold.seen_ptr is None:
+                raise ValueError("the fold-in record does not carry its rows' own ratings (seen_ptr / seen_ids)")
+            kw["exclude"] = (fold.seen_ptr, fold.seen_ids)
+        return (ITEM if fold.side == USER else USER), kw
+
+    def top_k_for(self, fold, k=10, exclude_seen=True):
+        """The k best candidates of the opposite side for every row of a fold-in record (`fold_in_users`: items;
+        `fold_in_items`: users) under `predict`'s score without `global_mean` -- what `fold.predict` gives.
+        `exclude_seen`: a row's own ratings are no candidates.  Returns (ids [n, k] int32, scores [n, k] float64)."""
+        cand_side, kw = self._fold_query(fold, exclude_seen)
+        return self._need_ctx().topk_query(cand_side, int(k), **kw)
+
+    def heldout_ranks_for(self, fold, df, exclude_seen=True):
+        """Where every row of the frame lands in the ranking of its folded-in row (matched by the fold's labels, column
+        `u` for a fold of users): (ranks, candidates), int64, aligned with the frame.  Rows whose label is not in the
+        fold, or whose id on the fitted side the fit has not seen, get -1 in both."""
+        cand_side, kw = self._fold_query(fold, exclude_seen)
+        new_col, old_col = ("u", "i") if fold.side == USER else ("i", "u")
+        label, other = df[new_col].to_numpy(), df[old_col].to_numpy(dtype=int)
+        n_other = self.n_items if fold.side == USER else self.n_users
+        row = np.searchsorted(fold.ids, label)
+        ok = (row < len(fold.ids)) & (other >= 0) & (other < n_other)
+        ok[ok] = fold.ids[row[ok]] == label[ok]
+        ranks = np.full(len(label), -1, dtype=np.int64)
+        cand = np.full(len(label), -1, dtype=np.int64)
+        if ok.any():
+            ranks[ok], cand[ok] = self._need_ctx().rank_query_pairs(cand_side, row[ok], other[ok], **kw)
+        return ranks, cand
+
+    def evaluate_ranking_fold_in(self, support_df, heldout_df, ks=(10,), n_iter=10):
+        """The cold-start number: fold in the users of `support_df`, rank their `heldout_df` items with the support items
+        left out, and return `ranking_metrics` of those ranks.  Held-out rows with an unknown item, or a user absent from
+        the support, count as skipped, as `evaluate_ranking` counts them."""
+        from src.evaluation.ranking import ranking_metrics
+        fold = self.fold_in_users(support_df, n_iter=n_iter)
+        ranks, cand = self.heldout_ranks_for(fold, heldout_df, exclude_seen=True)
+        return ranking_metrics(heldout_df["u"].to_numpy(), ranks, cand, ks=ks)
+
     def close(self):
         """Release the device context(s) (predict is unavailable afterwards)."""
         for name in ("_ctx", "_shard_ctx"):

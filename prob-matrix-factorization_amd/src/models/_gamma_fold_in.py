@@ -18,6 +18,9 @@ class GammaFoldIn:
     rate: np.ndarray                  # (n, K)
     prior_rate: Optional[np.ndarray]  # (n,) E_xi / E_eta of the rows (HPF), None for Poisson MF
     E_other: np.ndarray               # the fitted opposite side's expected factors
+    side: int = USER                          # the side the rows belong to
+    seen_ptr: Optional[np.ndarray] = None     # the batch `fold_in_batch` built: row r's own ratings are of the ids
+    seen_ids: Optional[np.ndarray] = None     # seen_ids[seen_ptr[r]:seen_ptr[r + 1]] on the opposite side
 
     def predict(self, rows, other_ids):
         """E[rows] . E_other[other_ids], on the host."""
@@ -31,4 +34,4 @@ def gamma_fold_in(model, side, df, n_iter, prior):
     ctx = model._need_ctx()
     ids, row_ptr, other, x = fold_in_batch(df, side, model.n_items if side == USER else model.n_users)
     E, shape, rate, prior_rate, _ = ctx.gamma_fold_in(side, row_ptr, other, x, *prior, n_iter=n_iter)
-    return GammaFoldIn(ids, E, shape, rate, prior_rate, model.E_beta if side == USER else model.E_theta)
+    return GammaFoldIn(ids, E, shape, rate, prior_rate, model.E_beta if side == USER else model.E_theta, side, row_ptr, other)

@@ -53,6 +53,9 @@ class FoldIn:
     bias: np.ndarray           # (n,), zeros for the bias-free model
     m_other: np.ndarray        # the fitted opposite side's means (and biases, or None)
     b_other: Optional[np.ndarray]
+    side: int = USER                          # the side the rows belong to
+    seen_ptr: Optional[np.ndarray] = None     # the batch `fold_in_batch` built: row r's own ratings are of the ids
+    seen_ids: Optional[np.ndarray] = None     # seen_ids[seen_ptr[r]:seen_ptr[r + 1]] on the opposite side
 
     def predict(self, rows, other_ids, global_mean=0.0):
         """mean[rows] . m_other[other_ids] + bias[rows] + b_other[other_ids] + global_mean, on the host."""
@@ -319,7 +322,7 @@ class GaussianHost(DeviceModel):
                                             cfg.eta_bias2 if self._uses_bias else 1.0, n_iter, want_cov=return_cov)
         m_other = self.m_beta if side == USER else self.m_theta
         b_other = (self.m_item_bias if side == USER else self.m_user_bias) if self._uses_bias else None
-        return FoldIn(ids, mean, cov, bias, m_other, b_other)
+        return FoldIn(ids, mean, cov, bias, m_other, b_other, side, row_ptr, other)
 
     def fold_in_users(self, df, n_iter=10, return_cov=False):
         """Posterior of users the fit has not seen, from their ratings of fitted items: `df` has columns u, i, rating
