@@ -308,37 +308,47 @@ static int fill_params(pmf_ctx *ctx, int use_bias, double offset, PredictParams<
     return PMF_OK;
 }
 
-template <typename T>
-static int run_predict(pmf_ctx *ctx, int64_t n, const int32_t *u, const int32_t *i, int use_bias,
-                       double offset, double *out) {
-    PredictParams<T> p;
-    int rc = fill_params(ctx, use_bias, offset, p, "pmf_predict");
-    if (rc) return rc;
+// The pairs (u, i) in staging rounds: ids up, launch(d_u, d_i, cnt, d_out) timed as `kernel`, cnt values down.
+template <typename Launch>
+static int pair_rounds(pmf_ctx *ctx, int kernel, int64_t n, const int32_t *u, const int32_t *i, double *out, Launch &&launch) {
     const int64_t step = 4 << 20;  // pairs per staging round
-    const int64_t m = std::min(n, step);
-    if ((rc = pmf_ensure_scratch(ctx, (size_t)m * 16))) return rc;
-    int32_t *d_u = ctx->d_scratch.as<int32_t>();
-    int32_t *d_i = d_u + m;
-    double *d_out = (double *)(d_i + m);
+    const size_t m = (size_t)std::min(n, step);
+    PmfLayout lay;
+    const auto u_at = lay.add<int32_t>(m), i_at = lay.add<int32_t>(m);
+    const auto out_at = lay.add<double>(m);
+    if (int rc = pmf_ensure_scratch(ctx, lay.bytes())) return rc;
+    void *base = ctx->d_scratch.as();
+    int32_t *d_u = u_at.at(base), *d_i = i_at.at(base);
+    double *d_out = out_at.at(base);
     for (int64_t at = 0; at < n; at += step) {
         const int64_t cnt = std::min(step, n - at);
         PMF_HIP_CHECK(hipMemcpyAsync(d_u, u + at, (size_t)cnt * 4, hipMemcpyHostToDevice, ctx->stream));
         PMF_HIP_CHECK(hipMemcpyAsync(d_i, i + at, (size_t)cnt * 4, hipMemcpyHostToDevice, ctx->stream));
-        p.u = d_u;
-        p.i = d_i;
-        p.n = cnt;
         {
-            PmfProfScope prof(ctx, PMF_KERNEL_PREDICT);
-            pmf_with_pow2<4>(pmf_lanes_per_row(ctx->kpad), [&](auto L) {
-                const int grid = (int)std::min<int64_t>((p.n + 256 / L - 1) / (256 / L), 8192);
-                hipLaunchKernelGGL((predict_kernel<T, L>), dim3(grid), dim3(256), 0, ctx->stream, p, d_out);
-            });
+            PmfProfScope prof(ctx, kernel);
+            launch(d_u, d_i, cnt, d_out);
         }
         PMF_HIP_CHECK(hipGetLastError());
         PMF_HIP_CHECK(hipMemcpyAsync(out + at, d_out, (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
         PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     return PMF_OK;
+}
+
+template <typename T>
+static int run_predict(pmf_ctx *ctx, int64_t n, const int32_t *u, const int32_t *i, int use_bias,
+                       double offset, double *out) {
+    PredictParams<T> p;
+    if (int rc = fill_params(ctx, use_bias, offset, p, "pmf_predict")) return rc;
+    return pair_rounds(ctx, PMF_KERNEL_PREDICT, n, u, i, out, [&](const int32_t *d_u, const int32_t *d_i, int64_t cnt, double *d_out) {
+        p.u = d_u;
+        p.i = d_i;
+        p.n = cnt;
+        pmf_with_pow2<4>(pmf_lanes_per_row(ctx->kpad), [&](auto L) {
+            const int grid = (int)std::min<int64_t>((p.n + 256 / L - 1) / (256 / L), 8192);
+            hipLaunchKernelGGL((predict_kernel<T, L>), dim3(grid), dim3(256), 0, ctx->stream, p, d_out);
+        });
+    });
 }
 
 extern "C" int pmf_predict(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, const int32_t *item_ids,
@@ -461,33 +471,16 @@ static size_t var_lds_bytes(const pmf_ctx *ctx, int lanes) {
 template <typename T>
 static int run_predict_var(pmf_ctx *ctx, int64_t n, const int32_t *u, const int32_t *i, double *out) {
     VarParams<T> q;
-    int rc = fill_var_params(ctx, 0, 0.0, q, "pmf_predict_var");
-    if (rc) return rc;
-    const int64_t step = 4 << 20;  // pairs per staging round
-    const int64_t m = std::min(n, step);
-    if ((rc = pmf_ensure_scratch(ctx, (size_t)m * 16))) return rc;
-    int32_t *d_u = ctx->d_scratch.as<int32_t>();
-    int32_t *d_i = d_u + m;
-    double *d_out = (double *)(d_i + m);
-    for (int64_t at = 0; at < n; at += step) {
-        const int64_t cnt = std::min(step, n - at);
-        PMF_HIP_CHECK(hipMemcpyAsync(d_u, u + at, (size_t)cnt * 4, hipMemcpyHostToDevice, ctx->stream));
-        PMF_HIP_CHECK(hipMemcpyAsync(d_i, i + at, (size_t)cnt * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = fill_var_params(ctx, 0, 0.0, q, "pmf_predict_var")) return rc;
+    return pair_rounds(ctx, PMF_KERNEL_PREDICT_VAR, n, u, i, out, [&](const int32_t *d_u, const int32_t *d_i, int64_t cnt, double *d_out) {
         q.p.u = d_u;
         q.p.i = d_i;
         q.p.n = cnt;
-        {
-            PmfProfScope prof(ctx, PMF_KERNEL_PREDICT_VAR);
-            pmf_with_pow2<4>(pmf_var_lanes(ctx->cov_stride), [&](auto L) {
-                const int grid = (int)std::min<int64_t>((cnt + 256 / L - 1) / (256 / L), 8192);
-                hipLaunchKernelGGL((predict_var_kernel<T, L>), dim3(grid), dim3(256), var_lds_bytes<T>(ctx, L), ctx->stream, q, d_out);
-            });
-        }
-        PMF_HIP_CHECK(hipGetLastError());
-        PMF_HIP_CHECK(hipMemcpyAsync(out + at, d_out, (size_t)cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
-        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return PMF_OK;
+        pmf_with_pow2<4>(pmf_var_lanes(ctx->cov_stride), [&](auto L) {
+            const int grid = (int)std::min<int64_t>((cnt + 256 / L - 1) / (256 / L), 8192);
+            hipLaunchKernelGGL((predict_var_kernel<T, L>), dim3(grid), dim3(256), var_lds_bytes<T>(ctx, L), ctx->stream, q, d_out);
+        });
+    });
 }
 
 extern "C" int pmf_predict_var(pmf_ctx *ctx, int64_t n, const int32_t *user_ids, const int32_t *item_ids, double *out_var) {

@@ -729,23 +729,16 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
     const int64_t by_bytes = std::max<int64_t>(1, kGammaFoldRowBytes / ((int64_t)kpad * (int64_t)sizeof(T)));
     const int64_t max_rows = std::min(by_bytes, ctx->fold_in_rows > 0 ? ctx->fold_in_rows : (int64_t)INT32_MAX);
     const bool hier = a.pr.hierarchical != 0;
-    PmfBuf d_ptr, d_other, d_val, d_list, d_init, d_init_rate, d_factor, d_shape, d_rate, d_prior_rate, d_hyper_rate;
-    std::vector<int64_t> ptr;
+    PmfFoldStage<T> st;
+    PmfBuf d_list, d_init, d_init_rate, d_factor, d_shape, d_rate, d_prior_rate, d_hyper_rate;
     std::vector<int32_t> list;   // the short rows, then the long rows
-    std::vector<T> val, init, init_rate;
+    std::vector<T> init, init_rate;
     int rc;
-    for (int64_t r0 = 0, r1; r0 < a.n_rows; r0 = r1) {
-        int64_t nnz = 0;
-        for (r1 = r0; r1 < a.n_rows && r1 - r0 < max_rows; ++r1) {
-            const int64_t n = a.row_ptr[r1 + 1] - a.row_ptr[r1];
-            if (r1 > r0 && nnz + n > PMF_FOLD_IN_BLOCK_NNZ) break;
-            nnz += n;
-        }
-        const int64_t B = r1 - r0, at = a.row_ptr[r0];
-        ptr.resize((size_t)B + 1);
-        for (int64_t r = 0; r <= B; ++r) ptr[(size_t)r] = a.row_ptr[r0 + r] - at;
-        val.resize((size_t)nnz);
-        for (int64_t k = 0; k < nnz; ++k) val[(size_t)k] = (T)a.ratings[at + k];
+    for (int64_t r0 = 0; r0 < a.n_rows; r0 = st.r1) {
+        // (the previous block ended with a stream synchronise: nothing queued still reads the block's buffers)
+        if ((rc = st.stage(ctx, a.n_rows, a.row_ptr, a.ratings, r0, max_rows))) return rc;
+        const std::vector<int64_t> &ptr = st.ptr;
+        const int64_t B = st.r1 - r0;
         list.clear();
         for (int64_t r = 0; r < B; ++r)
             if (ptr[(size_t)r + 1] - ptr[(size_t)r] <= long_row) list.push_back((int32_t)r);
@@ -764,11 +757,7 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
             init_rate.resize((size_t)B);
             for (int64_t r = 0; r < B; ++r) init_rate[(size_t)r] = (T)a.init_prior_rate[r0 + r];
         }
-        // (the previous block ended with a stream synchronise: nothing queued still reads these buffers)
         const size_t row_bytes = (size_t)B * kpad * sizeof(T);
-        if ((rc = d_ptr.reserve(ctx, ptr.size() * sizeof(int64_t), {ctx->stream}))) return rc;
-        if ((rc = d_other.reserve(ctx, (size_t)nnz * sizeof(int32_t), {ctx->stream}))) return rc;
-        if ((rc = d_val.reserve(ctx, (size_t)nnz * sizeof(T), {ctx->stream}))) return rc;
         if ((rc = d_list.reserve(ctx, (size_t)B * sizeof(int32_t), {ctx->stream}))) return rc;
         if ((rc = d_factor.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
         if ((rc = d_shape.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
@@ -779,19 +768,15 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
             if ((rc = d_hyper_rate.reserve(ctx, (size_t)B * sizeof(T), {ctx->stream}))) return rc;
             if (a.init_prior_rate && (rc = d_init_rate.reserve(ctx, (size_t)B * sizeof(T), {ctx->stream}))) return rc;
         }
-        PMF_HIP_CHECK(hipMemcpy(d_ptr.as(), ptr.data(), ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        if ((rc = st.upload(a.other_ids))) return rc;
         PMF_HIP_CHECK(hipMemcpy(d_list.as(), list.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
-        if (nnz) {
-            PMF_HIP_CHECK(hipMemcpy(d_other.as(), a.other_ids + at, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-            PMF_HIP_CHECK(hipMemcpy(d_val.as(), val.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
-        }
         if (a.init_factor) PMF_HIP_CHECK(hipMemcpy(d_init.as(), init.data(), row_bytes, hipMemcpyHostToDevice));
         if (hier && a.init_prior_rate)
             PMF_HIP_CHECK(hipMemcpy(d_init_rate.as(), init_rate.data(), (size_t)B * sizeof(T), hipMemcpyHostToDevice));
         GammaFoldParams<T> p;
-        p.ptr = d_ptr.as<const int64_t>();
-        p.other = d_other.as<const int32_t>();
-        p.val = d_val.as<const T>();
+        p.ptr = st.d_ptr.template as<const int64_t>();
+        p.other = st.d_other.template as<const int32_t>();
+        p.val = st.d_val.template as<const T>();
         p.factor_other = ctx->arr[1 - side][PMF_ARR_FACTOR].as<const T>();
         p.init_factor = a.init_factor ? d_init.as<const T>() : nullptr;
         p.init_prior_rate = hier && a.init_prior_rate ? d_init_rate.as<const T>() : nullptr;
@@ -844,9 +829,8 @@ extern "C" int pmf_gamma_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
     PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_gamma_fold_in: negative row count");
     if (n_rows == 0) return PMF_OK;
     PMF_REQUIRE(row_ptr && out_factor, PMF_EINVAL, "pmf_gamma_fold_in: null argument");
-    PMF_REQUIRE(row_ptr[0] == 0, PMF_EINVAL, "pmf_gamma_fold_in: row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
-    for (int64_t r = 0; r < n_rows; ++r)
-        PMF_REQUIRE(row_ptr[r + 1] >= row_ptr[r], PMF_EINVAL, "pmf_gamma_fold_in: row_ptr decreases at row %lld", (long long)r);
+    int rc;
+    if ((rc = pmf_check_offsets("pmf_gamma_fold_in", "row_ptr", row_ptr, n_rows))) return rc;
     const int64_t nnz = row_ptr[n_rows];
     PMF_REQUIRE(nnz == 0 || (other_ids && ratings), PMF_EINVAL, "pmf_gamma_fold_in: null argument");
     PMF_REQUIRE(shape_prior > 0, PMF_EINVAL, "pmf_gamma_fold_in: shape_prior must be positive");
@@ -856,7 +840,6 @@ extern "C" int pmf_gamma_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
         PMF_REQUIRE(rate_prior > 0, PMF_EINVAL, "pmf_gamma_fold_in: rate_prior must be positive");
     PMF_REQUIRE(n_iter >= 1, PMF_EINVAL, "pmf_gamma_fold_in: n_iter = %d, must be at least 1", n_iter);
     const int other = 1 - side;
-    int rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gamma_fold_in"))) return rc;
     if ((rc = pmf_check_ids(other_ids, nnz, ctx->rows[other], "pmf_gamma_fold_in", "id"))) return rc;
     const GammaFoldBatch a = {n_rows, row_ptr, other_ids, ratings, {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior},
@@ -1137,20 +1120,17 @@ static int run_gamma_elbo_terms(pmf_ctx *ctx, int side, bool with_data, bool hie
     const int lpr = pmf_lanes_per_row(kpad);
     PmfTaskView tl;
     if (with_data) tl = pmf_task_view(ctx, side, ctx->index[side].gamma_tasks, false);
-    const auto aligned = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t out_bytes = aligned((size_t)rows * PMF_GAMMA_ELBO_TERMS * sizeof(double));
-    const size_t lf_bytes = aligned((size_t)tl.n_slots * sizeof(double));
-    const size_t pd_bytes = aligned((size_t)tl.n_slots * sizeof(T));
-    const size_t self_bytes = aligned((size_t)rows * 2 * kpad * sizeof(T));
-    const size_t other_bytes = with_data ? aligned((size_t)rows_o * 2 * kpad * sizeof(T)) : 0;
+    PmfLayout lay(256);
+    const auto out_at = lay.add<double>((size_t)rows * PMF_GAMMA_ELBO_TERMS);
+    const auto lf_at = lay.add<double>((size_t)tl.n_slots);
+    const auto pd_at = lay.add<T>((size_t)tl.n_slots);
+    const auto self_at = lay.add<T>((size_t)rows * 2 * kpad);
+    const auto other_at = lay.add<T>(with_data ? (size_t)rows_o * 2 * kpad : 0);
     int rc;
-    if ((rc = pmf_ensure_scratch(ctx, out_bytes + lf_bytes + pd_bytes + self_bytes + other_bytes))) return rc;
-    char *base = ctx->d_scratch.as<char>();
-    double *d_out = reinterpret_cast<double *>(base);
-    double *d_lf = reinterpret_cast<double *>(base + out_bytes);
-    T *d_pd = reinterpret_cast<T *>(base + out_bytes + lf_bytes);
-    T *d_self = reinterpret_cast<T *>(base + out_bytes + lf_bytes + pd_bytes);
-    T *d_other = reinterpret_cast<T *>(base + out_bytes + lf_bytes + pd_bytes + self_bytes);
+    if ((rc = pmf_ensure_scratch(ctx, lay.bytes()))) return rc;
+    void *base = ctx->d_scratch.as();
+    double *d_out = out_at.at(base), *d_lf = lf_at.at(base);
+    T *d_pd = pd_at.at(base), *d_self = self_at.at(base), *d_other = other_at.at(base);
 
     GammaElboDataParams<T> d;
     d.tasks = tl.d_tasks;
@@ -1650,15 +1630,18 @@ static int run_gamma_predictive(pmf_ctx *ctx, int64_t n, const int32_t *u, const
     const int kpad = ctx->kpad;
     const int64_t step = ctx->gamma_pred_pairs > 0 ? ctx->gamma_pred_pairs : kGammaPredPairs;
     const int64_t m = std::min(n, step);
-    const size_t part_bytes = (size_t)kGammaPredMaxGrid * PMF_GAMMA_PRED_TOTALS * sizeof(double);
+    const size_t n_part = (size_t)kGammaPredMaxGrid * PMF_GAMMA_PRED_TOTALS;
+    PmfLayout lay;
+    const auto part_at = lay.add<double>(n_part), x_at = lay.add<double>((size_t)m), mean_at = lay.add<double>((size_t)m);
+    const auto var_at = lay.add<double>((size_t)m), logp_at = lay.add<double>((size_t)m * PMF_GAMMA_PRED_KINDS);
+    const auto u_at = lay.add<int32_t>((size_t)m), i_at = lay.add<int32_t>((size_t)m);
     int rc;
-    if ((rc = pmf_ensure_scratch(ctx, part_bytes + (size_t)m * ((3 + PMF_GAMMA_PRED_KINDS) * sizeof(double) + 2 * sizeof(int32_t))))) return rc;
-    if ((rc = pmf_ensure_pinned(ctx, part_bytes))) return rc;
-    double *d_part = ctx->d_scratch.as<double>();
-    double *d_x = d_part + (size_t)kGammaPredMaxGrid * PMF_GAMMA_PRED_TOTALS;
-    double *d_mean = d_x + m, *d_var = d_mean + m, *d_logp = d_var + m;
-    int32_t *d_u = reinterpret_cast<int32_t *>(d_logp + (size_t)m * PMF_GAMMA_PRED_KINDS);
-    int32_t *d_i = d_u + m;
+    if ((rc = pmf_ensure_scratch(ctx, lay.bytes()))) return rc;
+    if ((rc = pmf_ensure_pinned(ctx, n_part * sizeof(double)))) return rc;
+    void *base = ctx->d_scratch.as();
+    double *d_part = part_at.at(base), *d_x = x_at.at(base), *d_mean = mean_at.at(base), *d_var = var_at.at(base);
+    double *d_logp = logp_at.at(base);
+    int32_t *d_u = u_at.at(base), *d_i = i_at.at(base);
     if (bound && (rc = gamma_exact_build_tables<T>(ctx))) return rc;
 
     GammaPredParams<T> p;

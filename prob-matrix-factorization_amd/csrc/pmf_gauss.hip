@@ -1919,48 +1919,31 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
     const int chunk = pmf_task_chunk(ctx, PMF_GAUSS_CHUNK);
     const int64_t max_units = std::max<int64_t>(1, kFoldInStatsBytes / ((int64_t)(width + 1) * (int64_t)sizeof(T)));
     const int64_t max_rows = ctx->fold_in_rows > 0 ? ctx->fold_in_rows : (int64_t)INT32_MAX;
-    PmfBuf d_tasks, d_split, d_ptr, d_other, d_val, d_s, d_w, d_b, d_partial;
-    std::vector<int64_t> ptr, task_off, split_off;
+    PmfFoldStage<T> st;
+    PmfBuf d_tasks, d_split, d_s, d_w, d_b, d_partial;
+    std::vector<int64_t> task_off, split_off;
     std::vector<PmfTask> tasks;
     std::vector<PmfSplitRow> split;
-    std::vector<T> val;
     int rc;
-    for (int64_t r0 = 0, r1; r0 < a.n_rows; r0 = r1) {
-        int64_t units = 0, nnz = 0;
-        bool has_empty = false;
-        for (r1 = r0; r1 < a.n_rows && r1 - r0 < max_rows; ++r1) {
-            const int64_t n = a.row_ptr[r1 + 1] - a.row_ptr[r1];
-            const int64_t u = 1 + (n > chunk ? (n + chunk - 1) / chunk : 0);
-            if (r1 > r0 && (units + u > max_units || nnz + n > PMF_FOLD_IN_BLOCK_NNZ)) break;
-            units += u;
-            nnz += n;
-            has_empty |= n == 0;
-        }
-        const int64_t B = r1 - r0, at = a.row_ptr[r0];
-        ptr.resize((size_t)B + 1);
-        for (int64_t r = 0; r <= B; ++r) ptr[(size_t)r] = a.row_ptr[r0 + r] - at;
-        val.resize((size_t)nnz);
-        for (int64_t k = 0; k < nnz; ++k) val[(size_t)k] = (T)a.ratings[at + k];
+    for (int64_t r0 = 0; r0 < a.n_rows; r0 = st.r1) {
+        int64_t units = 0;   // a row's statistics, and the partial slots of a row that is split
+        const auto fits = [&](int64_t n) { return (units += 1 + (n > chunk ? (n + chunk - 1) / chunk : 0)) <= max_units; };
+        // (the previous block ended with a stream synchronise: nothing queued still reads the block's buffers)
+        if ((rc = st.stage(ctx, a.n_rows, a.row_ptr, a.ratings, r0, max_rows, fits))) return rc;
+        const int64_t B = st.r1 - r0, nnz = st.nnz;
+        const bool has_empty = std::adjacent_find(st.ptr.begin(), st.ptr.end()) != st.ptr.end();
         tasks.clear();
         split.clear();
         int64_t n_slots = 0;
-        pmf_build_tasks(ptr, B, chunk, false, {0, B}, tasks, split, n_slots, task_off, split_off);
-        // (the previous block ended with a stream synchronise: nothing queued still reads these buffers)
+        pmf_build_tasks(st.ptr, B, chunk, false, {0, B}, tasks, split, n_slots, task_off, split_off);
         if ((rc = d_tasks.reserve(ctx, tasks.size() * sizeof(PmfTask), {ctx->stream}))) return rc;
         if ((rc = d_split.reserve(ctx, split.size() * sizeof(PmfSplitRow), {ctx->stream}))) return rc;
-        if ((rc = d_ptr.reserve(ctx, ptr.size() * sizeof(int64_t), {ctx->stream}))) return rc;
-        if ((rc = d_other.reserve(ctx, (size_t)nnz * sizeof(int32_t), {ctx->stream}))) return rc;
-        if ((rc = d_val.reserve(ctx, (size_t)nnz * sizeof(T), {ctx->stream}))) return rc;
         if ((rc = d_s.reserve(ctx, (size_t)B * cs * sizeof(T), {ctx->stream}))) return rc;
         if ((rc = d_w.reserve(ctx, (size_t)B * kpad * sizeof(T), {ctx->stream}))) return rc;
         if ((rc = d_b.reserve(ctx, (size_t)B * sizeof(T), {ctx->stream}))) return rc;
         if ((rc = d_partial.reserve(ctx, (size_t)n_slots * width * sizeof(T), {ctx->stream}))) return rc;
-        PMF_HIP_CHECK(hipMemcpy(d_ptr.as(), ptr.data(), ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        if (nnz) {
-            PMF_HIP_CHECK(hipMemcpy(d_tasks.as(), tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
-            PMF_HIP_CHECK(hipMemcpy(d_other.as(), a.other_ids + at, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
-            PMF_HIP_CHECK(hipMemcpy(d_val.as(), val.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
-        }
+        if ((rc = st.upload(a.other_ids))) return rc;
+        if (nnz) PMF_HIP_CHECK(hipMemcpy(d_tasks.as(), tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
         if (!split.empty())
             PMF_HIP_CHECK(hipMemcpy(d_split.as(), split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
         if (has_empty) {   // no task writes an empty row: zero sums, which the solvers skip
@@ -1971,8 +1954,8 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         p.tasks = d_tasks.as<PmfTask>();
         p.n_tasks = (int64_t)tasks.size();
         p.split = d_split.as<PmfSplitRow>();
-        p.other = d_other.as<int32_t>();
-        p.val = d_val.as<const T>();
+        p.other = st.d_other.template as<int32_t>();
+        p.val = st.d_val.template as<const T>();
         p.hot = nullptr;
         p.bias_self = nullptr;
         p.partial = d_partial.as<T>();
@@ -1994,7 +1977,7 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         if ((rc = launch_solve<T>(ctx, sp))) return rc;
         if (bias) {
             FoldBiasParams<T> q;
-            q.ptr = d_ptr.as<const int64_t>();
+            q.ptr = st.d_ptr.template as<const int64_t>();
             q.n = B;
             q.other = p.other;
             q.val = p.val;
@@ -2025,7 +2008,7 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         if (ob && bias && (rc = pmf_fold_in_download(ctx, PMF_ARR_BIAS, d_b.as(), ob, B))) return rc;
         if (ob && !bias) std::fill_n(ob, (size_t)B, 0.0);
         for (int64_t r = 0; has_empty && r < B; ++r) {
-            if (ptr[(size_t)r + 1] > ptr[(size_t)r]) continue;
+            if (st.ptr[(size_t)r + 1] > st.ptr[(size_t)r]) continue;
             // a row without ratings gets the prior: m = 0, V = eta2 I, b = 0
             std::fill_n(of + r * K, (size_t)K, 0.0);
             if (ob) ob[r] = 0.0;
@@ -2046,15 +2029,13 @@ extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
     PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_gauss_fold_in: negative row count");
     if (n_rows == 0) return PMF_OK;
     PMF_REQUIRE(row_ptr && out_factor, PMF_EINVAL, "pmf_gauss_fold_in: null argument");
-    PMF_REQUIRE(row_ptr[0] == 0, PMF_EINVAL, "pmf_gauss_fold_in: row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
-    for (int64_t r = 0; r < n_rows; ++r)
-        PMF_REQUIRE(row_ptr[r + 1] >= row_ptr[r], PMF_EINVAL, "pmf_gauss_fold_in: row_ptr decreases at row %lld", (long long)r);
+    int rc;
+    if ((rc = pmf_check_offsets("pmf_gauss_fold_in", "row_ptr", row_ptr, n_rows))) return rc;
     const int64_t nnz = row_ptr[n_rows];
     PMF_REQUIRE(nnz == 0 || (other_ids && ratings), PMF_EINVAL, "pmf_gauss_fold_in: null argument");
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0 && eta_bias2 > 0, PMF_EINVAL, "pmf_gauss_fold_in: variances must be positive");
     PMF_REQUIRE(n_iter >= 1, PMF_EINVAL, "pmf_gauss_fold_in: n_iter = %d, must be at least 1", n_iter);
     const int other = 1 - side;
-    int rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_fold_in"))) return rc;
     if ((rc = pmf_require_array(ctx, other, PMF_ARR_COV, "pmf_gauss_fold_in"))) return rc;
     if ((rc = pmf_check_ids(other_ids, nnz, ctx->rows[other], "pmf_gauss_fold_in", "id"))) return rc;

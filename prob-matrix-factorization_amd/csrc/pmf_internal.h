@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "pmf_hip.h"
+#include "pmf_batch.h"   // pmf_set_error, pmf_check_offsets, PmfLayout, pmf_block_cut
 
 #ifndef PMF_TRANSPORT_HOSTSHM
 #define PMF_TRANSPORT_HOSTSHM 1   // declared by the header in test builds only (-DPMF_TEST_TRANSPORT)
@@ -23,8 +24,6 @@
 #define PMF_VEC 4               // elements per lane access (16 B fp32 / 32 B fp64)
 #define PMF_RATE_FLOOR 1e-10    // hpf_cavi.py:141
 #define PMF_MAX_LABELS 32
-
-void pmf_set_error(const char *fmt, ...);
 
 #define PMF_HIP_CHECK(expr)                                                         \
     do {                                                                            \
@@ -272,6 +271,43 @@ struct pmf_ctx {
 #define PMF_GAUSS_CHUNK 512
 #define PMF_FOLD_IN_BLOCK_NNZ (32ll << 20)   // staged ratings of one row block of the fold-ins (a longer single row still goes)
 #define PMF_GAUSS_HOT_MB_DEFAULT 224   // hot-row budget when PMF_GAUSS_HOT_MB is unset
+
+// The row blocks of a fold-in's CSR batch (row_ptr, other_ids, ratings), staged one at a time in buffers of the call.
+// stage() takes the block that begins at row r0: it ends at r1 (pmf_block_cut: at most max_rows rows and
+// PMF_FOLD_IN_BLOCK_NNZ ratings, and `fits` if given), holds the nnz ratings from offset `at` of the batch, and has its
+// offsets (`ptr`, rebased to 0) and ratings (`val`, in the context dtype T) on the host and room for them and the ids on
+// the device; upload(), after the caller's own reserves, puts them there.  The previous block must have ended with a
+// stream synchronise: nothing queued may still read the buffers.
+template <typename T>
+struct PmfFoldStage {
+    PmfBuf d_ptr, d_other, d_val;   // int64_t [r1 - r0 + 1], int32_t [nnz], T [nnz]
+    std::vector<int64_t> ptr;
+    std::vector<T> val;
+    int64_t r1 = 0, nnz = 0, at = 0;
+
+    int stage(pmf_ctx *ctx, int64_t n_rows, const int64_t *row_ptr, const double *ratings, int64_t r0, int64_t max_rows,
+              const std::function<bool(int64_t)> &fits = nullptr) {
+        r1 = pmf_block_cut(row_ptr, n_rows, r0, max_rows, PMF_FOLD_IN_BLOCK_NNZ, [&](int64_t n) { return !fits || fits(n); });
+        at = row_ptr[r0];
+        nnz = row_ptr[r1] - at;
+        ptr.resize((size_t)(r1 - r0) + 1);
+        for (int64_t r = r0; r <= r1; ++r) ptr[(size_t)(r - r0)] = row_ptr[r] - at;
+        val.resize((size_t)nnz);
+        for (int64_t k = 0; k < nnz; ++k) val[(size_t)k] = (T)ratings[at + k];
+        int rc;
+        if ((rc = d_ptr.reserve(ctx, ptr.size() * sizeof(int64_t), {ctx->stream}))) return rc;
+        if ((rc = d_other.reserve(ctx, (size_t)nnz * sizeof(int32_t), {ctx->stream}))) return rc;
+        return d_val.reserve(ctx, (size_t)nnz * sizeof(T), {ctx->stream});
+    }
+    int upload(const int32_t *other_ids) {
+        PMF_HIP_CHECK(hipMemcpy(d_ptr.as(), ptr.data(), ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (nnz) {
+            PMF_HIP_CHECK(hipMemcpy(d_other.as(), other_ids + at, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
+            PMF_HIP_CHECK(hipMemcpy(d_val.as(), val.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
+        }
+        return PMF_OK;
+    }
+};
 
 // first row of chunk c of a side (c = n_chunks gives the row count)
 static inline int64_t pmf_chunk_row0(const pmf_ctx *ctx, int side, int c) {

@@ -910,56 +910,28 @@ static int topk_round_source(pmf_ctx *ctx, const TopkSource &src, int64_t row0, 
 // ... and the round's A ids on the device, one per row
 static int topk_round_ids(pmf_ctx *ctx, const TopkSource &src, int64_t row0, int n, int32_t *d_ids);
 
-// fp32, Kpad <= 128, k <= 64
-// (cu / ci / the exclusion lists: src's, per round)
-static int run_topk_fused(pmf_ctx *ctx, const TopkSource &src, int64_t n_query, int k, int mode, int32_t *out_items,
-                          double *out_scores) {
-    const int64_t I = src.n_cand;
-    const int64_t Q = std::min<int64_t>(n_query, topk_round_rows(ctx));   // query users per launch
-    int64_t seg_items;
-    const int nseg = topk_segments(Q, I, &seg_items);
-    const size_t n_cand = nseg > 1 ? (size_t)nseg * k : 0;
-    const size_t id_bytes = ((size_t)Q * sizeof(int32_t) + 15) / 16 * 16;
-    const size_t out_i = ((size_t)Q * k * sizeof(int32_t) + 15) / 16 * 16, out_s = (size_t)Q * k * sizeof(double);
-    const size_t cv_bytes = ((size_t)Q * n_cand * sizeof(float) + 15) / 16 * 16;
+// The rounds of both top-k paths: per round of at most Q query rows its source and A ids (d_users), launch(p, r, nq) --
+// the path's kernels over the round's parameters `p` and source `r`, timed as PMF_KERNEL_TOPK -- and the nq x k results
+// from d_out_items / d_out_scores to the caller's arrays.
+template <typename Launch>
+static int topk_rounds(pmf_ctx *ctx, const TopkSource &src, int64_t n_query, int64_t Q, int k, int32_t *d_users,
+                       int32_t *d_out_items, double *d_out_scores, int32_t *out_items, double *out_scores, Launch &&launch) {
     int rc;
-    if ((rc = pmf_ensure_scratch(ctx, id_bytes + out_s + out_i + 2 * cv_bytes + 64))) return rc;
-    char *base = ctx->d_scratch.as<char>();
-    double *d_out_scores = (double *)base;
-    int32_t *d_out_items = (int32_t *)(base + out_s);
-    int32_t *d_users = (int32_t *)(base + out_s + out_i);
-    float *d_cv = (float *)(base + out_s + out_i + id_bytes);
-    int32_t *d_ci = (int32_t *)(base + out_s + out_i + id_bytes + cv_bytes);
     for (int64_t at = 0; at < n_query; at += Q) {
         const int nq = (int)std::min<int64_t>(Q, n_query - at);
         TopkSource r;
         if ((rc = topk_round_source(ctx, src, at, nq, &r)) || (rc = topk_round_ids(ctx, src, at, nq, d_users))) return rc;
-        const float *fu = static_cast<const float *>(r.fa), *fi = static_cast<const float *>(r.fb);
-        const float *cu = static_cast<const float *>(r.ca), *ci = static_cast<const float *>(r.cb);
         TopkExcludeParams p;
         p.users = d_users;
         p.nq = nq;
-        p.n_items = I;
+        p.n_items = src.n_cand;
         p.K = ctx->K;
         p.kpad = ctx->kpad;
         p.ex_ptr = r.ex_ptr;
         p.ex_items = r.ex_ids;
         {
             PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
-            dim3 grid((unsigned)((nq + 127) / 128), (unsigned)nseg);
-            // the instantiation for the K class KH and the bias mode
-            PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, [&](auto kh) {   // KH: kpad / 2 rounded up to 8, 16, 32 or 64
-                return pmf_with_predict_mode(mode, [&](auto m) {
-                    if (p.ex_ptr)
-                        return launch_topk_fused_mode<kh, m>(ctx, p, grid, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci,
-                                                             d_out_items, d_out_scores);
-                    return launch_topk_fused_mode<kh, m>(ctx, static_cast<const TopkParams &>(p), grid, fu, fi, cu, ci, k, seg_items,
-                                                         nseg, d_cv, d_ci, d_out_items, d_out_scores);
-                });
-            }));
-            if (nseg > 1)
-                hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, d_cv, d_ci, nq,
-                                   (int)n_cand, k, d_out_items, d_out_scores);
+            if ((rc = launch(p, r, nq))) return rc;
         }
         PMF_HIP_CHECK(hipGetLastError());
         PMF_HIP_CHECK(hipMemcpyAsync(out_items + at * k, d_out_items, (size_t)nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -969,12 +941,51 @@ static int run_topk_fused(pmf_ctx *ctx, const TopkSource &src, int64_t n_query, 
     return PMF_OK;
 }
 
+// fp32, Kpad <= 128, k <= 64
+// (cu / ci / the exclusion lists: src's, per round)
+static int run_topk_fused(pmf_ctx *ctx, const TopkSource &src, int64_t n_query, int k, int mode, int32_t *out_items,
+                          double *out_scores) {
+    const int64_t Q = std::min<int64_t>(n_query, topk_round_rows(ctx));   // query users per launch
+    int64_t seg_items;
+    const int nseg = topk_segments(Q, src.n_cand, &seg_items);
+    const size_t n_cand = nseg > 1 ? (size_t)nseg * k : 0;
+    PmfLayout lay;
+    const auto scores_at = lay.add<double>((size_t)Q * k);
+    const auto items_at = lay.add<int32_t>((size_t)Q * k), users_at = lay.add<int32_t>((size_t)Q);
+    const auto cv_at = lay.add<float>((size_t)Q * n_cand);
+    const auto ci_at = lay.add<int32_t>((size_t)Q * n_cand);
+    if (int rc = pmf_ensure_scratch(ctx, lay.bytes())) return rc;
+    void *base = ctx->d_scratch.as();
+    double *d_out_scores = scores_at.at(base);
+    int32_t *d_out_items = items_at.at(base), *d_ci = ci_at.at(base);
+    float *d_cv = cv_at.at(base);
+    return topk_rounds(ctx, src, n_query, Q, k, users_at.at(base), d_out_items, d_out_scores, out_items, out_scores,
+                       [&](const TopkExcludeParams &p, const TopkSource &r, int nq) {
+        const float *fu = static_cast<const float *>(r.fa), *fi = static_cast<const float *>(r.fb);
+        const float *cu = static_cast<const float *>(r.ca), *ci = static_cast<const float *>(r.cb);
+        dim3 grid((unsigned)((nq + 127) / 128), (unsigned)nseg);
+        // the instantiation for the K class KH and the bias mode
+        PMF_HIP_CHECK(pmf_with_pow2<8>(ctx->kpad / 2, [&](auto kh) {   // KH: kpad / 2 rounded up to 8, 16, 32 or 64
+            return pmf_with_predict_mode(mode, [&](auto m) {
+                if (p.ex_ptr)
+                    return launch_topk_fused_mode<kh, m>(ctx, p, grid, fu, fi, cu, ci, k, seg_items, nseg, d_cv, d_ci,
+                                                         d_out_items, d_out_scores);
+                return launch_topk_fused_mode<kh, m>(ctx, static_cast<const TopkParams &>(p), grid, fu, fi, cu, ci, k, seg_items,
+                                                     nseg, d_cv, d_ci, d_out_items, d_out_scores);
+            });
+        }));
+        if (nseg > 1)
+            hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream, d_cv, d_ci, nq,
+                               (int)n_cand, k, d_out_items, d_out_scores);
+        return PMF_OK;
+    });
+}
+
 // (arguments, arrays and flag are checked: topk_items_impl)
 template <typename T>
 static int run_topk(pmf_ctx *ctx, const TopkSource &src, int64_t n_query, int k, int use_bias, int32_t *out_items,
                     double *out_scores) {
     const int64_t I = src.n_cand;
-    int rc;
     if constexpr (std::is_same<T, float>::value) {
         if (ctx->kpad <= 128 && k <= 64 && I <= (int64_t)INT32_MAX - 64 && !ctx->topk_two_phase)   // (the fused scan counts items in ints)
             return run_topk_fused(ctx, src, n_query, k, use_bias, out_items, out_scores);
@@ -983,51 +994,34 @@ static int run_topk(pmf_ctx *ctx, const TopkSource &src, int64_t n_query, int k,
     int64_t Q = std::max<int64_t>(32, (512ll << 20) / (I * (int64_t)sizeof(T)));
     Q = std::min<int64_t>(Q / 32 * 32, (n_query + 31) / 32 * 32);
     if (ctx->topk_query_rows > 0) Q = std::min(Q, ctx->topk_query_rows);
-    const size_t score_bytes = (size_t)Q * I * sizeof(T);
-    const size_t id_bytes = (size_t)Q * sizeof(int32_t);
-    const size_t out_bytes = (size_t)Q * k * (sizeof(int32_t) + sizeof(double));
-    if ((rc = pmf_ensure_scratch(ctx, score_bytes + id_bytes + out_bytes + 64))) return rc;
-    char *base = ctx->d_scratch.as<char>();
-    T *d_scores = (T *)base;
-    double *d_out_scores = (double *)(base + score_bytes);
-    int32_t *d_out_items = (int32_t *)(base + score_bytes + (size_t)Q * k * sizeof(double));
-    int32_t *d_users = d_out_items + (size_t)Q * k;
-    for (int64_t at = 0; at < n_query; at += Q) {
-        const int nq = (int)std::min<int64_t>(Q, n_query - at);
-        TopkSource r;
-        if ((rc = topk_round_source(ctx, src, at, nq, &r)) || (rc = topk_round_ids(ctx, src, at, nq, d_users))) return rc;
+    PmfLayout lay;
+    const auto all_at = lay.add<T>((size_t)Q * I);
+    const auto scores_at = lay.add<double>((size_t)Q * k);
+    const auto items_at = lay.add<int32_t>((size_t)Q * k), users_at = lay.add<int32_t>((size_t)Q);
+    if (int rc = pmf_ensure_scratch(ctx, lay.bytes())) return rc;
+    void *base = ctx->d_scratch.as();
+    T *d_scores = all_at.at(base);
+    double *d_out_scores = scores_at.at(base);
+    int32_t *d_out_items = items_at.at(base);
+    return topk_rounds(ctx, src, n_query, Q, k, users_at.at(base), d_out_items, d_out_scores, out_items, out_scores,
+                       [&](const TopkExcludeParams &p, const TopkSource &r, int nq) {
         const T *fu = static_cast<const T *>(r.fa), *fi = static_cast<const T *>(r.fb);
         const T *bu = static_cast<const T *>(r.ca), *bi = static_cast<const T *>(r.cb);
-        TopkExcludeParams p;
-        p.users = d_users;
-        p.nq = nq;
-        p.n_items = I;
-        p.K = ctx->K;
-        p.kpad = ctx->kpad;
-        p.ex_ptr = r.ex_ptr;
-        p.ex_items = r.ex_ids;
-        {
-            PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
-            if constexpr (std::is_same<T, float>::value) {
-                dim3 grid((unsigned)((nq + 31) / 32), (unsigned)((I + 127) / 128));
-                hipLaunchKernelGGL(topk_scores_f32_kernel, grid, dim3(256), 0, ctx->stream, p, fu, fi, bu, bi, use_bias, d_scores);
-            } else {
-                const int64_t total = (int64_t)nq * I;
-                hipLaunchKernelGGL(topk_scores_f64_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65535)),
-                                   dim3(256), 0, ctx->stream, p, fu, fi, bu, bi, use_bias, d_scores);
-            }
-            if (p.ex_ptr)   // excluded pairs score NaN from here on: the select never ranks them
-                hipLaunchKernelGGL((topk_exclude_scores_kernel<T>), dim3((unsigned)std::min(nq, 65535)), dim3(256), 0, ctx->stream,
-                                   p, d_scores);
-            hipLaunchKernelGGL((topk_select_kernel<T>), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream,
-                               d_scores, nq, I, k, d_out_items, d_out_scores);
+        if constexpr (std::is_same<T, float>::value) {
+            dim3 grid((unsigned)((nq + 31) / 32), (unsigned)((I + 127) / 128));
+            hipLaunchKernelGGL(topk_scores_f32_kernel, grid, dim3(256), 0, ctx->stream, p, fu, fi, bu, bi, use_bias, d_scores);
+        } else {
+            const int64_t total = (int64_t)nq * I;
+            hipLaunchKernelGGL(topk_scores_f64_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 65535)),
+                               dim3(256), 0, ctx->stream, p, fu, fi, bu, bi, use_bias, d_scores);
         }
-        PMF_HIP_CHECK(hipGetLastError());
-        PMF_HIP_CHECK(hipMemcpyAsync(out_items + at * k, d_out_items, (size_t)nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        PMF_HIP_CHECK(hipMemcpyAsync(out_scores + at * k, d_out_scores, (size_t)nq * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    }
-    return PMF_OK;
+        if (p.ex_ptr)   // excluded pairs score NaN from here on: the select never ranks them
+            hipLaunchKernelGGL((topk_exclude_scores_kernel<T>), dim3((unsigned)std::min(nq, 65535)), dim3(256), 0, ctx->stream,
+                               p, d_scores);
+        hipLaunchKernelGGL((topk_select_kernel<T>), dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, ctx->stream,
+                           d_scores, nq, I, k, d_out_items, d_out_scores);
+        return PMF_OK;
+    });
 }
 
 // the source of the item calls: the context's users (by the caller's ids) against its items under `mode`, with the users'
@@ -1530,15 +1524,14 @@ static int run_rank(pmf_ctx *ctx, const TopkSource &src, int64_t n_rows, const i
     }
     const int64_t n_query = (int64_t)qrows.size();
     const int64_t Q = std::min<int64_t>(n_query, topk_round_rows(ctx));   // query rows per launch
-    const size_t id_bytes = ((size_t)Q * sizeof(int32_t) + 15) / 16 * 16;
-    const size_t slot_bytes = (size_t)Q * RANK_SLOTS * 8;     // targets (int32) / thresholds (context dtype), 16-byte multiples
-    const size_t cnt_bytes = ((size_t)Q * RANK_STRIDE * sizeof(int32_t) + 15) / 16 * 16;
-    if ((rc = pmf_ensure_scratch(ctx, id_bytes + 2 * slot_bytes + cnt_bytes))) return rc;
-    char *base = ctx->d_scratch.as<char>();
-    int32_t *d_users = (int32_t *)base;
-    int32_t *d_tgt = (int32_t *)(base + id_bytes);
-    void *d_th = base + id_bytes + slot_bytes;
-    int32_t *d_cnt = (int32_t *)(base + id_bytes + 2 * slot_bytes);
+    PmfLayout lay;
+    const auto users_at = lay.add<int32_t>((size_t)Q), tgt_at = lay.add<int32_t>((size_t)Q * RANK_SLOTS);
+    const auto th_at = lay.add<double>((size_t)Q * RANK_SLOTS);     // thresholds, context dtype
+    const auto cnt_at = lay.add<int32_t>((size_t)Q * RANK_STRIDE);
+    if ((rc = pmf_ensure_scratch(ctx, lay.bytes()))) return rc;
+    void *base = ctx->d_scratch.as();
+    int32_t *d_users = users_at.at(base), *d_tgt = tgt_at.at(base), *d_cnt = cnt_at.at(base);
+    void *d_th = th_at.at(base);
     std::vector<int32_t> h_users((size_t)Q), h_tgt((size_t)Q * RANK_SLOTS), h_cnt((size_t)Q * RANK_STRIDE);
     for (int64_t at = 0; at < n_query; at += Q) {
         const int nq = (int)std::min<int64_t>(Q, n_query - at);
@@ -1585,14 +1578,12 @@ static int rank_items_impl(pmf_ctx *ctx, int64_t n_rows, const int32_t *user_ids
                            int64_t *out_candidates) {
     const int64_t U = ctx->rows[PMF_SIDE_USER], I = ctx->rows[PMF_SIDE_ITEM];
     PMF_REQUIRE(user_ids && row_ptr, PMF_EINVAL, "pmf_rank_items: null user_ids or row_ptr");
-    PMF_REQUIRE(row_ptr[0] == 0, PMF_EINVAL, "pmf_rank_items: row_ptr[0] = %lld, not 0", (long long)row_ptr[0]);
-    for (int64_t n = 0; n < n_rows; ++n)
-        PMF_REQUIRE(row_ptr[n + 1] >= row_ptr[n], PMF_EINVAL, "pmf_rank_items: row_ptr decreases at row %lld", (long long)n);
+    int rc;
+    if ((rc = pmf_check_offsets("pmf_rank_items", "row_ptr", row_ptr, n_rows))) return rc;
     const int64_t n_targets = row_ptr[n_rows];
     PMF_REQUIRE(n_targets == 0 || (item_ids && out_rank), PMF_EINVAL, "pmf_rank_items: null item_ids or out_rank");
     PMF_REQUIRE(use_bias == 0 || use_bias == PMF_PREDICT_BIAS || use_bias == PMF_PREDICT_SCALE, PMF_EINVAL,
                 "pmf_rank_items: use_bias must be 0, PMF_PREDICT_BIAS or PMF_PREDICT_SCALE (got %d)", use_bias);
-    int rc;
     if ((rc = pmf_require_array(ctx, PMF_SIDE_USER, PMF_ARR_FACTOR, "pmf_rank_items"))) return rc;
     if ((rc = pmf_require_array(ctx, PMF_SIDE_ITEM, PMF_ARR_FACTOR, "pmf_rank_items"))) return rc;
     if (use_bias) {
@@ -1701,13 +1692,14 @@ template <typename T>
 static int query_stage_rows(pmf_ctx *ctx, const QueryStage &st, int64_t row0, int64_t n, TopkSource *round) {
     const int K = ctx->K, kpad = ctx->kpad;
     const size_t row_bytes = (size_t)kpad * sizeof(T);
-    const size_t table_bytes = (size_t)n * row_bytes, coef_bytes = ((size_t)n * sizeof(T) + 15) / 16 * 16;
-    const size_t id_bytes = ((size_t)n * sizeof(int32_t) + 15) / 16 * 16;
+    PmfLayout lay;
+    const auto rows_at = lay.add<T>((size_t)n * kpad), coef_at = lay.add<T>((size_t)n);
+    const auto ids_at = lay.add<int32_t>((size_t)n);
     int rc;
-    if ((rc = ctx->d_query_rows.reserve(ctx, table_bytes + coef_bytes + id_bytes, {ctx->stream}))) return rc;
-    char *base = ctx->d_query_rows.as<char>();
-    T *d_rows = (T *)base, *d_coef = (T *)(base + table_bytes);
-    int32_t *d_ids = (int32_t *)(base + table_bytes + coef_bytes);
+    if ((rc = ctx->d_query_rows.reserve(ctx, lay.bytes(), {ctx->stream}))) return rc;
+    void *base = ctx->d_query_rows.as();
+    T *d_rows = rows_at.at(base), *d_coef = coef_at.at(base);
+    int32_t *d_ids = ids_at.at(base);
     if (st.ids) {
         PMF_HIP_CHECK(hipMemcpyAsync(d_ids, st.ids + row0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
@@ -1801,9 +1793,7 @@ static int query_check(const char *fn, pmf_ctx *ctx, int cand_side, int64_t n_qu
     if ((rc = pmf_require_array(ctx, cand_side, PMF_ARR_FACTOR, fn))) return rc;
     if (model_coef && (rc = pmf_require_array(ctx, cand_side, carr, fn))) return rc;
     if (ex_ptr) {
-        PMF_REQUIRE(ex_ptr[0] == 0, PMF_EINVAL, "%s: ex_ptr[0] = %lld, not 0", fn, (long long)ex_ptr[0]);
-        for (int64_t n = 0; n < n_query; ++n)
-            PMF_REQUIRE(ex_ptr[n + 1] >= ex_ptr[n], PMF_EINVAL, "%s: ex_ptr decreases at row %lld", fn, (long long)n);
+        if ((rc = pmf_check_offsets(fn, "ex_ptr", ex_ptr, n_query))) return rc;
         PMF_REQUIRE(ex_ptr[n_query] == 0 || ex_ids, PMF_EINVAL, "%s: null ex_ids", fn);
         if ((rc = pmf_check_ids(ex_ids, ex_ptr[n_query], C, fn, "excluded id"))) return rc;
         // the fused scan's cursor and the counts of the ranking need ascending distinct ids
@@ -1838,24 +1828,26 @@ static int query_check(const char *fn, pmf_ctx *ctx, int cand_side, int64_t n_qu
 // candidates' inverse norms from cand_side's FACTOR as it is now.
 template <typename T>
 static int query_begin(pmf_ctx *ctx, QueryCall *qc) {
-    const size_t ptr_bytes = qc->ex_ptr.size() * sizeof(int64_t);
-    // (16-byte multiples; the id part is never empty when there are lists, so that its pointer lies inside the buffer)
-    const size_t ptr_pad = (ptr_bytes + 15) / 16 * 16, ids_pad = ptr_bytes ? (qc->ex_ids.size() * sizeof(int32_t) + 16) / 16 * 16 : 0;
-    const size_t norm_bytes = qc->stage.cosine ? (size_t)qc->src.n_cand * sizeof(T) : 0;
-    if (ptr_pad + ids_pad + norm_bytes == 0) return PMF_OK;
+    const bool lists = !qc->ex_ptr.empty();
+    PmfLayout lay;
+    const auto ptr_at = lay.add<int64_t>(qc->ex_ptr.size());
+    const auto ids_at = lay.add<int32_t>(qc->ex_ids.size(), lists);   // (the kernels get the pointer even when every list is empty)
+    const auto norm_at = lay.add<T>(qc->stage.cosine ? (size_t)qc->src.n_cand : 0);
+    if (lay.bytes() == 0) return PMF_OK;
     int rc;
-    if ((rc = ctx->d_query_call.reserve(ctx, ptr_pad + ids_pad + norm_bytes, {ctx->stream}))) return rc;
-    char *base = ctx->d_query_call.as<char>();
-    if (!qc->ex_ptr.empty()) {
-        PMF_HIP_CHECK(hipMemcpyAsync(base, qc->ex_ptr.data(), ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = ctx->d_query_call.reserve(ctx, lay.bytes(), {ctx->stream}))) return rc;
+    void *base = ctx->d_query_call.as();
+    if (lists) {
+        PMF_HIP_CHECK(hipMemcpyAsync(ptr_at.at(base), qc->ex_ptr.data(), qc->ex_ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice,
+                                     ctx->stream));
         if (!qc->ex_ids.empty())
-            PMF_HIP_CHECK(hipMemcpyAsync(base + ptr_pad, qc->ex_ids.data(), qc->ex_ids.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+            PMF_HIP_CHECK(hipMemcpyAsync(ids_at.at(base), qc->ex_ids.data(), qc->ex_ids.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                                          ctx->stream));
-        qc->stage.d_ex_ptr = (const int64_t *)base;
-        qc->src.ex_ids = (const int32_t *)(base + ptr_pad);
+        qc->stage.d_ex_ptr = ptr_at.at(base);
+        qc->src.ex_ids = ids_at.at(base);
     }
     if (qc->stage.cosine) {
-        T *inv = (T *)(base + ptr_pad + ids_pad);
+        T *inv = norm_at.at(base);
         PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
         launch_inv_norm<T>(ctx, static_cast<const T *>(qc->src.fb), qc->src.n_cand, inv);
         qc->src.cb = inv;
@@ -1897,9 +1889,7 @@ extern "C" int pmf_rank_query(pmf_ctx *ctx, int cand_side, int64_t n_query, int 
     return pmf_no_throw(fn, [&] {
         QueryCall qc;
         PMF_REQUIRE(tgt_ptr, PMF_EINVAL, "%s: null tgt_ptr", fn);
-        PMF_REQUIRE(tgt_ptr[0] == 0, PMF_EINVAL, "%s: tgt_ptr[0] = %lld, not 0", fn, (long long)tgt_ptr[0]);
-        for (int64_t n = 0; n < n_query; ++n)
-            PMF_REQUIRE(tgt_ptr[n + 1] >= tgt_ptr[n], PMF_EINVAL, "%s: tgt_ptr decreases at row %lld", fn, (long long)n);
+        if (int rc = pmf_check_offsets(fn, "tgt_ptr", tgt_ptr, n_query)) return rc;
         PMF_REQUIRE(tgt_ptr[n_query] == 0 || (tgt_ids && out_rank), PMF_EINVAL, "%s: null tgt_ids or out_rank", fn);
         if (int rc = query_check(fn, ctx, cand_side, n_query, query_side, query_ids, query_factor, query_coef, score, ex_ptr, ex_ids, &qc))
             return rc;

@@ -15,6 +15,31 @@ from . import (ARR_COV, ELBO_TERMS, EXCHANGE, F32, F64, GAMMA_ELBO_TERMS, GAMMA_
                UNIQUE_ID_BYTES, USER, PmfError, PmfLibraryError, as_f64, as_i32, check, load, ptr)
 
 
+def group_rows(row, n):
+    """Entries labelled with their row in [0, n) -> (row_ptr int64 [n + 1], order): order[row_ptr[r]:row_ptr[r + 1]] are the
+    positions of row r's entries, in input order."""
+    row = np.asarray(row).reshape(-1)
+    row_ptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=n))]).astype(np.int64)
+    return row_ptr, np.argsort(row, kind="stable")
+
+
+def csr_batch(message, row_ptr, ids=None, what="ids", values=None, n_rows=None):
+    """A CSR batch in the ABI's types: [row_ptr as contiguous int64, then `ids` (named `what`) as int32 and `values` as
+    float64, each if given].  ValueError(message) unless there are `n_rows` + 1 offsets (None: at least one), the columns
+    have one length and the offsets of a batch with rows end at it."""
+    rp = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.int64).reshape(-1))
+    cols = ([] if ids is None else [as_i32(ids, what)]) + ([] if values is None else [as_f64(values)])
+    n = len(rp) - 1 if n_rows is None else n_rows
+    if n < 0 or len(rp) != n + 1 or any(len(c) != len(cols[0]) for c in cols) or (cols and n and rp[-1] != len(cols[0])):
+        raise ValueError(message)
+    return [rp] + cols
+
+
+def opt_ptr(a, ctype=C.c_double):
+    """`ptr`, or None for an array the caller leaves out"""
+    return None if a is None else ptr(a, ctype)
+
+
 def rank_batch(user_ids, item_ids):
     """Flat (user, item) pairs -> the CSR batch `pmf_rank_items` takes: (users, row_ptr, items, order) with `users` the
     sorted distinct user ids, row r holding items[row_ptr[r]:row_ptr[r + 1]] -- user r's items in input order -- and
@@ -23,8 +48,7 @@ def rank_batch(user_ids, item_ids):
     if len(u) != len(i):
         raise ValueError("user_ids and item_ids must have the same length")
     users, row = np.unique(u, return_inverse=True)
-    order = np.argsort(row.reshape(-1), kind="stable")
-    row_ptr = np.concatenate([[0], np.cumsum(np.bincount(row.reshape(-1), minlength=len(users)))]).astype(np.int64)
+    row_ptr, order = group_rows(row, len(users))
     return users, row_ptr, i[order], order
 
 
@@ -244,10 +268,8 @@ class Context:
         (factor [n, K], shape [n, K], rate [n, K], prior_rate [n], hyper_rate [n]) as float64.  `shape` and `rate` are None
         unless `want_params`, `prior_rate` and `hyper_rate` are None unless `hierarchical`.  `init_factor` [n, K] /
         `init_prior_rate` [n] warm-start the rows.  The context is only read."""
-        rp = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.int64).reshape(-1))
-        o, x = as_i32(other_ids, "other_ids"), as_f64(ratings)
-        if len(rp) < 1 or len(o) != len(x) or (len(rp) > 1 and rp[-1] != len(o)):
-            raise ValueError("row_ptr must hold n_rows + 1 offsets ending at len(other_ids) == len(ratings)")
+        rp, o, x = csr_batch("row_ptr must hold n_rows + 1 offsets ending at len(other_ids) == len(ratings)", row_ptr,
+                             other_ids, "other_ids", ratings)
         n = len(rp) - 1
         init_f = None if init_factor is None else as_f64(init_factor)
         init_r = None if init_prior_rate is None else as_f64(init_prior_rate)
@@ -261,11 +283,10 @@ class Context:
         rate = np.zeros((n, self.K), dtype=np.float64) if want_params else None
         prior_rate = np.zeros(n, dtype=np.float64) if hier else None
         hyper_rate = np.zeros(n, dtype=np.float64) if hier else None
-        opt = lambda a: None if a is None else ptr(a, C.c_double)
         check(self._lib.pmf_gamma_fold_in(self._h, side, n, ptr(rp, C.c_int64), ptr(o, C.c_int32), ptr(x, C.c_double),
                                           float(shape_prior), float(rate_prior), int(hier), float(hyper_shape),
-                                          float(hyper_rate_prior), int(n_iter), opt(init_f), opt(init_r), ptr(factor, C.c_double),
-                                          opt(shape), opt(rate), opt(prior_rate), opt(hyper_rate)), "pmf_gamma_fold_in")
+                                          float(hyper_rate_prior), int(n_iter), opt_ptr(init_f), opt_ptr(init_r), ptr(factor, C.c_double),
+                                          opt_ptr(shape), opt_ptr(rate), opt_ptr(prior_rate), opt_ptr(hyper_rate)), "pmf_gamma_fold_in")
         return factor, shape, rate, prior_rate, hyper_rate
 
     def gamma_elbo_terms(self, side, with_data=False, hierarchical=False, per_row=False):
@@ -325,9 +346,8 @@ class Context:
             totals[1:] = 0.0
             if not with_bound:
                 totals[2] = np.nan
-        opt = lambda a: None if a is None else ptr(a, C.c_double)
-        check(self._lib.pmf_gamma_predictive(self._h, n, ptr(u, C.c_int32), ptr(i, C.c_int32), opt(x), int(bool(with_bound)),
-                                             opt(mean), opt(var), opt(logp), ptr(totals, C.c_double)), "pmf_gamma_predictive")
+        check(self._lib.pmf_gamma_predictive(self._h, n, ptr(u, C.c_int32), ptr(i, C.c_int32), opt_ptr(x), int(bool(with_bound)),
+                                             opt_ptr(mean), opt_ptr(var), opt_ptr(logp), ptr(totals, C.c_double)), "pmf_gamma_predictive")
         return GammaPredictive(mean, var, logp, totals)
 
     # ---- Gaussian -------------------------------------------------------
@@ -358,10 +378,8 @@ class Context:
     def gauss_fold_in(self, side, row_ptr, other_ids, ratings, sigma2, eta2, eta_bias2=1.0, n_iter=1, want_cov=True):
         """Posterior of new rows of `side` (CSR batch: `row_ptr`, ids on the opposite side, ratings) against the
         fitted opposite side: (factor [n, K], cov [n, K, K] or None, bias [n]) as float64.  The context is only read."""
-        rp = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.int64).reshape(-1))
-        o, x = as_i32(other_ids, "other_ids"), as_f64(ratings)
-        if len(rp) < 1 or len(o) != len(x) or (len(rp) > 1 and rp[-1] != len(o)):
-            raise ValueError("row_ptr must hold n_rows + 1 offsets ending at len(other_ids) == len(ratings)")
+        rp, o, x = csr_batch("row_ptr must hold n_rows + 1 offsets ending at len(other_ids) == len(ratings)", row_ptr,
+                             other_ids, "other_ids", ratings)
         n = len(rp) - 1
         factor = np.zeros((n, self.K), dtype=np.float64)
         cov = np.zeros((n, self.K, self.K), dtype=np.float64) if want_cov else None
@@ -505,9 +523,7 @@ class Context:
         """`pmf_rank_items` on a CSR batch: row r is user user_ids[r] (repeats allowed) with the targets
         item_ids[row_ptr[r]:row_ptr[r + 1]].  Returns (ranks int64 [len(item_ids)], candidates int64 [len(user_ids)])."""
         u, i = as_i32(user_ids, "user_ids"), as_i32(item_ids, "item_ids")
-        rp = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.int64).reshape(-1))
-        if len(rp) != len(u) + 1:
-            raise ValueError("row_ptr must hold len(user_ids) + 1 offsets")
+        rp, = csr_batch("row_ptr must hold len(user_ids) + 1 offsets", row_ptr, n_rows=len(u))
         ranks = np.empty(len(i), dtype=np.int64)
         cand = np.empty(len(u), dtype=np.int64)
         check(self._lib.pmf_rank_items(self._h, len(u), ptr(u, C.c_int32), ptr(rp, C.c_int64), ptr(i, C.c_int32), int(use_bias),
@@ -553,10 +569,8 @@ class Context:
                 keep.append(c)
         ex_ptr = ex_ids = None
         if exclude is not None:
-            ep = np.ascontiguousarray(np.asarray(exclude[0], dtype=np.int64).reshape(-1))
-            ei = as_i32(np.asarray(exclude[1]).reshape(-1), "exclude ids")
-            if len(ep) != n + 1 or (n and ep[-1] != len(ei)):
-                raise ValueError("exclude must be (row_ptr, ids): one offset per query row and one more, ending at len(ids)")
+            ep, ei = csr_batch("exclude must be (row_ptr, ids): one offset per query row and one more, ending at len(ids)", exclude[0],
+                               np.asarray(exclude[1]).reshape(-1), "exclude ids", n_rows=n)
             ex_ptr, ex_ids = ptr(ep, C.c_int64), ptr(ei, C.c_int32)
             keep += [ep, ei]
         return n, (int(cand_side), n, side, q_ids, q_factor, q_coef), (ex_ptr, ex_ids), keep
@@ -578,10 +592,8 @@ class Context:
         """`pmf_rank_query`: `targets` = (row_ptr, ids), the rows of `cand_side` whose ranks query row q asks for.  Returns
         (ranks int64 [len(target ids)], candidates int64 [n]); the other arguments are those of `topk_query`."""
         n, query, ex, keep = self._query_args(cand_side, ids, query_side, factor, coef, exclude)
-        tp = np.ascontiguousarray(np.asarray(targets[0], dtype=np.int64).reshape(-1))
-        ti = as_i32(np.asarray(targets[1]).reshape(-1), "target ids")
-        if len(tp) != n + 1 or (n and tp[-1] != len(ti)):
-            raise ValueError("targets must be (row_ptr, ids): one offset per query row and one more, ending at len(ids)")
+        tp, ti = csr_batch("targets must be (row_ptr, ids): one offset per query row and one more, ending at len(ids)", targets[0],
+                           np.asarray(targets[1]).reshape(-1), "target ids", n_rows=n)
         ranks = np.empty(len(ti), dtype=np.int64)
         cand = np.empty(n, dtype=np.int64)
         check(self._lib.pmf_rank_query(self._h, *query, int(score), *ex, ptr(tp, C.c_int64), ptr(ti, C.c_int32),
@@ -599,8 +611,7 @@ class Context:
         n = len(ids) if ids is not None else len(factor)
         if len(rows) and (rows.min() < 0 or rows.max() >= n):
             raise ValueError("rows must index the query rows")
-        order = np.argsort(rows, kind="stable")
-        row_ptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=n))]).astype(np.int64)
+        row_ptr, order = group_rows(rows, n)
         r, c = self.rank_query(cand_side, (row_ptr, tgt[order]), ids=ids, query_side=query_side, factor=factor, coef=coef,
                                score=score, exclude=exclude)
         ranks = np.empty(len(rows), dtype=np.int64)

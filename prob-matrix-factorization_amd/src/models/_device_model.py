@@ -44,8 +44,7 @@ def fold_in_batch(df, side, n_other):
     other = df[old_col].to_numpy(dtype=int)
     keep = (other >= 0) & (other < n_other)
     row, other, x = row[keep], other[keep], df["rating"].to_numpy(dtype=float)[keep]
-    order = np.argsort(row, kind="stable")
-    row_ptr = np.concatenate([[0], np.cumsum(np.bincount(row, minlength=len(ids)))])
+    row_ptr, order = pmf_hip.engine.group_rows(row, len(ids))
     return ids, row_ptr, other[order], x[order]
 
 
