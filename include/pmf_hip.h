@@ -343,6 +343,54 @@ int pmf_gamma_exact_sweep(pmf_ctx *ctx, int side, double shape_prior, double rat
                           int hierarchical, double hyper_shape, double hyper_rate_prior);
 int pmf_gamma_exact_accumulate(pmf_ctx *ctx, int side, void *stats_dev);
 
+/* Implicit feedback: unlisted cells counted as zeros.  No reference counterpart (the reference
+ * treats the rating list as the whole data set; that stays the default).  pmf_ctx_set_gamma_zeros selects, for the
+ * Poisson MF / HPF calls of this context, what a (user, item) cell without a rating is:
+ *     PMF_ZEROS_MISSING   (default) not an observation: every sum runs over the listed ratings, bit for bit as before
+ *     PMF_ZEROS_OBSERVED  a count of 0, the model of the HPF paper: every one of the U x I cells is an observation
+ * A zero adds nothing to a shape sum (its weight is x / rate = 0, or x phi = 0) and its row of the other side's expected
+ * factors to the rate sum -- for every row alike.  With C_k = sum over ALL rows o of the other side of E_other[o,k]:
+ *   pmf_gamma_sweep        SHAPE as before;  RATE[r,k] = rate_prior_r + C_k, C from FACTOR of the other side as it is when
+ *                          the call starts;  FACTOR, the hierarchical epilogue and the split-row path as before
+ *   pmf_gamma_exact_sweep  the same, C from the E half of the other side's freshly built table
+ *   pmf_gamma_fold_in      B = C of the opposite side's FACTOR for every row (a new row's unlisted cells are zeros), formed
+ *                          once per call; the recursion, the long-row kernel and the warm start as before
+ *   pmf_gamma_elbo_terms   PMF_GAMMA_ELBO_DATA of row r = sum_j x_j lse_j - sum_k E_rk C_k, C from the other side's E table:
+ *                          sum over all cells of E_u . E_i = (sum_u E_u) . (sum_i E_i).  LOGFACT as before (lgamma(0 + 1) = 0).
+ *                          DATA - LOGFACT from either side still gives the same total.
+ * A row without ratings is no special case: SHAPE = shape_prior, RATE = rate_prior_r + C, DATA = -E_r . C, which is what
+ * listing its zeros would give.  The result equals what PMF_ZEROS_MISSING computes on the same matrix with every missing
+ * cell listed as an explicit rating of 0, up to rounding (C is summed in double, the listed rate sums in the context's
+ * dtype), at the cost of two small launches per call instead of U x I ratings.  C is rounded once to the context's dtype
+ * before it is added to the prior rate; the E . C products of the bound are formed in double.
+ * Duplicate (u, i) pairs (pmf_ctx_set_ratings keeps them): the shape sums add their counts, the cell enters the rate
+ * sums once, LOGFACT treats them as separate ratings -- a cell with one count is the caller's to ensure (the model
+ * classes refuse duplicates).
+ * A property of the context, like the row chunks: no state array changes, and a mode may be set before or after the
+ * ratings.  pmf_gamma_predictive, pmf_predict, the top-k / ranking calls and the Gaussian calls do not read it.
+ * Not covered, PMF_EINVAL naming the mode: pmf_gamma_accumulate, pmf_gamma_exact_accumulate, pmf_gamma_finalize (the
+ * caller-driven multi-GPU form) and pmf_gamma_ext_sweep (the extended model) while the mode is PMF_ZEROS_OBSERVED; and
+ * several ranks -- the user-side column sums would have to be added over the ranks: PMF_ZEROS_OBSERVED on a context
+ * with a communicator is PMF_EINVAL, as are pmf_comm_init / pmf_comm_attach (and the test build's
+ * pmf_comm_init_hostshm) on a context in that mode.  PMF_EINVAL also for a null context, a mode that is neither value and
+ * a null `mode` of the getter.  An error changes nothing. */
+#define PMF_ZEROS_MISSING 0
+#define PMF_ZEROS_OBSERVED 1
+int pmf_ctx_set_gamma_zeros(pmf_ctx *ctx, int mode);
+int pmf_ctx_get_gamma_zeros(pmf_ctx *ctx, int *mode);
+/* C_k, k < K, of `side` in either mode: the sum over ALL its rows of FACTOR[r,k] (from_q == 0) or of E[r,k] =
+ * SHAPE[r,k] / RATE[r,k] (from_q != 0), formed as pmf_gamma_elbo_terms and pmf_gamma_exact_sweep form the E half of their
+ * (E log, E) table: the quotient in double, rounded once to the context's dtype.  The sum itself is in DOUBLE whatever
+ * the dtype.  A fixed number of blocks each add a contiguous row range in a fixed order (16-byte loads per lane, lane
+ * groups over the rows of the range, group sums added in group order); a second launch adds the block sums in a fixed
+ * order as well (contiguous runs of blocks in block order, the runs' sums in run order).  No atomics and no work list: two calls give the same bits, whatever the task length.  Reads the model state
+ * only (from_q: the table is rebuilt into the context-owned storage of pmf_gamma_exact_sweep); the block sums live in the
+ * context's scratch buffer: pmf_ctx_device_bytes may grow on the first call and does not grow after it.  Timed as
+ * PMF_KERNEL_GAMMA_FINAL.  This is the building block of PMF_ZEROS_OBSERVED, visible for tests and callers.
+ * PMF_EINVAL, with the missing thing named: null context, bad side, null out, FACTOR (from_q == 0) or SHAPE / RATE
+ * (from_q != 0) of `side` not set.  Cost: DESIGN.md section 4.16. */
+int pmf_gamma_column_sums(pmf_ctx *ctx, int side, int from_q, double *out /* [K] */);
+
 /* Posterior predictive of the Poisson MF and HPF models for n (user, item) pairs: mean and variance of the rate under
  * q and, with ratings, three log densities of the count.  No reference counterpart beyond PLUGIN (the reference's
  * PoissonLogPredictiveLikelihood, metrics.py:53-66, on the host).  q is defined by SHAPE and RATE alone, as for

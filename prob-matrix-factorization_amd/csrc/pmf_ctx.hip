@@ -687,6 +687,25 @@ extern "C" int pmf_ctx_select_chunk(pmf_ctx *ctx, int side, int chunk) {
     return PMF_OK;
 }
 
+// Poisson MF / HPF: whether an unlisted (user, item) cell is missing or a count of 0.  A property of the context; no
+// state array changes.
+extern "C" int pmf_ctx_set_gamma_zeros(pmf_ctx *ctx, int mode) {
+    CHECK_CTX(ctx, "pmf_ctx_set_gamma_zeros");
+    PMF_REQUIRE(mode == PMF_ZEROS_MISSING || mode == PMF_ZEROS_OBSERVED, PMF_EINVAL, "pmf_ctx_set_gamma_zeros: bad mode %d", mode);
+    PMF_REQUIRE(mode == PMF_ZEROS_MISSING || ctx->comm == nullptr, PMF_EINVAL,
+                "pmf_ctx_set_gamma_zeros: PMF_ZEROS_OBSERVED is not available on a context with a communicator "
+                "(the user-side column sums would have to be added over the ranks)");
+    ctx->gamma_zeros = mode;
+    return PMF_OK;
+}
+
+extern "C" int pmf_ctx_get_gamma_zeros(pmf_ctx *ctx, int *mode) {
+    CHECK_CTX(ctx, "pmf_ctx_get_gamma_zeros");
+    PMF_REQUIRE(mode != nullptr, PMF_EINVAL, "pmf_ctx_get_gamma_zeros: null argument");
+    *mode = ctx->gamma_zeros;
+    return PMF_OK;
+}
+
 // ---------------------------------------------------------------------------
 // model state exchange (host float64 <-> device dtype, padded / packed layouts)
 // ---------------------------------------------------------------------------

@@ -36,6 +36,7 @@ struct GammaParams {
     int pw;             // partial slot width: 2*kpad (+ PMF_VEC carrying sum x when EXT)
     T *partial;         // [n_slots][pw]
     T *stats;           // [rows][2][kpad], STATS mode only
+    const T *colsum;    // [kpad] column sums of the other side's expected factors (PMF_ZEROS_OBSERVED: every row's rate sum), or null
     T shape_prior, rate_prior, hyper_shape, hyper_rate_prior;
     int hierarchical;
     int K, kpad;
@@ -51,12 +52,15 @@ __device__ __forceinline__ void gamma_finalize_row(const GammaParams<T> &p, int 
     const int koff = c * PMF_VEC;
     const T rp = p.hierarchical ? p.prior_rate_vec[row] : p.rate_prior;
     Vec4<T> sh, rt, ex;
+    // unlisted cells counted as zeros: every row's rate sum is the other side's column sum (the same for all lanes of the launch)
+    Vec4<T> rsum = sum_b;
+    if (!EXT && p.colsum && active) rsum = load4(p.colsum + koff);
     T esum = (T)0;
 #pragma unroll
     for (int e = 0; e < PMF_VEC; ++e) {
         const bool ok = active && (koff + e) < p.K;
         T s = p.shape_prior + sum_a.v[e];
-        T r = rp + sum_b.v[e];
+        T r = rp + rsum.v[e];
         T x = s / r;
         sh.v[e] = ok ? s : (T)0;
         rt.v[e] = ok ? r : (T)0;
@@ -293,6 +297,81 @@ __global__ __launch_bounds__(256) void gamma_finalize_all_kernel(GammaParams<T> 
 }
 
 // ---------------------------------------------------------------------------
+// column sums (pmf_gamma_column_sums; the rate sums of PMF_ZEROS_OBSERVED): C_k = sum over all rows of src[row * stride + k]
+// ---------------------------------------------------------------------------
+// `src` is a FACTOR array (stride kpad) or the E half of an (E log, E) table (stride 2 kpad, src offset by kpad), in the
+// context dtype; the sums are formed in DOUBLE whatever the dtype.  Two stages, no atomics, the same order every time
+// and for every task length (the work lists are not read):
+//   stage 1  kGammaColsumBlocks blocks; block b owns the contiguous rows [rows b / NB, rows (b + 1) / NB).  Lane c of a lane
+//            group owns elements [4c, 4c + 4) (one 16-byte load per lane per row, UN rows in flight); group g adds rows
+//            g, g + G, ... of the range in ascending order, the G group sums are added in group order through LDS.
+//   stage 2  one block of 1024 threads = 1024 / kpad thread groups; thread k of group g adds the block sums of element k
+//            of the contiguous blocks [NB g / groups, NB (g + 1) / groups) in block order, the group sums are added in group
+//            order through LDS, and C_k is written as double and, rounded once, in the context dtype (what the sweeps add
+//            to the prior rate).
+// Pad elements are 0 in both kinds of source, so C is 0 there.
+static const int kGammaColsumBlocks = 1024;
+
+template <typename T>
+__global__ __launch_bounds__(256) void gamma_colsum_kernel(const T *src, int64_t rows, int64_t stride, int kpad, int lpr_shift,
+                                                           double *partial /* [gridDim.x][kpad] */) {
+    constexpr int UN = 4;
+    __shared__ double s_sum[256 * PMF_VEC];   // [G][4 LPR]
+    const int lpr = 1 << lpr_shift, G = 256 >> lpr_shift;
+    const int c = threadIdx.x & (lpr - 1), g = threadIdx.x >> lpr_shift;
+    const int koff = c * PMF_VEC;
+    const bool active = koff < kpad;
+    const int64_t r0 = rows * (int64_t)blockIdx.x / gridDim.x, r1 = rows * ((int64_t)blockIdx.x + 1) / gridDim.x;
+    double acc[PMF_VEC] = {0.0, 0.0, 0.0, 0.0};
+    if (active) {
+        const T *at = src + koff;
+        int64_t r = r0 + g;
+        for (; r + (int64_t)(UN - 1) * G < r1; r += (int64_t)UN * G) {
+            Vec4<T> v[UN];
+#pragma unroll
+            for (int q = 0; q < UN; ++q) v[q] = load4(at + (r + (int64_t)q * G) * stride);
+#pragma unroll
+            for (int q = 0; q < UN; ++q)
+#pragma unroll
+                for (int e = 0; e < PMF_VEC; ++e) acc[e] += (double)v[q].v[e];
+        }
+        for (; r < r1; r += G) {
+            const Vec4<T> v = load4(at + r * stride);
+#pragma unroll
+            for (int e = 0; e < PMF_VEC; ++e) acc[e] += (double)v.v[e];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) s_sum[threadIdx.x * PMF_VEC + e] = acc[e];   // = s_sum[g][koff + e], rows of 4 LPR
+    __syncthreads();
+    if ((int)threadIdx.x < kpad) {
+        double t = 0.0;
+        for (int k = 0; k < G; ++k) t += s_sum[k * lpr * PMF_VEC + threadIdx.x];
+        partial[(int64_t)blockIdx.x * kpad + threadIdx.x] = t;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void gamma_colsum_final_kernel(const double *partial, int n_blocks, int kpad, double *out, T *out_t) {
+    __shared__ double s_group[1024];   // [groups][kpad]
+    const int groups = 1024 / kpad;    // >= 4: kpad <= 256
+    const int k = threadIdx.x % kpad, g = threadIdx.x / kpad;
+    if (g < groups) {   // (the threads past groups * kpad have no element)
+        const int b0 = (int)((int64_t)n_blocks * g / groups), b1 = (int)((int64_t)n_blocks * (g + 1) / groups);
+        double t = 0.0;
+#pragma unroll 8
+        for (int b = b0; b < b1; ++b) t += partial[(int64_t)b * kpad + k];
+        s_group[g * kpad + k] = t;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x >= kpad) return;
+    double t = 0.0;
+    for (int j = 0; j < groups; ++j) t += s_group[j * kpad + threadIdx.x];
+    out[threadIdx.x] = t;
+    out_t[threadIdx.x] = (T)t;
+}
+
+// ---------------------------------------------------------------------------
 // fold-in (pmf_gamma_fold_in): the whole n_iter recursion of NEW rows against the frozen other side
 // ---------------------------------------------------------------------------
 // A fold-in row depends on no other row, so its recursion
@@ -315,6 +394,7 @@ struct GammaFoldParams {
     const T *factor_other;
     const T *init_factor;      // [rows][kpad] or null: shape_prior / rho in every element
     const T *init_prior_rate;  // [rows] or null: hyper_shape / hyper_rate_prior
+    const T *colsum;           // [kpad] or null.  PMF_ZEROS_OBSERVED: B of every row is the column sum of factor_other
     T *factor, *shape, *rate;  // [rows][kpad]
     T *prior_rate, *hyper_rate;   // [rows], hierarchical only
     T shape_prior, rate_prior, hyper_shape, hyper_rate_prior;
@@ -444,10 +524,10 @@ __global__ __launch_bounds__(256) void gamma_fold_kernel(GammaFoldParams<T> p) {
         const int32_t *col = p.other + start;
         const T *val = p.val + start;
         GammaFoldRow<T> st = gamma_fold_start(p, row, c, active);
-        Vec4<T> bsum = zero4<T>();
+        Vec4<T> bsum = (p.colsum && active) ? load4(p.colsum + koff) : zero4<T>();
         for (int t = 0; t < p.n_iter; ++t) {
             Vec4<T> acc = zero4<T>();
-            gamma_fold_pass<T, LPR>(p, col, val, n, 0, 1, c, active, t == 0, st.theta, acc, bsum);
+            gamma_fold_pass<T, LPR>(p, col, val, n, 0, 1, c, active, t == 0 && !p.colsum, st.theta, acc, bsum);
             gamma_fold_update<T, LPR>(p, c, active, acc, bsum, st);
         }
         gamma_fold_store(p, row, c, active, st);
@@ -463,13 +543,14 @@ __global__ __launch_bounds__(256) void gamma_fold_kernel(GammaFoldParams<T> p) {
         const int32_t *col = p.other + start;
         const T *val = p.val + start;
         GammaFoldRow<T> st = gamma_fold_start(p, row, c, active);
-        Vec4<T> bsum = zero4<T>();
+        Vec4<T> bsum = (p.colsum && active) ? load4(p.colsum + koff) : zero4<T>();
         for (int t = 0; t < p.n_iter; ++t) {
+            const bool with_b = t == 0 && !p.colsum;   // (the same in every thread)
             Vec4<T> acc = zero4<T>(), bpart = zero4<T>();
-            gamma_fold_pass<T, LPR>(p, col, val, n, g, G, c, active, t == 0, st.theta, acc, bpart);
+            gamma_fold_pass<T, LPR>(p, col, val, n, g, G, c, active, with_b, st.theta, acc, bpart);
             if (active) {
                 store4(part + g * kpad + koff, acc);
-                if (t == 0) store4(part + (G + g) * kpad + koff, bpart);
+                if (with_b) store4(part + (G + g) * kpad + koff, bpart);
             }
             __syncthreads();
             acc = zero4<T>();
@@ -479,7 +560,7 @@ __global__ __launch_bounds__(256) void gamma_fold_kernel(GammaFoldParams<T> p) {
                     const Vec4<T> a = load4(part + s * kpad + koff);
 #pragma unroll
                     for (int e = 0; e < PMF_VEC; ++e) acc.v[e] += a.v[e];
-                    if (t == 0) {
+                    if (with_b) {
                         const Vec4<T> b = load4(part + (G + s) * kpad + koff);
 #pragma unroll
                         for (int e = 0; e < PMF_VEC; ++e) bsum.v[e] += b.v[e];
@@ -520,6 +601,53 @@ template <typename F>
 static int gamma_launch(pmf_ctx *ctx, F &&f) {
     pmf_with_pow2<1>(pmf_lanes_per_row(ctx->kpad), f);
     PMF_HIP_CHECK(hipGetLastError());
+    return PMF_OK;
+}
+
+static bool gamma_zeros_observed(const pmf_ctx *ctx) { return ctx->gamma_zeros == PMF_ZEROS_OBSERVED; }
+
+// the caller-driven and extended forms, which PMF_ZEROS_OBSERVED does not cover
+#define PMF_REQUIRE_ZEROS_MISSING(fn)                                                                                      \
+    PMF_REQUIRE(!gamma_zeros_observed(ctx), PMF_EINVAL,                                                                    \
+                fn ": not available while the context counts unobserved cells as zeros (pmf_ctx_set_gamma_zeros, PMF_ZEROS_OBSERVED)")
+
+// The work area of one column sum inside a scratch layout -- the block sums, C in double, C in the context dtype -- and
+// its two launches (the caller holds the profile bracket -- brackets do not nest -- and checks the launch).  `on` false:
+// the layout gets nothing and launch() must not be called.
+template <typename T>
+struct GammaColsum {
+    PmfLayout::Piece<double> part_at, sum_at;
+    PmfLayout::Piece<T> sum_t_at;
+    GammaColsum(PmfLayout &lay, int kpad, bool on = true)
+        : part_at(lay.add<double>(on ? (size_t)kGammaColsumBlocks * kpad : 0)), sum_at(lay.add<double>(on ? (size_t)kpad : 0)),
+          sum_t_at(lay.add<T>(on ? (size_t)kpad : 0)) {}
+    void launch(pmf_ctx *ctx, void *base, const T *src, int64_t rows, int64_t stride) const {
+        int shift = 0;
+        while ((1 << shift) < pmf_lanes_per_row(ctx->kpad)) ++shift;
+        hipLaunchKernelGGL((gamma_colsum_kernel<T>), dim3(kGammaColsumBlocks), dim3(256), 0, ctx->stream, src, rows, stride, ctx->kpad, shift,
+                           part_at.at(base));
+        hipLaunchKernelGGL((gamma_colsum_final_kernel<T>), dim3(1), dim3(1024), 0, ctx->stream, part_at.at(base), kGammaColsumBlocks, ctx->kpad,
+                           sum_at.at(base), sum_t_at.at(base));
+    }
+};
+
+// The column sums of `src` ([rows][stride]) into the context's scratch buffer, which holds nothing else for the caller:
+// *sum (double) and *sum_t (context dtype) stay valid until the next call that lays out the scratch buffer.  Timed as
+// PMF_KERNEL_GAMMA_FINAL, in a bracket of its own: call it outside any other.
+template <typename T>
+static int gamma_colsum_scratch(pmf_ctx *ctx, const T *src, int64_t rows, int64_t stride, const double **sum, const T **sum_t) {
+    PmfLayout lay(256);
+    const GammaColsum<T> cs(lay, ctx->kpad);
+    int rc;
+    if ((rc = pmf_ensure_scratch(ctx, lay.bytes()))) return rc;
+    void *base = ctx->d_scratch.as();
+    {
+        PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
+        cs.launch(ctx, base, src, rows, stride);
+    }
+    PMF_HIP_CHECK(hipGetLastError());
+    if (sum) *sum = cs.sum_at.at(base);
+    if (sum_t) *sum_t = cs.sum_t_at.at(base);
     return PMF_OK;
 }
 
@@ -565,6 +693,7 @@ static GammaParams<T> gamma_params(const pmf_ctx *ctx, int side, const PmfTaskVi
     p.pw = pw;
     p.partial = ctx->d_partial.as<T>();
     p.stats = (T *)stats;
+    p.colsum = nullptr;
     p.shape_prior = (T)pr.shape;
     p.rate_prior = (T)pr.rate;
     p.hyper_shape = (T)pr.hyper_shape;
@@ -605,7 +734,12 @@ static int run_gamma(pmf_ctx *ctx, int side, PmfPass pass, bool ext, void *stats
         if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SCALE_SHAPE))) return rc;
         if ((rc = pmf_alloc_array(ctx, side, PMF_ARR_SCALE_RATE))) return rc;
     }
-    const GammaParams<T> p = gamma_params<T>(ctx, side, tl, stats, pr, pw);
+    GammaParams<T> p = gamma_params<T>(ctx, side, tl, stats, pr, pw);
+    // unlisted cells as zeros (fused pass of the plain model only: the entry points refuse the rest): every row's rate sum
+    // is the column sum of the other side's FACTOR as it is now
+    if (gamma_zeros_observed(ctx) && pass == PMF_PASS_FUSED && !ext &&
+        (rc = gamma_colsum_scratch<T>(ctx, p.factor_other, ctx->rows[1 - side], ctx->kpad, nullptr, &p.colsum)))
+        return rc;
     return gamma_launch(ctx, [&](auto L) {
         constexpr int G = 256 / L;
         if (pass == PMF_PASS_FINALIZE) {
@@ -670,6 +804,7 @@ extern "C" int pmf_gamma_sweep(pmf_ctx *ctx, int side, double shape_prior, doubl
 
 extern "C" int pmf_gamma_ext_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior) {
     PMF_SIDE_ENTRY("pmf_gamma_ext_sweep");
+    PMF_REQUIRE_ZEROS_MISSING("pmf_gamma_ext_sweep");
     PMF_REQUIRE(!pmf_comm_active(ctx), PMF_EINVAL, "pmf_gamma_ext_sweep: the extended model is not available on several ranks");
     const GammaPriors pr = {shape_prior, rate_prior};
     return pmf_with_dtype(ctx, [&](auto t) { return run_gamma<decltype(t)>(ctx, side, PMF_PASS_FUSED, true, nullptr, pr); });
@@ -677,6 +812,7 @@ extern "C" int pmf_gamma_ext_sweep(pmf_ctx *ctx, int side, double shape_prior, d
 
 extern "C" int pmf_gamma_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
     PMF_SIDE_ENTRY("pmf_gamma_accumulate");
+    PMF_REQUIRE_ZEROS_MISSING("pmf_gamma_accumulate");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gamma_accumulate: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_gamma<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, false, stats_dev, {}); });
 }
@@ -685,6 +821,7 @@ extern "C" int pmf_gamma_finalize(pmf_ctx *ctx, int side, const void *stats_dev,
                                   double rate_prior, int hierarchical, double hyper_shape,
                                   double hyper_rate_prior) {
     PMF_SIDE_ENTRY("pmf_gamma_finalize");
+    PMF_REQUIRE_ZEROS_MISSING("pmf_gamma_finalize");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gamma_finalize: null stats buffer");
     const GammaPriors pr = {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior};
     return pmf_with_dtype(ctx, [&](auto t) { return run_gamma<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, false, (void *)stats_dev, pr); });
@@ -734,6 +871,11 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
     std::vector<int32_t> list;   // the short rows, then the long rows
     std::vector<T> init, init_rate;
     int rc;
+    // unlisted cells as zeros: B of every row is the column sum of the other side's FACTOR, formed once per call
+    const T *colsum = nullptr;
+    if (gamma_zeros_observed(ctx) &&
+        (rc = gamma_colsum_scratch<T>(ctx, ctx->arr[1 - side][PMF_ARR_FACTOR].as<const T>(), ctx->rows[1 - side], kpad, nullptr, &colsum)))
+        return rc;
     for (int64_t r0 = 0; r0 < a.n_rows; r0 = st.r1) {
         // (the previous block ended with a stream synchronise: nothing queued still reads the block's buffers)
         if ((rc = st.stage(ctx, a.n_rows, a.row_ptr, a.ratings, r0, max_rows))) return rc;
@@ -780,6 +922,7 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
         p.factor_other = ctx->arr[1 - side][PMF_ARR_FACTOR].as<const T>();
         p.init_factor = a.init_factor ? d_init.as<const T>() : nullptr;
         p.init_prior_rate = hier && a.init_prior_rate ? d_init_rate.as<const T>() : nullptr;
+        p.colsum = colsum;
         p.factor = d_factor.as<T>();
         p.shape = d_shape.as<T>();
         p.rate = d_rate.as<T>();
@@ -917,6 +1060,7 @@ struct GammaElboRowParams {
     const T *hyper_rate;     // [rows], or null: not hierarchical
     T *table;                // [rows][2][kpad]
     double *out;             // [rows][PMF_GAMMA_ELBO_TERMS], or null: the table only (the other side of a data call)
+    const double *colsum;    // [kpad] column sums of the other side's E, or null.  PMF_ZEROS_OBSERVED: DATA starts at -E_r . C
     int64_t rows;
     int K, kpad;
 };
@@ -935,7 +1079,7 @@ __global__ __launch_bounds__(256) void gamma_elbo_row_kernel(GammaElboRowParams<
         b4 = load4(p.rate + row * p.kpad + koff);
     }
     Vec4<T> elog, ex;
-    double sum_e = 0.0, sum_elog = 0.0, entropy = 0.0;
+    double sum_e = 0.0, sum_elog = 0.0, entropy = 0.0, zeros = 0.0;
 #pragma unroll
     for (int e = 0; e < PMF_VEC; ++e) {
         elog.v[e] = (T)(-INFINITY);
@@ -948,6 +1092,7 @@ __global__ __launch_bounds__(256) void gamma_elbo_row_kernel(GammaElboRowParams<
             if (p.out) entropy += a - lb + lgamma(a) + (1.0 - a) * psi;
             elog.v[e] = (T)el;
             ex.v[e] = (T)x;
+            if (p.out && p.colsum) zeros += (double)ex.v[e] * p.colsum[koff + e];   // (the table's E: what C of this side sums)
         }
     }
     if (active) {
@@ -959,6 +1104,7 @@ __global__ __launch_bounds__(256) void gamma_elbo_row_kernel(GammaElboRowParams<
     sum_e = group_sum<LPR>(sum_e);
     sum_elog = group_sum<LPR>(sum_elog);
     entropy = group_sum<LPR>(entropy);
+    if (p.colsum) zeros = group_sum<LPR>(zeros);   // (the same in every lane)
     if (c == 0) {
         double *o = p.out + row * PMF_GAMMA_ELBO_TERMS;
         o[PMF_GAMMA_ELBO_SUM_FACTOR] = sum_e;
@@ -969,7 +1115,7 @@ __global__ __launch_bounds__(256) void gamma_elbo_row_kernel(GammaElboRowParams<
         o[PMF_GAMMA_ELBO_LOG_HYPER] = hier ? log(h) : 0.0;
         o[PMF_GAMMA_ELBO_INV_HYPER] = hier ? 1.0 / h : 0.0;
         o[PMF_GAMMA_ELBO_FACTOR_OVER_HYPER] = hier ? sum_e / h : 0.0;
-        o[PMF_GAMMA_ELBO_DATA] = 0.0;      // (the data pass writes over these two)
+        o[PMF_GAMMA_ELBO_DATA] = p.colsum ? -zeros : 0.0;   // (the data pass writes over these two; with `colsum` it adds to DATA)
         o[PMF_GAMMA_ELBO_LOGFACT] = 0.0;
     }
 }
@@ -985,6 +1131,7 @@ struct GammaElboDataParams {
     double *part_logfact;                // [n_slots]
     double *out;                         // [rows][PMF_GAMMA_ELBO_TERMS]
     int kpad;
+    int zeros;                           // PMF_ZEROS_OBSERVED: no E . E per rating; DATA is added to what the row pass left (-E_r . C)
 };
 
 template <typename T, int LPR>
@@ -1037,7 +1184,7 @@ __global__ __launch_bounds__(256) void gamma_elbo_data_kernel(GammaElboDataParam
                 if (active) {
                     const T *src = p.table_other + (int64_t)o[q] * 2 * kpad + koff;
                     bl[q] = load4(src);
-                    be[q] = load4(src + kpad);
+                    if (!p.zeros) be[q] = load4(src + kpad);   // (else d below is 0: the row pass has the product over ALL cells)
                 }
             }
 #pragma unroll
@@ -1069,7 +1216,7 @@ __global__ __launch_bounds__(256) void gamma_elbo_data_kernel(GammaElboDataParam
         p.part_logfact[t.slot] = logfact;
     } else {
         double *o = p.out + (int64_t)t.row * PMF_GAMMA_ELBO_TERMS;
-        o[PMF_GAMMA_ELBO_DATA] = (double)acc;
+        o[PMF_GAMMA_ELBO_DATA] = p.zeros ? o[PMF_GAMMA_ELBO_DATA] + (double)acc : (double)acc;
         o[PMF_GAMMA_ELBO_LOGFACT] = logfact;
     }
 }
@@ -1077,7 +1224,7 @@ __global__ __launch_bounds__(256) void gamma_elbo_data_kernel(GammaElboDataParam
 // one thread per split row: its partial sums in slot order
 template <typename T>
 __global__ void gamma_elbo_split_kernel(const PmfSplitRow *split, int64_t n_split, const T *part_data, const double *part_logfact,
-                                        double *out) {
+                                        double *out, int zeros) {
     const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (at >= n_split) return;
     const PmfSplitRow sr = split[at];
@@ -1088,14 +1235,14 @@ __global__ void gamma_elbo_split_kernel(const PmfSplitRow *split, int64_t n_spli
         lf += part_logfact[sr.first_slot + s];
     }
     double *o = out + (int64_t)sr.row * PMF_GAMMA_ELBO_TERMS;
-    o[PMF_GAMMA_ELBO_DATA] = (double)d;
+    o[PMF_GAMMA_ELBO_DATA] = zeros ? o[PMF_GAMMA_ELBO_DATA] + (double)d : (double)d;
     o[PMF_GAMMA_ELBO_LOGFACT] = lf;
 }
 
 // gamma_elbo_row_kernel over the rows of side `s`: their (E log, E) table into `table` and, with `out`, the per-row
 // terms (`hierarchical`: those of HYPER_RATE among them).  The caller holds the profile bracket and checks the launch.
 template <typename T, int LPR>
-static void launch_gamma_row_table(pmf_ctx *ctx, int s, T *table, double *out, bool hierarchical) {
+static void launch_gamma_row_table(pmf_ctx *ctx, int s, T *table, double *out, bool hierarchical, const double *colsum = nullptr) {
     constexpr int G = 256 / LPR;
     GammaElboRowParams<T> r;
     r.shape = ctx->arr[s][PMF_ARR_SHAPE].as<const T>();
@@ -1103,6 +1250,7 @@ static void launch_gamma_row_table(pmf_ctx *ctx, int s, T *table, double *out, b
     r.hyper_rate = hierarchical ? ctx->arr[s][PMF_ARR_HYPER_RATE].as<const T>() : nullptr;
     r.table = table;
     r.out = out;
+    r.colsum = colsum;
     r.rows = ctx->rows[s];
     r.K = ctx->K;
     r.kpad = ctx->kpad;
@@ -1126,6 +1274,9 @@ static int run_gamma_elbo_terms(pmf_ctx *ctx, int side, bool with_data, bool hie
     const auto pd_at = lay.add<T>((size_t)tl.n_slots);
     const auto self_at = lay.add<T>((size_t)rows * 2 * kpad);
     const auto other_at = lay.add<T>(with_data ? (size_t)rows_o * 2 * kpad : 0);
+    // unlisted cells as zeros: sum over ALL cells of E_r . E_o = E_r . C, C the column sums of the other side's E half
+    const bool zeros = with_data && gamma_zeros_observed(ctx);
+    const GammaColsum<T> cs(lay, kpad, zeros);   // (the default mode's scratch layout stays what it was)
     int rc;
     if ((rc = pmf_ensure_scratch(ctx, lay.bytes()))) return rc;
     void *base = ctx->d_scratch.as();
@@ -1143,12 +1294,14 @@ static int run_gamma_elbo_terms(pmf_ctx *ctx, int side, bool with_data, bool hie
     d.part_logfact = d_lf;
     d.out = d_out;
     d.kpad = kpad;
+    d.zeros = zeros;
     pmf_with_pow2<1>(lpr, [&](auto L) {
         constexpr int G = 256 / L;
         if (rows > 0) {
             PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
-            launch_gamma_row_table<T, L>(ctx, side, d_self, d_out, hierarchical);
             if (with_data) launch_gamma_row_table<T, L>(ctx, other, d_other, nullptr, false);   // the other side: its table only
+            if (zeros) cs.launch(ctx, base, d_other + kpad, rows_o, 2 * (int64_t)kpad);   // (inside this bracket: the row pass)
+            launch_gamma_row_table<T, L>(ctx, side, d_self, d_out, hierarchical, zeros ? cs.sum_at.at(base) : nullptr);
         }
         if (with_data && tl.n_tasks > 0) {
             PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
@@ -1157,7 +1310,7 @@ static int run_gamma_elbo_terms(pmf_ctx *ctx, int side, bool with_data, bool hie
         if (with_data && tl.n_split > 0) {
             PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
             hipLaunchKernelGGL((gamma_elbo_split_kernel<T>), dim3((unsigned)((tl.n_split + 255) / 256)), dim3(256), 0, ctx->stream,
-                               tl.d_split, tl.n_split, d_pd, d_lf, d_out);
+                               tl.d_split, tl.n_split, d_pd, d_lf, d_out, (int)zeros);
         }
     });
     PMF_HIP_CHECK(hipGetLastError());
@@ -1311,12 +1464,12 @@ static T *gamma_exact_table(const pmf_ctx *ctx, int side) {
 
 // Both sides' (E log, E) tables from SHAPE and RATE as they are now, on the context's stream (timed as the row pass).
 template <typename T>
-static int gamma_exact_build_tables(pmf_ctx *ctx) {
+static int gamma_exact_build_tables(pmf_ctx *ctx, std::initializer_list<int> sides = {PMF_SIDE_USER, PMF_SIDE_ITEM}) {
     int rc;
     if ((rc = ctx->d_gamma_tables.reserve(ctx, (size_t)(ctx->rows[0] + ctx->rows[1]) * 2 * ctx->kpad * sizeof(T), {ctx->stream}))) return rc;
     PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
     pmf_with_pow2<1>(pmf_lanes_per_row(ctx->kpad), [&](auto L) {
-        for (int s = 0; s < 2; ++s) launch_gamma_row_table<T, L>(ctx, s, gamma_exact_table<T>(ctx, s), nullptr, false);
+        for (int s : sides) launch_gamma_row_table<T, L>(ctx, s, gamma_exact_table<T>(ctx, s), nullptr, false);
     });
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
@@ -1336,8 +1489,12 @@ static int run_gamma_exact(pmf_ctx *ctx, int side, PmfPass pass, bool tables, vo
     const int pw = 2 * ctx->kpad;
     if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * pw * sizeof(T)))) return rc;
     if (tables && (rc = gamma_exact_build_tables<T>(ctx))) return rc;
-    const GammaParams<T> p = gamma_params<T>(ctx, side, tl, stats, pr, pw);
+    GammaParams<T> p = gamma_params<T>(ctx, side, tl, stats, pr, pw);
     const T *table_self = gamma_exact_table<T>(ctx, side), *table_other = gamma_exact_table<T>(ctx, 1 - side);
+    // unlisted cells as zeros (fused pass only): every row's rate sum is the column sum of the other table's E half
+    if (gamma_zeros_observed(ctx) && pass == PMF_PASS_FUSED &&
+        (rc = gamma_colsum_scratch<T>(ctx, table_other + ctx->kpad, ctx->rows[1 - side], 2 * (int64_t)ctx->kpad, nullptr, &p.colsum)))
+        return rc;
     return gamma_launch(ctx, [&](auto L) {
         if (pass == PMF_PASS_ACCUMULATE)   // (the split kernel is the reference sweep's)
             launch_gamma<T, L, true, false, gamma_exact_kernel<T, L, true>>(ctx, p, tl, table_self, table_other);
@@ -1368,10 +1525,39 @@ extern "C" int pmf_gamma_exact_sweep(pmf_ctx *ctx, int side, double shape_prior,
 
 extern "C" int pmf_gamma_exact_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
     PMF_SIDE_ENTRY("pmf_gamma_exact_accumulate");
+    PMF_REQUIRE_ZEROS_MISSING("pmf_gamma_exact_accumulate");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gamma_exact_accumulate: null stats buffer");
     int rc;
     if ((rc = check_gamma_exact_inputs(ctx, side, "pmf_gamma_exact_accumulate"))) return rc;
     return pmf_with_dtype(ctx, [&](auto t) { return run_gamma_exact<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, true, stats_dev, {}); });
+}
+
+// C_k of `side`: the column sums of FACTOR, or (from_q) of the E half of the side's freshly built (E log, E) table
+extern "C" int pmf_gamma_column_sums(pmf_ctx *ctx, int side, int from_q, double *out) {
+    PMF_SIDE_ENTRY("pmf_gamma_column_sums");
+    PMF_REQUIRE(out != nullptr, PMF_EINVAL, "pmf_gamma_column_sums: null out");
+    int rc;
+    if (from_q) {
+        if ((rc = require_gamma_q(ctx, {side}, "pmf_gamma_column_sums"))) return rc;
+    } else if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gamma_column_sums"))) {
+        return rc;
+    }
+    return pmf_with_dtype(ctx, [&](auto t) {
+        using T = decltype(t);
+        int rc;
+        const T *src = ctx->arr[side][PMF_ARR_FACTOR].as<const T>();
+        int64_t stride = ctx->kpad;
+        if (from_q) {
+            if ((rc = gamma_exact_build_tables<T>(ctx, {side}))) return rc;
+            src = gamma_exact_table<T>(ctx, side) + ctx->kpad;
+            stride = 2 * (int64_t)ctx->kpad;
+        }
+        const double *sum = nullptr;
+        if ((rc = gamma_colsum_scratch<T>(ctx, src, ctx->rows[side], stride, &sum, nullptr))) return rc;
+        PMF_HIP_CHECK(hipMemcpyAsync(out, sum, (size_t)ctx->K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return PMF_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------

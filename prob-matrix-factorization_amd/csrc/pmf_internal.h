@@ -206,6 +206,9 @@ struct pmf_ctx {
     // owns under the SCATTER_GATHER exchange); -1 = the whole selected chunk
     int64_t fin_row0 = -1, fin_row1 = -1;
     int exchange = PMF_EXCHANGE_AUTO;   // pmf_comm_set_exchange
+    // pmf_ctx_set_gamma_zeros: PMF_ZEROS_OBSERVED makes the Poisson / HPF calls count every unlisted cell as a rating of 0
+    // (the rate sums come from the other side's column sums, pmf_gamma.hip).  Never set together with a communicator.
+    int gamma_zeros = PMF_ZEROS_MISSING;
 
     PmfBuf arr[2][PMF_ARR_COUNT];   // model state, pmf_array_elems(side, array) elements of the context dtype
     PmfSideIndex index[2];

@@ -40,6 +40,7 @@ ELBO_SQNORM, ELBO_LOGDET, ELBO_BIAS_SQ, ELBO_ESS, ELBO_TERMS = 0, 1, 2, 3, 4    
 # columns of pmf_gamma_predictive's log densities; its totals are [sum of var, then one sum per column]
 GAMMA_PRED_PLUGIN, GAMMA_PRED_BOUND, GAMMA_PRED_NEGBIN, GAMMA_PRED_KINDS, GAMMA_PRED_TOTALS = 0, 1, 2, 3, 4
 TASK_LISTS = {"gamma": 0, "gauss": 1, "bias": 2, "sgd": 3}
+ZEROS_MISSING, ZEROS_OBSERVED = 0, 1          # pmf_ctx_set_gamma_zeros
 
 
 class PmfLibraryError(RuntimeError):
@@ -90,6 +91,9 @@ SIGNATURES = {
     "pmf_gamma_finalize": (C.c_int, [_p, C.c_int, _p, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]),
     "pmf_gamma_exact_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double]),
     "pmf_gamma_exact_accumulate": (C.c_int, [_p, C.c_int, _p]),
+    "pmf_ctx_set_gamma_zeros": (C.c_int, [_p, C.c_int]),
+    "pmf_ctx_get_gamma_zeros": (C.c_int, [_p, C.POINTER(C.c_int)]),
+    "pmf_gamma_column_sums": (C.c_int, [_p, C.c_int, C.c_int, _f64p]),
     "pmf_gamma_predictive": (C.c_int, [_p, C.c_int64, _i32p, _i32p, _f64p, C.c_int, _f64p, _f64p, _f64p, _f64p]),
     "pmf_gauss_factor_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),
     "pmf_gauss_bias_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),

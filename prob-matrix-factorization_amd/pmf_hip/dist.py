@@ -281,7 +281,8 @@ def gamma_iteration(engine, comm, stats_item, user_prior, item_prior, exact=Fals
     hyper_shape, hyper_rate_prior) as taken by `gamma_sweep`.  `stats_item` is only used with an
     external collective: the [I x 2 x Kpad] buffer object with `.ptr` and `.tensor`.  `exact`: the
     exact coordinate-ascent update (`gamma_exact_sweep` / `gamma_exact_accumulate`) instead of the
-    reference's."""
+    reference's.  A context that counts unobserved cells as zeros (`set_gamma_zeros`) cannot have a
+    communicator and refuses the accumulate / finalize pair: it runs the two fused calls."""
     sweep = engine.gamma_exact_sweep if exact else engine.gamma_sweep
     sweep(USER, *user_prior)
     if _fused_item(comm):

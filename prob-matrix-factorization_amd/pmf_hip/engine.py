@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import (ARR_COV, ELBO_TERMS, EXCHANGE, F32, F64, GAMMA_ELBO_TERMS, GAMMA_PRED_KINDS, GAMMA_PRED_TOTALS, ITEM, KERNEL_NAMES, MAX_LABELS, OP_MAX, OP_SUM, TASK_LISTS, TEST_LIB_PATH,
-               UNIQUE_ID_BYTES, USER, PmfError, PmfLibraryError, as_f64, as_i32, check, load, ptr)
+               UNIQUE_ID_BYTES, USER, ZEROS_MISSING, ZEROS_OBSERVED, PmfError, PmfLibraryError, as_f64, as_i32, check, load, ptr)
 
 
 def group_rows(row, n):
@@ -321,6 +321,28 @@ class Context:
     def gamma_exact_accumulate(self, side, stats_ptr):
         """The raw sums of `gamma_exact_sweep` in `gamma_accumulate`'s layout; `gamma_finalize` finalises them."""
         check(self._lib.pmf_gamma_exact_accumulate(self._h, side, C.c_void_p(stats_ptr)), "pmf_gamma_exact_accumulate")
+
+    # ---- Poisson / HPF with unlisted cells counted as zeros (implicit feedback) ----
+    def set_gamma_zeros(self, observed):
+        """`observed=True`: the Poisson MF / HPF calls of this context count every (user, item) cell without a rating
+        as a count of 0 (`pmf_ctx_set_gamma_zeros`, PMF_ZEROS_OBSERVED) -- the sweeps, the fold-in and the ELBO's data
+        term; `False` (the default of a new context): only the listed ratings are data.  Not available with a communicator,
+        nor for the accumulate / finalize pair and the extended model."""
+        check(self._lib.pmf_ctx_set_gamma_zeros(self._h, ZEROS_OBSERVED if observed else ZEROS_MISSING), "pmf_ctx_set_gamma_zeros")
+
+    @property
+    def gamma_zeros(self):
+        """True when unlisted cells count as zeros."""
+        mode = C.c_int(0)
+        check(self._lib.pmf_ctx_get_gamma_zeros(self._h, C.byref(mode)), "pmf_ctx_get_gamma_zeros")
+        return mode.value == ZEROS_OBSERVED
+
+    def gamma_column_sums(self, side, from_q=False):
+        """[K] float64: the sum over all rows of `side` of FACTOR, or with `from_q` of SHAPE / RATE as the (E log, E)
+        tables hold it (`pmf_gamma_column_sums`); summed in double on the device, the same bits on every call."""
+        out = np.zeros(self.K, dtype=np.float64)
+        check(self._lib.pmf_gamma_column_sums(self._h, side, int(bool(from_q)), ptr(out, C.c_double)), "pmf_gamma_column_sums")
+        return out
 
     def gamma_predictive(self, user_ids, item_ids, ratings=None, with_bound=True, per_pair=True):
         """Posterior predictive of the Poisson MF / HPF models for the pairs (`pmf_gamma_predictive`; q is SHAPE and RATE

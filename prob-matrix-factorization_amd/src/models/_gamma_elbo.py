@@ -66,6 +66,23 @@ def check_update(update, train_df):
     return update == "exact"
 
 
+def check_unobserved(model, unobserved, train_df):
+    """`fit`'s `unobserved` argument -> whether unlisted cells count as zeros; refuses an unknown value and, for "zero",
+    what the mode does not cover, before any device call.  The frame is looked at only under "zero"."""
+    if unobserved not in ("missing", "zero"):
+        raise ValueError(f"unobserved must be 'missing' or 'zero', not {unobserved!r}")
+    if unobserved == "missing":
+        return False
+    if model._comm is not None:
+        raise ValueError("unobserved='zero' with comm=: counting unobserved cells as zeros is not available on several ranks")
+    ratings = train_df["rating"].to_numpy(dtype=float)
+    if len(ratings) and float(np.min(ratings)) < 0:
+        raise ValueError("unobserved='zero': a training rating is negative; the Poisson likelihood is not defined for it")
+    if train_df.duplicated(subset=["u", "i"]).any():
+        raise ValueError("unobserved='zero': train_df lists a (u, i) pair more than once; a cell has one count")
+    return True
+
+
 def model_elbo(model, ctx):
     """(value, parts) for the state `ctx` holds: the data term from the user side, whose gathers hit the smaller item
     table, and the item side without data."""

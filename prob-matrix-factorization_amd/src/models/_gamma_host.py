@@ -15,7 +15,7 @@ from pmf_hip import dist as pdist
 
 class GammaModel(DeviceModel):
     def fit(self, train_df, val_df=None, *, track_elbo=False, elbo_tol=None, update="reference", track_loglik=False, loglik_tol=None,
-            loglik_kind="plugin"):
+            loglik_kind="plugin", unobserved="missing"):
         """`track_elbo`: evaluate the evidence lower bound after every iteration (`history_["elbo"]`, an `ELBO:` line
         when verbose; measured at K = 64 fp32, 1M users, 50M ratings: the user call's two kernels take 3.00 times a user
         half-sweep (the data pass 2.34 times the sweep's gather ceiling); an `elbo()` takes 5.27 times a whole iteration by wall
@@ -34,8 +34,17 @@ class GammaModel(DeviceModel):
         "plugin" (default: the reference's PoissonLogPredictiveLikelihood at the factor means), "bound" or "negbin", as
         for `log_predictive_density`.  `loglik_tol` (implies `track_loglik`): stop when (L_t - L_{t-1}) / |L_{t-1}| falls
         below it -- the stopping rule of the HPF paper; it fires on a decrease too.  It is independent of, and checked after,
-        the RMSE rule and `elbo_tol`.  Cost: DESIGN.md section 4.13."""
+        the RMSE rule and `elbo_tol`.  Cost: DESIGN.md section 4.13.
+        `unobserved`: "missing" (default) -- the rating list is the whole data set, as in the reference; "zero" -- every
+        (user, item) cell without a rating is a count of 0, the model of the HPF paper and the one click, purchase or play
+        counts need (`pmf_ctx_set_gamma_zeros`: the rate sums come from the other side's column sums, the cost does not
+        depend on the number of cells).  The fit equals a "missing" fit of the frame with every
+        missing cell listed as an explicit 0.  Works with both `update`s; recorded in `history_["unobserved"]` and kept
+        with the model: `elbo()`, `track_elbo`, `fold_in_users` and `fold_in_items` of the fitted model run in the same
+        mode (a new row's unlisted cells are zeros too).  "zero" refuses a negative rating, duplicate (u, i) pairs (a cell
+        has one count) and `comm=` (not available on several ranks)."""
         cfg = self.config
+        zeros = _gamma_elbo.check_unobserved(self, unobserved, train_df)
         exact = _gamma_elbo.check_update(update, train_df)
         track_elbo = _gamma_elbo.check_tracking(self, track_elbo, elbo_tol, train_df)
         track_loglik = _gamma_predictive.check_tracking(self, track_loglik, loglik_tol, loglik_kind, val_df)
@@ -43,6 +52,10 @@ class GammaModel(DeviceModel):
         self._draw_start()
         u, i, x = frame_arrays(train_df)
         ctx = self._open_context(u, i, x)
+        if zeros:                      # (a new context starts in "missing": a default fit makes the calls it made)
+            ctx.set_gamma_zeros(True)
+        self.unobserved_ = unobserved
+        self.history_["unobserved"] = unobserved
         self.history_.pop("elbo", None)
         if track_elbo:
             self.history_["elbo"] = []
@@ -101,7 +114,9 @@ class GammaModel(DeviceModel):
         (poisson_mf_cavi.py:135-167; theta then xi, hpf_cavi.py:126-159) from the prior mean, on the device
         (`pmf_gamma_fold_in`), without a refit.  Rows with an item id the fit has not seen are dropped; a user left
         without ratings runs the same updates on empty sums.  The row update is the reference's even for a model fitted
-        with `update="exact"`.  Returns a `GammaFoldIn`, one row per label in sorted order."""
+        with `update="exact"`.  After `fit(unobserved="zero")` a new user's unlisted items are zeros too: the rate is the
+        prior rate plus the column sum of the fitted items' factors.  Returns a `GammaFoldIn`, one row per label in sorted
+        order."""
         return gamma_fold_in(self, USER, df, n_iter, self._priors()[USER])
 
     def fold_in_items(self, df, n_iter=10):
