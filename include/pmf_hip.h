@@ -478,7 +478,8 @@ int pmf_gauss_bias_sweep(pmf_ctx *ctx, int side, double sigma2, double eta_bias2
  * out_factor[r] = m^n_iter, out_cov[r] = V (full K x K), out_bias[r] = b^n_iter.  V does not depend on b and m is
  * affine in it, so the covariance rows are gathered once per call whatever n_iter is.  Unless both sides have a
  * BIAS array, b = 0 throughout, n_iter has no effect and out_bias is zeros.  A row without ratings gets the prior:
- * m = 0, V = eta2 I, b = 0.  out_cov / out_bias may be NULL (nothing K x K is then expanded or copied).
+ * m = 0, V = eta2 I, b = 0 (under pmf_ctx_set_gauss_zeros' PMF_ZEROS_OBSERVED, below, every row is blended with the
+ * opposite side's Gram matrix and solved instead).  out_cov / out_bias may be NULL (nothing K x K is then expanded or copied).
  * Reads the context's model state only: state, ratings, work lists and the stored validation set stay as they
  * are; FACTOR / COV of `side` itself are not needed; never a collective, with or without a communicator.
  * PMF_EINVAL: null context (whatever n_rows is), bad side, n_rows < 0, a null array that is needed, row_ptr[0] != 0
@@ -526,10 +527,59 @@ int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row
 #define PMF_ELBO_SQNORM 0    /* |m_r|^2 + tr V_r */
 #define PMF_ELBO_LOGDET 1    /* log det V_r; NaN for a row whose COV is not positive definite */
 #define PMF_ELBO_BIAS_SQ 2   /* BIAS[r]^2; 0 unless both sides have a BIAS array */
-#define PMF_ELBO_ESS 3       /* c_r - 2 m_r.w_r + <V_r + m_r m_r', S_r>; 0 for a row without ratings or when with_data == 0 */
+#define PMF_ELBO_ESS 3       /* c_r - 2 m_r.w_r + <V_r + m_r m_r', S_r>; 0 for a row without ratings (PMF_ZEROS_MISSING) or when with_data == 0 */
 #define PMF_ELBO_TERMS 4
 int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, double *totals /* [PMF_ELBO_TERMS] */,
                          double *per_row /* rows x PMF_ELBO_TERMS, may be NULL */);
+
+/* Implicit feedback for the bias-free Gaussian model: unlisted cells as weighted zeros.  No
+ * reference counterpart (the reference treats the rating list as the whole data set; that stays the default).
+ * pmf_ctx_set_gauss_zeros selects, for pmf_gauss_factor_sweep, pmf_gauss_fold_in and pmf_gauss_elbo_terms of this
+ * context, what a (user, item) cell without a rating is:
+ *     PMF_ZEROS_MISSING   (default) not an observation: every sum runs over the listed ratings, bit for bit as before
+ *     PMF_ZEROS_OBSERVED  an observation of 0 (in pmf_ctx_set_ratings' convention) with variance sigma2 / weight,
+ *                         weight in (0, 1]: 1 = every missing cell listed as an explicit 0, 1 / (1 + alpha) = the
+ *                         confidence ratio of implicit ALS (Hu, Koren & Volinsky 2008)
+ * With A_o = COV[o] + FACTOR[o] FACTOR[o]^T of a row of the other side, S_r and w_r the listed sums above and
+ * G = sum over ALL rows o of the other side of A_o (K x K, the Gram matrix):
+ *     S'_r   = (1 - weight) S_r + weight G
+ *     COV[r] = inv(I/eta2 + S'_r/sigma2),  FACTOR[r] = COV[r] w_r / sigma2     for EVERY row, with or without ratings
+ *     ESS_r  = c_r - 2 m_r . w_r + < V_r + m_r m_r^T, S'_r >                    (c_r = 0 for a row without ratings)
+ *     L      = -1/2 [ N log(2 pi sigma2) + (U I - N) log(2 pi sigma2 / weight) ] - sum_r ESS_r / (2 sigma2)
+ *              + the prior and entropy blocks as above
+ * A row without ratings is no special case: m = 0 exactly and V = inv(I/eta2 + weight G/sigma2).  ESS summed over the
+ * rows of either side gives the same total.
+ *   pmf_gauss_factor_sweep  G of the other side from its state as it is when the call starts (pmf_gauss_gram's two
+ *                           launches), then per row window (the windows of pmf_gauss_elbo_terms, PMF_ELBO_ROWS):
+ *                           accumulate into a context-owned window, blend (S = fma(T(1 - weight), S, T(weight G)), one
+ *                           element-wise pass), and the row solver over all rows of the window.
+ *   pmf_gauss_fold_in       G of the opposite side once per call; every row of the batch is blended and solved, so a row
+ *                           without ratings gets inv(I/eta2 + weight G/sigma2), not the prior.
+ *   pmf_gauss_elbo_terms    with_data != 0: ESS from S'; every row has an ESS.  with_data == 0: unchanged.
+ * A property of the context, independent of pmf_ctx_set_gamma_zeros: no state array changes, and it may be set before or
+ * after the ratings.  `weight` is ignored (and the stored weight kept) under PMF_ZEROS_MISSING; the getter returns the
+ * stored weight, 1.0 for a new context.  pmf_predict*, the top-k / rank calls and the Poisson / HPF calls do not read
+ * the mode.  Duplicate (u, i) pairs are each a listed rating; a cell with one rating is the caller's to ensure (the
+ * model classes refuse duplicates).
+ * Not covered, PMF_EINVAL naming the mode, while the mode is PMF_ZEROS_OBSERVED: the three calls above when both sides
+ * have a BIAS array; pmf_gauss_bias_sweep / _accumulate / _finalize; pmf_gauss_factor_accumulate / _finalize;
+ * pmf_gauss_sgd_sweep / _accumulate / _finalize; and several ranks -- PMF_ZEROS_OBSERVED on a context with a
+ * communicator, and pmf_comm_init / pmf_comm_attach (and the test build's pmf_comm_init_hostshm) on a context in the
+ * mode.  PMF_EINVAL also for a null context, a mode that is neither value, a weight that is not finite or outside
+ * (0, 1] under PMF_ZEROS_OBSERVED, and two null outputs of the getter.  An error changes nothing. */
+int pmf_ctx_set_gauss_zeros(pmf_ctx *ctx, int mode, double weight);
+int pmf_ctx_get_gauss_zeros(pmf_ctx *ctx, int *mode /* may be NULL */, double *weight /* may be NULL */);
+/* G of `side` in either mode, as a full symmetric K x K matrix (row-major, double): G[i][j] = sum over ALL rows r of
+ * COV[r][i][j] + FACTOR[r][i] FACTOR[r][j].  Every addend is formed in double from the stored values and the sum is in
+ * double.  Two stages, no atomics and no work list: a fixed grid of blocks, each owning a tile of 256 packed positions
+ * and a contiguous row range (16-byte loads per lane; a lane owns the same packed positions for every row, so its mean
+ * indices are loop constants; the mean rows are staged in LDS as doubles), the four wavefronts' sums added in wavefront
+ * order; a second launch adds the block sums of a position in block order and writes G packed in double and
+ * weight x G, formed in double and rounded once to the context dtype.  Two calls give the same bits, whatever the task
+ * length.  Reads the model state only; its work area is context-owned: pmf_ctx_device_bytes may grow on the first
+ * call and does not grow after it.  Timed as PMF_KERNEL_GAUSS_COMBINE.  PMF_EINVAL, with the missing thing named: null
+ * context, bad side, null out, FACTOR or COV of `side` not set.  Cost: DESIGN.md section 4.17. */
+int pmf_gauss_gram(pmf_ctx *ctx, int side, double *out /* K x K */);
 
 /* Multi-GPU forms: raw per-row sums into / from a caller-owned DEVICE buffer.
  * Factor: [rows x (Kp + Kpad)] = packed lower triangle of S, then the

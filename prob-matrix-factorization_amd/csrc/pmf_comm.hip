@@ -398,6 +398,8 @@ int comm_create(pmf_ctx *ctx, int nranks, int rank, const void *unique_id, int t
     PMF_REQUIRE(ctx->comm == nullptr, PMF_EINVAL, "pmf_comm_init: the context already has a communicator");
     PMF_REQUIRE(ctx->gamma_zeros == PMF_ZEROS_MISSING, PMF_EINVAL,
                 "pmf_comm_init: the context counts unobserved cells as zeros (pmf_ctx_set_gamma_zeros), which is not available with a communicator");
+    PMF_REQUIRE(!pmf_gauss_zeros_observed(ctx), PMF_EINVAL,
+                "pmf_comm_init: the context counts unobserved cells as weighted zeros (pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED), which is not available with a communicator");
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     PmfComm *cm = new (std::nothrow) PmfComm();
     PMF_REQUIRE(cm, PMF_ENOMEM, "pmf_comm_init: out of host memory");
@@ -667,6 +669,8 @@ extern "C" int pmf_comm_attach(pmf_ctx *ctx, pmf_ctx *owner) {
     PMF_REQUIRE(ctx->comm == nullptr, PMF_EINVAL, "pmf_comm_attach: the context already has a communicator");
     PMF_REQUIRE(ctx->gamma_zeros == PMF_ZEROS_MISSING, PMF_EINVAL,
                 "pmf_comm_attach: the context counts unobserved cells as zeros (pmf_ctx_set_gamma_zeros), which is not available with a communicator");
+    PMF_REQUIRE(!pmf_gauss_zeros_observed(ctx), PMF_EINVAL,
+                "pmf_comm_attach: the context counts unobserved cells as weighted zeros (pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED), which is not available with a communicator");
     PMF_REQUIRE(ctx->device == owner->device, PMF_EINVAL, "pmf_comm_attach: contexts on different devices (%d, %d)",
                 ctx->device, owner->device);
     ctx->comm = owner->comm;

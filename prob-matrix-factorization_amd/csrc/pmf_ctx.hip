@@ -706,6 +706,31 @@ extern "C" int pmf_ctx_get_gamma_zeros(pmf_ctx *ctx, int *mode) {
     return PMF_OK;
 }
 
+// Bias-free Gaussian model: whether an unlisted (user, item) cell is missing or an observation of 0 with variance
+// sigma2 / weight.  A property of the context; no state array changes (the statistics windows are rebuilt by every call).
+extern "C" int pmf_ctx_set_gauss_zeros(pmf_ctx *ctx, int mode, double weight) {
+    CHECK_CTX(ctx, "pmf_ctx_set_gauss_zeros");
+    PMF_REQUIRE(mode == PMF_ZEROS_MISSING || mode == PMF_ZEROS_OBSERVED, PMF_EINVAL, "pmf_ctx_set_gauss_zeros: bad mode %d", mode);
+    if (mode == PMF_ZEROS_OBSERVED) {
+        PMF_REQUIRE(weight > 0.0 && weight <= 1.0, PMF_EINVAL,   // (false for a NaN as well)
+                    "pmf_ctx_set_gauss_zeros: weight %g of PMF_ZEROS_OBSERVED must be finite and in (0, 1]", weight);
+        PMF_REQUIRE(ctx->comm == nullptr, PMF_EINVAL,
+                    "pmf_ctx_set_gauss_zeros: PMF_ZEROS_OBSERVED is not available on a context with a communicator "
+                    "(the user-side Gram matrix would have to be added over the ranks)");
+        ctx->gauss_zero_weight = weight;
+    }
+    ctx->gauss_zeros = mode;
+    return PMF_OK;
+}
+
+extern "C" int pmf_ctx_get_gauss_zeros(pmf_ctx *ctx, int *mode, double *weight) {
+    CHECK_CTX(ctx, "pmf_ctx_get_gauss_zeros");
+    PMF_REQUIRE(mode != nullptr || weight != nullptr, PMF_EINVAL, "pmf_ctx_get_gauss_zeros: null argument");
+    if (mode) *mode = ctx->gauss_zeros;
+    if (weight) *weight = ctx->gauss_zero_weight;
+    return PMF_OK;
+}
+
 // ---------------------------------------------------------------------------
 // model state exchange (host float64 <-> device dtype, padded / packed layouts)
 // ---------------------------------------------------------------------------

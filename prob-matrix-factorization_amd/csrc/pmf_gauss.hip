@@ -1738,6 +1738,182 @@ static SolveParams<T> solve_params(const pmf_ctx *ctx, double sigma2, double eta
     return sp;
 }
 
+// ---------------------------------------------------------------------------
+// unlisted cells as weighted zeros (pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED): Gram matrix and blend
+// ---------------------------------------------------------------------------
+// G[p] = sum over ALL rows r of a side of V_r[p] + m_r[row p] m_r[col p], p over the packed lower triangle: the S every
+// row of the other side would accumulate if all cells were listed.  One streaming pass over COV, two stages, no atomics
+// and no work list:
+//   stage 1  grid (column tiles, row blocks).  A tile is kGramTile 16-byte chunks (256 packed positions): lane l of every
+//            wavefront owns chunk tile * 64 + l for every row, so the (row, col) of its four entries -- its mean indices --
+//            are loop constants.  Block (t, b) owns the contiguous rows [rows b / NB, rows (b + 1) / NB); wavefront w adds
+//            rows w, w + 4, ... of the range in ascending order, UN rows in flight (one 16-byte load per lane per row; the
+//            UN mean rows are staged in the wavefront's LDS slice as doubles).  Every addend is (double)V + (double)m_r
+//            (double)m_c, one fma, added in double; the four wavefronts' sums are added in wavefront order through LDS.
+//   stage 2  one thread per packed position adds the NB block sums in block order; G goes out packed in double and, as
+//            w0 G formed in double and rounded once, in the context dtype.
+// Entries at or past kp (the padding of the packed row) come out as 0.
+static const int kGramTile = 64;          // chunks per column tile = lanes of a wavefront
+static const int kGramBlocks = 4096;      // blocks aimed at (column tiles x row blocks)
+static const int kGramRowBlocks = 1024;   // row blocks at most
+
+template <typename T>
+__global__ __launch_bounds__(256) void gauss_gram_kernel(const T *cov, const T *factor, int64_t rows, int kpad, int kp,
+                                                         int cov_stride, double *partial /* [gridDim.y][cov_stride] */) {
+    constexpr int UN = 4;
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    __shared__ double s_sum[4][kGramTile * PMF_VEC];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double *mw = reinterpret_cast<double *>(smem_raw) + (int64_t)wave * UN * kpad;   // [UN][kpad]
+    const int chunks = cov_stride / PMF_VEC;
+    const int q = min((int)blockIdx.x * kGramTile + lane, chunks - 1);   // clamped lanes are never stored
+    int ri[PMF_VEC], ci[PMF_VEC];
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) {
+        ri[e] = ci[e] = 0;
+        if (q * PMF_VEC + e < kp) tri_rc(q * PMF_VEC + e, ri[e], ci[e]);
+    }
+    const int64_t r0 = rows * (int64_t)blockIdx.y / gridDim.y, r1 = rows * ((int64_t)blockIdx.y + 1) / gridDim.y;
+    double acc[PMF_VEC] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t r = r0 + wave; r < r1; r += 4 * UN) {
+        Vec4<T> v[UN];
+#pragma unroll
+        for (int u = 0; u < UN; ++u) {
+            const bool live = r + 4 * u < r1;                 // wave-uniform
+            const int64_t rr = live ? r + 4 * u : r;          // (a row past the range: row r again, never added)
+            v[u] = load4(cov + rr * cov_stride + (int64_t)q * PMF_VEC);
+            for (int k = lane; k < kpad; k += 64) mw[u * kpad + k] = (double)factor[rr * kpad + k];
+        }
+        wave_lds_fence();
+#pragma unroll
+        for (int u = 0; u < UN; ++u)
+            if (r + 4 * u < r1) {
+#pragma unroll
+                for (int e = 0; e < PMF_VEC; ++e) acc[e] += fma(mw[u * kpad + ri[e]], mw[u * kpad + ci[e]], (double)v[u].v[e]);
+            }
+        wave_lds_fence();
+    }
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) s_sum[wave][lane * PMF_VEC + e] = acc[e];
+    __syncthreads();
+    const int pos = (int)blockIdx.x * kGramTile * PMF_VEC + (int)threadIdx.x;
+    if (pos < cov_stride) {
+        const double t = ((s_sum[0][threadIdx.x] + s_sum[1][threadIdx.x]) + s_sum[2][threadIdx.x]) + s_sum[3][threadIdx.x];
+        partial[(int64_t)blockIdx.y * cov_stride + pos] = pos < kp ? t : 0.0;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void gauss_gram_final_kernel(const double *partial, int n_blocks, int cov_stride, double w0,
+                                                               double *g, T *gw) {
+    const int pos = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (pos >= cov_stride) return;
+    double t = 0.0;
+#pragma unroll 8
+    for (int b = 0; b < n_blocks; ++b) t += partial[(int64_t)b * cov_stride + pos];
+    g[pos] = t;
+    gw[pos] = (T)(w0 * t);
+}
+
+// S[p] = fma(T(1 - w0), S[p], gw[p]) over the packed S of `n` statistics rows `stride` elements apart; what follows S
+// in a row (the right-hand side) is not touched.  One 16-byte chunk per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void gauss_zero_blend_kernel(T *stats, int64_t n, int64_t stride, int chunks, T one_minus_w0,
+                                                               const T *gw) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= n * chunks) return;
+    const int64_t row = idx / chunks;
+    const int q = (int)(idx - row * chunks) * PMF_VEC;
+    T *s = stats + row * stride + q;
+    Vec4<T> v = load4(s);
+    const Vec4<T> g = load4(gw + q);
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) v.v[e] = fma(one_minus_w0, v.v[e], g.v[e]);
+    store4(s, v);
+}
+
+// the work area of the Gram pass in pmf_ctx::d_gauss_gram: block sums, packed G (double), w0 G (context dtype)
+template <typename T>
+struct GaussGram {
+    int tiles, row_blocks;
+    PmfLayout lay{256};
+    PmfLayout::Piece<double> part_at, g_at;
+    PmfLayout::Piece<T> gw_at;
+    explicit GaussGram(const pmf_ctx *ctx)
+        : tiles((ctx->cov_stride / PMF_VEC + kGramTile - 1) / kGramTile),
+          row_blocks(std::max(1, std::min(kGramRowBlocks, kGramBlocks / tiles))),
+          part_at(lay.add<double>((size_t)row_blocks * ctx->cov_stride)), g_at(lay.add<double>((size_t)ctx->cov_stride)),
+          gw_at(lay.add<T>((size_t)ctx->cov_stride)) {}
+};
+
+// G of `side` and w0 G into the context's Gram work area (the two launches, in a profile bracket of their own: call it
+// outside any other); *g / *gw stay valid until the next Gram pass of the context.
+template <typename T>
+static int gauss_gram_run(pmf_ctx *ctx, int side, const double **g, const T **gw) {
+    const GaussGram<T> gg(ctx);
+    int rc;
+    if ((rc = ctx->d_gauss_gram.reserve(ctx, gg.lay.bytes(), {ctx->stream}))) return rc;
+    void *base = ctx->d_gauss_gram.as();
+    {
+        PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
+        hipLaunchKernelGGL((gauss_gram_kernel<T>), dim3((unsigned)gg.tiles, (unsigned)gg.row_blocks), dim3(256),
+                           (size_t)4 * 4 * ctx->kpad * sizeof(double), ctx->stream, ctx->arr[side][PMF_ARR_COV].as<const T>(),
+                           ctx->arr[side][PMF_ARR_FACTOR].as<const T>(), ctx->rows[side], ctx->kpad, ctx->kp, ctx->cov_stride,
+                           gg.part_at.at(base));
+        hipLaunchKernelGGL((gauss_gram_final_kernel<T>), dim3((unsigned)((ctx->cov_stride + 255) / 256)), dim3(256), 0, ctx->stream,
+                           gg.part_at.at(base), gg.row_blocks, ctx->cov_stride, ctx->gauss_zero_weight, gg.g_at.at(base),
+                           gg.gw_at.at(base));
+    }
+    PMF_HIP_CHECK(hipGetLastError());
+    if (g) *g = gg.g_at.at(base);
+    if (gw) *gw = gg.gw_at.at(base);
+    return PMF_OK;
+}
+
+// the blend of `n` statistics rows at `stats` (the caller holds no profile bracket; timed with the combine)
+template <typename T>
+static int launch_zero_blend(pmf_ctx *ctx, T *stats, int64_t n, int64_t stride, const T *gw) {
+    if (n == 0) return PMF_OK;
+    const int chunks = ctx->cov_stride / PMF_VEC;
+    PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
+    hipLaunchKernelGGL((gauss_zero_blend_kernel<T>), dim3((unsigned)((n * chunks + 255) / 256)), dim3(256), 0, ctx->stream, stats, n,
+                       stride, chunks, (T)(1.0 - ctx->gauss_zero_weight), gw);
+    PMF_HIP_CHECK(hipGetLastError());
+    return PMF_OK;
+}
+
+// what the Gaussian calls under PMF_ZEROS_OBSERVED share: the bias model is not covered
+#define PMF_REQUIRE_ZERO_MODE_BIAS_FREE(fn)                                                                                  \
+    PMF_REQUIRE(!(pmf_gauss_zeros_observed(ctx) && pmf_has_bias(ctx)), PMF_EINVAL,                                           \
+                fn ": the bias model is not available while the context counts unobserved cells as weighted zeros "         \
+                   "(pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED)")
+
+template <typename T>
+static int run_zero_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2);   // (below, with the row windows it shares with the ELBO)
+
+extern "C" int pmf_gauss_gram(pmf_ctx *ctx, int side, double *out) {
+    PMF_SIDE_ENTRY("pmf_gauss_gram");
+    PMF_REQUIRE(out != nullptr, PMF_EINVAL, "pmf_gauss_gram: null out");
+    int rc;
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_gram"))) return rc;
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_gram"))) return rc;
+    return pmf_no_throw("pmf_gauss_gram", [&] {
+        return pmf_with_dtype(ctx, [&](auto t) {
+            using T = decltype(t);
+            const double *g = nullptr;
+            int rc2;
+            if ((rc2 = gauss_gram_run<T>(ctx, side, &g, nullptr))) return rc2;
+            std::vector<double> packed((size_t)ctx->cov_stride);
+            PMF_HIP_CHECK(hipMemcpyAsync(packed.data(), g, packed.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            const int K = ctx->K;
+            for (int i = 0; i < K; ++i)
+                for (int j = 0; j <= i; ++j) out[(size_t)i * K + j] = out[(size_t)j * K + i] = packed[(size_t)i * (i + 1) / 2 + j];
+            return (int)PMF_OK;
+        });
+    });
+}
+
 // finalize pass: every row of the selected range from `stats`; fused pass: the rows with ratings (the split rows only
 // when the accumulate kernel solved the others) from the sums in COV / FACTOR.  `sums` (with split_rows_only): the
 // accumulate emitted the mean sums, so the split rows' solve completes ctx->d_mdot[side].
@@ -1771,7 +1947,12 @@ static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *st
 extern "C" int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
     PMF_SIDE_ENTRY("pmf_gauss_factor_sweep");
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0, PMF_EINVAL, "pmf_gauss_factor_sweep: variances must be positive");
+    PMF_REQUIRE_ZERO_MODE_BIAS_FREE("pmf_gauss_factor_sweep");
     pmf_factor_written(ctx);   // the other side's mean sums were taken against this side's old means
+    if (pmf_gauss_zeros_observed(ctx))   // (never with a communicator)
+        return pmf_no_throw("pmf_gauss_factor_sweep", [&] {
+            return pmf_with_dtype(ctx, [&](auto t) { return run_zero_sweep<decltype(t)>(ctx, side, sigma2, eta2); });
+        });
     return pmf_with_dtype(ctx, [&](auto t) {
         using T = decltype(t);
         if (side == PMF_SIDE_ITEM && pmf_comm_active(ctx)) {
@@ -1793,6 +1974,7 @@ extern "C" int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, dou
 
 extern "C" int pmf_gauss_factor_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
     PMF_SIDE_ENTRY("pmf_gauss_factor_accumulate");
+    PMF_REQUIRE_GAUSS_ZEROS_MISSING("pmf_gauss_factor_accumulate");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_factor_accumulate: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_factor_accumulate<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, stats_dev, 1, 1); });
 }
@@ -1800,6 +1982,7 @@ extern "C" int pmf_gauss_factor_accumulate(pmf_ctx *ctx, int side, void *stats_d
 extern "C" int pmf_gauss_factor_finalize(pmf_ctx *ctx, int side, const void *stats_dev, double sigma2,
                                          double eta2) {
     PMF_SIDE_ENTRY("pmf_gauss_factor_finalize");
+    PMF_REQUIRE_GAUSS_ZEROS_MISSING("pmf_gauss_factor_finalize");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_factor_finalize: null stats buffer");
     pmf_factor_written(ctx);
     return pmf_with_dtype(ctx, [&](auto t) { return run_factor_solve<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, stats_dev, sigma2, eta2); });
@@ -1873,6 +2056,7 @@ static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double si
 
 extern "C" int pmf_gauss_bias_sweep(pmf_ctx *ctx, int side, double sigma2, double eta_bias2) {
     PMF_SIDE_ENTRY("pmf_gauss_bias_sweep");
+    PMF_REQUIRE_GAUSS_ZEROS_MISSING("pmf_gauss_bias_sweep");
     return pmf_with_dtype(ctx, [&](auto t) {
         using T = decltype(t);
         if (side != PMF_SIDE_ITEM || !pmf_comm_active(ctx)) return run_bias<T>(ctx, side, PMF_PASS_FUSED, nullptr, sigma2, eta_bias2);
@@ -1885,6 +2069,7 @@ extern "C" int pmf_gauss_bias_sweep(pmf_ctx *ctx, int side, double sigma2, doubl
 
 extern "C" int pmf_gauss_bias_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
     PMF_SIDE_ENTRY("pmf_gauss_bias_accumulate");
+    PMF_REQUIRE_GAUSS_ZEROS_MISSING("pmf_gauss_bias_accumulate");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_bias_accumulate: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_bias<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, stats_dev, 1, 1); });
 }
@@ -1892,6 +2077,7 @@ extern "C" int pmf_gauss_bias_accumulate(pmf_ctx *ctx, int side, void *stats_dev
 extern "C" int pmf_gauss_bias_finalize(pmf_ctx *ctx, int side, const void *stats_dev, double sigma2,
                                        double eta_bias2) {
     PMF_SIDE_ENTRY("pmf_gauss_bias_finalize");
+    PMF_REQUIRE_GAUSS_ZEROS_MISSING("pmf_gauss_bias_finalize");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_bias_finalize: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_bias<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, (void *)stats_dev, sigma2, eta_bias2); });
 }
@@ -1925,6 +2111,11 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
     std::vector<PmfTask> tasks;
     std::vector<PmfSplitRow> split;
     int rc;
+    // unlisted cells as weighted zeros: every row's S is blended with w0 G of the opposite side (formed once), and a row
+    // without ratings is solved like the rest
+    const bool zeros = pmf_gauss_zeros_observed(ctx);
+    const T *gw = nullptr;
+    if (zeros && (rc = gauss_gram_run<T>(ctx, 1 - side, nullptr, &gw))) return rc;
     for (int64_t r0 = 0; r0 < a.n_rows; r0 = st.r1) {
         int64_t units = 0;   // a row's statistics, and the partial slots of a row that is split
         const auto fits = [&](int64_t n) { return (units += 1 + (n > chunk ? (n + chunk - 1) / chunk : 0)) <= max_units; };
@@ -1964,6 +2155,7 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         p.dst_w = d_w.as<T>();
         p.dst_w_stride = kpad;
         if ((rc = launch_accumulate<T>(ctx, p, (int64_t)split.size()))) return rc;
+        if (zeros && (rc = launch_zero_blend<T>(ctx, d_s.as<T>(), B, cs, gw))) return rc;
         SolveParams<T> sp = solve_params<T>(ctx, a.sigma2, a.eta2);
         sp.rows = nullptr;
         sp.row0 = 0;
@@ -2007,7 +2199,7 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         if (oc && (rc = pmf_fold_in_download(ctx, PMF_ARR_COV, d_s.as(), oc, B))) return rc;
         if (ob && bias && (rc = pmf_fold_in_download(ctx, PMF_ARR_BIAS, d_b.as(), ob, B))) return rc;
         if (ob && !bias) std::fill_n(ob, (size_t)B, 0.0);
-        for (int64_t r = 0; has_empty && r < B; ++r) {
+        for (int64_t r = 0; has_empty && !zeros && r < B; ++r) {
             if (st.ptr[(size_t)r + 1] > st.ptr[(size_t)r]) continue;
             // a row without ratings gets the prior: m = 0, V = eta2 I, b = 0
             std::fill_n(of + r * K, (size_t)K, 0.0);
@@ -2027,6 +2219,7 @@ extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
                                  double *out_factor, double *out_cov, double *out_bias) {
     PMF_SIDE_ENTRY("pmf_gauss_fold_in");
     PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_gauss_fold_in: negative row count");
+    PMF_REQUIRE_ZERO_MODE_BIAS_FREE("pmf_gauss_fold_in");
     if (n_rows == 0) return PMF_OK;
     PMF_REQUIRE(row_ptr && out_factor, PMF_EINVAL, "pmf_gauss_fold_in: null argument");
     int rc;
@@ -2065,7 +2258,7 @@ struct ElboParams {
     int64_t row0, n;       // rows [row0, row0 + n) of the side
     const T *stats;        // the window: row row0 + i at stats + i * (cov_stride + kpad), packed S then w; null = no data term
     const T *csum;         // [n] c_r of the window's rows (with stats)
-    const int64_t *ptr;    // the side's row offsets (with stats)
+    const int64_t *ptr;    // the side's row offsets (with stats): a row without ratings has no statistics; null = every row of the window has (PMF_ZEROS_OBSERVED)
     const T *cov, *factor;
     const T *bias;         // null unless both sides have a BIAS array
     double *out;           // [rows of the side][PMF_ELBO_TERMS]
@@ -2183,7 +2376,7 @@ __global__ __launch_bounds__(256) void gauss_elbo_row_reg_kernel(ElboParams<T> p
     const T *m = p.factor + row * p.kpad;
     for (int k = lane; k < p.kpad; k += 64) ms[k] = m[k];
     wave_lds_fence();
-    const bool data = p.stats != nullptr && p.ptr[row + 1] > p.ptr[row];
+    const bool data = p.stats != nullptr && (p.ptr == nullptr || p.ptr[row + 1] > p.ptr[row]);
     const T *S = p.stats ? p.stats + idx * width : nullptr;
     T acc[PMF_VEC] = {(T)0, (T)0, (T)0, (T)0}, tr = (T)0;
     for (int q = lane * PMF_VEC; q < p.cov_stride; q += 64 * PMF_VEC) {
@@ -2269,7 +2462,7 @@ __global__ __launch_bounds__(256) void gauss_elbo_row_lds_kernel(ElboParams<T> p
         __syncthreads();
         for (int k = tid; k < p.kpad; k += 256) ms[k] = m[k];
         __syncthreads();
-        const bool data = p.stats != nullptr && p.ptr[row + 1] > p.ptr[row];
+        const bool data = p.stats != nullptr && (p.ptr == nullptr || p.ptr[row + 1] > p.ptr[row]);
         const T *S = p.stats ? p.stats + idx * width : nullptr;
         T acc[PMF_VEC] = {(T)0, (T)0, (T)0, (T)0}, tr = (T)0;
         for (int q = tid * PMF_VEC; q < p.cov_stride; q += 256 * PMF_VEC) {
@@ -2377,8 +2570,72 @@ static int ensure_elbo_tasks(pmf_ctx *ctx, int side, int64_t win_rows) {
     PmfTaskList tl;   // (no solve list: the ELBO solves nothing)
     int rc;
     if ((rc = pmf_upload_tasks(ctx, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAUSS_CHUNK), false, bounds, false, tl))) return rc;
+    ix.elbo_win_empty.assign(bounds.size() - 1, 0);
+    for (size_t w = 0; w + 1 < bounds.size(); ++w)
+        ix.elbo_win_empty[w] = std::adjacent_find(ix.h_ptr.begin() + bounds[w], ix.h_ptr.begin() + bounds[w + 1] + 1) !=
+                               ix.h_ptr.begin() + bounds[w + 1] + 1;
     ix.elbo_tasks = std::move(tl);
     ix.elbo_bounds.swap(bounds);
+    return PMF_OK;
+}
+
+// The tasks of window `w` of the side's ELBO list into `p`, summing into the window buffer `win` ([rows of the window]
+// [cov_stride + kpad]); returns the window's split-row count.  Tasks carry the row's id in the side: the window's first
+// row is the buffer's row 0.
+template <typename T>
+static int64_t elbo_window_params(const PmfSideIndex &ix, size_t w, T *win, int width, int cs, GaussParams<T> &p) {
+    const PmfTaskList &tl = ix.elbo_tasks;
+    p.tasks = tl.d_tasks.as<PmfTask>() + tl.task_off[w];
+    p.n_tasks = tl.task_off[w + 1] - tl.task_off[w];
+    p.split = tl.d_split.as<PmfSplitRow>() + tl.split_off[w];
+    p.dst_s = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(win) - (uintptr_t)ix.elbo_bounds[w] * width * sizeof(T));
+    p.dst_s_stride = width;
+    p.dst_w = p.dst_s + cs;
+    p.dst_w_stride = width;
+    return tl.split_off[w + 1] - tl.split_off[w];
+}
+
+// pmf_gauss_factor_sweep under PMF_ZEROS_OBSERVED: G of the other side, then per row window of the side accumulate the
+// listed sums into the context's window (zeroed first where the window has rows no task writes), blend S with w0 G and
+// solve every row of the window into COV / FACTOR.
+template <typename T>
+static int run_zero_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
+    const int other = 1 - side, cs = ctx->cov_stride, width = cs + ctx->kpad;
+    const int64_t rows = ctx->rows[side];
+    PmfSideIndex &ix = ctx->index[side];
+    int rc;
+    PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_gauss_factor_sweep: ratings have not been set");
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_factor_sweep"))) return rc;
+    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_factor_sweep"))) return rc;
+    if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_factor_sweep"))) return rc;
+    if ((rc = pmf_require_array(ctx, other, PMF_ARR_COV, "pmf_gauss_factor_sweep"))) return rc;
+    const int64_t win_rows = std::min(elbo_window_rows<T>(ctx), rows);
+    if ((rc = ensure_elbo_tasks(ctx, side, win_rows))) return rc;
+    const PmfTaskList &tl = ix.elbo_tasks;
+    if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * width * sizeof(T)))) return rc;
+    if ((rc = ctx->d_gauss_window.reserve(ctx, (size_t)win_rows * width * sizeof(T), {ctx->stream}))) return rc;
+    const T *gw = nullptr;
+    if ((rc = gauss_gram_run<T>(ctx, other, nullptr, &gw))) return rc;
+    T *win = ctx->d_gauss_window.as<T>();
+    GaussParams<T> p = gauss_params<T>(ctx, side);
+    SolveParams<T> sp = solve_params<T>(ctx, sigma2, eta2);
+    sp.rows = nullptr;   // every row: S'[0] = (1 - w0) S[0] + w0 G[0] > 0
+    sp.src_s_stride = width;
+    sp.src_w_stride = width;
+    sp.cov = ctx->arr[side][PMF_ARR_COV].as<T>();
+    sp.factor = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
+    for (size_t w = 0; w + 1 < ix.elbo_bounds.size(); ++w) {
+        const int64_t r0 = ix.elbo_bounds[w], n = ix.elbo_bounds[w + 1] - r0;
+        const int64_t ns = elbo_window_params<T>(ix, w, win, width, cs, p);
+        if (ix.elbo_win_empty[w]) PMF_HIP_CHECK(hipMemsetAsync(win, 0, (size_t)n * width * sizeof(T), ctx->stream));
+        if ((rc = launch_accumulate<T>(ctx, p, ns))) return rc;
+        if ((rc = launch_zero_blend<T>(ctx, win, n, width, gw))) return rc;
+        sp.row0 = r0;
+        sp.n = n;
+        sp.src_s = p.dst_s;
+        sp.src_w = p.dst_w;
+        if ((rc = launch_solve<T>(ctx, sp))) return rc;
+    }
     return PMF_OK;
 }
 
@@ -2416,24 +2673,26 @@ static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals
         if ((rc = d_cpart.alloc(ctx, (size_t)tl.n_slots * sizeof(T)))) return rc;
         if ((rc = d_win.alloc(ctx, (size_t)win_rows * width * sizeof(T)))) return rc;
         if ((rc = d_c.alloc(ctx, (size_t)win_rows * sizeof(T)))) return rc;
+        // unlisted cells as weighted zeros: S of EVERY row is blended with w0 G of the other side, so every row has
+        // statistics (e.ptr stays null) and the rows no task writes start from zero sums and c_r = 0
+        const bool zeros = pmf_gauss_zeros_observed(ctx);
+        const T *gw = nullptr;
+        if (zeros && (rc = gauss_gram_run<T>(ctx, 1 - side, nullptr, &gw))) return rc;
         GaussParams<T> p = gauss_params<T>(ctx, side);
-        p.dst_s_stride = width;
-        p.dst_w_stride = width;
         e.stats = d_win.as<const T>();
         e.csum = d_c.as<const T>();
-        e.ptr = ix.d_ptr.as<const int64_t>();
+        e.ptr = zeros ? nullptr : ix.d_ptr.as<const int64_t>();
         for (size_t w = 0; w + 1 < ix.elbo_bounds.size(); ++w) {
             const int64_t r0 = ix.elbo_bounds[w], n = ix.elbo_bounds[w + 1] - r0;
-            const int64_t nt = tl.task_off[w + 1] - tl.task_off[w], ns = tl.split_off[w + 1] - tl.split_off[w];
-            // (the window is not zeroed: every row with a rating is written whole by its task or by the combine, and
-            //  the row kernel does not read the statistics or c_r of a row without ratings)
-            // tasks carry the row's id in the side: the window's row r0 is the buffer's row 0
-            p.tasks = tl.d_tasks.as<PmfTask>() + tl.task_off[w];
-            p.n_tasks = nt;
-            p.split = tl.d_split.as<PmfSplitRow>() + tl.split_off[w];
-            p.dst_s = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(d_win.as<T>()) - (uintptr_t)r0 * width * sizeof(T));
-            p.dst_w = p.dst_s + cs;
+            // (default mode: the window is not zeroed -- every row with a rating is written whole by its task or by the
+            //  combine, and the row kernel does not read the statistics or c_r of a row without ratings)
+            const int64_t ns = elbo_window_params<T>(ix, w, d_win.as<T>(), width, cs, p), nt = p.n_tasks;
+            if (zeros && ix.elbo_win_empty[w]) {
+                PMF_HIP_CHECK(hipMemsetAsync(d_win.as(), 0, (size_t)n * width * sizeof(T), ctx->stream));
+                PMF_HIP_CHECK(hipMemsetAsync(d_c.as(), 0, (size_t)n * sizeof(T), ctx->stream));
+            }
             if ((rc = launch_accumulate<T>(ctx, p, ns))) return rc;
+            if (zeros && (rc = launch_zero_blend<T>(ctx, d_win.as<T>(), n, width, gw))) return rc;
             PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SOLVE);
             if (nt > 0) {
                 ElboSqParams<T> q;
@@ -2481,6 +2740,7 @@ extern "C" int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, doubl
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_elbo_terms"))) return rc;
     if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_elbo_terms"))) return rc;
     if (with_data) {
+        PMF_REQUIRE_ZERO_MODE_BIAS_FREE("pmf_gauss_elbo_terms");
         if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_FACTOR, "pmf_gauss_elbo_terms"))) return rc;
         if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_COV, "pmf_gauss_elbo_terms"))) return rc;
         PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gauss_elbo_terms: ratings have not been set");

@@ -160,6 +160,7 @@ struct PmfSideIndex {
     // elbo_bounds instead of the row chunks.  Built on the first call with a data term; goes with the ratings.
     PmfTaskList elbo_tasks;
     std::vector<int64_t> elbo_bounds;   // [n_windows + 1] first row of every window; empty = not built
+    std::vector<uint8_t> elbo_win_empty;   // [n_windows] 1 if the window has a row without ratings (PMF_ZEROS_OBSERVED zeroes such a window first)
     // pmf_rank_items with exclude_train (USER side only): every row's DISTINCT ids on the opposite side, ascending --
     // pmf_ctx_set_ratings keeps duplicate pairs.  Built on the first such call (pmf_index_distinct); goes with the ratings.
     PmfBuf d_distinct_ptr;       // int64_t [rows + 1]; null = not built
@@ -209,6 +210,11 @@ struct pmf_ctx {
     // pmf_ctx_set_gamma_zeros: PMF_ZEROS_OBSERVED makes the Poisson / HPF calls count every unlisted cell as a rating of 0
     // (the rate sums come from the other side's column sums, pmf_gamma.hip).  Never set together with a communicator.
     int gamma_zeros = PMF_ZEROS_MISSING;
+    // pmf_ctx_set_gauss_zeros: PMF_ZEROS_OBSERVED makes pmf_gauss_factor_sweep / _fold_in / _elbo_terms count every unlisted
+    // cell as an observation of 0 with variance sigma2 / gauss_zero_weight (the row statistics are blended with the other
+    // side's Gram matrix, pmf_gauss.hip).  Independent of gamma_zeros; never set together with a communicator.
+    int gauss_zeros = PMF_ZEROS_MISSING;
+    double gauss_zero_weight = 1.0;
 
     PmfBuf arr[2][PMF_ARR_COUNT];   // model state, pmf_array_elems(side, array) elements of the context dtype
     PmfSideIndex index[2];
@@ -225,6 +231,10 @@ struct pmf_ctx {
     // pmf_gamma_exact_sweep / _accumulate: the (E log, E) tables [rows][2][kpad] of the users, then of the items; rebuilt
     // by every call, in storage of their own so that a pmf_gamma_elbo_terms call (d_scratch) cannot write over them
     PmfBuf d_gamma_tables;
+    // pmf_gauss_gram and the Gaussian calls under PMF_ZEROS_OBSERVED (pmf_gauss.hip): the Gram pass's block sums, the packed
+    // G in double and w0 G in the context dtype; and the statistics window of the zero-mode sweep.  In storage of their own:
+    // the row solvers and the ELBO row kernel lay out d_scratch while G is still needed.
+    PmfBuf d_gauss_gram, d_gauss_window;
     // pmf_topk_query / pmf_rank_query (pmf_topk.hip): what a call keeps for all its rounds -- the sorted exclusion CSR and
     // the candidates' inverse norms -- and the staged query rows of one round (table, coefficients, gather ids).  Grown on
     // demand, in storage of their own: the scans' outputs and score matrix live in d_scratch.
@@ -419,3 +429,9 @@ static inline auto pmf_with_predict_mode(int mode, F &&f) {
 static inline void pmf_factor_written(pmf_ctx *ctx) { ctx->gauss_mdot_valid[0] = ctx->gauss_mdot_valid[1] = false; }
 
 static inline bool pmf_has_bias(const pmf_ctx *ctx) { return ctx->arr[0][PMF_ARR_BIAS] && ctx->arr[1][PMF_ARR_BIAS]; }
+
+static inline bool pmf_gauss_zeros_observed(const pmf_ctx *ctx) { return ctx->gauss_zeros == PMF_ZEROS_OBSERVED; }
+// the Gaussian calls that PMF_ZEROS_OBSERVED (pmf_ctx_set_gauss_zeros) does not cover
+#define PMF_REQUIRE_GAUSS_ZEROS_MISSING(fn)                         \
+    PMF_REQUIRE(!pmf_gauss_zeros_observed(ctx), PMF_EINVAL,         \
+                fn ": not available while the context counts unobserved cells as weighted zeros (pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED)")

@@ -100,6 +100,9 @@ SIGNATURES = {
     "pmf_gauss_fold_in": (C.c_int, [_p, C.c_int, C.c_int64, _i64p, _i32p, _f64p, C.c_double, C.c_double, C.c_double, C.c_int,
                                     _f64p, _f64p, _f64p]),
     "pmf_gauss_elbo_terms": (C.c_int, [_p, C.c_int, C.c_int, _f64p, _f64p]),
+    "pmf_ctx_set_gauss_zeros": (C.c_int, [_p, C.c_int, C.c_double]),
+    "pmf_ctx_get_gauss_zeros": (C.c_int, [_p, C.POINTER(C.c_int), _f64p]),
+    "pmf_gauss_gram": (C.c_int, [_p, C.c_int, _f64p]),
     "pmf_ctx_cov_stride": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "pmf_gauss_factor_accumulate": (C.c_int, [_p, C.c_int, _p]),
     "pmf_gauss_factor_finalize": (C.c_int, [_p, C.c_int, _p, C.c_double, C.c_double]),

@@ -422,6 +422,31 @@ class Context:
                                              ptr(rows, C.c_double) if per_row else None), "pmf_gauss_elbo_terms")
         return (totals, rows) if per_row else totals
 
+    # ---- bias-free Gaussian model with unlisted cells counted as weighted zeros (implicit feedback) ----
+    def set_gauss_zeros(self, observed, weight=1.0):
+        """`observed=True`: `gauss_factor_sweep`, `gauss_fold_in` and `gauss_elbo_terms(with_data=True)` of this context
+        count every (user, item) cell without a rating as an observation of 0 with variance sigma2 / `weight`, `weight`
+        in (0, 1] (`pmf_ctx_set_gauss_zeros`, PMF_ZEROS_OBSERVED); `False` (the default of a new context): only the listed
+        ratings are data, and `weight` is ignored.  Not available with a communicator, for the bias model, the
+        accumulate / finalize pairs and the gradient mode."""
+        check(self._lib.pmf_ctx_set_gauss_zeros(self._h, ZEROS_OBSERVED if observed else ZEROS_MISSING, float(weight)),
+              "pmf_ctx_set_gauss_zeros")
+
+    @property
+    def gauss_zeros(self):
+        """(observed, weight): whether unlisted cells count as weighted zeros, and the stored weight (1.0 by default)."""
+        mode = C.c_int(0)
+        weight = np.zeros(1, dtype=np.float64)
+        check(self._lib.pmf_ctx_get_gauss_zeros(self._h, C.byref(mode), ptr(weight, C.c_double)), "pmf_ctx_get_gauss_zeros")
+        return mode.value == ZEROS_OBSERVED, float(weight[0])
+
+    def gauss_gram(self, side):
+        """(K, K) float64, symmetric: the sum over ALL rows of `side` of COV[r] + FACTOR[r] FACTOR[r]^T (`pmf_gauss_gram`);
+        summed in double on the device, the same bits on every call.  The context is only read."""
+        out = np.zeros((self.K, self.K), dtype=np.float64)
+        check(self._lib.pmf_gauss_gram(self._h, side, ptr(out, C.c_double)), "pmf_gauss_gram")
+        return out
+
     # ---- Gaussian MAP by gradient steps (no reference counterpart) -------
     def gauss_sgd_sweep(self, side, lr, sigma2, eta2, eta_bias2=1.0):
         check(self._lib.pmf_gauss_sgd_sweep(self._h, side, float(lr), float(sigma2), float(eta2), float(eta_bias2)),

@@ -15,12 +15,14 @@ from pmf_hip import ARR_BIAS, ARR_COV, ARR_FACTOR, ELBO_BIAS_SQ, ELBO_ESS, ELBO_
 
 
 def elbo_from_terms(user_terms, item_terms, user_counts, item_counts, n_ratings, n_factors, sigma2, eta_theta2, eta_beta2,
-                    eta_bias2=None, data_side=USER):
+                    eta_bias2=None, data_side=USER, zero_weight=None):
     """The evidence lower bound of a Gaussian CAVI model from the sums `pmf_gauss_elbo_terms` returns (include/pmf_hip.h
     has the definition): `user_terms` / `item_terms` are the two sides' total vectors (columns `pmf_hip.ELBO_*`),
     `user_counts` / `item_counts` the ratings per row of each side (their lengths are the row counts), `eta_bias2=None`
     the bias-free model.  The data term takes the ESS entry of `data_side`; either side's gives the same sum.  Pure
-    host arithmetic in float64.  Returns (L, parts): parts names the data term and, per block of q, the expected log
+    host arithmetic in float64.  `zero_weight` (bias-free model only): the terms come from a context that counts unlisted
+    cells as zeros of variance sigma2 / zero_weight (`pmf_ctx_set_gauss_zeros`), so the data constant also has the
+    U I - N unlisted cells, U and I being the lengths of the two count vectors.  Returns (L, parts): parts names the data term and, per block of q, the expected log
     prior and the entropy; the parts add up to L."""
     terms = (np.asarray(user_terms, dtype=np.float64), np.asarray(item_terms, dtype=np.float64))
     counts = (np.asarray(user_counts, dtype=np.float64), np.asarray(item_counts, dtype=np.float64))
@@ -31,6 +33,11 @@ def elbo_from_terms(user_terms, item_terms, user_counts, item_counts, n_ratings,
         var = [1.0 / (1.0 / eta_bias2 + n / sigma2) for n in counts]       # gaussian_mf_cavi_bias.py:222 / :253
         ess += sum(float(np.sum(n * v)) for n, v in zip(counts, var))
     parts["data"] = -0.5 * n_ratings * np.log(two_pi * sigma2) - ess / (2.0 * sigma2)
+    if zero_weight is not None:
+        if eta_bias2 is not None:
+            raise ValueError("zero_weight: unlisted cells as weighted zeros are defined for the bias-free model only")
+        n_unlisted = float(len(counts[0])) * float(len(counts[1])) - n_ratings
+        parts["data"] -= 0.5 * n_unlisted * np.log(two_pi * sigma2 / zero_weight)
     for name, t, n, eta2 in (("theta", terms[0], counts[0], eta_theta2), ("beta", terms[1], counts[1], eta_beta2)):
         rk = len(n) * K
         parts["prior_" + name] = -0.5 * rk * np.log(two_pi * eta2) - float(t[ELBO_SQNORM]) / (2.0 * eta2)
@@ -177,11 +184,40 @@ class GaussianHost(DeviceModel):
         pdist.gaussian_iteration(ctx, self._comm, None, None, cfg.sigma2, cfg.eta_theta2,
                                  cfg.eta_beta2, cfg.eta_bias2 if self._uses_bias else None)
 
-    def fit(self, train_df, val_df=None, global_mean=0.0, *, track_elbo=False, elbo_tol=None):
+    def _check_unobserved(self, unobserved, zero_weight, train_df):
+        """`fit`'s `unobserved` / `zero_weight` -> whether unlisted cells count as weighted zeros; every refusal is made
+        here, before any device call."""
+        if unobserved not in ("missing", "zero"):
+            raise ValueError(f"unobserved must be 'missing' or 'zero', not {unobserved!r}")
+        if unobserved == "missing":
+            return False
+        if self._uses_bias or not self._has_covariances:
+            raise NotImplementedError(f"unobserved='zero' is not available for {type(self).__module__.split('.')[-1]}."
+                                      f"{type(self).__name__}: the bias-free gaussian_mf_cavi.GaussianMFCAVI supports it")
+        if self._comm is not None:
+            raise ValueError("unobserved='zero' with comm=: counting unobserved cells as zeros is not available on several ranks")
+        if not (np.isfinite(zero_weight) and 0.0 < zero_weight <= 1.0):
+            raise ValueError(f"zero_weight must lie in (0, 1], not {zero_weight!r}")
+        if train_df.duplicated(subset=["u", "i"]).any():
+            raise ValueError("unobserved='zero': train_df lists a (u, i) pair more than once; a cell has one rating")
+        return True
+
+    def fit(self, train_df, val_df=None, global_mean=0.0, *, track_elbo=False, elbo_tol=None, unobserved="missing",
+            zero_weight=1.0):
         """`track_elbo`: evaluate the evidence lower bound after every iteration (`history_["elbo"]`; about 1.3
         accumulates of the user side more per iteration).  `elbo_tol` (implies `track_elbo`): stop when the relative increase
-        (L_t - L_{t-1}) / |L_{t-1}| falls below it -- an early stop that needs no `val_df`."""
+        (L_t - L_{t-1}) / |L_{t-1}| falls below it -- an early stop that needs no `val_df`.
+        `unobserved`: "missing" (default) -- the rating list is the whole data set, as in the reference; "zero"
+        (`gaussian_mf_cavi.GaussianMFCAVI` only) -- every (user, item) cell without a rating is an observation of 0, in
+        this call's rating convention, with variance sigma2 / `zero_weight`, `zero_weight` in (0, 1]: the model clicks,
+        purchases and plays need, "implicit ALS" with full posterior covariances (`pmf_ctx_set_gauss_zeros`: the row
+        statistics are blended with the other side's Gram matrix).  `zero_weight=1` equals the
+        default fit of the frame with every missing cell listed as 0; 1 / (1 + alpha) is the usual confidence ratio.
+        Recorded in `history_["unobserved"]` / `history_["zero_weight"]` and kept on the fit's context: `elbo()`,
+        `track_elbo`, `fold_in_users` and `fold_in_items` run in the same mode.  "zero" refuses duplicate (u, i) pairs
+        and `comm=`; negative ratings are fine."""
         cfg = self.config
+        zeros = self._check_unobserved(unobserved, zero_weight, train_df)
         track_elbo = bool(track_elbo) or elbo_tol is not None
         if track_elbo:
             if not self._has_covariances:
@@ -193,6 +229,9 @@ class GaussianHost(DeviceModel):
         self._initialize_variational_params()
         u, i, x = frame_arrays(train_df)
         ctx = self._open_context(u, i, x)
+        if zeros:
+            ctx.set_gauss_zeros(True, zero_weight)
+        self.history_["unobserved"], self.history_["zero_weight"] = unobserved, float(zero_weight)
         self.history_.pop("elbo", None)
         self._elbo_counts = None
         if self._comm is None:      # rating counts per row: what `elbo` needs besides the device's sums
@@ -300,8 +339,9 @@ class GaussianHost(DeviceModel):
         if self._elbo_counts is None:
             raise NotImplementedError("elbo after a fit under a communicator: the ELBO of a sharded fit is not implemented")
         nu, ni = self._elbo_counts
+        observed, weight = ctx.gauss_zeros
         return elbo_from_terms(user, item, nu, ni, int(nu.sum()), cfg.n_factors, cfg.sigma2, cfg.eta_theta2, cfg.eta_beta2,
-                               cfg.eta_bias2 if self._uses_bias else None)
+                               cfg.eta_bias2 if self._uses_bias else None, zero_weight=weight if observed else None)
 
     def elbo(self, parts=False):
         """The evidence lower bound of the fitted q on the training ratings, for the config's sigma2 / eta2 (float64):
@@ -329,7 +369,8 @@ class GaussianHost(DeviceModel):
         in `fit`'s rating convention; `u` holds arbitrary labels.  The item side stays frozen; each user gets the
         factor update and (bias model) `n_iter` factor / bias alternations from a zero bias -- the reference's own
         row updates, on the device (`pmf_gauss_fold_in`), without a refit.  Rows with an item id the fit has not seen
-        are dropped; a user left without ratings gets the prior.  Returns a `FoldIn`, one row per label in sorted
+        are dropped; a user left without ratings gets the prior (after `fit(unobserved="zero")`: the posterior of a row of
+        zeros, as every other row's unlisted cells are zeros too).  Returns a `FoldIn`, one row per label in sorted
         order."""
         return self._fold_in("fold_in_users", USER, df, n_iter, return_cov)
 
