@@ -516,8 +516,9 @@ int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row
  * (src/models/_gaussian_host.py:elbo_from_terms is this formula).  `totals[t]` is the sum of the per-row values in row
  * order, in double: two calls give the same bits, whatever the row windows are.  `per_row` (rows x PMF_ELBO_TERMS,
  * row-major) may be NULL.  Sums inside a row are in the context's dtype.  With a data term the rows go in windows whose
- * statistics fit a fixed scratch budget (PMF_ELBO_ROWS=n, read when the context is created, caps the rows of a window);
- * per window the sweep's own accumulate kernels run on the sweep's own task cuts; measured at K = 64 fp32 on 1M users
+ * statistics fit a fixed scratch budget (PMF_ELBO_ROWS=n, read when the context is created, caps the rows of a window).
+ * The same variable also sizes the windows of pmf_gauss_factor_sweep under PMF_ZEROS_OBSERVED, which are these windows.
+ * Per window the sweep's own accumulate kernels run on the sweep's own task cuts; measured at K = 64 fp32 on 1M users
  * and 50M ratings, one call with a data term takes 1.3 times an accumulate of `side`.  Reads the context only: model state, ratings, work lists and the stored validation set stay
  * as they are; never a collective, with or without a communicator.  Needs FACTOR and COV of `side`; with_data != 0
  * also FACTOR and COV of the other side and the ratings.  PMF_EINVAL: null context, bad side, null totals, a missing

@@ -202,7 +202,7 @@ extern "C" int pmf_ctx_create(int device, int64_t n_users, int64_t n_items, int 
     }
     if (const char *fr = getenv("PMF_FOLD_IN_ROWS")) ctx->fold_in_rows = std::max(atoll(fr), 0LL);
     if (const char *fl = getenv("PMF_GAMMA_FOLD_LONG")) ctx->gamma_fold_long = std::max(atoll(fl), 0LL);
-    if (const char *er = getenv("PMF_ELBO_ROWS")) ctx->elbo_rows = std::max(atoll(er), 0LL);
+    if (const char *er = getenv("PMF_ELBO_ROWS")) ctx->window_rows = std::max(atoll(er), 0LL);
     if (const char *pp = getenv("PMF_GAMMA_PRED_PAIRS")) ctx->gamma_pred_pairs = std::max(atoll(pp), 0LL);
     if (const char *qr = getenv("PMF_TOPK_QUERY_ROWS")) {
         const long long n = atoll(qr);

@@ -1473,6 +1473,42 @@ __global__ __launch_bounds__(256) void gauss_fold_bias_kernel(FoldBiasParams<T> 
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+// Where the statistics of the rows row0, row0 + 1, ... of a side live: S of row row0 + i at s + i * s_stride, its w at w + i *
+// w_stride.  One constructor per layout in use; launch_accumulate alone calls set_dst and solve_params alone set_src.
+template <typename T>
+struct GaussStats {
+    T *s, *w;
+    int64_t s_stride, w_stride, row0;
+    bool one_buffer;   // a row's w follows its S: the rows are one run of memory
+    // in place: COV / FACTOR of `side` (the fused pass: nobody gathers a side during its own sweep)
+    static GaussStats in_place(const pmf_ctx *ctx, int side) {
+        return {ctx->arr[side][PMF_ARR_COV].as<T>(), ctx->arr[side][PMF_ARR_FACTOR].as<T>(), ctx->cov_stride, ctx->kpad, 0, false};
+    }
+    // interleaved: rows of [cov_stride + kpad] in `buf` from row `row0` on (accumulate / finalize and communicator: 0; a window)
+    static GaussStats interleaved(const pmf_ctx *ctx, T *buf, int64_t row0) {
+        return {buf, buf + ctx->cov_stride, ctx->cov_stride + ctx->kpad, ctx->cov_stride + ctx->kpad, row0, true};
+    }
+    // separate: an S buffer [rows][cov_stride] and a w buffer [rows][kpad] (a fold-in block, solved in place)
+    static GaussStats separate(const pmf_ctx *ctx, T *s, T *w) { return {s, w, ctx->cov_stride, ctx->kpad, 0, false}; }
+    // What a kernel gets for `at` = s or w.  Tasks and solves name a row by its id in the side, so the base is biased to
+    // at - row0 * stride; only rows from row0 on are ever addressed.  In integers: it may lie outside the allocation.
+    T *base(T *at, int64_t stride) const {
+        return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(at) - (uintptr_t)row0 * stride * sizeof(T));
+    }
+    void set_dst(GaussParams<T> &p) const {
+        p.dst_s = base(s, s_stride);
+        p.dst_s_stride = s_stride;
+        p.dst_w = base(w, w_stride);
+        p.dst_w_stride = w_stride;
+    }
+    void set_src(SolveParams<T> &sp) const {
+        sp.src_s = base(s, s_stride);
+        sp.src_s_stride = s_stride;
+        sp.src_w = base(w, w_stride);
+        sp.src_w_stride = w_stride;
+    }
+};
+
 // fuse: sums in place, then solve   !fuse: sums only (into the statistics or in place)
 template <int KB, int NT, int KS = KB>
 static void launch_accum_mfma_nt(pmf_ctx *ctx, const GaussParams<float> &p, dim3 grid, bool fuse, float is2, float ie2,
@@ -1554,17 +1590,17 @@ static void launch_accum_mfma128(pmf_ctx *ctx, const GaussParams<float> &p, dim3
 }
 
 // fp32, K <= 128: the MFMA accumulate kernels.  Returns whether they also solved the rows that are one task (`fuse`:
-// the fused pass sums in place, so dst_s / dst_w are COV / FACTOR).
-static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParams<float> &p, bool fuse, float is2, float ie2) {
+// the fused pass sums in place, so the solved rows go where the sums went, `cov` / `fac` = COV / FACTOR).
+static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParams<float> &p, bool fuse, float is2, float ie2, float *cov, float *fac) {
     if (ctx->K <= 64) {
-        launch_accum_mfma(ctx, p, dim3((unsigned)((p.n_tasks + 3) / 4)), fuse, is2, ie2, p.dst_s, p.dst_w);
+        launch_accum_mfma(ctx, p, dim3((unsigned)((p.n_tasks + 3) / 4)), fuse, is2, ie2, cov, fac);
     } else {  // 64 < K <= 128: one 128-thread block (two wavefronts) per task
         const size_t smem = (size_t)PAIR_LDS_FLOATS * sizeof(float);
         dim3 g2((unsigned)p.n_tasks);
         const int chunks = ctx->cov_stride / PMF_VEC, nt = ((chunks + 1) / 2 + 63) / 64;
-        if (nt <= 9) launch_accum_mfma128<9>(ctx, p, g2, smem, fuse, is2, ie2, p.dst_s, p.dst_w);
-        else if (nt <= 13) launch_accum_mfma128<13>(ctx, p, g2, smem, fuse, is2, ie2, p.dst_s, p.dst_w);
-        else launch_accum_mfma128<17>(ctx, p, g2, smem, fuse, is2, ie2, p.dst_s, p.dst_w);
+        if (nt <= 9) launch_accum_mfma128<9>(ctx, p, g2, smem, fuse, is2, ie2, cov, fac);
+        else if (nt <= 13) launch_accum_mfma128<13>(ctx, p, g2, smem, fuse, is2, ie2, cov, fac);
+        else launch_accum_mfma128<17>(ctx, p, g2, smem, fuse, is2, ie2, cov, fac);
     }
     return fuse;
 }
@@ -1573,13 +1609,13 @@ static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParams<float> &p, bo
 // accumulate kernel.  Returns whether it also solved the rows that are one task (`fuse`, K <= 64: fp64 only -- the
 // fp32 build has no fused generic kernel, so fuse / is2 / ie2 do not apply to it).
 template <typename T>
-static bool launch_accum_generic(pmf_ctx *ctx, const GaussParams<T> &p, bool fuse, T is2, T ie2) {
+static bool launch_accum_generic(pmf_ctx *ctx, const GaussParams<T> &p, bool fuse, T is2, T ie2, T *cov, T *fac) {
     dim3 grid((unsigned)((p.n_tasks + 3) / 4));
     const size_t plain = (size_t)4 * 2 * ctx->kpad * sizeof(T), lds = plain + (size_t)4 * ctx->cov_stride * sizeof(T);
     if constexpr (std::is_same<T, double>::value) {
         if (fuse) {
             pmf_with_pow2<8>(ctx->K, [&](auto KR) {
-                hipLaunchKernelGGL((gauss_accum_generic_kernel<T, KR>), grid, dim3(256), lds, ctx->stream, p, is2, ie2, p.dst_s, p.dst_w);
+                hipLaunchKernelGGL((gauss_accum_generic_kernel<T, KR>), grid, dim3(256), lds, ctx->stream, p, is2, ie2, cov, fac);
             });
             return true;
         }
@@ -1589,8 +1625,15 @@ static bool launch_accum_generic(pmf_ctx *ctx, const GaussParams<T> &p, bool fus
     return false;
 }
 
+// FACTOR and COV of `side`, then (with `both`) of the other side, have been set: PMF_EINVAL in the name of `fn` if not
+static int gauss_require_state(pmf_ctx *ctx, int side, bool both, const char *fn) {
+    int rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, fn);
+    if (!rc) rc = pmf_require_array(ctx, side, PMF_ARR_COV, fn);
+    return rc || !both ? rc : gauss_require_state(ctx, 1 - side, false, fn);
+}
+
 // What the accumulate kernels take from the context: the gathered tables of the other side, `side`'s ratings, hot
-// flags and bias, the partial slots and the geometry.  The caller sets the tasks, the split rows and the destination.
+// flags and bias, the partial slots and the geometry.  The caller sets the tasks and the split rows.
 template <typename T>
 static GaussParams<T> gauss_params(const pmf_ctx *ctx, int side) {
     const int other = 1 - side;
@@ -1612,20 +1655,21 @@ static GaussParams<T> gauss_params(const pmf_ctx *ctx, int side) {
     return p;
 }
 
-// S and w of p's tasks by the accumulate kernel for the context's K and dtype, then the combine of the `n_split` split
-// rows p.split lists.  `fuse`: the sums go in place (dst_s / dst_w are COV / FACTOR) and the kernel, where it has a fused
+// S and w of p's tasks into `st` by the accumulate kernel for the context's K and dtype, then the combine of the `n_split`
+// split rows p.split lists.  `fuse`: the sums go in place (`st` is COV / FACTOR) and the kernel, where it has a fused
 // form, also solves every row that is one task; *solved tells whether it did, so that the caller solves the rest.
 template <typename T>
-static int launch_accumulate(pmf_ctx *ctx, const GaussParams<T> &p, int64_t n_split, bool fuse = false, double sigma2 = 1,
-                             double eta2 = 1, bool *solved = nullptr) {
+static int launch_accumulate(pmf_ctx *ctx, GaussParams<T> &p, int64_t n_split, const GaussStats<T> &st, bool fuse = false,
+                             double sigma2 = 1, double eta2 = 1, bool *solved = nullptr) {
     bool did = false;
+    st.set_dst(p);
     if (p.n_tasks > 0) {
         PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_ACCUM);
         const T is2 = (T)(1.0 / sigma2), ie2 = (T)(1.0 / eta2);
         if (std::is_same<T, float>::value && !ctx->gauss_generic && ctx->K <= 128) {
-            if constexpr (std::is_same<T, float>::value) did = launch_accum_mfma_fp32(ctx, p, fuse, is2, ie2);
+            if constexpr (std::is_same<T, float>::value) did = launch_accum_mfma_fp32(ctx, p, fuse, is2, ie2, st.s, st.w);
         } else {
-            did = launch_accum_generic(ctx, p, fuse && ctx->K <= 64, is2, ie2);
+            did = launch_accum_generic(ctx, p, fuse && ctx->K <= 64, is2, ie2, st.s, st.w);
         }
     }
     if (solved) *solved = did;
@@ -1650,16 +1694,12 @@ static T *gauss_partial_h(const pmf_ctx *ctx, const PmfTaskView &tl) {
 template <typename T>
 static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double sigma2, double eta2,
                                  bool *fused = nullptr, bool *sums = nullptr) {
-    const int other = 1 - side;
     const PmfSideIndex &ix = ctx->index[side];
     const bool acc = pass == PMF_PASS_ACCUMULATE;
     const PmfTaskView tl = pmf_task_view(ctx, side, ix.gauss_tasks, acc);
     int rc;
     PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_gauss_factor_sweep: ratings have not been set");
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_factor_sweep"))) return rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_factor_sweep"))) return rc;
-    if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_factor_sweep"))) return rc;
-    if ((rc = pmf_require_array(ctx, other, PMF_ARR_COV, "pmf_gauss_factor_sweep"))) return rc;
+    if ((rc = gauss_require_state(ctx, side, true, "pmf_gauss_factor_sweep"))) return rc;
     const int width = ctx->cov_stride + ctx->kpad;
     const bool fuse = !acc && !ctx->gauss_unfused;
     const bool emit = sums && fuse && std::is_same<T, float>::value && !ctx->gauss_generic && ctx->K <= 64 &&
@@ -1679,11 +1719,8 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *sta
         p.hsplit = p.partial_h + tl.n_slots * ctx->kpad;
     }
     if (sums) *sums = emit;
-    p.dst_s = acc ? (T *)stats : ctx->arr[side][PMF_ARR_COV].as<T>();
-    p.dst_s_stride = acc ? width : ctx->cov_stride;
-    p.dst_w = acc ? (T *)stats + ctx->cov_stride : ctx->arr[side][PMF_ARR_FACTOR].as<T>();
-    p.dst_w_stride = acc ? width : ctx->kpad;
-    return launch_accumulate<T>(ctx, p, tl.n_split, fuse, sigma2, eta2, fused);
+    const GaussStats<T> st = acc ? GaussStats<T>::interleaved(ctx, (T *)stats, 0) : GaussStats<T>::in_place(ctx, side);
+    return launch_accumulate<T>(ctx, p, tl.n_split, st, fuse, sigma2, eta2, fused);
 }
 
 // the row solver for the context's K and dtype over the rows `sp` names
@@ -1725,10 +1762,16 @@ static int launch_solve(pmf_ctx *ctx, const SolveParams<T> &sp) {
     return PMF_OK;
 }
 
-// the geometry and the two inverse variances of a row solve; the caller sets rows, sources and destinations
+// A row solve from the statistics `src` into `dst`.s / .w (COV / FACTOR of a side, or a fold-in block in place), with the
+// geometry and the two inverse variances; every row from 0 on unless the caller sets rows / row0, and the caller sets n.
 template <typename T>
-static SolveParams<T> solve_params(const pmf_ctx *ctx, double sigma2, double eta2) {
+static SolveParams<T> solve_params(const pmf_ctx *ctx, double sigma2, double eta2, const GaussStats<T> &src, const GaussStats<T> &dst) {
     SolveParams<T> sp;
+    src.set_src(sp);
+    sp.cov = dst.s;
+    sp.factor = dst.w;
+    sp.rows = nullptr;
+    sp.row0 = 0;
     sp.inv_sigma2 = (T)(1.0 / sigma2);
     sp.inv_eta2 = (T)(1.0 / eta2);
     sp.K = ctx->K;
@@ -1870,33 +1913,75 @@ static int gauss_gram_run(pmf_ctx *ctx, int side, const double **g, const T **gw
     return PMF_OK;
 }
 
-// the blend of `n` statistics rows at `stats` (the caller holds no profile bracket; timed with the combine)
+// *gw = w0 G of the side opposite `side`, for the blend of `side`'s statistics; null when unlisted cells are missing
 template <typename T>
-static int launch_zero_blend(pmf_ctx *ctx, T *stats, int64_t n, int64_t stride, const T *gw) {
-    if (n == 0) return PMF_OK;
+static int gauss_zero_gram(pmf_ctx *ctx, int side, const T **gw) {
+    *gw = nullptr;
+    return pmf_gauss_zeros_observed(ctx) ? gauss_gram_run<T>(ctx, 1 - side, nullptr, gw) : PMF_OK;
+}
+
+// The statistics of the first `n_rows` rows of `st`, the one way for the window and block loops: accumulate p's tasks,
+// combine the split rows and, with gw (gauss_zero_gram), blend every row's S with w0 G (timed with the combine).
+// `zero_first` clears the rows before that.  The rule: zero when a row that no task writes -- a row without ratings --
+// will be read.  Fold-in solves every row of a block, and under PMF_ZEROS_OBSERVED every row of a window is blended and
+// read; the default-mode ELBO never zeroes: its row kernel reads neither the statistics nor c_r of a row without ratings.
+template <typename T>
+static int gauss_block_stats(pmf_ctx *ctx, GaussParams<T> &p, int64_t n_split, const GaussStats<T> &st, int64_t n_rows,
+                             bool zero_first, const T *gw) {
+    int rc;
+    if (zero_first) PMF_HIP_CHECK(hipMemsetAsync(st.s, 0, (size_t)n_rows * st.s_stride * sizeof(T), ctx->stream));
+    if (zero_first && !st.one_buffer) PMF_HIP_CHECK(hipMemsetAsync(st.w, 0, (size_t)n_rows * st.w_stride * sizeof(T), ctx->stream));
+    if ((rc = launch_accumulate<T>(ctx, p, n_split, st))) return rc;
+    if (!gw || n_rows == 0) return PMF_OK;
     const int chunks = ctx->cov_stride / PMF_VEC;
     PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
-    hipLaunchKernelGGL((gauss_zero_blend_kernel<T>), dim3((unsigned)((n * chunks + 255) / 256)), dim3(256), 0, ctx->stream, stats, n,
-                       stride, chunks, (T)(1.0 - ctx->gauss_zero_weight), gw);
+    hipLaunchKernelGGL((gauss_zero_blend_kernel<T>), dim3((unsigned)((n_rows * chunks + 255) / 256)), dim3(256), 0, ctx->stream, st.s,
+                       n_rows, st.s_stride, chunks, (T)(1.0 - ctx->gauss_zero_weight), gw);
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
 }
 
-// what the Gaussian calls under PMF_ZEROS_OBSERVED share: the bias model is not covered
-#define PMF_REQUIRE_ZERO_MODE_BIAS_FREE(fn)                                                                                  \
-    PMF_REQUIRE(!(pmf_gauss_zeros_observed(ctx) && pmf_has_bias(ctx)), PMF_EINVAL,                                           \
-                fn ": the bias model is not available while the context counts unobserved cells as weighted zeros "         \
-                   "(pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED)")
-
+static const int64_t kWindowStatsBytes = 256ll << 20;   // statistics of one row window (PmfRowWindows)
+// The side's windows (built once per set of ratings) and the partial slots of their split rows.  *win_rows = the rows of
+// a full window: what fits kWindowStatsBytes, at most PMF_ELBO_ROWS.
 template <typename T>
-static int run_zero_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2);   // (below, with the row windows it shares with the ELBO)
+static int gauss_ensure_windows(pmf_ctx *ctx, int side, int64_t *win_rows) {
+    const int64_t rows = ctx->rows[side], width = ctx->cov_stride + ctx->kpad;
+    const int64_t by_bytes = std::max<int64_t>(1, kWindowStatsBytes / (width * (int64_t)sizeof(T)));
+    *win_rows = std::min(ctx->window_rows > 0 ? std::min(ctx->window_rows, by_bytes) : by_bytes, rows);
+    const std::vector<int64_t> &ptr = ctx->index[side].h_ptr;
+    PmfRowWindows &rw = ctx->index[side].windows;
+    int rc;
+    if (rw.bounds.empty()) {
+        std::vector<int64_t> bounds;
+        for (int64_t r = 0; r < rows; r += *win_rows) bounds.push_back(r);
+        bounds.push_back(rows);
+        PmfTaskList tl;   // (no solve list: a window's rows are all solved, or none is)
+        if ((rc = pmf_upload_tasks(ctx, ptr, rows, pmf_task_chunk(ctx, PMF_GAUSS_CHUNK), false, bounds, false, tl))) return rc;
+        rw.has_empty.assign(bounds.size() - 1, 0);
+        for (size_t w = 0; w + 1 < bounds.size(); ++w)
+            rw.has_empty[w] = std::adjacent_find(ptr.begin() + bounds[w], ptr.begin() + bounds[w + 1] + 1) != ptr.begin() + bounds[w + 1] + 1;
+        rw.tasks = std::move(tl);
+        rw.bounds.swap(bounds);
+    }
+    return rw.tasks.n_slots > 0 ? pmf_ensure_partial(ctx, (size_t)rw.tasks.n_slots * width * sizeof(T)) : PMF_OK;
+}
+
+// the tasks and split rows of window `w` (rows bounds[w] .. bounds[w + 1]) into `p`; returns the window's split-row count
+template <typename T>
+static int64_t gauss_window_tasks(const PmfRowWindows &rw, size_t w, GaussParams<T> &p) {
+    const PmfTaskList &tl = rw.tasks;
+    p.tasks = tl.d_tasks.as<PmfTask>() + tl.task_off[w];
+    p.n_tasks = tl.task_off[w + 1] - tl.task_off[w];
+    p.split = tl.d_split.as<PmfSplitRow>() + tl.split_off[w];
+    return tl.split_off[w + 1] - tl.split_off[w];
+}
 
 extern "C" int pmf_gauss_gram(pmf_ctx *ctx, int side, double *out) {
     PMF_SIDE_ENTRY("pmf_gauss_gram");
     PMF_REQUIRE(out != nullptr, PMF_EINVAL, "pmf_gauss_gram: null out");
     int rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_gram"))) return rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_gram"))) return rc;
+    if ((rc = gauss_require_state(ctx, side, false, "pmf_gauss_gram"))) return rc;
     return pmf_no_throw("pmf_gauss_gram", [&] {
         return pmf_with_dtype(ctx, [&](auto t) {
             using T = decltype(t);
@@ -1922,26 +2007,47 @@ static int run_factor_solve(pmf_ctx *ctx, int side, PmfPass pass, const void *st
                             bool split_rows_only = false, bool sums = false) {
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0, PMF_EINVAL, "pmf_gauss_factor_sweep: variances must be positive");
     int rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_factor_finalize"))) return rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_factor_finalize"))) return rc;
-    const int width = ctx->cov_stride + ctx->kpad;
+    if ((rc = gauss_require_state(ctx, side, false, "pmf_gauss_factor_finalize"))) return rc;
     const bool fin = pass == PMF_PASS_FINALIZE;
     const PmfTaskView tl = pmf_task_view(ctx, side, ctx->index[side].gauss_tasks, fin);
-    SolveParams<T> sp = solve_params<T>(ctx, sigma2, eta2);
+    const GaussStats<T> self = GaussStats<T>::in_place(ctx, side);
+    SolveParams<T> sp = solve_params<T>(ctx, sigma2, eta2, fin ? GaussStats<T>::interleaved(ctx, (T *)stats, 0) : self, self);
     sp.rows = fin ? nullptr : split_rows_only ? tl.d_split_rows : tl.d_nonempty;
     sp.row0 = fin ? tl.row0 : 0;
     sp.n = fin ? tl.row1 - tl.row0 : split_rows_only ? tl.n_split : tl.n_nonempty;
-    sp.src_s = fin ? (const T *)stats : ctx->arr[side][PMF_ARR_COV].as<const T>();
-    sp.src_s_stride = fin ? width : ctx->cov_stride;
-    sp.src_w = fin ? (const T *)stats + ctx->cov_stride : ctx->arr[side][PMF_ARR_FACTOR].as<const T>();
-    sp.src_w_stride = fin ? width : ctx->kpad;
-    sp.cov = ctx->arr[side][PMF_ARR_COV].as<T>();
-    sp.factor = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
     if (sums && split_rows_only && sp.n > 0) {
         sp.hsum = gauss_partial_h<T>(ctx, tl) + tl.n_slots * ctx->kpad;
         sp.mdot = ctx->d_mdot[side].as<T>();
     }
     return launch_solve<T>(ctx, sp);
+}
+
+// pmf_gauss_factor_sweep under PMF_ZEROS_OBSERVED: G of the other side, then per row window of the side the listed sums
+// into the context's window (zeroed first where the window has rows no task writes), blended with w0 G, and a solve of
+// every row of the window into COV / FACTOR.
+template <typename T>
+static int run_zero_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
+    const PmfRowWindows &rw = ctx->index[side].windows;
+    int64_t win_rows;
+    int rc;
+    PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gauss_factor_sweep: ratings have not been set");
+    if ((rc = gauss_require_state(ctx, side, true, "pmf_gauss_factor_sweep"))) return rc;
+    if ((rc = gauss_ensure_windows<T>(ctx, side, &win_rows))) return rc;
+    if ((rc = ctx->d_gauss_window.reserve(ctx, (size_t)win_rows * (ctx->cov_stride + ctx->kpad) * sizeof(T), {ctx->stream}))) return rc;
+    const T *gw;
+    if ((rc = gauss_zero_gram<T>(ctx, side, &gw))) return rc;
+    GaussParams<T> p = gauss_params<T>(ctx, side);
+    for (size_t w = 0; w + 1 < rw.bounds.size(); ++w) {
+        const int64_t r0 = rw.bounds[w], n = rw.bounds[w + 1] - r0, ns = gauss_window_tasks<T>(rw, w, p);
+        const GaussStats<T> st = GaussStats<T>::interleaved(ctx, ctx->d_gauss_window.as<T>(), r0);   // (tasks carry the row's id in the side)
+        if ((rc = gauss_block_stats<T>(ctx, p, ns, st, n, rw.has_empty[w], gw))) return rc;
+        // (no row list: every row is solved, S'[0] = (1 - w0) S[0] + w0 G[0] > 0)
+        SolveParams<T> sp = solve_params<T>(ctx, sigma2, eta2, st, GaussStats<T>::in_place(ctx, side));
+        sp.row0 = r0;
+        sp.n = n;
+        if ((rc = launch_solve<T>(ctx, sp))) return rc;
+    }
+    return PMF_OK;
 }
 
 extern "C" int pmf_gauss_factor_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
@@ -2113,9 +2219,8 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
     int rc;
     // unlisted cells as weighted zeros: every row's S is blended with w0 G of the opposite side (formed once), and a row
     // without ratings is solved like the rest
-    const bool zeros = pmf_gauss_zeros_observed(ctx);
-    const T *gw = nullptr;
-    if (zeros && (rc = gauss_gram_run<T>(ctx, 1 - side, nullptr, &gw))) return rc;
+    const T *gw;
+    if ((rc = gauss_zero_gram<T>(ctx, side, &gw))) return rc;
     for (int64_t r0 = 0; r0 < a.n_rows; r0 = st.r1) {
         int64_t units = 0;   // a row's statistics, and the partial slots of a row that is split
         const auto fits = [&](int64_t n) { return (units += 1 + (n > chunk ? (n + chunk - 1) / chunk : 0)) <= max_units; };
@@ -2137,10 +2242,6 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         if (nnz) PMF_HIP_CHECK(hipMemcpy(d_tasks.as(), tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
         if (!split.empty())
             PMF_HIP_CHECK(hipMemcpy(d_split.as(), split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
-        if (has_empty) {   // no task writes an empty row: zero sums, which the solvers skip
-            PMF_HIP_CHECK(hipMemsetAsync(d_s.as(), 0, (size_t)B * cs * sizeof(T), ctx->stream));
-            PMF_HIP_CHECK(hipMemsetAsync(d_w.as(), 0, (size_t)B * kpad * sizeof(T), ctx->stream));
-        }
         GaussParams<T> p = gauss_params<T>(ctx, side);   // over the block's own buffers; no hot flags, and b = 0
         p.tasks = d_tasks.as<PmfTask>();
         p.n_tasks = (int64_t)tasks.size();
@@ -2150,22 +2251,10 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         p.hot = nullptr;
         p.bias_self = nullptr;
         p.partial = d_partial.as<T>();
-        p.dst_s = d_s.as<T>();
-        p.dst_s_stride = cs;
-        p.dst_w = d_w.as<T>();
-        p.dst_w_stride = kpad;
-        if ((rc = launch_accumulate<T>(ctx, p, (int64_t)split.size()))) return rc;
-        if (zeros && (rc = launch_zero_blend<T>(ctx, d_s.as<T>(), B, cs, gw))) return rc;
-        SolveParams<T> sp = solve_params<T>(ctx, a.sigma2, a.eta2);
-        sp.rows = nullptr;
-        sp.row0 = 0;
+        const GaussStats<T> stats = GaussStats<T>::separate(ctx, d_s.as<T>(), d_w.as<T>());
+        if ((rc = gauss_block_stats<T>(ctx, p, (int64_t)split.size(), stats, B, has_empty, gw))) return rc;
+        SolveParams<T> sp = solve_params<T>(ctx, a.sigma2, a.eta2, stats, stats);   // (in place)
         sp.n = B;
-        sp.src_s = d_s.as<const T>();
-        sp.src_s_stride = cs;
-        sp.src_w = d_w.as<const T>();
-        sp.src_w_stride = kpad;
-        sp.cov = d_s.as<T>();
-        sp.factor = d_w.as<T>();
         if ((rc = launch_solve<T>(ctx, sp))) return rc;
         if (bias) {
             FoldBiasParams<T> q;
@@ -2199,7 +2288,7 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         if (oc && (rc = pmf_fold_in_download(ctx, PMF_ARR_COV, d_s.as(), oc, B))) return rc;
         if (ob && bias && (rc = pmf_fold_in_download(ctx, PMF_ARR_BIAS, d_b.as(), ob, B))) return rc;
         if (ob && !bias) std::fill_n(ob, (size_t)B, 0.0);
-        for (int64_t r = 0; has_empty && !zeros && r < B; ++r) {
+        for (int64_t r = 0; has_empty && !gw && r < B; ++r) {
             if (st.ptr[(size_t)r + 1] > st.ptr[(size_t)r]) continue;
             // a row without ratings gets the prior: m = 0, V = eta2 I, b = 0
             std::fill_n(of + r * K, (size_t)K, 0.0);
@@ -2229,8 +2318,7 @@ extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
     PMF_REQUIRE(sigma2 > 0 && eta2 > 0 && eta_bias2 > 0, PMF_EINVAL, "pmf_gauss_fold_in: variances must be positive");
     PMF_REQUIRE(n_iter >= 1, PMF_EINVAL, "pmf_gauss_fold_in: n_iter = %d, must be at least 1", n_iter);
     const int other = 1 - side;
-    if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_fold_in"))) return rc;
-    if ((rc = pmf_require_array(ctx, other, PMF_ARR_COV, "pmf_gauss_fold_in"))) return rc;
+    if ((rc = gauss_require_state(ctx, other, false, "pmf_gauss_fold_in"))) return rc;
     if ((rc = pmf_check_ids(other_ids, nnz, ctx->rows[other], "pmf_gauss_fold_in", "id"))) return rc;
     const FoldInBatch a = {n_rows, row_ptr, other_ids, ratings, sigma2, eta2, eta_bias2, n_iter, out_factor, out_cov, out_bias};
     return pmf_no_throw("pmf_gauss_fold_in", [&] {
@@ -2246,12 +2334,11 @@ extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
 //     SQNORM = |m_r|^2 + tr V_r      LOGDET = log det V_r      BIAS_SQ = BIAS[r]^2
 //     ESS    = c_r - 2 m_r . w_r + <V_r + m_r m_r^T, S_r>,     c_r = sum_j (x_j - b_r - b_o)^2
 // ESS is the expected squared residual of all of the row's ratings (bias variances aside: the host adds them).
-// The rows go in windows whose statistics ([rows x (cov_stride + kpad)]) fit a fixed budget: per window run the
-// sweep's accumulate kernels (accumulate-only form) and the split-row combine on the window's tasks, then c_r and the
-// row reduction.  The task list is the Gaussian one again (same task length, so every row is cut and summed as in the
-// sweep), grouped by window.  Sums inside a row are in the context dtype; the logarithms and everything across rows are
-// double.
-static const int64_t kElboStatsBytes = 256ll << 20;   // statistics of one row window
+// The rows go in the side's row windows (gauss_ensure_windows: statistics [rows x (cov_stride + kpad)] within a fixed
+// budget): per window run the sweep's accumulate kernels (accumulate-only form) and the split-row combine on the window's
+// tasks, then c_r and the row reduction.  The windows' task list is the Gaussian one again (same task length, so every row
+// is cut and summed as in the sweep).  Sums inside a row are in the context dtype; the logarithms and everything across
+// rows are double.
 
 template <typename T>
 struct ElboParams {
@@ -2552,93 +2639,6 @@ static int launch_elbo_rows(pmf_ctx *ctx, const ElboParams<T> &e) {
     return PMF_OK;
 }
 
-// rows of one statistics window
-template <typename T>
-static int64_t elbo_window_rows(const pmf_ctx *ctx) {
-    const int64_t by_bytes = std::max<int64_t>(1, kElboStatsBytes / ((int64_t)(ctx->cov_stride + ctx->kpad) * (int64_t)sizeof(T)));
-    return ctx->elbo_rows > 0 ? std::min(ctx->elbo_rows, by_bytes) : by_bytes;
-}
-
-// the side's Gaussian tasks grouped by row window (built once per set of ratings)
-static int ensure_elbo_tasks(pmf_ctx *ctx, int side, int64_t win_rows) {
-    PmfSideIndex &ix = ctx->index[side];
-    if (!ix.elbo_bounds.empty()) return PMF_OK;
-    const int64_t rows = ctx->rows[side];
-    std::vector<int64_t> bounds;
-    for (int64_t r = 0; r < rows; r += win_rows) bounds.push_back(r);
-    bounds.push_back(rows);
-    PmfTaskList tl;   // (no solve list: the ELBO solves nothing)
-    int rc;
-    if ((rc = pmf_upload_tasks(ctx, ix.h_ptr, rows, pmf_task_chunk(ctx, PMF_GAUSS_CHUNK), false, bounds, false, tl))) return rc;
-    ix.elbo_win_empty.assign(bounds.size() - 1, 0);
-    for (size_t w = 0; w + 1 < bounds.size(); ++w)
-        ix.elbo_win_empty[w] = std::adjacent_find(ix.h_ptr.begin() + bounds[w], ix.h_ptr.begin() + bounds[w + 1] + 1) !=
-                               ix.h_ptr.begin() + bounds[w + 1] + 1;
-    ix.elbo_tasks = std::move(tl);
-    ix.elbo_bounds.swap(bounds);
-    return PMF_OK;
-}
-
-// The tasks of window `w` of the side's ELBO list into `p`, summing into the window buffer `win` ([rows of the window]
-// [cov_stride + kpad]); returns the window's split-row count.  Tasks carry the row's id in the side: the window's first
-// row is the buffer's row 0.
-template <typename T>
-static int64_t elbo_window_params(const PmfSideIndex &ix, size_t w, T *win, int width, int cs, GaussParams<T> &p) {
-    const PmfTaskList &tl = ix.elbo_tasks;
-    p.tasks = tl.d_tasks.as<PmfTask>() + tl.task_off[w];
-    p.n_tasks = tl.task_off[w + 1] - tl.task_off[w];
-    p.split = tl.d_split.as<PmfSplitRow>() + tl.split_off[w];
-    p.dst_s = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(win) - (uintptr_t)ix.elbo_bounds[w] * width * sizeof(T));
-    p.dst_s_stride = width;
-    p.dst_w = p.dst_s + cs;
-    p.dst_w_stride = width;
-    return tl.split_off[w + 1] - tl.split_off[w];
-}
-
-// pmf_gauss_factor_sweep under PMF_ZEROS_OBSERVED: G of the other side, then per row window of the side accumulate the
-// listed sums into the context's window (zeroed first where the window has rows no task writes), blend S with w0 G and
-// solve every row of the window into COV / FACTOR.
-template <typename T>
-static int run_zero_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
-    const int other = 1 - side, cs = ctx->cov_stride, width = cs + ctx->kpad;
-    const int64_t rows = ctx->rows[side];
-    PmfSideIndex &ix = ctx->index[side];
-    int rc;
-    PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_gauss_factor_sweep: ratings have not been set");
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_factor_sweep"))) return rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_factor_sweep"))) return rc;
-    if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gauss_factor_sweep"))) return rc;
-    if ((rc = pmf_require_array(ctx, other, PMF_ARR_COV, "pmf_gauss_factor_sweep"))) return rc;
-    const int64_t win_rows = std::min(elbo_window_rows<T>(ctx), rows);
-    if ((rc = ensure_elbo_tasks(ctx, side, win_rows))) return rc;
-    const PmfTaskList &tl = ix.elbo_tasks;
-    if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * width * sizeof(T)))) return rc;
-    if ((rc = ctx->d_gauss_window.reserve(ctx, (size_t)win_rows * width * sizeof(T), {ctx->stream}))) return rc;
-    const T *gw = nullptr;
-    if ((rc = gauss_gram_run<T>(ctx, other, nullptr, &gw))) return rc;
-    T *win = ctx->d_gauss_window.as<T>();
-    GaussParams<T> p = gauss_params<T>(ctx, side);
-    SolveParams<T> sp = solve_params<T>(ctx, sigma2, eta2);
-    sp.rows = nullptr;   // every row: S'[0] = (1 - w0) S[0] + w0 G[0] > 0
-    sp.src_s_stride = width;
-    sp.src_w_stride = width;
-    sp.cov = ctx->arr[side][PMF_ARR_COV].as<T>();
-    sp.factor = ctx->arr[side][PMF_ARR_FACTOR].as<T>();
-    for (size_t w = 0; w + 1 < ix.elbo_bounds.size(); ++w) {
-        const int64_t r0 = ix.elbo_bounds[w], n = ix.elbo_bounds[w + 1] - r0;
-        const int64_t ns = elbo_window_params<T>(ix, w, win, width, cs, p);
-        if (ix.elbo_win_empty[w]) PMF_HIP_CHECK(hipMemsetAsync(win, 0, (size_t)n * width * sizeof(T), ctx->stream));
-        if ((rc = launch_accumulate<T>(ctx, p, ns))) return rc;
-        if ((rc = launch_zero_blend<T>(ctx, win, n, width, gw))) return rc;
-        sp.row0 = r0;
-        sp.n = n;
-        sp.src_s = p.dst_s;
-        sp.src_w = p.dst_w;
-        if ((rc = launch_solve<T>(ctx, sp))) return rc;
-    }
-    return PMF_OK;
-}
-
 template <typename T>
 static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals, double *per_row) {
     const int64_t rows = ctx->rows[side];
@@ -2666,33 +2666,25 @@ static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals
         PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SOLVE);
         if ((rc = launch_elbo_rows<T>(ctx, e))) return rc;
     } else {
-        const int64_t win_rows = std::min(elbo_window_rows<T>(ctx), rows);
-        if ((rc = ensure_elbo_tasks(ctx, side, win_rows))) return rc;
-        const PmfTaskList &tl = ix.elbo_tasks;
-        if (tl.n_slots > 0 && (rc = pmf_ensure_partial(ctx, (size_t)tl.n_slots * width * sizeof(T)))) return rc;
-        if ((rc = d_cpart.alloc(ctx, (size_t)tl.n_slots * sizeof(T)))) return rc;
+        const PmfRowWindows &rw = ix.windows;
+        int64_t win_rows;
+        if ((rc = gauss_ensure_windows<T>(ctx, side, &win_rows))) return rc;
+        if ((rc = d_cpart.alloc(ctx, (size_t)rw.tasks.n_slots * sizeof(T)))) return rc;
         if ((rc = d_win.alloc(ctx, (size_t)win_rows * width * sizeof(T)))) return rc;
         if ((rc = d_c.alloc(ctx, (size_t)win_rows * sizeof(T)))) return rc;
-        // unlisted cells as weighted zeros: S of EVERY row is blended with w0 G of the other side, so every row has
-        // statistics (e.ptr stays null) and the rows no task writes start from zero sums and c_r = 0
-        const bool zeros = pmf_gauss_zeros_observed(ctx);
-        const T *gw = nullptr;
-        if (zeros && (rc = gauss_gram_run<T>(ctx, 1 - side, nullptr, &gw))) return rc;
+        // unlisted cells as weighted zeros (gw is set): S of EVERY row is blended with w0 G of the other side, so every
+        // row has statistics (e.ptr stays null) and the rows no task writes start from zero sums and c_r = 0
+        const T *gw;
+        if ((rc = gauss_zero_gram<T>(ctx, side, &gw))) return rc;
         GaussParams<T> p = gauss_params<T>(ctx, side);
         e.stats = d_win.as<const T>();
         e.csum = d_c.as<const T>();
-        e.ptr = zeros ? nullptr : ix.d_ptr.as<const int64_t>();
-        for (size_t w = 0; w + 1 < ix.elbo_bounds.size(); ++w) {
-            const int64_t r0 = ix.elbo_bounds[w], n = ix.elbo_bounds[w + 1] - r0;
-            // (default mode: the window is not zeroed -- every row with a rating is written whole by its task or by the
-            //  combine, and the row kernel does not read the statistics or c_r of a row without ratings)
-            const int64_t ns = elbo_window_params<T>(ix, w, d_win.as<T>(), width, cs, p), nt = p.n_tasks;
-            if (zeros && ix.elbo_win_empty[w]) {
-                PMF_HIP_CHECK(hipMemsetAsync(d_win.as(), 0, (size_t)n * width * sizeof(T), ctx->stream));
-                PMF_HIP_CHECK(hipMemsetAsync(d_c.as(), 0, (size_t)n * sizeof(T), ctx->stream));
-            }
-            if ((rc = launch_accumulate<T>(ctx, p, ns))) return rc;
-            if (zeros && (rc = launch_zero_blend<T>(ctx, d_win.as<T>(), n, width, gw))) return rc;
+        e.ptr = gw ? nullptr : ix.d_ptr.as<const int64_t>();
+        for (size_t w = 0; w + 1 < rw.bounds.size(); ++w) {
+            const int64_t r0 = rw.bounds[w], n = rw.bounds[w + 1] - r0, ns = gauss_window_tasks<T>(rw, w, p), nt = p.n_tasks;
+            const bool zero_first = gw && rw.has_empty[w];
+            if (zero_first) PMF_HIP_CHECK(hipMemsetAsync(d_c.as(), 0, (size_t)n * sizeof(T), ctx->stream));
+            if ((rc = gauss_block_stats<T>(ctx, p, ns, GaussStats<T>::interleaved(ctx, d_win.as<T>(), r0), n, zero_first, gw))) return rc;
             PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SOLVE);
             if (nt > 0) {
                 ElboSqParams<T> q;
@@ -2737,12 +2729,10 @@ extern "C" int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, doubl
     PMF_SIDE_ENTRY("pmf_gauss_elbo_terms");
     PMF_REQUIRE(totals, PMF_EINVAL, "pmf_gauss_elbo_terms: null totals");
     int rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_FACTOR, "pmf_gauss_elbo_terms"))) return rc;
-    if ((rc = pmf_require_array(ctx, side, PMF_ARR_COV, "pmf_gauss_elbo_terms"))) return rc;
+    if ((rc = gauss_require_state(ctx, side, false, "pmf_gauss_elbo_terms"))) return rc;
     if (with_data) {
         PMF_REQUIRE_ZERO_MODE_BIAS_FREE("pmf_gauss_elbo_terms");
-        if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_FACTOR, "pmf_gauss_elbo_terms"))) return rc;
-        if ((rc = pmf_require_array(ctx, 1 - side, PMF_ARR_COV, "pmf_gauss_elbo_terms"))) return rc;
+        if ((rc = gauss_require_state(ctx, 1 - side, false, "pmf_gauss_elbo_terms"))) return rc;
         PMF_REQUIRE(ctx->index[side].d_ptr, PMF_EINVAL, "pmf_gauss_elbo_terms: ratings have not been set");
     }
     return pmf_no_throw("pmf_gauss_elbo_terms", [&] {

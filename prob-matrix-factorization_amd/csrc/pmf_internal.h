@@ -141,6 +141,14 @@ struct PmfTaskView {
     int64_t n_nonempty = 0;
 };
 
+// The rows of a side in windows whose Gaussian statistics fit a fixed budget (pmf_gauss.hip), for the factor sweep under
+// PMF_ZEROS_OBSERVED and for pmf_gauss_elbo_terms.  The tasks are the Gaussian list again (same length, same cuts) by window.
+struct PmfRowWindows {
+    PmfTaskList tasks;
+    std::vector<int64_t> bounds;      // [n_windows + 1] first row of every window; empty = not built
+    std::vector<uint8_t> has_empty;   // [n_windows] 1 if the window has a row without ratings, which no task writes
+};
+
 // Ratings ordered by one side (CSR when side = user, CSC when side = item).  A default-constructed value is
 // "no ratings": d_ptr is what the sweeps test.
 struct PmfSideIndex {
@@ -156,11 +164,7 @@ struct PmfSideIndex {
     PmfTaskList gauss_tasks;     // chunk = PMF_GAUSS_CHUNK, empty rows excluded
     PmfTaskList bias_tasks;      // chunk <= PMF_GAMMA_CHUNK, empty rows excluded
     PmfTaskList sgd_tasks;       // chunk = PMF_SGD_CHUNK exactly (the gradient mode is defined by it), empty rows excluded
-    // pmf_gauss_elbo_terms: the Gaussian list again (same task length, same cuts), grouped by the row windows of
-    // elbo_bounds instead of the row chunks.  Built on the first call with a data term; goes with the ratings.
-    PmfTaskList elbo_tasks;
-    std::vector<int64_t> elbo_bounds;   // [n_windows + 1] first row of every window; empty = not built
-    std::vector<uint8_t> elbo_win_empty;   // [n_windows] 1 if the window has a row without ratings (PMF_ZEROS_OBSERVED zeroes such a window first)
+    PmfRowWindows windows;       // built by the first call that needs them; goes with the ratings
     // pmf_rank_items with exclude_train (USER side only): every row's DISTINCT ids on the opposite side, ascending --
     // pmf_ctx_set_ratings keeps duplicate pairs.  Built on the first such call (pmf_index_distinct); goes with the ratings.
     PmfBuf d_distinct_ptr;       // int64_t [rows + 1]; null = not built
@@ -256,7 +260,7 @@ struct pmf_ctx {
     int64_t gamma_pred_pairs = 0;  // PMF_GAMMA_PRED_PAIRS=n caps the pairs of one staging round of pmf_gamma_predictive (tests: many rounds on a small batch; 0: kGammaPredPairs)
     int64_t topk_query_rows = 0;   // PMF_TOPK_QUERY_ROWS=n caps the query rows of one round of pmf_topk_items*, pmf_rank_items and the two query calls, rounded down to a multiple of 32 and at least 32 (tests: many rounds on a small batch; 0: 1 << 20 rows, or 512 MB of scores on the two-phase path)
     int64_t stage_bytes = 64ll << 20;   // PMF_STAGE_BYTES=n: bytes of one staging round of pmf_set_array / pmf_get_array, the row exchanges, the fold-ins' downloads and pmf_comm_gather_user_rows, at least one row (tests: many rounds on a few rows; 0 / unset: 64 MiB)
-    int64_t elbo_rows = 0;         // PMF_ELBO_ROWS=n caps the rows of one statistics window of pmf_gauss_elbo_terms (tests: many windows on a small problem; 0: by scratch size)
+    int64_t window_rows = 0;       // PMF_ELBO_ROWS=n caps the rows of one statistics window (PmfRowWindows) of pmf_gauss_elbo_terms and of the zero-mode factor sweep (tests: many windows on a small problem; 0: by scratch size)
     size_t elbo_lds_bytes = 0;     // dynamic LDS size the ELBO row kernel of this context's K and dtype has been allowed (0: not yet asked)
     int task_chunk = 0;            // PMF_TASK_CHUNK=n (power of two in [32, 512]) fixes the task length of the gamma / Gaussian / bias lists (tests: long tasks on small problems; 0: by nnz)
 
@@ -431,7 +435,12 @@ static inline void pmf_factor_written(pmf_ctx *ctx) { ctx->gauss_mdot_valid[0] =
 static inline bool pmf_has_bias(const pmf_ctx *ctx) { return ctx->arr[0][PMF_ARR_BIAS] && ctx->arr[1][PMF_ARR_BIAS]; }
 
 static inline bool pmf_gauss_zeros_observed(const pmf_ctx *ctx) { return ctx->gauss_zeros == PMF_ZEROS_OBSERVED; }
-// the Gaussian calls that PMF_ZEROS_OBSERVED (pmf_ctx_set_gauss_zeros) does not cover
+// PMF_ZEROS_OBSERVED (pmf_ctx_set_gauss_zeros) at the Gaussian entry points.  _GAUSS_ZEROS_MISSING: the calls the mode does
+// not cover refuse it (pmf_gauss_factor_accumulate / _finalize, pmf_gauss_bias_sweep / _accumulate / _finalize).  _ZERO_MODE_
+// BIAS_FREE: the calls it covers refuse the bias model under it (pmf_gauss_factor_sweep, _fold_in, _elbo_terms with data).
 #define PMF_REQUIRE_GAUSS_ZEROS_MISSING(fn)                         \
     PMF_REQUIRE(!pmf_gauss_zeros_observed(ctx), PMF_EINVAL,         \
                 fn ": not available while the context counts unobserved cells as weighted zeros (pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED)")
+#define PMF_REQUIRE_ZERO_MODE_BIAS_FREE(fn)                                         \
+    PMF_REQUIRE(!(pmf_gauss_zeros_observed(ctx) && pmf_has_bias(ctx)), PMF_EINVAL,  \
+                fn ": the bias model is not available while the context counts unobserved cells as weighted zeros (pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED)")
