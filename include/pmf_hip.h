@@ -150,6 +150,28 @@ int pmf_ctx_task_max_len(pmf_ctx *ctx, int side, int list, int *max_len);
  * (row chunks) the sweep kernels consume. */
 int pmf_ctx_set_ratings(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids,
                         const int32_t *item_ids, const double *ratings);
+/* The same with a confidence weight c_j per rating (Gaussian CAVI models): rating j has precision c_j / sigma2,
+ *     x_j ~ N(b_r + b_o + theta_r . beta_o, sigma2 / c_j),   c_j > 0,
+ * so every sum the Gaussian calls form over a row's ratings takes c_j inside: S_r = sum_j c_j (COV[o_j] + m_j m_j^T),
+ * w_r = sum_j c_j m_j (x_j - b_r - b_o), C_r = sum_j c_j in the place of the row's rating count in the bias update, and
+ * c_r = sum_j c_j (x_j - b_r - b_o)^2 in pmf_gauss_elbo_terms.  The weights go through the same stable permutation as
+ * the ratings into a per-side [nnz] array of the context dtype, and C_r of both sides is formed once (in double, in
+ * the row's rating order, rounded once to the context dtype).  `weights` = NULL is pmf_ctx_set_ratings, which is this
+ * call with NULL: it clears the weights.  While the context holds weights, pmf_gauss_factor_sweep / _accumulate /
+ * _finalize, pmf_gauss_bias_sweep / _accumulate / _finalize (second statistic: C_r) and pmf_gauss_elbo_terms follow
+ * them, also under pmf_ctx_set_gauss_zeros' PMF_ZEROS_OBSERVED (a listed cell then has precision c_j / sigma2, an
+ * unlisted one weight / sigma2: S'_r = sum_j (c_j - weight) A_j + weight G).  With all weights 1.0 the default mode
+ * gives the bytes of the unweighted context.  pmf_predict*, pmf_eval_* and the top-k / rank calls do not read them.
+ * PMF_EINVAL: a weight that is not finite or not > 0 (its position is named; checked on the host before anything is
+ * touched: the context keeps its previous ratings); a context with a communicator.  While the context holds weights
+ * pmf_comm_init / _attach, pmf_gauss_sgd_* and every pmf_gamma_* call that reads the ratings are PMF_EINVAL. */
+int pmf_ctx_set_ratings_weighted(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, const int32_t *item_ids,
+                                 const double *ratings, const double *weights /* [nnz], may be NULL */);
+/* *has = 1 while the context's ratings came with weights */
+int pmf_ctx_has_rating_weights(pmf_ctx *ctx, int *has);
+/* C_r of every row of `side` as the kernels read it (the row's weights summed in double, rounded once to the context
+ * dtype); the rating counts when the context holds no weights.  PMF_EINVAL: ratings have not been set. */
+int pmf_ctx_rating_weight_sums(pmf_ctx *ctx, int side, double *out /* rows */);
 
 /* Host float64 -> device (and back).  `host` holds rows x K (FACTOR, SHAPE,
  * RATE), rows (PRIOR_RATE, HYPER_RATE, BIAS) or rows x K x K (COV) doubles,
@@ -491,6 +513,14 @@ int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row
                       const double *ratings, double sigma2, double eta2, double eta_bias2, int n_iter,
                       double *out_factor /* n_rows x K */, double *out_cov /* n_rows x K x K, may be NULL */,
                       double *out_bias /* n_rows, may be NULL */);
+/* The same with a weight per rating of the batch (pmf_ctx_set_ratings_weighted's model): S, the right-hand side, g =
+ * sum_j c_j m_j, c0 = sum_j c_j (x_j - BIAS_other[o_j]) and kappa = 1 / (sigma2 (1/eta_bias2 + C/sigma2)), C = sum_j c_j.
+ * `weights` = NULL is pmf_gauss_fold_in, which is this call with NULL.  Independent of whether the context's own
+ * ratings have weights.  PMF_EINVAL also for a weight that is not finite or not > 0 (its position is named). */
+int pmf_gauss_fold_in_weighted(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
+                               const double *ratings, const double *weights /* [row_ptr[n_rows]], may be NULL */,
+                               double sigma2, double eta2, double eta_bias2, int n_iter, double *out_factor, double *out_cov,
+                               double *out_bias);
 
 /* Evidence lower bound of the Gaussian models: the per-row sums that do not depend on the hyperparameters.  No
  * reference counterpart (the reference never evaluates its objective).  q is what the reference's updates imply:

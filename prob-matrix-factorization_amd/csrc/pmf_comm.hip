@@ -400,6 +400,8 @@ int comm_create(pmf_ctx *ctx, int nranks, int rank, const void *unique_id, int t
                 "pmf_comm_init: the context counts unobserved cells as zeros (pmf_ctx_set_gamma_zeros), which is not available with a communicator");
     PMF_REQUIRE(!pmf_gauss_zeros_observed(ctx), PMF_EINVAL,
                 "pmf_comm_init: the context counts unobserved cells as weighted zeros (pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED), which is not available with a communicator");
+    PMF_REQUIRE(!ctx->weighted, PMF_EINVAL,
+                "pmf_comm_init: the context holds rating weights (pmf_ctx_set_ratings_weighted), which are not available with a communicator");
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     PmfComm *cm = new (std::nothrow) PmfComm();
     PMF_REQUIRE(cm, PMF_ENOMEM, "pmf_comm_init: out of host memory");
@@ -671,6 +673,8 @@ extern "C" int pmf_comm_attach(pmf_ctx *ctx, pmf_ctx *owner) {
                 "pmf_comm_attach: the context counts unobserved cells as zeros (pmf_ctx_set_gamma_zeros), which is not available with a communicator");
     PMF_REQUIRE(!pmf_gauss_zeros_observed(ctx), PMF_EINVAL,
                 "pmf_comm_attach: the context counts unobserved cells as weighted zeros (pmf_ctx_set_gauss_zeros, PMF_ZEROS_OBSERVED), which is not available with a communicator");
+    PMF_REQUIRE(!ctx->weighted, PMF_EINVAL,
+                "pmf_comm_attach: the context holds rating weights (pmf_ctx_set_ratings_weighted), which are not available with a communicator");
     PMF_REQUIRE(ctx->device == owner->device, PMF_EINVAL, "pmf_comm_attach: contexts on different devices (%d, %d)",
                 ctx->device, owner->device);
     ctx->comm = owner->comm;

@@ -226,6 +226,7 @@ static void drop_ratings(pmf_ctx *ctx) {
     ctx->index[0] = PmfSideIndex();
     ctx->index[1] = PmfSideIndex();
     ctx->nnz = 0;
+    ctx->weighted = false;
 }
 
 // Armed once the old index (or its work lists) has been dropped: a rebuild that fails or throws leaves the context
@@ -533,12 +534,17 @@ static int build_hot_rows(pmf_ctx *ctx) {
 }
 
 static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, const int32_t *item_ids,
-                            const double *ratings);
+                            const double *ratings, const double *weights);
 
 extern "C" int pmf_ctx_set_ratings(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids,
                                    const int32_t *item_ids, const double *ratings) {
+    return pmf_ctx_set_ratings_weighted(ctx, nnz, user_ids, item_ids, ratings, nullptr);
+}
+
+extern "C" int pmf_ctx_set_ratings_weighted(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, const int32_t *item_ids,
+                                            const double *ratings, const double *weights) {
     try {  // host containers may throw: nothing propagates across the C boundary
-        return set_ratings_impl(ctx, nnz, user_ids, item_ids, ratings);
+        return set_ratings_impl(ctx, nnz, user_ids, item_ids, ratings, weights);
     } catch (const std::bad_alloc &) {
         pmf_set_error("pmf_ctx_set_ratings: out of host memory");
         return PMF_ENOMEM;
@@ -551,21 +557,43 @@ extern "C" int pmf_ctx_set_ratings(pmf_ctx *ctx, int64_t nnz, const int32_t *use
 // Host build of one side (stable counting sort).  Used for nnz >= 2^31 - 1 and with
 // PMF_INDEX_HOST=1 (the tests compare it with the device build of pmf_index.hip).
 static int fill_side_host(pmf_ctx *ctx, int side, int64_t nnz, const int32_t *key, const int32_t *oth,
-                          const double *ratings, std::vector<int32_t> &other, std::vector<char> &val) {
+                          const double *ratings, const double *weights, std::vector<int32_t> &other, std::vector<char> &val,
+                          std::vector<char> &wgt) {
     const int64_t rows = ctx->rows[side];
     PmfSideIndex &ix = ctx->index[side];
     ix.h_ptr.assign((size_t)rows + 1, 0);
     for (int64_t n = 0; n < nnz; ++n) ix.h_ptr[(size_t)key[n] + 1]++;
     for (int64_t r = 0; r < rows; ++r) ix.h_ptr[(size_t)r + 1] += ix.h_ptr[(size_t)r];
     std::vector<int64_t> cursor(ix.h_ptr.begin(), ix.h_ptr.end() - 1);
+    std::vector<double> wd(weights ? (size_t)nnz : 0);   // the weights in row order, in double
     pmf_with_dtype(ctx, [&](auto t) {
         auto *v = (decltype(t) *)val.data();
+        auto *w = (decltype(t) *)wgt.data();
         for (int64_t n = 0; n < nnz; ++n) {
             int64_t d = cursor[(size_t)key[n]]++;
             other[(size_t)d] = oth[n];
             v[d] = (decltype(t))ratings[n];
+            if (weights) {
+                w[d] = (decltype(t))weights[n];
+                wd[(size_t)d] = weights[n];
+            }
         }
     });
+    if (weights) {   // C_r: in double in the row's rating order, rounded once
+        ix.h_wsum.assign((size_t)rows, 0.0);
+        std::vector<char> sums((size_t)rows * ctx->elem);
+        pmf_with_dtype(ctx, [&](auto t) {
+            auto *st = (decltype(t) *)sums.data();
+            for (int64_t r = 0; r < rows; ++r) {
+                double c = 0.0;
+                for (int64_t k = ix.h_ptr[(size_t)r]; k < ix.h_ptr[(size_t)r + 1]; ++k) c += wd[(size_t)k];
+                ix.h_wsum[(size_t)r] = c;
+                st[r] = (decltype(t))c;
+            }
+        });
+        if (rows) PMF_HIP_CHECK(hipMemcpy(ix.d_wsum.as(), sums.data(), sums.size(), hipMemcpyHostToDevice));
+        if (nnz) PMF_HIP_CHECK(hipMemcpy(ix.d_wgt.as(), wgt.data(), (size_t)nnz * ctx->elem, hipMemcpyHostToDevice));
+    }
     PMF_HIP_CHECK(hipMemcpy(ix.d_ptr.as(), ix.h_ptr.data(), (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     if (nnz) {
         PMF_HIP_CHECK(hipMemcpy(ix.d_other.as(), other.data(), (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -586,16 +614,22 @@ static int bad_id_error(const pmf_ctx *ctx, const int32_t *user_ids, const int32
 }
 
 static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, const int32_t *item_ids,
-                            const double *ratings) {
+                            const double *ratings, const double *weights) {
     CHECK_CTX(ctx, "pmf_ctx_set_ratings");
     PMF_REQUIRE(nnz >= 0, PMF_EINVAL, "pmf_ctx_set_ratings: negative nnz");
     PMF_REQUIRE(nnz == 0 || (user_ids && item_ids && ratings), PMF_EINVAL,
                 "pmf_ctx_set_ratings: null input array");
+    int rc;
+    if (weights) {   // on the host, before anything is touched: a bad weight leaves the context's previous ratings in place
+        PMF_REQUIRE(ctx->comm == nullptr, PMF_EINVAL,
+                    "pmf_ctx_set_ratings_weighted: rating weights are not available on a context with a communicator "
+                    "(the per-row weight sums would have to be added over the ranks)");
+        if ((rc = pmf_check_weights(weights, nnz, "pmf_ctx_set_ratings_weighted"))) return rc;
+    }
     PMF_HIP_CHECK(hipSetDevice(ctx->device));
     PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     // positions are sorted as 32-bit values on the device
     const bool on_host = nnz >= (int64_t)INT32_MAX || getenv("PMF_INDEX_HOST") != nullptr;
-    int rc;
     PmfIndexBuild *build = nullptr;
     // validation comes first: a bad id leaves the context's previous ratings in place
     if (on_host) {
@@ -603,7 +637,7 @@ static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, 
             if ((rc = bad_id_error(ctx, user_ids, item_ids, n))) return rc;
     } else {
         int64_t bad = -1;
-        if ((rc = pmf_index_device_begin(ctx, nnz, user_ids, item_ids, ratings, &build, &bad))) return rc;
+        if ((rc = pmf_index_device_begin(ctx, nnz, user_ids, item_ids, ratings, weights, &build, &bad))) return rc;
         if (bad >= 0) return bad_id_error(ctx, user_ids, item_ids, bad);
     }
     drop_ratings(ctx);
@@ -614,6 +648,8 @@ static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, 
         rc = ix.d_ptr.alloc(ctx, (size_t)(ctx->rows[side] + 1) * sizeof(int64_t));
         if (!rc) rc = ix.d_other.alloc(ctx, (size_t)nnz * sizeof(int32_t));
         if (!rc) rc = ix.d_val.alloc(ctx, (size_t)nnz * ctx->elem);
+        if (!rc && weights) rc = ix.d_wgt.alloc(ctx, (size_t)nnz * ctx->elem);
+        if (!rc && weights) rc = ix.d_wsum.alloc(ctx, (size_t)ctx->rows[side] * ctx->elem);
         if (rc) {
             pmf_index_device_abort(build);
             return rc;
@@ -621,9 +657,9 @@ static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, 
     }
     if (on_host) {
         std::vector<int32_t> other((size_t)nnz);
-        std::vector<char> val((size_t)nnz * ctx->elem);
-        if ((rc = fill_side_host(ctx, PMF_SIDE_USER, nnz, user_ids, item_ids, ratings, other, val))) return rc;
-        if ((rc = fill_side_host(ctx, PMF_SIDE_ITEM, nnz, item_ids, user_ids, ratings, other, val))) return rc;
+        std::vector<char> val((size_t)nnz * ctx->elem), wgt(weights ? (size_t)nnz * ctx->elem : 0);
+        if ((rc = fill_side_host(ctx, PMF_SIDE_USER, nnz, user_ids, item_ids, ratings, weights, other, val, wgt))) return rc;
+        if ((rc = fill_side_host(ctx, PMF_SIDE_ITEM, nnz, item_ids, user_ids, ratings, weights, other, val, wgt))) return rc;
     } else {
         if ((rc = pmf_index_device_finish(ctx, build, nnz))) return rc;  // consumes `build`
     }
@@ -640,7 +676,29 @@ static int set_ratings_impl(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, 
         ix.h_nonempty.swap(nonempty);
         if ((rc = build_work_lists(ctx, side))) return rc;
     }
+    ctx->weighted = weights != nullptr;
     return guard.finish(build_hot_rows(ctx));
+}
+
+extern "C" int pmf_ctx_has_rating_weights(pmf_ctx *ctx, int *has) {
+    CHECK_CTX(ctx, "pmf_ctx_has_rating_weights");
+    PMF_REQUIRE(has != nullptr, PMF_EINVAL, "pmf_ctx_has_rating_weights: null argument");
+    *has = ctx->weighted ? 1 : 0;
+    return PMF_OK;
+}
+
+extern "C" int pmf_ctx_rating_weight_sums(pmf_ctx *ctx, int side, double *out) {
+    CHECK_CTX(ctx, "pmf_ctx_rating_weight_sums");
+    CHECK_SIDE(side, "pmf_ctx_rating_weight_sums");
+    PMF_REQUIRE(out != nullptr, PMF_EINVAL, "pmf_ctx_rating_weight_sums: null argument");
+    const PmfSideIndex &ix = ctx->index[side];
+    PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_ctx_rating_weight_sums: ratings have not been set");
+    // C_r as the kernels read it: the double sum rounded once to the context dtype; the counts without weights
+    for (int64_t r = 0; r < ctx->rows[side]; ++r) {
+        const double c = ctx->weighted ? ix.h_wsum[(size_t)r] : (double)(ix.h_ptr[(size_t)r + 1] - ix.h_ptr[(size_t)r]);
+        out[r] = ctx->dtype == PMF_F64 ? c : (double)(float)c;
+    }
+    return PMF_OK;
 }
 
 // ---------------------------------------------------------------------------

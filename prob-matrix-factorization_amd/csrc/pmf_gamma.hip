@@ -791,6 +791,7 @@ static int gamma_comm_half_sweep(pmf_ctx *ctx, int side, const GammaPriors &pr, 
 extern "C" int pmf_gamma_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior,
                                int hierarchical, double hyper_shape, double hyper_rate_prior) {
     PMF_SIDE_ENTRY("pmf_gamma_sweep");
+    PMF_REQUIRE_UNWEIGHTED("pmf_gamma_sweep");
     const GammaPriors pr = {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior};
     return pmf_with_dtype(ctx, [&](auto t) {
         using T = decltype(t);
@@ -804,6 +805,7 @@ extern "C" int pmf_gamma_sweep(pmf_ctx *ctx, int side, double shape_prior, doubl
 
 extern "C" int pmf_gamma_ext_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior) {
     PMF_SIDE_ENTRY("pmf_gamma_ext_sweep");
+    PMF_REQUIRE_UNWEIGHTED("pmf_gamma_ext_sweep");
     PMF_REQUIRE_ZEROS_MISSING("pmf_gamma_ext_sweep");
     PMF_REQUIRE(!pmf_comm_active(ctx), PMF_EINVAL, "pmf_gamma_ext_sweep: the extended model is not available on several ranks");
     const GammaPriors pr = {shape_prior, rate_prior};
@@ -812,6 +814,7 @@ extern "C" int pmf_gamma_ext_sweep(pmf_ctx *ctx, int side, double shape_prior, d
 
 extern "C" int pmf_gamma_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
     PMF_SIDE_ENTRY("pmf_gamma_accumulate");
+    PMF_REQUIRE_UNWEIGHTED("pmf_gamma_accumulate");
     PMF_REQUIRE_ZEROS_MISSING("pmf_gamma_accumulate");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gamma_accumulate: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_gamma<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, false, stats_dev, {}); });
@@ -1334,6 +1337,7 @@ static int run_gamma_elbo_terms(pmf_ctx *ctx, int side, bool with_data, bool hie
 extern "C" int pmf_gamma_elbo_terms(pmf_ctx *ctx, int side, int with_data, int hierarchical, double *totals, double *per_row) {
     PMF_SIDE_ENTRY("pmf_gamma_elbo_terms");
     PMF_REQUIRE(totals, PMF_EINVAL, "pmf_gamma_elbo_terms: null totals");
+    if (with_data) PMF_REQUIRE_UNWEIGHTED("pmf_gamma_elbo_terms");
     int rc;
     if ((rc = require_gamma_q(ctx, {side}, "pmf_gamma_elbo_terms"))) return rc;
     if (with_data) {
@@ -1506,6 +1510,7 @@ static int run_gamma_exact(pmf_ctx *ctx, int side, PmfPass pass, bool tables, vo
 extern "C" int pmf_gamma_exact_sweep(pmf_ctx *ctx, int side, double shape_prior, double rate_prior,
                                      int hierarchical, double hyper_shape, double hyper_rate_prior) {
     PMF_SIDE_ENTRY("pmf_gamma_exact_sweep");
+    PMF_REQUIRE_UNWEIGHTED("pmf_gamma_exact_sweep");
     const GammaPriors pr = {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior};
     int rc;
     if ((rc = check_gamma_exact_inputs(ctx, side, "pmf_gamma_exact_sweep"))) return rc;
@@ -1525,6 +1530,7 @@ extern "C" int pmf_gamma_exact_sweep(pmf_ctx *ctx, int side, double shape_prior,
 
 extern "C" int pmf_gamma_exact_accumulate(pmf_ctx *ctx, int side, void *stats_dev) {
     PMF_SIDE_ENTRY("pmf_gamma_exact_accumulate");
+    PMF_REQUIRE_UNWEIGHTED("pmf_gamma_exact_accumulate");
     PMF_REQUIRE_ZEROS_MISSING("pmf_gamma_exact_accumulate");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gamma_exact_accumulate: null stats buffer");
     int rc;

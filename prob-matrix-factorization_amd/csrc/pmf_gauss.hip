@@ -56,6 +56,19 @@ struct GaussParams {
     T *hsplit = nullptr;      // [n_split][kpad]
 };
 
+// What the host code carries, and the argument of the weighted instantiations (WT) of the accumulate kernels: wgt[j] =
+// the confidence weight c_j of rating j ([nnz], beside val; null: no weights).  S takes c_j - zero_w, w takes c_j;
+// zero_w = the zero weight w0 under PMF_ZEROS_OBSERVED (the blend then adds w0 G), else 0.  The unweighted
+// instantiations keep GaussParams as their argument, so their code does not depend on this struct.
+template <typename T>
+struct GaussParamsW : GaussParams<T> {
+    const T *wgt = nullptr;
+    T zero_w = (T)0;
+    const GaussParams<T> &plain() const { return *this; }
+};
+template <typename T, bool WT>
+using GaussArgs = std::conditional_t<WT, GaussParamsW<T>, GaussParams<T>>;
+
 __device__ __forceinline__ void wave_lds_fence() {
     // LDS operations of one wavefront execute in order; this only stops the
     // compiler from moving LDS accesses across the point.
@@ -101,8 +114,8 @@ __device__ __forceinline__ T solve_from_image(const T *img, T wj, int K, int kpa
 // KS > 0 (K <= 64): a task that is a whole row keeps its sums in an LDS image and is solved on the spot by the
 // same wavefront (the KS-row register sweep), as in the MFMA kernels -- this is how fp64 contexts (parity mode)
 // stop paying a separate solve launch.
-template <typename T, int KS = 0>
-__global__ __launch_bounds__(256) void gauss_accum_generic_kernel(GaussParams<T> p, T inv_sigma2 = (T)0, T inv_eta2 = (T)0,
+template <typename T, int KS = 0, bool WT = false>
+__global__ __launch_bounds__(256) void gauss_accum_generic_kernel(GaussArgs<T, WT> p, T inv_sigma2 = (T)0, T inv_eta2 = (T)0,
                                                                   T *cov_self = nullptr, T *factor_self = nullptr) {
     constexpr int CH = sizeof(T) == 8 ? 5 : 4;  // chunks per lane per pass -> 64 * CH * 4 packed entries per pass (fp64, K = 64: 2 passes instead of 3)
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -117,6 +130,8 @@ __global__ __launch_bounds__(256) void gauss_accum_generic_kernel(GaussParams<T>
     const bool solve_here = KS > 0 && t.slot < 0;
     const int32_t *col = p.other + t.start;
     const T *val = p.val + t.start;
+    const T *wgt = nullptr;
+    if constexpr (WT) wgt = p.wgt + t.start;
     const T b_self = p.bias_self ? p.bias_self[t.row] : (T)0;
     const int chunks = p.cov_stride / PMF_VEC;
     T *out_s, *out_w;
@@ -159,10 +174,19 @@ __global__ __launch_bounds__(256) void gauss_accum_generic_kernel(GaussParams<T>
                 a[s] = load4(v0 + (int64_t)q * PMF_VEC);
                 b[s] = two ? load4(v1 + (int64_t)q * PMF_VEC) : zero4<T>();
             }
+            T c0 = (T)1, c1 = (T)1;   // WT: the pair's weights (the absent second rating: 0, its addends are zeros)
+            if constexpr (WT) {
+                c0 = wgt[j];
+                c1 = two ? wgt[j + 1] : (T)0;
+            }
             wave_lds_fence();
             if (q0 == 0) {
-                const T r0 = val[j] - b_self - (p.bias_other ? p.bias_other[o0] : (T)0);
-                const T r1 = two ? val[j + 1] - b_self - (p.bias_other ? p.bias_other[o1] : (T)0) : (T)0;
+                T r0 = val[j] - b_self - (p.bias_other ? p.bias_other[o0] : (T)0);
+                T r1 = two ? val[j + 1] - b_self - (p.bias_other ? p.bias_other[o1] : (T)0) : (T)0;
+                if constexpr (WT) {
+                    r0 *= c0;
+                    r1 *= c1;
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int k = lane + 64 * e;
@@ -175,8 +199,13 @@ __global__ __launch_bounds__(256) void gauss_accum_generic_kernel(GaussParams<T>
                 for (int e = 0; e < PMF_VEC; ++e) {
                     const int r = rc[s][e] & 255, c = rc[s][e] >> 8;
                     // reference order: (V_j + m_j m_j^T) added rating by rating
-                    acc[s].v[e] += fma(m0[r], m0[c], a[s].v[e]);
-                    acc[s].v[e] += fma(m1[r], m1[c], b[s].v[e]);
+                    if constexpr (WT) {
+                        acc[s].v[e] += (c0 - p.zero_w) * fma(m0[r], m0[c], a[s].v[e]);
+                        if (two) acc[s].v[e] += (c1 - p.zero_w) * fma(m1[r], m1[c], b[s].v[e]);
+                    } else {
+                        acc[s].v[e] += fma(m0[r], m0[c], a[s].v[e]);
+                        acc[s].v[e] += fma(m1[r], m1[c], b[s].v[e]);
+                    }
                 }
             wave_lds_fence();
         }
@@ -613,8 +642,8 @@ __global__ __launch_bounds__(128, 2) void gauss_solve_pair_kernel(SolveParams<fl
 // solved in place by the same two waves (pair_solve_mfma).
 // NT = chunk columns per wave (host picks the smallest that covers ceil(chunks / 2) / 64):
 // 17 for K = 128 (1032 chunks per wave), 13 for K <= 114, 9 for K <= 95.
-template <int NT, bool FUSE, int MT = 0>
-__global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams<float> p, float inv_sigma2, float inv_eta2,
+template <int NT, bool FUSE, int MT = 0, bool WT = false>
+__global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussArgs<float, WT> p, float inv_sigma2, float inv_eta2,
                                                                      float *cov_self, float *factor_self) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     float *img = reinterpret_cast<float *>(smem_raw);
@@ -652,11 +681,13 @@ __global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams
     const int bias_mul = has_bias ? 1 : 0;
     int idx_b = 0;
     float val_b = 0.f;
+    float wgt_b = 1.f;   // WT: the batch's weights, handed out like val_b
     for (int j = 0; j < t.len; j += 2) {
         if ((j & 63) == 0) {
             const int jj = min(j + lane, t.len - 1);
             idx_b = col[jj];
             val_b = val[jj];
+            if constexpr (WT) wgt_b = p.wgt[t.start + jj];
         }
         const bool two = j + 1 < t.len;
         const int l0 = j & 63;   // even: l0 + 1 is in the same batch
@@ -673,7 +704,16 @@ __global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams
         const float bo = bias_ptr[(int64_t)oh * bias_mul];
 #pragma unroll
         for (int b = 0; b < 4; ++b) m[b] = (live && 32 * b + c < K) ? m[b] : 0.f;
-        const float res = live ? (h ? x1 : x0) - b_self - (has_bias ? bo : 0.f) : 0.f;
+        float res = live ? (h ? x1 : x0) - b_self - (has_bias ? bo : 0.f) : 0.f;
+        // WT: c0 / c1 = the S-side weights of the pair (uniform), cm = this lane half's scale of the MFMA A operand
+        float c0 = 1.f, c1 = 1.f, cm = 1.f;
+        if constexpr (WT) {
+            const float g0 = readlane_dyn(wgt_b, l0), g1 = readlane_dyn(wgt_b, two ? l0 + 1 : l0);
+            res *= h ? g1 : g0;
+            c0 = g0 - p.zero_w;
+            c1 = g1 - p.zero_w;
+            cm = h ? c1 : c0;
+        }
         const float4 *v0 = reinterpret_cast<const float4 *>(p.cov_other + (int64_t)o0 * stride);
         // one rating's chunks in flight at a time (68 VGPRs): with the MFMA blocks the kernel then
         // fits 256 registers, i.e. two blocks' worth of waves per SIMD, so one block can solve
@@ -703,32 +743,48 @@ __global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams
         wA = fmaf(wave ? m[2] : m[0], res, wA);
         wB = fmaf(wave ? m[3] : m[1], res, wB);
         // operand pairs of this wave's five blocks (wave is uniform: scalar selects)
-        const float A0 = wave ? m[2] : m[0], B0 = wave ? m[2] : m[0];
-        const float A1 = wave ? m[3] : m[1], B1 = m[0];
-        const float A2 = wave ? m[3] : m[1], B2 = m[1];
-        const float A3 = wave ? m[3] : m[2], B3 = wave ? m[2] : m[0];
-        const float A4 = wave ? m[3] : m[2], B4 = wave ? m[3] : m[1];
+        // (WT: the scaled mean c m is the A operand only, B stays m)
+        const float A0 = (wave ? m[2] : m[0]) * cm, B0 = wave ? m[2] : m[0];
+        const float A1 = (wave ? m[3] : m[1]) * cm, B1 = m[0];
+        const float A2 = A1, B2 = m[1];
+        const float A3 = (wave ? m[3] : m[2]) * cm, B3 = wave ? m[2] : m[0];
+        const float A4 = A3, B4 = wave ? m[3] : m[1];
         d[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(A0, B0, d[0], 0, 0, 0);
         d[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(A1, B1, d[1], 0, 0, 0);
         d[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(A2, B2, d[2], 0, 0, 0);
         d[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(A3, B3, d[3], 0, 0, 0);
         d[4] = __builtin_amdgcn_mfma_f32_32x32x2f32(A4, B4, d[4], 0, 0, 0);
+        // (WT: fmaf(1, a, acc) = acc + a, the unweighted bits when every weight is 1)
 #pragma unroll
         for (int s = 0; s < NT; ++s) {
-            acc[s].x += a[s].x;
-            acc[s].y += a[s].y;
-            acc[s].z += a[s].z;
-            acc[s].w += a[s].w;
+            if constexpr (WT) {
+                acc[s].x = fmaf(c0, a[s].x, acc[s].x);
+                acc[s].y = fmaf(c0, a[s].y, acc[s].y);
+                acc[s].z = fmaf(c0, a[s].z, acc[s].z);
+                acc[s].w = fmaf(c0, a[s].w, acc[s].w);
+            } else {
+                acc[s].x += a[s].x;
+                acc[s].y += a[s].y;
+                acc[s].z += a[s].z;
+                acc[s].w += a[s].w;
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (BOTH) {
             if (two) {
 #pragma unroll
                 for (int s = 0; s < NT; ++s) {
-                    acc[s].x += a2[s].x;
-                    acc[s].y += a2[s].y;
-                    acc[s].z += a2[s].z;
-                    acc[s].w += a2[s].w;
+                    if constexpr (WT) {
+                        acc[s].x = fmaf(c1, a2[s].x, acc[s].x);
+                        acc[s].y = fmaf(c1, a2[s].y, acc[s].y);
+                        acc[s].z = fmaf(c1, a2[s].z, acc[s].z);
+                        acc[s].w = fmaf(c1, a2[s].w, acc[s].w);
+                    } else {
+                        acc[s].x += a2[s].x;
+                        acc[s].y += a2[s].y;
+                        acc[s].z += a2[s].z;
+                        acc[s].w += a2[s].w;
+                    }
                 }
             }
         } else if (two) {
@@ -740,10 +796,17 @@ __global__ __launch_bounds__(128, 2) void gauss_accum_mfma128_kernel(GaussParams
                                                          (unsigned)min(qb + 64 * s, q_end - 1) * 16u);
 #pragma unroll
             for (int s = 0; s < NT; ++s) {
-                acc[s].x += a[s].x;
-                acc[s].y += a[s].y;
-                acc[s].z += a[s].z;
-                acc[s].w += a[s].w;
+                if constexpr (WT) {
+                    acc[s].x = fmaf(c1, a[s].x, acc[s].x);
+                    acc[s].y = fmaf(c1, a[s].y, acc[s].y);
+                    acc[s].z = fmaf(c1, a[s].z, acc[s].z);
+                    acc[s].w = fmaf(c1, a[s].w, acc[s].w);
+                } else {
+                    acc[s].x += a[s].x;
+                    acc[s].y += a[s].y;
+                    acc[s].z += a[s].z;
+                    acc[s].w += a[s].w;
+                }
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -856,8 +919,12 @@ __device__ __forceinline__ float gather_ld(const float *ptr) {
     else return __builtin_nontemporal_load(ptr);
 }
 
-template <int KB, int NT, bool FUSE, int KS = KB>
-__global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel(GaussParams<float> p, float inv_sigma2,
+// WT (weighted ratings, GaussParams::wgt): a third batch register carries the weights.  Per pair the two S-side weights
+// c0 / c1 (c_j - zero_w) are uniform: the covariance adds become acc += fmaf(c0, a, c1 * b) (the pair sum first, then the
+// accumulator, as in the unweighted form: the same bits when every weight is 1), the MFMA takes c_h m as its A operand
+// only (B stays m), the residual is multiplied by the lane half's c_j, and the mean sums (mdot) become H_r = sum_j c_j m_j.
+template <int KB, int NT, bool FUSE, int KS = KB, bool WT = false>
+__global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel(GaussArgs<float, WT> p, float inv_sigma2,
                                                                                 float inv_eta2, float *cov_self,
                                                                                 float *factor_self) {
     constexpr int NB = KB == 64 ? 3 : 1;
@@ -902,6 +969,7 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
     // PU = 8 trip of K <= 16 used to wait for eight of them in turn).
     int idx_b = 0;
     float val_b = 0.f;
+    float wgt_b = 1.f;        // WT: the batch's weights
     uint64_t hot_b = ~0ull;   // bit l: rating l of the batch gathers a hot row
     const uint8_t *hot = p.hot ? p.hot + t.start : nullptr;
     auto fetch = [&](int j) {
@@ -909,6 +977,7 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
             const int jj = min(j + lane, t.len - 1);
             idx_b = col[jj];
             val_b = val[jj];
+            if constexpr (WT) wgt_b = p.wgt[t.start + jj];
             if (hot) hot_b = __builtin_amdgcn_ballot_w64(__builtin_nontemporal_load(hot + jj) != 0);
         }
     };
@@ -918,6 +987,7 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
         constexpr int POL = decltype(pol_tag)::value;
         float4 a[PU][NT], b[PU][NT];
         float mlo[PU], mhi[PU], res[PU];
+        float cs0[PU], cs1[PU], ch[PU];   // WT: the pair's S-side weights (uniform) and the lane half's own c_j
 #pragma unroll
         for (int u = 0; u < PU; ++u) {
             const int j0 = j + 2 * u, l0 = j0 & 63;
@@ -931,6 +1001,13 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
             const float *mrow = p.factor_other + (int64_t)oh * kpad;
             const float xh = h ? x1 : x0;
             res[u] = live ? xh - b_self - (p.bias_other ? p.bias_other[oh] : 0.f) : 0.f;
+            if constexpr (WT) {   // (a rating past the task: the weight of the task's last one, times zeros)
+                const float g0 = readlane_dyn(wgt_b, l0), g1 = readlane_dyn(wgt_b, l0 + 1);
+                ch[u] = h ? g1 : g0;
+                res[u] *= ch[u];
+                cs0[u] = g0 - p.zero_w;
+                cs1[u] = g1 - p.zero_w;
+            }
             const float4 *v0 = reinterpret_cast<const float4 *>(p.cov_other + (int64_t)o0 * stride);
             const float4 *v1 = reinterpret_cast<const float4 *>(p.cov_other + (int64_t)o1 * stride);
             auto loads = [&](auto h0_tag, auto h1_tag) {
@@ -962,21 +1039,38 @@ __global__ __launch_bounds__(256, KB == 64 ? 2 : 3) void gauss_accum_mfma_kernel
         for (int u = 0; u < PU; ++u) {
             wlo = fmaf(mlo[u], res[u], wlo);
             whi = fmaf(mhi[u], res[u], whi);
-            if constexpr (FUSE) {
+            if constexpr (FUSE && !WT) {
                 hlo += mlo[u];
                 if constexpr (KB == 64) hhi += mhi[u];
             }
-            d[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(mlo[u], mlo[u], d[0], 0, 0, 0);
+            if constexpr (FUSE && WT) {   // H_r = sum_j c_j m_j
+                hlo = fmaf(ch[u], mlo[u], hlo);
+                if constexpr (KB == 64) hhi = fmaf(ch[u], mhi[u], hhi);
+            }
+            float alo = mlo[u], ahi = mhi[u];   // the A operands
+            if constexpr (WT) {
+                const float cm = h ? cs1[u] : cs0[u];
+                alo *= cm;
+                ahi *= cm;
+            }
+            d[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(alo, mlo[u], d[0], 0, 0, 0);
             if constexpr (KB == 64) {
-                d[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(mhi[u], mlo[u], d[1], 0, 0, 0);
-                d[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(mhi[u], mhi[u], d[2], 0, 0, 0);
+                d[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ahi, mlo[u], d[1], 0, 0, 0);
+                d[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(ahi, mhi[u], d[2], 0, 0, 0);
             }
 #pragma unroll
             for (int s = 0; s < NT; ++s) {
-                acc[s].x += a[u][s].x + b[u][s].x;
-                acc[s].y += a[u][s].y + b[u][s].y;
-                acc[s].z += a[u][s].z + b[u][s].z;
-                acc[s].w += a[u][s].w + b[u][s].w;
+                if constexpr (WT) {
+                    acc[s].x += fmaf(cs0[u], a[u][s].x, cs1[u] * b[u][s].x);
+                    acc[s].y += fmaf(cs0[u], a[u][s].y, cs1[u] * b[u][s].y);
+                    acc[s].z += fmaf(cs0[u], a[u][s].z, cs1[u] * b[u][s].z);
+                    acc[s].w += fmaf(cs0[u], a[u][s].w, cs1[u] * b[u][s].w);
+                } else {
+                    acc[s].x += a[u][s].x + b[u][s].x;
+                    acc[s].y += a[u][s].y + b[u][s].y;
+                    acc[s].z += a[u][s].z + b[u][s].z;
+                    acc[s].w += a[u][s].w + b[u][s].w;
+                }
             }
         }
     };
@@ -1214,6 +1308,10 @@ struct BiasParams {
     T inv_sigma2, inv_eta_bias2;
     int kpad;
     int64_t row0, rows;  // finalize-from-stats covers rows [row0, rows)
+    // weighted ratings (both or neither): wgt[j] = c_j beside val, wsum[r] = C_r = the sum of row r's weights, which takes
+    // the place of the row's rating count
+    const T *wgt = nullptr;
+    const T *wsum = nullptr;
 };
 
 template <typename T>
@@ -1223,7 +1321,7 @@ __device__ __forceinline__ T bias_from_sum(const BiasParams<T> &p, T sum, T coun
     return (var * p.inv_sigma2) * sum;
 }
 
-template <typename T, int LPR, bool STATS>
+template <typename T, int LPR, bool STATS, bool WT = false>
 __global__ __launch_bounds__(256) void gauss_bias_kernel(BiasParams<T> p) {
     constexpr int G = 256 / LPR;
     constexpr int UN = LPR < 4 ? LPR : 4;
@@ -1240,19 +1338,21 @@ __global__ __launch_bounds__(256) void gauss_bias_kernel(BiasParams<T> p) {
     for (int base = 0; base < t.len; base += LPR) {
         const int n = min(LPR, t.len - base);
         int my_o = 0;
-        T my_r = (T)0;
+        T my_r = (T)0, my_w = (T)1;
         if (c < n) {
             my_o = col[base + c];
             my_r = val[base + c] - p.bias_other[my_o];
+            if constexpr (WT) my_w = p.wgt[t.start + base + c];
         }
         for (int tt = 0; tt < n; tt += UN) {
             int o[UN];
-            T rv[UN];
+            T rv[UN], cw[UN];
             Vec4<T> b[UN];
 #pragma unroll
             for (int q = 0; q < UN; ++q) {
                 o[q] = __shfl(my_o, tt + q, LPR);
                 rv[q] = __shfl(my_r, tt + q, LPR);
+                if constexpr (WT) cw[q] = __shfl(my_w, tt + q, LPR);
             }
 #pragma unroll
             for (int q = 0; q < UN; ++q)
@@ -1265,7 +1365,8 @@ __global__ __launch_bounds__(256) void gauss_bias_kernel(BiasParams<T> p) {
                     d = fma(b[q].v[2], self.v[2], d);
                     d = fma(b[q].v[3], self.v[3], d);
                     d = group_sum<LPR>(d);
-                    sum += rv[q] - d;
+                    if constexpr (WT) sum += cw[q] * (rv[q] - d);
+                    else sum += rv[q] - d;
                 }
             }
         }
@@ -1273,11 +1374,15 @@ __global__ __launch_bounds__(256) void gauss_bias_kernel(BiasParams<T> p) {
     if (c != 0) return;
     if (t.slot >= 0) {
         p.partial[t.slot] = sum;
-    } else if (STATS) {
+        return;
+    }
+    T cnt = (T)t.len;
+    if constexpr (WT) cnt = p.wsum[t.row];
+    if (STATS) {
         p.stats[(int64_t)t.row * 2] = sum;
-        p.stats[(int64_t)t.row * 2 + 1] = (T)t.len;
+        p.stats[(int64_t)t.row * 2 + 1] = cnt;
     } else {
-        p.bias_self[t.row] = bias_from_sum(p, sum, (T)t.len);
+        p.bias_self[t.row] = bias_from_sum(p, sum, cnt);
     }
 }
 
@@ -1287,7 +1392,7 @@ __global__ __launch_bounds__(256) void gauss_bias_kernel(BiasParams<T> p) {
 // What is left is a stream of 8 bytes per rating (id and rating, coalesced over the LPR lanes of the task's group)
 // and one 4-byte gather from the other side's bias table; LPR follows the task length, not K.  A split task leaves
 // its part of the first sum in its slot and gauss_bias_split_kernel subtracts the dot product once per row.
-template <typename T, int LPR>
+template <typename T, int LPR, bool WT = false>
 __global__ __launch_bounds__(256) void gauss_bias_sums_kernel(BiasParams<T> p, const T *mdot) {
     constexpr int G = 256 / LPR;
     constexpr int UN = 4;
@@ -1300,23 +1405,29 @@ __global__ __launch_bounds__(256) void gauss_bias_sums_kernel(BiasParams<T> p, c
     T sum = (T)0;
     for (int base = c; base < t.len; base += UN * LPR) {
         int o[UN];
-        T x[UN], b[UN];
+        T x[UN], b[UN], cw[UN];
 #pragma unroll
         for (int q = 0; q < UN; ++q) {   // (past the task: its last rating again, not added)
             const int j = min(base + q * LPR, t.len - 1);
             o[q] = col[j];
             x[q] = val[j];
+            if constexpr (WT) cw[q] = p.wgt[t.start + j];
         }
 #pragma unroll
         for (int q = 0; q < UN; ++q) b[q] = p.bias_other[o[q]];
 #pragma unroll
         for (int q = 0; q < UN; ++q)
-            if (base + q * LPR < t.len) sum += x[q] - b[q];
+            if (base + q * LPR < t.len) {
+                if constexpr (WT) sum += cw[q] * (x[q] - b[q]);
+                else sum += x[q] - b[q];
+            }
     }
     sum = group_sum<LPR>(sum);
     if (c != 0) return;
+    T cnt = (T)t.len;
+    if constexpr (WT) cnt = p.wsum[t.row];
     if (t.slot >= 0) p.partial[t.slot] = sum;
-    else p.bias_self[t.row] = bias_from_sum(p, sum - mdot[t.row], (T)t.len);
+    else p.bias_self[t.row] = bias_from_sum(p, sum - mdot[t.row], cnt);
 }
 
 // `mdot` (may be null): subtracted from a split row's sum, see gauss_bias_sums_kernel
@@ -1328,7 +1439,7 @@ __global__ void gauss_bias_split_kernel(BiasParams<T> p, int64_t n_split, const 
     T sum = (T)0;
     for (int k = 0; k < sr.n_slots; ++k) sum += p.partial[sr.first_slot + k];
     if (mdot) sum -= mdot[sr.row];
-    const T cnt = (T)(ptr[sr.row + 1] - ptr[sr.row]);
+    const T cnt = p.wsum ? p.wsum[sr.row] : (T)(ptr[sr.row + 1] - ptr[sr.row]);
     if (STATS) {
         p.stats[(int64_t)sr.row * 2] = sum;
         p.stats[(int64_t)sr.row * 2 + 1] = cnt;
@@ -1372,6 +1483,9 @@ struct FoldBiasParams {
     T *bias;              // [n] out
     T inv_sigma2, inv_eta_bias2;
     int n_iter, K, kpad, cov_stride;
+    // weighted batch (both or neither): wgt[j] = c_j beside val, wsum[row] = C = the sum of the row's weights
+    const T *wgt = nullptr;
+    const T *wsum = nullptr;
 };
 
 template <typename T, int LPR>
@@ -1395,21 +1509,36 @@ __global__ __launch_bounds__(256) void gauss_fold_bias_kernel(FoldBiasParams<T> 
     for (int64_t base = 0; base < n; base += LPR) {
         const int cnt = (int)min((int64_t)LPR, n - base);
         int my_o = 0;
+        T my_w = (T)1;
         if (c < cnt) {
             my_o = col[base + c];
-            c0 += val[base + c] - p.bias_other[my_o];
+            if (p.wgt) {
+                my_w = p.wgt[start + base + c];
+                c0 += my_w * (val[base + c] - p.bias_other[my_o]);
+            } else {
+                c0 += val[base + c] - p.bias_other[my_o];
+            }
         }
         for (int tt = 0; tt < cnt; tt += UN) {
             Vec4<T> b[UN];
+            T cw[UN];
 #pragma unroll
             for (int q = 0; q < UN; ++q) {
                 const int o = __shfl(my_o, tt + q, LPR);   // (lanes past the batch hold id 0: never loaded)
+                cw[q] = __shfl(my_w, tt + q, LPR);
                 b[q] = (active && tt + q < cnt) ? load4(p.factor_other + (int64_t)o * p.kpad + koff) : zero4<T>();
             }
+            if (p.wgt) {   // (uniform)
 #pragma unroll
-            for (int q = 0; q < UN; ++q)
+                for (int q = 0; q < UN; ++q)
 #pragma unroll
-                for (int e = 0; e < PMF_VEC; ++e) g.v[e] += b[q].v[e];
+                    for (int e = 0; e < PMF_VEC; ++e) g.v[e] += cw[q] * b[q].v[e];
+            } else {
+#pragma unroll
+                for (int q = 0; q < UN; ++q)
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) g.v[e] += b[q].v[e];
+            }
         }
     }
     c0 = group_sum<LPR>(c0);
@@ -1455,7 +1584,7 @@ __global__ __launch_bounds__(256) void gauss_fold_bias_kernel(FoldBiasParams<T> 
     alpha = group_sum<LPR>(alpha);
     beta = group_sum<LPR>(beta);
     // gaussian_mf_cavi_bias.py:222-230: var = 1/(1/eta_b2 + n/sigma2); b = var/sigma2 * sum
-    const T kappa = p.inv_sigma2 / (p.inv_eta_bias2 + (T)n * p.inv_sigma2);
+    const T kappa = p.inv_sigma2 / (p.inv_eta_bias2 + (p.wsum ? p.wsum[row] : (T)n) * p.inv_sigma2);
     T b_prev = (T)0, b_cur = (T)0;
     for (int t = 0; t < p.n_iter; ++t) {
         b_prev = b_cur;
@@ -1495,7 +1624,7 @@ struct GaussStats {
     T *base(T *at, int64_t stride) const {
         return reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(at) - (uintptr_t)row0 * stride * sizeof(T));
     }
-    void set_dst(GaussParams<T> &p) const {
+    void set_dst(GaussParamsW<T> &p) const {
         p.dst_s = base(s, s_stride);
         p.dst_s_stride = s_stride;
         p.dst_w = base(w, w_stride);
@@ -1511,18 +1640,26 @@ struct GaussStats {
 
 // fuse: sums in place, then solve   !fuse: sums only (into the statistics or in place)
 template <int KB, int NT, int KS = KB>
-static void launch_accum_mfma_nt(pmf_ctx *ctx, const GaussParams<float> &p, dim3 grid, bool fuse, float is2, float ie2,
+static void launch_accum_mfma_nt(pmf_ctx *ctx, const GaussParamsW<float> &p, dim3 grid, bool fuse, float is2, float ie2,
                                  float *cov, float *fac) {
     const size_t smem = (size_t)4 * ctx->cov_stride * sizeof(float);
+    if (p.wgt) {   // weighted ratings
+        if (fuse)
+            hipLaunchKernelGGL((gauss_accum_mfma_kernel<KB, NT, true, KS, true>), grid, dim3(256), smem, ctx->stream, p, is2, ie2, cov, fac);
+        else
+            hipLaunchKernelGGL((gauss_accum_mfma_kernel<KB, NT, false, KB, true>), grid, dim3(256), smem, ctx->stream, p, 0.f, 0.f,
+                               (float *)nullptr, (float *)nullptr);
+        return;
+    }
     if (fuse)
-        hipLaunchKernelGGL((gauss_accum_mfma_kernel<KB, NT, true, KS>), grid, dim3(256), smem, ctx->stream, p, is2, ie2, cov, fac);
+        hipLaunchKernelGGL((gauss_accum_mfma_kernel<KB, NT, true, KS>), grid, dim3(256), smem, ctx->stream, p.plain(), is2, ie2, cov, fac);
     else
-        hipLaunchKernelGGL((gauss_accum_mfma_kernel<KB, NT, false>), grid, dim3(256), smem, ctx->stream, p, 0.f, 0.f,
+        hipLaunchKernelGGL((gauss_accum_mfma_kernel<KB, NT, false>), grid, dim3(256), smem, ctx->stream, p.plain(), 0.f, 0.f,
                            (float *)nullptr, (float *)nullptr);
 }
 
 // K <= 64, fp32: pick the instantiation by MFMA block count and packed-row chunk count
-static void launch_accum_mfma(pmf_ctx *ctx, const GaussParams<float> &p, dim3 grid, bool fuse, float is2, float ie2,
+static void launch_accum_mfma(pmf_ctx *ctx, const GaussParamsW<float> &p, dim3 grid, bool fuse, float is2, float ie2,
                               float *cov, float *fac) {
     const int nt = (ctx->cov_stride / PMF_VEC + 63) / 64;  // 1..9
     if (ctx->K <= 8) {
@@ -1563,17 +1700,24 @@ static void launch_accum_mfma(pmf_ctx *ctx, const GaussParams<float> &p, dim3 gr
 // MT = 16-row tiles per dimension of the fused MFMA block sweep: ceil(K / 16), from K alone.  NT follows the chunk
 // count and its classes end elsewhere (NT = 9 reaches K = 95, NT = 13 K = 114), so NT = 13 meets MT = 8 at K = 113, 114.
 template <int NT, int MT>
-static void launch_accum_mfma128_fused(pmf_ctx *ctx, const GaussParams<float> &p, dim3 grid, size_t smem, float is2, float ie2,
+static void launch_accum_mfma128_fused(pmf_ctx *ctx, const GaussParamsW<float> &p, dim3 grid, size_t smem, float is2, float ie2,
                                        float *cov, float *fac) {
-    hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, true, MT>), grid, dim3(128), smem, ctx->stream, p, is2, ie2, cov, fac);
+    if (p.wgt)
+        hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, true, MT, true>), grid, dim3(128), smem, ctx->stream, p, is2, ie2, cov, fac);
+    else
+        hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, true, MT>), grid, dim3(128), smem, ctx->stream, p.plain(), is2, ie2, cov, fac);
 }
 
 template <int NT>
-static void launch_accum_mfma128(pmf_ctx *ctx, const GaussParams<float> &p, dim3 grid, size_t smem, bool fuse, float is2,
+static void launch_accum_mfma128(pmf_ctx *ctx, const GaussParamsW<float> &p, dim3 grid, size_t smem, bool fuse, float is2,
                                  float ie2, float *cov, float *fac) {
     if (!fuse) {
-        hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, false>), grid, dim3(128), smem, ctx->stream, p, 0.f, 0.f,
-                           (float *)nullptr, (float *)nullptr);
+        if (p.wgt)
+            hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, false, 0, true>), grid, dim3(128), smem, ctx->stream, p, 0.f, 0.f,
+                               (float *)nullptr, (float *)nullptr);
+        else
+            hipLaunchKernelGGL((gauss_accum_mfma128_kernel<NT, false>), grid, dim3(128), smem, ctx->stream, p.plain(), 0.f, 0.f,
+                               (float *)nullptr, (float *)nullptr);
         return;
     }
     const int mt = (ctx->K + 15) / 16;   // 5..8
@@ -1591,7 +1735,7 @@ static void launch_accum_mfma128(pmf_ctx *ctx, const GaussParams<float> &p, dim3
 
 // fp32, K <= 128: the MFMA accumulate kernels.  Returns whether they also solved the rows that are one task (`fuse`:
 // the fused pass sums in place, so the solved rows go where the sums went, `cov` / `fac` = COV / FACTOR).
-static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParams<float> &p, bool fuse, float is2, float ie2, float *cov, float *fac) {
+static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParamsW<float> &p, bool fuse, float is2, float ie2, float *cov, float *fac) {
     if (ctx->K <= 64) {
         launch_accum_mfma(ctx, p, dim3((unsigned)((p.n_tasks + 3) / 4)), fuse, is2, ie2, cov, fac);
     } else {  // 64 < K <= 128: one 128-thread block (two wavefronts) per task
@@ -1609,19 +1753,26 @@ static bool launch_accum_mfma_fp32(pmf_ctx *ctx, const GaussParams<float> &p, bo
 // accumulate kernel.  Returns whether it also solved the rows that are one task (`fuse`, K <= 64: fp64 only -- the
 // fp32 build has no fused generic kernel, so fuse / is2 / ie2 do not apply to it).
 template <typename T>
-static bool launch_accum_generic(pmf_ctx *ctx, const GaussParams<T> &p, bool fuse, T is2, T ie2, T *cov, T *fac) {
+static bool launch_accum_generic(pmf_ctx *ctx, const GaussParamsW<T> &p, bool fuse, T is2, T ie2, T *cov, T *fac) {
     dim3 grid((unsigned)((p.n_tasks + 3) / 4));
     const size_t plain = (size_t)4 * 2 * ctx->kpad * sizeof(T), lds = plain + (size_t)4 * ctx->cov_stride * sizeof(T);
     if constexpr (std::is_same<T, double>::value) {
         if (fuse) {
             pmf_with_pow2<8>(ctx->K, [&](auto KR) {
-                hipLaunchKernelGGL((gauss_accum_generic_kernel<T, KR>), grid, dim3(256), lds, ctx->stream, p, is2, ie2, cov, fac);
+                if (p.wgt)
+                    hipLaunchKernelGGL((gauss_accum_generic_kernel<T, KR, true>), grid, dim3(256), lds, ctx->stream, p, is2, ie2, cov, fac);
+                else
+                    hipLaunchKernelGGL((gauss_accum_generic_kernel<T, KR>), grid, dim3(256), lds, ctx->stream, p.plain(), is2, ie2, cov, fac);
             });
             return true;
         }
     }
-    hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 0>), grid, dim3(256), plain, ctx->stream, p, (T)0, (T)0,
-                       (T *)nullptr, (T *)nullptr);
+    if (p.wgt)
+        hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 0, true>), grid, dim3(256), plain, ctx->stream, p, (T)0, (T)0,
+                           (T *)nullptr, (T *)nullptr);
+    else
+        hipLaunchKernelGGL((gauss_accum_generic_kernel<T, 0>), grid, dim3(256), plain, ctx->stream, p.plain(), (T)0, (T)0,
+                           (T *)nullptr, (T *)nullptr);
     return false;
 }
 
@@ -1635,11 +1786,11 @@ static int gauss_require_state(pmf_ctx *ctx, int side, bool both, const char *fn
 // What the accumulate kernels take from the context: the gathered tables of the other side, `side`'s ratings, hot
 // flags and bias, the partial slots and the geometry.  The caller sets the tasks and the split rows.
 template <typename T>
-static GaussParams<T> gauss_params(const pmf_ctx *ctx, int side) {
+static GaussParamsW<T> gauss_params(const pmf_ctx *ctx, int side) {
     const int other = 1 - side;
     const PmfSideIndex &ix = ctx->index[side];
     const bool bias = pmf_has_bias(ctx);
-    GaussParams<T> p;
+    GaussParamsW<T> p;
     p.other = ix.d_other.as<int32_t>();
     p.val = ix.d_val.as<const T>();
     p.factor_other = ctx->arr[other][PMF_ARR_FACTOR].as<const T>();
@@ -1652,6 +1803,8 @@ static GaussParams<T> gauss_params(const pmf_ctx *ctx, int side) {
     p.kpad = ctx->kpad;
     p.kp = ctx->kp;
     p.cov_stride = ctx->cov_stride;
+    p.wgt = ctx->weighted ? ix.d_wgt.as<const T>() : nullptr;
+    p.zero_w = pmf_gauss_zeros_observed(ctx) ? (T)ctx->gauss_zero_weight : (T)0;
     return p;
 }
 
@@ -1659,7 +1812,7 @@ static GaussParams<T> gauss_params(const pmf_ctx *ctx, int side) {
 // split rows p.split lists.  `fuse`: the sums go in place (`st` is COV / FACTOR) and the kernel, where it has a fused
 // form, also solves every row that is one task; *solved tells whether it did, so that the caller solves the rest.
 template <typename T>
-static int launch_accumulate(pmf_ctx *ctx, GaussParams<T> &p, int64_t n_split, const GaussStats<T> &st, bool fuse = false,
+static int launch_accumulate(pmf_ctx *ctx, GaussParamsW<T> &p, int64_t n_split, const GaussStats<T> &st, bool fuse = false,
                              double sigma2 = 1, double eta2 = 1, bool *solved = nullptr) {
     bool did = false;
     st.set_dst(p);
@@ -1675,7 +1828,7 @@ static int launch_accumulate(pmf_ctx *ctx, GaussParams<T> &p, int64_t n_split, c
     if (solved) *solved = did;
     if (n_split > 0) {
         PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
-        hipLaunchKernelGGL((gauss_combine_kernel<T>), dim3((unsigned)n_split), dim3(256), 0, ctx->stream, p);
+        hipLaunchKernelGGL((gauss_combine_kernel<T>), dim3((unsigned)n_split), dim3(256), 0, ctx->stream, p.plain());
     }
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
@@ -1709,7 +1862,7 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *sta
     if (emit && (rc = ctx->d_mdot[side].reserve(ctx, (size_t)ctx->rows[side] * sizeof(T), {ctx->stream}))) return rc;
     if (acc && tl.row1 > tl.row0)  // rows without ratings on this rank contribute zeros
         PMF_HIP_CHECK(hipMemsetAsync((T *)stats + tl.row0 * width, 0, (size_t)(tl.row1 - tl.row0) * width * sizeof(T), ctx->stream));
-    GaussParams<T> p = gauss_params<T>(ctx, side);
+    GaussParamsW<T> p = gauss_params<T>(ctx, side);
     p.tasks = tl.d_tasks;
     p.n_tasks = tl.n_tasks;
     p.split = tl.d_split;
@@ -1921,12 +2074,13 @@ static int gauss_zero_gram(pmf_ctx *ctx, int side, const T **gw) {
 }
 
 // The statistics of the first `n_rows` rows of `st`, the one way for the window and block loops: accumulate p's tasks,
-// combine the split rows and, with gw (gauss_zero_gram), blend every row's S with w0 G (timed with the combine).
+// combine the split rows and, with gw (gauss_zero_gram), blend every row's S with w0 G (timed with the combine; weighted
+// tasks have summed (c_j - w0) A_j, so their blend is S + w0 G).
 // `zero_first` clears the rows before that.  The rule: zero when a row that no task writes -- a row without ratings --
 // will be read.  Fold-in solves every row of a block, and under PMF_ZEROS_OBSERVED every row of a window is blended and
 // read; the default-mode ELBO never zeroes: its row kernel reads neither the statistics nor c_r of a row without ratings.
 template <typename T>
-static int gauss_block_stats(pmf_ctx *ctx, GaussParams<T> &p, int64_t n_split, const GaussStats<T> &st, int64_t n_rows,
+static int gauss_block_stats(pmf_ctx *ctx, GaussParamsW<T> &p, int64_t n_split, const GaussStats<T> &st, int64_t n_rows,
                              bool zero_first, const T *gw) {
     int rc;
     if (zero_first) PMF_HIP_CHECK(hipMemsetAsync(st.s, 0, (size_t)n_rows * st.s_stride * sizeof(T), ctx->stream));
@@ -1936,7 +2090,7 @@ static int gauss_block_stats(pmf_ctx *ctx, GaussParams<T> &p, int64_t n_split, c
     const int chunks = ctx->cov_stride / PMF_VEC;
     PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_COMBINE);
     hipLaunchKernelGGL((gauss_zero_blend_kernel<T>), dim3((unsigned)((n_rows * chunks + 255) / 256)), dim3(256), 0, ctx->stream, st.s,
-                       n_rows, st.s_stride, chunks, (T)(1.0 - ctx->gauss_zero_weight), gw);
+                       n_rows, st.s_stride, chunks, p.wgt ? (T)1 : (T)(1.0 - ctx->gauss_zero_weight), gw);
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
 }
@@ -1969,7 +2123,7 @@ static int gauss_ensure_windows(pmf_ctx *ctx, int side, int64_t *win_rows) {
 
 // the tasks and split rows of window `w` (rows bounds[w] .. bounds[w + 1]) into `p`; returns the window's split-row count
 template <typename T>
-static int64_t gauss_window_tasks(const PmfRowWindows &rw, size_t w, GaussParams<T> &p) {
+static int64_t gauss_window_tasks(const PmfRowWindows &rw, size_t w, GaussParamsW<T> &p) {
     const PmfTaskList &tl = rw.tasks;
     p.tasks = tl.d_tasks.as<PmfTask>() + tl.task_off[w];
     p.n_tasks = tl.task_off[w + 1] - tl.task_off[w];
@@ -2036,7 +2190,7 @@ static int run_zero_sweep(pmf_ctx *ctx, int side, double sigma2, double eta2) {
     if ((rc = ctx->d_gauss_window.reserve(ctx, (size_t)win_rows * (ctx->cov_stride + ctx->kpad) * sizeof(T), {ctx->stream}))) return rc;
     const T *gw;
     if ((rc = gauss_zero_gram<T>(ctx, side, &gw))) return rc;
-    GaussParams<T> p = gauss_params<T>(ctx, side);
+    GaussParamsW<T> p = gauss_params<T>(ctx, side);
     for (size_t w = 0; w + 1 < rw.bounds.size(); ++w) {
         const int64_t r0 = rw.bounds[w], n = rw.bounds[w + 1] - r0, ns = gauss_window_tasks<T>(rw, w, p);
         const GaussStats<T> st = GaussStats<T>::interleaved(ctx, ctx->d_gauss_window.as<T>(), r0);   // (tasks carry the row's id in the side)
@@ -2126,6 +2280,10 @@ static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double si
     p.kpad = ctx->kpad;
     p.row0 = tl.row0;
     p.rows = tl.row1;
+    if (ctx->weighted) {
+        p.wgt = ix.d_wgt.as<const T>();
+        p.wsum = ix.d_wsum.as<const T>();
+    }
     // fused single-rank fp32 pass after this side's fused factor sweep, nothing written since: the sums form
     const bool from_sums = pass == PMF_PASS_FUSED && std::is_same<T, float>::value && ctx->gauss_mdot_valid[side] &&
                            !ctx->gauss_bias_gather && !pmf_comm_active(ctx);
@@ -2140,14 +2298,22 @@ static int run_bias(pmf_ctx *ctx, int side, PmfPass pass, void *stats, double si
             PMF_HIP_CHECK(hipMemsetAsync((T *)stats + p.row0 * 2, 0, (size_t)(p.rows - p.row0) * 2 * sizeof(T), ctx->stream));
         if (tl.n_tasks > 0 && from_sums) {
             // a wavefront per task where the tasks are long (the benchmark's item side: 512), 16 lanes otherwise
-            if (ctx->nnz / tl.n_tasks >= 64)
-                hipLaunchKernelGGL((gauss_bias_sums_kernel<T, 64>), dim3((unsigned)((p.n_tasks + 3) / 4)), dim3(256), 0, ctx->stream, p, mdot);
+            const bool wide = ctx->nnz / tl.n_tasks >= 64;
+            const dim3 grid((unsigned)(wide ? (p.n_tasks + 3) / 4 : (p.n_tasks + 15) / 16));
+            if (p.wgt) {
+                if (wide) hipLaunchKernelGGL((gauss_bias_sums_kernel<T, 64, true>), grid, dim3(256), 0, ctx->stream, p, mdot);
+                else hipLaunchKernelGGL((gauss_bias_sums_kernel<T, 16, true>), grid, dim3(256), 0, ctx->stream, p, mdot);
+            } else if (wide)
+                hipLaunchKernelGGL((gauss_bias_sums_kernel<T, 64>), grid, dim3(256), 0, ctx->stream, p, mdot);
             else
-                hipLaunchKernelGGL((gauss_bias_sums_kernel<T, 16>), dim3((unsigned)((p.n_tasks + 15) / 16)), dim3(256), 0, ctx->stream, p, mdot);
+                hipLaunchKernelGGL((gauss_bias_sums_kernel<T, 16>), grid, dim3(256), 0, ctx->stream, p, mdot);
         } else if (tl.n_tasks > 0)
             pmf_with_pow2<1>(pmf_lanes_per_row(ctx->kpad), [&](auto L) {
                 dim3 grid((unsigned)((p.n_tasks + 256 / L - 1) / (256 / L)));
-                if (acc) hipLaunchKernelGGL((gauss_bias_kernel<T, L, true>), grid, dim3(256), 0, ctx->stream, p);
+                if (p.wgt) {
+                    if (acc) hipLaunchKernelGGL((gauss_bias_kernel<T, L, true, true>), grid, dim3(256), 0, ctx->stream, p);
+                    else hipLaunchKernelGGL((gauss_bias_kernel<T, L, false, true>), grid, dim3(256), 0, ctx->stream, p);
+                } else if (acc) hipLaunchKernelGGL((gauss_bias_kernel<T, L, true>), grid, dim3(256), 0, ctx->stream, p);
                 else hipLaunchKernelGGL((gauss_bias_kernel<T, L, false>), grid, dim3(256), 0, ctx->stream, p);
             });
         if (tl.n_split > 0) {
@@ -2195,6 +2361,7 @@ struct FoldInBatch {
     const int64_t *row_ptr;
     const int32_t *other_ids;
     const double *ratings;
+    const double *weights;   // [row_ptr[n_rows]] or null
     double sigma2, eta2, eta_bias2;
     int n_iter;
     double *out_factor, *out_cov, *out_bias;
@@ -2225,7 +2392,7 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         int64_t units = 0;   // a row's statistics, and the partial slots of a row that is split
         const auto fits = [&](int64_t n) { return (units += 1 + (n > chunk ? (n + chunk - 1) / chunk : 0)) <= max_units; };
         // (the previous block ended with a stream synchronise: nothing queued still reads the block's buffers)
-        if ((rc = st.stage(ctx, a.n_rows, a.row_ptr, a.ratings, r0, max_rows, fits))) return rc;
+        if ((rc = st.stage(ctx, a.n_rows, a.row_ptr, a.ratings, r0, max_rows, fits, a.weights))) return rc;
         const int64_t B = st.r1 - r0, nnz = st.nnz;
         const bool has_empty = std::adjacent_find(st.ptr.begin(), st.ptr.end()) != st.ptr.end();
         tasks.clear();
@@ -2242,12 +2409,13 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
         if (nnz) PMF_HIP_CHECK(hipMemcpy(d_tasks.as(), tasks.data(), tasks.size() * sizeof(PmfTask), hipMemcpyHostToDevice));
         if (!split.empty())
             PMF_HIP_CHECK(hipMemcpy(d_split.as(), split.data(), split.size() * sizeof(PmfSplitRow), hipMemcpyHostToDevice));
-        GaussParams<T> p = gauss_params<T>(ctx, side);   // over the block's own buffers; no hot flags, and b = 0
+        GaussParamsW<T> p = gauss_params<T>(ctx, side);   // over the block's own buffers; no hot flags, and b = 0
         p.tasks = d_tasks.as<PmfTask>();
         p.n_tasks = (int64_t)tasks.size();
         p.split = d_split.as<PmfSplitRow>();
         p.other = st.d_other.template as<int32_t>();
         p.val = st.d_val.template as<const T>();
+        p.wgt = a.weights ? st.d_wgt.template as<const T>() : nullptr;   // (the batch's own weights, not the context's)
         p.hot = nullptr;
         p.bias_self = nullptr;
         p.partial = d_partial.as<T>();
@@ -2273,6 +2441,10 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
             q.K = K;
             q.kpad = kpad;
             q.cov_stride = cs;
+            if (a.weights) {
+                q.wgt = p.wgt;
+                q.wsum = st.d_wsum.template as<const T>();
+            }
             PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_BIAS);
             pmf_with_pow2<1>(pmf_lanes_per_row(kpad), [&](auto L) {
                 dim3 grid((unsigned)((B + 256 / L - 1) / (256 / L)));
@@ -2306,6 +2478,14 @@ static int run_fold_in(pmf_ctx *ctx, int side, const FoldInBatch &a) {
 extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
                                  const double *ratings, double sigma2, double eta2, double eta_bias2, int n_iter,
                                  double *out_factor, double *out_cov, double *out_bias) {
+    return pmf_gauss_fold_in_weighted(ctx, side, n_rows, row_ptr, other_ids, ratings, nullptr, sigma2, eta2, eta_bias2, n_iter,
+                                      out_factor, out_cov, out_bias);
+}
+
+extern "C" int pmf_gauss_fold_in_weighted(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr,
+                                          const int32_t *other_ids, const double *ratings, const double *weights, double sigma2,
+                                          double eta2, double eta_bias2, int n_iter, double *out_factor, double *out_cov,
+                                          double *out_bias) {
     PMF_SIDE_ENTRY("pmf_gauss_fold_in");
     PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_gauss_fold_in: negative row count");
     PMF_REQUIRE_ZERO_MODE_BIAS_FREE("pmf_gauss_fold_in");
@@ -2320,7 +2500,8 @@ extern "C" int pmf_gauss_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const i
     const int other = 1 - side;
     if ((rc = gauss_require_state(ctx, other, false, "pmf_gauss_fold_in"))) return rc;
     if ((rc = pmf_check_ids(other_ids, nnz, ctx->rows[other], "pmf_gauss_fold_in", "id"))) return rc;
-    const FoldInBatch a = {n_rows, row_ptr, other_ids, ratings, sigma2, eta2, eta_bias2, n_iter, out_factor, out_cov, out_bias};
+    if (weights && (rc = pmf_check_weights(weights, nnz, "pmf_gauss_fold_in"))) return rc;
+    const FoldInBatch a = {n_rows, row_ptr, other_ids, ratings, weights, sigma2, eta2, eta_bias2, n_iter, out_factor, out_cov, out_bias};
     return pmf_no_throw("pmf_gauss_fold_in", [&] {
         return pmf_with_dtype(ctx, [&](auto t) { return run_fold_in<decltype(t)>(ctx, side, a); });
     });
@@ -2362,6 +2543,7 @@ struct ElboSqParams {
     T *partial;                        // [n_slots] of split rows
     T *csum;                           // row r of the window at csum[r - row0]
     int64_t row0;
+    const T *wgt = nullptr;            // weighted ratings: c_j beside val, c_r = sum_j c_j e_j^2
 };
 
 // c_r: 16 lanes per task (a task is at most the context's task length), lane c takes ratings c, c + 16, ...
@@ -2375,10 +2557,11 @@ __global__ __launch_bounds__(256) void gauss_elbo_sq_kernel(ElboSqParams<T> p) {
     const T bs = p.bias_self ? p.bias_self[t.row] : (T)0;
     const int32_t *col = p.other + t.start;
     const T *val = p.val + t.start;
+    const T *wgt = p.wgt ? p.wgt + t.start : nullptr;
     T sum = (T)0;
     for (int j = c; j < t.len; j += LPR) {
         const T e = val[j] - bs - (p.bias_other ? p.bias_other[col[j]] : (T)0);
-        sum = fma(e, e, sum);
+        sum = fma(wgt ? wgt[j] * e : e, e, sum);
     }
     sum = group_sum<LPR>(sum);
     if (c != 0) return;
@@ -2676,7 +2859,7 @@ static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals
         // row has statistics (e.ptr stays null) and the rows no task writes start from zero sums and c_r = 0
         const T *gw;
         if ((rc = gauss_zero_gram<T>(ctx, side, &gw))) return rc;
-        GaussParams<T> p = gauss_params<T>(ctx, side);
+        GaussParamsW<T> p = gauss_params<T>(ctx, side);
         e.stats = d_win.as<const T>();
         e.csum = d_c.as<const T>();
         e.ptr = gw ? nullptr : ix.d_ptr.as<const int64_t>();
@@ -2697,6 +2880,7 @@ static int run_elbo_terms(pmf_ctx *ctx, int side, bool with_data, double *totals
                 q.partial = d_cpart.as<T>();
                 q.csum = d_c.as<T>();
                 q.row0 = r0;
+                q.wgt = p.wgt;
                 hipLaunchKernelGGL((gauss_elbo_sq_kernel<T>), dim3((unsigned)((nt + 15) / 16)), dim3(256), 0, ctx->stream, q);
             }
             if (ns > 0)

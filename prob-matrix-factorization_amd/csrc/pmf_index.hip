@@ -33,14 +33,28 @@ __global__ void iota_kernel(uint32_t *p, int64_t n) {
     if (k < n) p[k] = (uint32_t)k;
 }
 
+// w_in (with w_out) may be null: the ratings' weights go through the same permutation
 template <typename T>
-__global__ void gather_kernel(const uint32_t *perm, const int32_t *other_in, const double *x_in, int32_t *other_out,
-                              T *val_out, int64_t n) {
+__global__ void gather_kernel(const uint32_t *perm, const int32_t *other_in, const double *x_in, const double *w_in,
+                              int32_t *other_out, T *val_out, T *w_out, int64_t n) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const uint32_t src = perm[k];
     other_out[k] = other_in[src];
     val_out[k] = (T)x_in[src];
+    if (w_in) w_out[k] = (T)w_in[src];
+}
+
+// C_r of every row: its weights (in double, input order gathered by `perm`) added in the row's rating order
+template <typename T>
+__global__ void weight_sum_kernel(const uint32_t *perm, const double *w_in, const int64_t *ptr, int64_t rows, double *sum_out,
+                                  T *sum_out_t) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    double c = 0.0;
+    for (int64_t k = ptr[r]; k < ptr[r + 1]; ++k) c += w_in[perm[k]];
+    sum_out[r] = c;
+    sum_out_t[r] = (T)c;
 }
 
 // ptr[r] = number of ratings whose row id is < r (r = 0 .. rows)
@@ -73,23 +87,27 @@ inline unsigned key_bits(int64_t rows) {  // row ids are < rows
 struct PmfIndexBuild {
     PmfBuf d_u, d_i;   // int32_t [nnz], input order
     PmfBuf d_x;        // double [nnz]
+    PmfBuf d_w;        // double [nnz] the weights; null without
 };
 
 // Upload + validate.  On success the device copies live in `b` and *bad < 0; a bad id gives its
 // position in *bad (no device state of the context has been touched yet).
 static int upload_and_check(pmf_ctx *ctx, PmfIndexBuild &b, int64_t nnz, const int32_t *user_ids, const int32_t *item_ids,
-                            const double *ratings, int64_t *bad) {
+                            const double *ratings, const double *weights, int64_t *bad) {
     *bad = -1;
     int rc;
     PmfBuf d_bad;
     if ((rc = b.d_u.alloc(nullptr, (size_t)nnz * sizeof(int32_t)))) return rc;
     if ((rc = b.d_i.alloc(nullptr, (size_t)nnz * sizeof(int32_t)))) return rc;
     if ((rc = b.d_x.alloc(nullptr, (size_t)nnz * sizeof(double)))) return rc;
+    if (weights && (rc = b.d_w.alloc(nullptr, (size_t)nnz * sizeof(double)))) return rc;
     if ((rc = d_bad.alloc(nullptr, sizeof(unsigned long long)))) return rc;
     if (nnz == 0) return PMF_OK;
     PMF_HIP_CHECK(hipMemcpyAsync(b.d_u.as(), user_ids, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     PMF_HIP_CHECK(hipMemcpyAsync(b.d_i.as(), item_ids, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     PMF_HIP_CHECK(hipMemcpyAsync(b.d_x.as(), ratings, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (weights)
+        PMF_HIP_CHECK(hipMemcpyAsync(b.d_w.as(), weights, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     PMF_HIP_CHECK(hipMemsetAsync(d_bad.as(), 0xff, sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(check_ids_kernel, dim3(grid_for(nnz)), dim3(256), 0, ctx->stream, b.d_u.as<int32_t>(),
                        b.d_i.as<int32_t>(), nnz, ctx->rows[0], ctx->rows[1], d_bad.as<unsigned long long>());
@@ -103,7 +121,7 @@ static int upload_and_check(pmf_ctx *ctx, PmfIndexBuild &b, int64_t nnz, const i
 
 template <typename T>
 static int order_side(pmf_ctx *ctx, int side, int64_t nnz, const int32_t *d_key, const int32_t *d_oth,
-                      const double *d_x, uint32_t *d_keys_out, uint32_t *d_pos_in, uint32_t *d_pos_out, void *d_tmp,
+                      const double *d_x, const double *d_w, uint32_t *d_keys_out, uint32_t *d_pos_in, uint32_t *d_pos_out, void *d_tmp,
                       size_t tmp_bytes) {
     PmfSideIndex &ix = ctx->index[side];
     const int64_t rows = ctx->rows[side];
@@ -114,7 +132,7 @@ static int order_side(pmf_ctx *ctx, int side, int64_t nnz, const int32_t *d_key,
         PMF_HIP_CHECK(rocprim::radix_sort_pairs(d_tmp, bytes, (const uint32_t *)d_key, d_keys_out, (const uint32_t *)d_pos_in,
                                                 d_pos_out, (size_t)nnz, 0u, bits, ctx->stream));
         hipLaunchKernelGGL((gather_kernel<T>), dim3(grid_for(nnz)), dim3(256), 0, ctx->stream, d_pos_out, d_oth, d_x,
-                           ix.d_other.as<int32_t>(), ix.d_val.as<T>(), nnz);
+                           d_w, ix.d_other.as<int32_t>(), ix.d_val.as<T>(), ix.d_wgt.as<T>(), nnz);
     }
     hipLaunchKernelGGL(row_ptr_kernel, dim3(grid_for(rows + 1)), dim3(256), 0, ctx->stream, d_keys_out, nnz, rows,
                        ix.d_ptr.as<int64_t>());
@@ -122,14 +140,29 @@ static int order_side(pmf_ctx *ctx, int side, int64_t nnz, const int32_t *d_key,
     ix.h_ptr.resize((size_t)rows + 1);
     PMF_HIP_CHECK(hipMemcpyAsync(ix.h_ptr.data(), ix.d_ptr.as(), (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost,
                                  ctx->stream));
+    if (d_w) {   // (the double sums share the keys' successor on the stream: a buffer of this call)
+        PmfBuf d_sum;
+        int rc;
+        if ((rc = d_sum.alloc(nullptr, (size_t)rows * sizeof(double)))) return rc;
+        ix.h_wsum.assign((size_t)rows, 0.0);
+        if (rows > 0) {
+            hipLaunchKernelGGL((weight_sum_kernel<T>), dim3(grid_for(rows)), dim3(256), 0, ctx->stream, d_pos_out, d_w,
+                               ix.d_ptr.as<int64_t>(), rows, d_sum.as<double>(), ix.d_wsum.as<T>());
+            PMF_HIP_CHECK(hipGetLastError());
+            PMF_HIP_CHECK(hipMemcpyAsync(ix.h_wsum.data(), d_sum.as(), (size_t)rows * sizeof(double), hipMemcpyDeviceToHost,
+                                         ctx->stream));
+        }
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return PMF_OK;
+    }
     PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return PMF_OK;
 }
 
 int pmf_index_device_begin(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, const int32_t *item_ids,
-                           const double *ratings, PmfIndexBuild **out, int64_t *bad_position) {
+                           const double *ratings, const double *weights, PmfIndexBuild **out, int64_t *bad_position) {
     PmfIndexBuild *b = new PmfIndexBuild();
-    int rc = upload_and_check(ctx, *b, nnz, user_ids, item_ids, ratings, bad_position);
+    int rc = upload_and_check(ctx, *b, nnz, user_ids, item_ids, ratings, weights, bad_position);
     if (rc != PMF_OK || *bad_position >= 0) {
         delete b;
         b = nullptr;
@@ -166,10 +199,10 @@ int pmf_index_device_finish(pmf_ctx *ctx, PmfIndexBuild *b, int64_t nnz) {
     for (int side = 0; side < 2; ++side) {
         const int32_t *key = side == PMF_SIDE_USER ? d_u : d_i;
         const int32_t *oth = side == PMF_SIDE_USER ? d_i : d_u;
-        const double *x = b->d_x.as<double>();
+        const double *x = b->d_x.as<double>(), *w = b->d_w.as<double>();
         rc = ctx->dtype == PMF_F64
-                 ? order_side<double>(ctx, side, nnz, key, oth, x, keys_out, pos_in, pos_out, d_tmp.as(), tmp_bytes)
-                 : order_side<float>(ctx, side, nnz, key, oth, x, keys_out, pos_in, pos_out, d_tmp.as(), tmp_bytes);
+                 ? order_side<double>(ctx, side, nnz, key, oth, x, w, keys_out, pos_in, pos_out, d_tmp.as(), tmp_bytes)
+                 : order_side<float>(ctx, side, nnz, key, oth, x, w, keys_out, pos_in, pos_out, d_tmp.as(), tmp_bytes);
         if (rc) return rc;
     }
     return PMF_OK;

@@ -155,6 +155,11 @@ struct PmfSideIndex {
     PmfBuf d_ptr;                // int64_t [rows + 1]
     PmfBuf d_other;              // int32_t [nnz] id on the opposite side
     PmfBuf d_val;                // [nnz] rating, context dtype
+    // pmf_ctx_set_ratings_weighted: the per-rating confidence weights c_j in this side's order and the per-row sums C_r
+    // (summed in double in the row's rating order, rounded once).  Both null while the context holds no weights.
+    PmfBuf d_wgt;                // [nnz] context dtype
+    PmfBuf d_wsum;               // [rows] context dtype
+    std::vector<double> h_wsum;  // [rows] C_r in double (pmf_ctx_rating_weight_sums); empty without weights
     std::vector<int64_t> h_ptr;  // host copy of ptr (task building)
     PmfBuf d_nonempty;           // int32_t [n_nonempty]: rows with at least one rating (Gaussian solve list)
     int64_t n_nonempty = 0;
@@ -193,6 +198,7 @@ struct pmf_ctx {
     int kp = 0;          // K(K+1)/2
     int cov_stride = 0;  // kp rounded up to PMF_VEC
     int64_t nnz = 0;
+    bool weighted = false;   // the ratings came with weights (pmf_ctx_set_ratings_weighted): index[side].d_wgt / d_wsum are set
     // Members are destroyed in reverse order: every buffer below goes (and is taken off device_bytes) before the
     // context's own stream does.
     struct OwnStream {
@@ -298,12 +304,15 @@ struct pmf_ctx {
 template <typename T>
 struct PmfFoldStage {
     PmfBuf d_ptr, d_other, d_val;   // int64_t [r1 - r0 + 1], int32_t [nnz], T [nnz]
+    PmfBuf d_wgt, d_wsum;           // T [nnz], T [r1 - r0]: the ratings' weights and their row sums (stage() with weights only)
     std::vector<int64_t> ptr;
-    std::vector<T> val;
+    std::vector<T> val, wgt, wsum;
     int64_t r1 = 0, nnz = 0, at = 0;
 
+    // `weights` (may be null): one per rating of the batch; staged with the ratings, with every row's sum (formed in
+    // double in rating order, rounded once)
     int stage(pmf_ctx *ctx, int64_t n_rows, const int64_t *row_ptr, const double *ratings, int64_t r0, int64_t max_rows,
-              const std::function<bool(int64_t)> &fits = nullptr) {
+              const std::function<bool(int64_t)> &fits = nullptr, const double *weights = nullptr) {
         r1 = pmf_block_cut(row_ptr, n_rows, r0, max_rows, PMF_FOLD_IN_BLOCK_NNZ, [&](int64_t n) { return !fits || fits(n); });
         at = row_ptr[r0];
         nnz = row_ptr[r1] - at;
@@ -312,6 +321,20 @@ struct PmfFoldStage {
         val.resize((size_t)nnz);
         for (int64_t k = 0; k < nnz; ++k) val[(size_t)k] = (T)ratings[at + k];
         int rc;
+        wgt.clear();
+        wsum.clear();
+        if (weights) {
+            wgt.resize((size_t)nnz);
+            for (int64_t k = 0; k < nnz; ++k) wgt[(size_t)k] = (T)weights[at + k];
+            wsum.resize((size_t)(r1 - r0));
+            for (int64_t r = r0; r < r1; ++r) {
+                double c = 0.0;
+                for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; ++k) c += weights[k];
+                wsum[(size_t)(r - r0)] = (T)c;
+            }
+            if ((rc = d_wgt.reserve(ctx, (size_t)nnz * sizeof(T), {ctx->stream}))) return rc;
+            if ((rc = d_wsum.reserve(ctx, wsum.size() * sizeof(T), {ctx->stream}))) return rc;
+        }
         if ((rc = d_ptr.reserve(ctx, ptr.size() * sizeof(int64_t), {ctx->stream}))) return rc;
         if ((rc = d_other.reserve(ctx, (size_t)nnz * sizeof(int32_t), {ctx->stream}))) return rc;
         return d_val.reserve(ctx, (size_t)nnz * sizeof(T), {ctx->stream});
@@ -321,7 +344,9 @@ struct PmfFoldStage {
         if (nnz) {
             PMF_HIP_CHECK(hipMemcpy(d_other.as(), other_ids + at, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice));
             PMF_HIP_CHECK(hipMemcpy(d_val.as(), val.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
+            if (!wgt.empty()) PMF_HIP_CHECK(hipMemcpy(d_wgt.as(), wgt.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
         }
+        if (!wsum.empty()) PMF_HIP_CHECK(hipMemcpy(d_wsum.as(), wsum.data(), wsum.size() * sizeof(T), hipMemcpyHostToDevice));
         return PMF_OK;
     }
 };
@@ -355,7 +380,8 @@ int pmf_alloc_array(pmf_ctx *ctx, int side, int array);  // no-op if present (ze
 // device-side index build (pmf_index.hip)
 struct PmfIndexBuild;
 int pmf_index_device_begin(pmf_ctx *ctx, int64_t nnz, const int32_t *user_ids, const int32_t *item_ids,
-                           const double *ratings, PmfIndexBuild **out, int64_t *bad_position);
+                           const double *ratings, const double *weights /* may be null */, PmfIndexBuild **out,
+                           int64_t *bad_position);
 void pmf_index_device_abort(PmfIndexBuild *b);
 int pmf_index_device_finish(pmf_ctx *ctx, PmfIndexBuild *b, int64_t nnz);
 // index[side].d_distinct_ptr / d_distinct from the side's d_ptr / d_other (no-op once built)
@@ -431,6 +457,20 @@ static inline auto pmf_with_predict_mode(int mode, F &&f) {
 
 // a FACTOR array or the ratings are about to change: the mean sums of the last factor sweeps no longer describe them
 static inline void pmf_factor_written(pmf_ctx *ctx) { ctx->gauss_mdot_valid[0] = ctx->gauss_mdot_valid[1] = false; }
+
+// Calls that read the ratings but have no weighted form refuse a context that holds weights: a silently unweighted fit
+// is the worse failure.
+#define PMF_REQUIRE_UNWEIGHTED(fn)                      \
+    PMF_REQUIRE(!ctx->weighted, PMF_EINVAL,             \
+                fn ": not available while the context holds rating weights (pmf_ctx_set_ratings_weighted)")
+
+// every weights[k] is finite and > 0, or PMF_EINVAL naming the first that is not
+static inline int pmf_check_weights(const double *weights, int64_t n, const char *fn) {
+    for (int64_t k = 0; k < n; ++k)
+        PMF_REQUIRE(weights[k] > 0.0 && weights[k] <= 1.7976931348623157e308, PMF_EINVAL,   // (false for a NaN as well)
+                    "%s: weight %g at position %lld is not finite and > 0", fn, weights[k], (long long)k);
+    return PMF_OK;
+}
 
 static inline bool pmf_has_bias(const pmf_ctx *ctx) { return ctx->arr[0][PMF_ARR_BIAS] && ctx->arr[1][PMF_ARR_BIAS]; }
 

@@ -233,6 +233,7 @@ extern "C" int pmf_gauss_sgd_accumulate(pmf_ctx *ctx, int side, void *stats_dev,
                                         double eta_bias2) {
     PMF_SIDE_ENTRY("pmf_gauss_sgd_accumulate");
     PMF_REQUIRE_GAUSS_ZEROS_MISSING("pmf_gauss_sgd_accumulate");
+    PMF_REQUIRE_UNWEIGHTED("pmf_gauss_sgd_accumulate");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_sgd_accumulate: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) {
         return run_sgd<decltype(t)>(ctx, side, PMF_PASS_ACCUMULATE, stats_dev, lr, sigma2, eta2, eta_bias2);
@@ -242,6 +243,7 @@ extern "C" int pmf_gauss_sgd_accumulate(pmf_ctx *ctx, int side, void *stats_dev,
 extern "C" int pmf_gauss_sgd_finalize(pmf_ctx *ctx, int side, const void *stats_dev) {
     PMF_SIDE_ENTRY("pmf_gauss_sgd_finalize");
     PMF_REQUIRE_GAUSS_ZEROS_MISSING("pmf_gauss_sgd_finalize");
+    PMF_REQUIRE_UNWEIGHTED("pmf_gauss_sgd_finalize");
     PMF_REQUIRE(stats_dev, PMF_EINVAL, "pmf_gauss_sgd_finalize: null stats buffer");
     return pmf_with_dtype(ctx, [&](auto t) { return run_sgd<decltype(t)>(ctx, side, PMF_PASS_FINALIZE, (void *)stats_dev, 1, 1, 1, 1); });
 }
@@ -249,6 +251,7 @@ extern "C" int pmf_gauss_sgd_finalize(pmf_ctx *ctx, int side, const void *stats_
 extern "C" int pmf_gauss_sgd_sweep(pmf_ctx *ctx, int side, double lr, double sigma2, double eta2, double eta_bias2) {
     PMF_SIDE_ENTRY("pmf_gauss_sgd_sweep");
     PMF_REQUIRE_GAUSS_ZEROS_MISSING("pmf_gauss_sgd_sweep");
+    PMF_REQUIRE_UNWEIGHTED("pmf_gauss_sgd_sweep");
     if (side == PMF_SIDE_ITEM && pmf_comm_active(ctx)) {
         // several ranks: the items' rating-count-weighted displacement sums are all-reduced (pmf_comm.hip)
         const PmfExchange ex = {false, pmf_has_bias(ctx) ? 2 : 1, {PMF_ARR_FACTOR, PMF_ARR_BIAS}};

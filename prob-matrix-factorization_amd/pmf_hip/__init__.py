@@ -76,6 +76,9 @@ SIGNATURES = {
     "pmf_ctx_hot_rows": (C.c_int, [_p, C.c_int, _i32p, C.c_int64, _i64p]),
     "pmf_ctx_task_max_len": (C.c_int, [_p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pmf_ctx_set_ratings": (C.c_int, [_p, C.c_int64, _i32p, _i32p, _f64p]),
+    "pmf_ctx_set_ratings_weighted": (C.c_int, [_p, C.c_int64, _i32p, _i32p, _f64p, _f64p]),
+    "pmf_ctx_has_rating_weights": (C.c_int, [_p, C.POINTER(C.c_int)]),
+    "pmf_ctx_rating_weight_sums": (C.c_int, [_p, C.c_int, _f64p]),
     "pmf_set_array": (C.c_int, [_p, C.c_int, C.c_int, _f64p]),
     "pmf_get_array": (C.c_int, [_p, C.c_int, C.c_int, _f64p]),
     "pmf_get_array_rows": (C.c_int, [_p, C.c_int, C.c_int, C.c_int64, _i64p, _f64p]),
@@ -99,6 +102,8 @@ SIGNATURES = {
     "pmf_gauss_bias_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),
     "pmf_gauss_fold_in": (C.c_int, [_p, C.c_int, C.c_int64, _i64p, _i32p, _f64p, C.c_double, C.c_double, C.c_double, C.c_int,
                                     _f64p, _f64p, _f64p]),
+    "pmf_gauss_fold_in_weighted": (C.c_int, [_p, C.c_int, C.c_int64, _i64p, _i32p, _f64p, _f64p, C.c_double, C.c_double,
+                                             C.c_double, C.c_int, _f64p, _f64p, _f64p]),
     "pmf_gauss_elbo_terms": (C.c_int, [_p, C.c_int, C.c_int, _f64p, _f64p]),
     "pmf_ctx_set_gauss_zeros": (C.c_int, [_p, C.c_int, C.c_double]),
     "pmf_ctx_get_gauss_zeros": (C.c_int, [_p, C.POINTER(C.c_int), _f64p]),

@@ -201,13 +201,37 @@ class Context:
         return n.value
 
     # ---- data -----------------------------------------------------------
-    def set_ratings(self, user_ids, item_ids, ratings):
+    def set_ratings(self, user_ids, item_ids, ratings, weights=None):
+        """`weights` (one per rating, finite and > 0): the Gaussian CAVI calls give rating j the precision
+        weights[j] / sigma2 (`pmf_ctx_set_ratings_weighted`); None clears them."""
         u, i, x = as_i32(user_ids, "user_ids"), as_i32(item_ids, "item_ids"), as_f64(ratings)
         if not (len(u) == len(i) == len(x)):
             raise ValueError("user_ids, item_ids and ratings must have the same length")
-        check(self._lib.pmf_ctx_set_ratings(self._h, len(u), ptr(u, C.c_int32), ptr(i, C.c_int32),
-                                            ptr(x, C.c_double)), "pmf_ctx_set_ratings")
+        if weights is None:
+            check(self._lib.pmf_ctx_set_ratings(self._h, len(u), ptr(u, C.c_int32), ptr(i, C.c_int32),
+                                                ptr(x, C.c_double)), "pmf_ctx_set_ratings")
+        else:
+            w = as_f64(weights)
+            if len(w) != len(x):
+                raise ValueError("weights must have one entry per rating")
+            check(self._lib.pmf_ctx_set_ratings_weighted(self._h, len(u), ptr(u, C.c_int32), ptr(i, C.c_int32),
+                                                         ptr(x, C.c_double), ptr(w, C.c_double)),
+                  "pmf_ctx_set_ratings_weighted")
         self.nnz = len(u)
+
+    @property
+    def rating_weights(self):
+        """Whether the context's ratings came with weights."""
+        has = C.c_int(0)
+        check(self._lib.pmf_ctx_has_rating_weights(self._h, C.byref(has)), "pmf_ctx_has_rating_weights")
+        return bool(has.value)
+
+    def rating_weight_sums(self, side):
+        """C_r of every row of `side`: the sum of its ratings' weights as the kernels read it (summed in double, rounded
+        once to the context dtype); the rating counts without weights."""
+        out = np.zeros(self.rows(side), dtype=np.float64)
+        check(self._lib.pmf_ctx_rating_weight_sums(self._h, side, ptr(out, C.c_double)), "pmf_ctx_rating_weight_sums")
+        return out
 
     def _host_shape(self, side, array):
         r = self.rows(side)
@@ -397,15 +421,27 @@ class Context:
         check(self._lib.pmf_gauss_bias_finalize(self._h, side, C.c_void_p(stats_ptr), float(sigma2),
                                                 float(eta_bias2)), "pmf_gauss_bias_finalize")
 
-    def gauss_fold_in(self, side, row_ptr, other_ids, ratings, sigma2, eta2, eta_bias2=1.0, n_iter=1, want_cov=True):
+    def gauss_fold_in(self, side, row_ptr, other_ids, ratings, sigma2, eta2, eta_bias2=1.0, n_iter=1, want_cov=True,
+                      weights=None):
         """Posterior of new rows of `side` (CSR batch: `row_ptr`, ids on the opposite side, ratings) against the
-        fitted opposite side: (factor [n, K], cov [n, K, K] or None, bias [n]) as float64.  The context is only read."""
+        fitted opposite side: (factor [n, K], cov [n, K, K] or None, bias [n]) as float64.  The context is only read.
+        `weights`: one confidence weight per rating of the batch (`pmf_gauss_fold_in_weighted`)."""
         rp, o, x = csr_batch("row_ptr must hold n_rows + 1 offsets ending at len(other_ids) == len(ratings)", row_ptr,
                              other_ids, "other_ids", ratings)
         n = len(rp) - 1
         factor = np.zeros((n, self.K), dtype=np.float64)
         cov = np.zeros((n, self.K, self.K), dtype=np.float64) if want_cov else None
         bias = np.zeros(n, dtype=np.float64)
+        if weights is not None:
+            w = as_f64(weights)
+            if len(w) != len(x):
+                raise ValueError("weights must have one entry per rating of the batch")
+            check(self._lib.pmf_gauss_fold_in_weighted(self._h, side, n, ptr(rp, C.c_int64), ptr(o, C.c_int32),
+                                                       ptr(x, C.c_double), ptr(w, C.c_double), float(sigma2), float(eta2),
+                                                       float(eta_bias2), int(n_iter), ptr(factor, C.c_double),
+                                                       ptr(cov, C.c_double) if want_cov else None, ptr(bias, C.c_double)),
+                  "pmf_gauss_fold_in_weighted")
+            return factor, cov, bias
         check(self._lib.pmf_gauss_fold_in(self._h, side, n, ptr(rp, C.c_int64), ptr(o, C.c_int32), ptr(x, C.c_double),
                                           float(sigma2), float(eta2), float(eta_bias2), int(n_iter), ptr(factor, C.c_double),
                                           ptr(cov, C.c_double) if want_cov else None, ptr(bias, C.c_double)),

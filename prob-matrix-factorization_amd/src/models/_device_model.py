@@ -34,17 +34,34 @@ def frame_arrays(df):
             df["rating"].to_numpy(dtype=float))
 
 
-def fold_in_batch(df, side, n_other):
+def frame_weights(df, weights, what="weights"):
+    """`fit`'s / `fold_in_*`'s `weights` -> float64 array of len(df), or None: a column name of `df` or an array; every
+    entry finite and > 0 (ValueError otherwise, before any device call)."""
+    if weights is None:
+        return None
+    w = df[weights].to_numpy(dtype=float) if isinstance(weights, str) else np.asarray(weights, dtype=float).reshape(-1)
+    if len(w) != len(df):
+        raise ValueError(f"{what} must have one entry per row of the frame ({len(df)}), not {len(w)}")
+    bad = np.flatnonzero(~(np.isfinite(w) & (w > 0)))
+    if len(bad):
+        raise ValueError(f"{what} must be finite and > 0: {w[bad[0]]!r} at position {int(bad[0])}")
+    return w
+
+
+def fold_in_batch(df, side, n_other, weights=None):
     """The CSR batch of a fold-in frame (columns u, i, rating; the new rows of `side` carry arbitrary labels in their
     column): (ids, row_ptr, other_ids, ratings).  `ids` are the labels, sorted; row r of the batch belongs to ids[r].
     Rows of the frame whose id on the fitted side lies outside [0, n_other) are dropped, as ids the fit has not seen
-    are everywhere else; every row of the batch keeps its ratings in frame order."""
+    are everywhere else; every row of the batch keeps its ratings in frame order.  With `weights` (one per row of the
+    frame) a fifth entry: the kept rows' weights in batch order."""
     new_col, old_col = ("u", "i") if side == USER else ("i", "u")
     ids, row = np.unique(df[new_col].to_numpy(), return_inverse=True)
     other = df[old_col].to_numpy(dtype=int)
     keep = (other >= 0) & (other < n_other)
     row, other, x = row[keep], other[keep], df["rating"].to_numpy(dtype=float)[keep]
     row_ptr, order = pmf_hip.engine.group_rows(row, len(ids))
+    if weights is not None:
+        return ids, row_ptr, other[order], x[order], np.asarray(weights, dtype=float)[keep][order]
     return ids, row_ptr, other[order], x[order]
 
 
@@ -157,7 +174,7 @@ class DeviceModel:
             draw(min(block, self.n_users - at))
         return mine
 
-    def _open_context(self, u, i, x):
+    def _open_context(self, u, i, x, weights=None):
         if self._ctx is not None:
             self._ctx.close()
         n_local = self.n_users
@@ -177,7 +194,10 @@ class DeviceModel:
             self._comm.attach(self._ctx)
             self._ctx.set_row_chunks(pmf_hip.ITEM, pdist.default_item_chunks(
                 self._comm.world, pdist.item_message_bytes(self._ctx, self._gaussian)))
-        self._ctx.set_ratings(u, i, x)
+        if weights is None:
+            self._ctx.set_ratings(u, i, x)
+        else:                                   # (refused with comm= before this point)
+            self._ctx.set_ratings(u, i, x, weights)
         import time
         self._t_last = time.perf_counter()
         for key in ("val_rmse", "val_macro_mae", "seconds"):

@@ -10,29 +10,39 @@ from typing import Optional
 import numpy as np
 
 from src.evaluation.metrics import macro_mae, rmse
-from src.models._device_model import ITEM, USER, DeviceModel, fold_in_batch, frame_arrays
+from src.models._device_model import ITEM, USER, DeviceModel, fold_in_batch, frame_arrays, frame_weights
 from pmf_hip import ARR_BIAS, ARR_COV, ARR_FACTOR, ELBO_BIAS_SQ, ELBO_ESS, ELBO_LOGDET, ELBO_SQNORM, dist as pdist
 
 
 def elbo_from_terms(user_terms, item_terms, user_counts, item_counts, n_ratings, n_factors, sigma2, eta_theta2, eta_beta2,
-                    eta_bias2=None, data_side=USER, zero_weight=None):
+                    eta_bias2=None, data_side=USER, zero_weight=None, *, user_weight_sums=None, item_weight_sums=None,
+                    log_weight_sum=None):
     """The evidence lower bound of a Gaussian CAVI model from the sums `pmf_gauss_elbo_terms` returns (include/pmf_hip.h
     has the definition): `user_terms` / `item_terms` are the two sides' total vectors (columns `pmf_hip.ELBO_*`),
     `user_counts` / `item_counts` the ratings per row of each side (their lengths are the row counts), `eta_bias2=None`
     the bias-free model.  The data term takes the ESS entry of `data_side`; either side's gives the same sum.  Pure
     host arithmetic in float64.  `zero_weight` (bias-free model only): the terms come from a context that counts unlisted
     cells as zeros of variance sigma2 / zero_weight (`pmf_ctx_set_gauss_zeros`), so the data constant also has the
-    U I - N unlisted cells, U and I being the lengths of the two count vectors.  Returns (L, parts): parts names the data term and, per block of q, the expected log
+    U I - N unlisted cells, U and I being the lengths of the two count vectors.  `user_weight_sums` / `item_weight_sums`
+    / `log_weight_sum` (all three or none; the terms come from a context with rating weights, `pmf_ctx_set_ratings_weighted`):
+    C_r = the sum of the weights of every row's ratings, which takes the place of the row's count in the bias variances
+    and in the ESS, and sum_j log c_j, of which the data constant gains a half.  Returns (L, parts): parts names the data term and, per block of q, the expected log
     prior and the entropy; the parts add up to L."""
     terms = (np.asarray(user_terms, dtype=np.float64), np.asarray(item_terms, dtype=np.float64))
     counts = (np.asarray(user_counts, dtype=np.float64), np.asarray(item_counts, dtype=np.float64))
     K, two_pi = int(n_factors), 2.0 * np.pi
     ess = float(terms[data_side][ELBO_ESS])
     parts = {}
+    given = [a is not None for a in (user_weight_sums, item_weight_sums, log_weight_sum)]
+    if any(given) and not all(given):
+        raise ValueError("user_weight_sums, item_weight_sums and log_weight_sum go together")
+    mass = counts if not any(given) else (np.asarray(user_weight_sums, dtype=np.float64), np.asarray(item_weight_sums, dtype=np.float64))
     if eta_bias2 is not None:
-        var = [1.0 / (1.0 / eta_bias2 + n / sigma2) for n in counts]       # gaussian_mf_cavi_bias.py:222 / :253
-        ess += sum(float(np.sum(n * v)) for n, v in zip(counts, var))
+        var = [1.0 / (1.0 / eta_bias2 + n / sigma2) for n in mass]       # gaussian_mf_cavi_bias.py:222 / :253
+        ess += sum(float(np.sum(n * v)) for n, v in zip(mass, var))
     parts["data"] = -0.5 * n_ratings * np.log(two_pi * sigma2) - ess / (2.0 * sigma2)
+    if any(given):
+        parts["data"] += 0.5 * float(log_weight_sum)
     if zero_weight is not None:
         if eta_bias2 is not None:
             raise ValueError("zero_weight: unlisted cells as weighted zeros are defined for the bias-free model only")
@@ -79,6 +89,7 @@ class GaussianHost(DeviceModel):
         self.m_theta = self.m_beta = None
         self._V_theta = self._V_beta = None
         self._elbo_counts = None     # (ratings per user, per item) of the last single-process fit
+        self._log_weight_sum = None  # sum_j log c_j of the last fit with weights
         self.global_mean = 0.0
         if self._uses_bias:
             self.m_user_bias = self.m_item_bias = None
@@ -203,7 +214,7 @@ class GaussianHost(DeviceModel):
         return True
 
     def fit(self, train_df, val_df=None, global_mean=0.0, *, track_elbo=False, elbo_tol=None, unobserved="missing",
-            zero_weight=1.0):
+            zero_weight=1.0, weights=None):
         """`track_elbo`: evaluate the evidence lower bound after every iteration (`history_["elbo"]`; about 1.3
         accumulates of the user side more per iteration).  `elbo_tol` (implies `track_elbo`): stop when the relative increase
         (L_t - L_{t-1}) / |L_{t-1}| falls below it -- an early stop that needs no `val_df`.
@@ -215,9 +226,21 @@ class GaussianHost(DeviceModel):
         default fit of the frame with every missing cell listed as 0; 1 / (1 + alpha) is the usual confidence ratio.
         Recorded in `history_["unobserved"]` / `history_["zero_weight"]` and kept on the fit's context: `elbo()`,
         `track_elbo`, `fold_in_users` and `fold_in_items` run in the same mode.  "zero" refuses duplicate (u, i) pairs
-        and `comm=`; negative ratings are fine."""
+        and `comm=`; negative ratings are fine.
+        `weights`: None, the name of a column of `train_df`, or an array of len(train_df): a confidence weight c_j per
+        rating, finite and > 0, which gives rating j the precision c_j / sigma2 (`pmf_ctx_set_ratings_weighted`,
+        DESIGN.md section 4.18) -- `sample_weight` for explicit ratings (recency decay, de-duplicated counts,
+        inverse-propensity weights) and, with `unobserved="zero"`, `zero_weight=1`, ratings of 1 and c = 1 + alpha r, the
+        implicit-feedback model of Hu, Koren & Volinsky.  Recorded in `history_["weighted"]`; `elbo()`, `track_elbo` and
+        `elbo_tol` follow the weights.  Refused with `comm=` and by the gradient class."""
         cfg = self.config
         zeros = self._check_unobserved(unobserved, zero_weight, train_df)
+        weights = frame_weights(train_df, weights)
+        if weights is not None:
+            if not self._has_covariances:
+                raise NotImplementedError(f"{type(self).__name__}: rating weights are not available in the gradient mode")
+            if self._comm is not None:
+                raise ValueError("weights with comm=: rating weights are not available on several ranks")
         track_elbo = bool(track_elbo) or elbo_tol is not None
         if track_elbo:
             if not self._has_covariances:
@@ -228,7 +251,9 @@ class GaussianHost(DeviceModel):
         self._infer_dimensions(train_df)
         self._initialize_variational_params()
         u, i, x = frame_arrays(train_df)
-        ctx = self._open_context(u, i, x)
+        ctx = self._open_context(u, i, x, weights)
+        self.history_["weighted"] = weights is not None
+        self._log_weight_sum = None if weights is None else float(np.sum(np.log(weights)))
         if zeros:
             ctx.set_gauss_zeros(True, zero_weight)
         self.history_["unobserved"], self.history_["zero_weight"] = unobserved, float(zero_weight)
@@ -340,8 +365,12 @@ class GaussianHost(DeviceModel):
             raise NotImplementedError("elbo after a fit under a communicator: the ELBO of a sharded fit is not implemented")
         nu, ni = self._elbo_counts
         observed, weight = ctx.gauss_zeros
+        weighted = {}
+        if self.history_.get("weighted"):
+            weighted = dict(user_weight_sums=ctx.rating_weight_sums(USER), item_weight_sums=ctx.rating_weight_sums(ITEM),
+                            log_weight_sum=self._log_weight_sum)
         return elbo_from_terms(user, item, nu, ni, int(nu.sum()), cfg.n_factors, cfg.sigma2, cfg.eta_theta2, cfg.eta_beta2,
-                               cfg.eta_bias2 if self._uses_bias else None, zero_weight=weight if observed else None)
+                               cfg.eta_bias2 if self._uses_bias else None, zero_weight=weight if observed else None, **weighted)
 
     def elbo(self, parts=False):
         """The evidence lower bound of the fitted q on the training ratings, for the config's sigma2 / eta2 (float64):
@@ -353,30 +382,32 @@ class GaussianHost(DeviceModel):
         return (value, named) if parts else value
 
     # ---- fold-in of unseen users / items (extension: no reference counterpart as an operation) ----
-    def _fold_in(self, what, side, df, n_iter, return_cov):
+    def _fold_in(self, what, side, df, n_iter, return_cov, weights=None):
+        weights = frame_weights(df, weights)
         ctx = self._cov_ctx(what)
-        ids, row_ptr, other, x = fold_in_batch(df, side, self.n_items if side == USER else self.n_users)
+        ids, row_ptr, other, x, *w = fold_in_batch(df, side, self.n_items if side == USER else self.n_users, weights)
         cfg = self.config
         mean, cov, bias = ctx.gauss_fold_in(side, row_ptr, other, x, cfg.sigma2,
                                             cfg.eta_theta2 if side == USER else cfg.eta_beta2,
-                                            cfg.eta_bias2 if self._uses_bias else 1.0, n_iter, want_cov=return_cov)
+                                            cfg.eta_bias2 if self._uses_bias else 1.0, n_iter, want_cov=return_cov,
+                                            **({"weights": w[0]} if w else {}))
         m_other = self.m_beta if side == USER else self.m_theta
         b_other = (self.m_item_bias if side == USER else self.m_user_bias) if self._uses_bias else None
         return FoldIn(ids, mean, cov, bias, m_other, b_other, side, row_ptr, other)
 
-    def fold_in_users(self, df, n_iter=10, return_cov=False):
+    def fold_in_users(self, df, n_iter=10, return_cov=False, weights=None):
         """Posterior of users the fit has not seen, from their ratings of fitted items: `df` has columns u, i, rating
         in `fit`'s rating convention; `u` holds arbitrary labels.  The item side stays frozen; each user gets the
         factor update and (bias model) `n_iter` factor / bias alternations from a zero bias -- the reference's own
         row updates, on the device (`pmf_gauss_fold_in`), without a refit.  Rows with an item id the fit has not seen
         are dropped; a user left without ratings gets the prior (after `fit(unobserved="zero")`: the posterior of a row of
-        zeros, as every other row's unlisted cells are zeros too).  Returns a `FoldIn`, one row per label in sorted
-        order."""
-        return self._fold_in("fold_in_users", USER, df, n_iter, return_cov)
+        zeros, as every other row's unlisted cells are zeros too).  `weights`: as in `fit`, one confidence weight per row
+        of `df` (`pmf_gauss_fold_in_weighted`).  Returns a `FoldIn`, one row per label in sorted order."""
+        return self._fold_in("fold_in_users", USER, df, n_iter, return_cov, weights)
 
-    def fold_in_items(self, df, n_iter=10, return_cov=False):
+    def fold_in_items(self, df, n_iter=10, return_cov=False, weights=None):
         """The same for new items (labels in column `i`) against the fitted users."""
-        return self._fold_in("fold_in_items", ITEM, df, n_iter, return_cov)
+        return self._fold_in("fold_in_items", ITEM, df, n_iter, return_cov, weights)
 
     def _seen(self, df):
         keep = (df["u"] < self.n_users) & (df["i"] < self.n_items)
