@@ -563,6 +563,33 @@ int pmf_gauss_fold_in_weighted(pmf_ctx *ctx, int side, int64_t n_rows, const int
 int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, double *totals /* [PMF_ELBO_TERMS] */,
                          double *per_row /* rows x PMF_ELBO_TERMS, may be NULL */);
 
+/* Posterior draws of factor rows.  No reference counterpart.  A draw of row r of `side` is
+ *     x = m_r + C_r z,     C_r the lower Cholesky factor of V_r = COV[r] (C_r C_r' = V_r),  m_r = FACTOR[r],
+ * with z K standard normals from a counter-based stream that is a pure function of (seed, side, row id, draw index, k):
+ * it does not depend on the launch shape, the batch, the order of the rows or the context's dtype.
+ *   generator  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key = (seed low
+ *              32 bits, seed high 32 bits), counter = (row id, draw index, block b = k / 4, side); the four output words
+ *              give the normals of k = 4b .. 4b + 3.
+ *   normals    Box-Muller in double, for both dtypes: u = (word + 0.5) 2^-32, (z0, z1) = sqrt(-2 ln u0) (cos 2 pi u1,
+ *              sin 2 pi u1) from words 0 and 1, (z2, z3) the same from words 2 and 3 -- 2 pi the double 6.283185307179586,
+ *              the product 2 pi u1 rounded before the cosine; the result is rounded once to the context's dtype.
+ * C_r is never stored: the kernels eliminate the Jacobi-scaled matrix as pmf_gauss_elbo_terms does for LOGDET and add
+ * column k of the factor times z_k at step k.  Biases are NOT sampled: a draw keeps BIAS at its mean (the bias variance
+ * depends on sigma2 and eta_bias2, which the context does not hold).  A row whose COV is not positive definite (a pivot
+ * <= 0, or a NaN scale) gives NaN in every element of that row's draws, the rule of PMF_ELBO_LOGDET; no other row is touched.
+ *
+ * pmf_gauss_sample_rows: draw d (0 <= d < n_draws) of request q is the draw of row row_ids[q] with draw index draw0 + d, at
+ * out[(q * n_draws + d) * K ..].  Rows may repeat and come in any order.  `z` (NULL, or n_rows x n_draws x K) replaces the
+ * stream: it is converted to the context's dtype as pmf_set_array_rows converts, and `seed` and `draw0` are then ignored.
+ * Large requests go in rounds of bounded device scratch (PMF_STAGE_BYTES).  No atomics: two calls give the same bits.
+ * Timed under PMF_KERNEL_GAUSS_SOLVE.  The call only reads the context.  PMF_EINVAL: null context, bad side, negative
+ * n_rows, null row_ids or out, n_draws < 1, draw0 < 0, FACTOR or COV of the side missing (named; every count-model context).
+ * PMF_ERANGE: an id outside [0, rows), naming the id and its position.  n_rows = 0 touches nothing; an argument error
+ * writes nothing. */
+int pmf_gauss_sample_rows(pmf_ctx *ctx, int side, int64_t n_rows, const int32_t *row_ids, int n_draws, int draw0,
+                          uint64_t seed, const double *z /* NULL, or [n_rows x n_draws x K] */,
+                          double *out /* [n_rows x n_draws x K] */);
+
 /* Implicit feedback for the bias-free Gaussian model: unlisted cells as weighted zeros.  No
  * reference counterpart (the reference treats the rating list as the whole data set; that stays the default).
  * pmf_ctx_set_gauss_zeros selects, for pmf_gauss_factor_sweep, pmf_gauss_fold_in and pmf_gauss_elbo_terms of this
@@ -862,6 +889,20 @@ int pmf_rank_query(pmf_ctx *ctx, int cand_side, int64_t n_query, int query_side,
                    const double *query_factor, const double *query_coef, int score, const int64_t *ex_ptr,
                    const int32_t *ex_ids, const int64_t *tgt_ptr, const int32_t *tgt_ids, int64_t *out_rank,
                    int64_t *out_candidates);
+
+/* Thompson-sampled top-k: pmf_topk_query in ids mode, scored on ONE joint posterior draw (pmf_gauss_sample_rows defines a
+ * draw).  Every row of cand_side is sampled into a context-owned table of rows x Kpad elements (allocated on first use,
+ * counted by pmf_ctx_device_bytes, kept: a later call of the same size adds nothing) that takes the place of cand_side's
+ * FACTOR in the scan, and the query rows of every round are sampled into the staged query table; both sides use draw index
+ * `draw` under `seed`.  Contract, to the bit: the row of (side, id) the scan reads equals pmf_gauss_sample_rows(side, id,
+ * n_draws = 1, draw0 = draw, seed) converted to the context's dtype.  Biases (score = PMF_PREDICT_BIAS) are the stored
+ * means.  Exclusion lists, order, ties, the NaN rule (a row that is not positive definite scores NaN), the limits of k,
+ * the rounds and the fused / two-phase choice are pmf_topk_query's.  PMF_EINVAL besides pmf_topk_query's cases: null
+ * query_ids, a score other than 0 or PMF_PREDICT_BIAS (PMF_SCORE_COSINE and PMF_PREDICT_SCALE are refused), draw < 0, COV
+ * of either side missing.  The sampling is timed under PMF_KERNEL_GAUSS_SOLVE, the scan under PMF_KERNEL_TOPK. */
+int pmf_topk_sampled(pmf_ctx *ctx, int cand_side, int64_t n_query, int query_side, const int32_t *query_ids,
+                     int score /* 0 or PMF_PREDICT_BIAS */, const int64_t *ex_ptr, const int32_t *ex_ids, int k, uint64_t seed,
+                     int draw, int32_t *out_ids, double *out_scores);
 
 /* ---- profiling ----------------------------------------------------------
  * When enabled every kernel launch is bracketed by hipEvents on the context's

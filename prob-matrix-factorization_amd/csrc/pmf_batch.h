@@ -1,6 +1,7 @@
-// Host-side chores of the batched entry points: the offset-array check, the layout of one scratch buffer and the cut of
-// a CSR batch into row blocks.  Standard library only -- no HIP, no context -- so that tests/batch_host_main.cpp can
-// build it with a plain host compiler and run it under the sanitizers.
+// Host-side chores of the batched entry points: the offset-array check, the layout of one scratch buffer, the cut of
+// a CSR batch into row blocks and the argument check and round size of pmf_gauss_sample_rows.  Standard library only --
+// no HIP, no context -- so that tests/batch_host_main.cpp and tests/sample_host_main.cpp can build it with a plain host
+// compiler and run it under the sanitizers.
 #pragma once
 
 #include <stddef.h>
@@ -9,6 +10,7 @@
 #ifndef PMF_EINVAL   // (include/pmf_hip.h's values, for a unit that includes this header alone)
 #define PMF_OK 0
 #define PMF_EINVAL (-1)
+#define PMF_ERANGE (-4)
 #endif
 
 void pmf_set_error(const char *fmt, ...);
@@ -26,6 +28,46 @@ static inline int pmf_check_offsets(const char *fn, const char *name, const int6
             return PMF_EINVAL;
         }
     return PMF_OK;
+}
+
+// The arguments of pmf_gauss_sample_rows that need no context state, in the order the header lists them (`rows` = rows of
+// the side): PMF_EINVAL for a negative n_rows, null row_ids / out, n_draws < 1 or draw0 < 0, PMF_ERANGE naming the first
+// id outside [0, rows) and its position.  n_rows = 0 is accepted whatever the pointers are: the call touches nothing.
+static inline int pmf_sample_check(const char *fn, int64_t n_rows, const int32_t *row_ids, int n_draws, int draw0,
+                                   const void *out, int64_t rows) {
+    if (n_rows < 0) {
+        pmf_set_error("%s: negative n_rows", fn);
+        return PMF_EINVAL;
+    }
+    if (n_rows == 0) return PMF_OK;
+    if (!row_ids || !out) {
+        pmf_set_error("%s: null %s", fn, !row_ids ? "row_ids" : "out");
+        return PMF_EINVAL;
+    }
+    if (n_draws < 1) {
+        pmf_set_error("%s: n_draws=%d, at least 1 is needed", fn, n_draws);
+        return PMF_EINVAL;
+    }
+    if (draw0 < 0) {
+        pmf_set_error("%s: negative draw0 %d", fn, draw0);
+        return PMF_EINVAL;
+    }
+    for (int64_t q = 0; q < n_rows; ++q)
+        if (row_ids[q] < 0 || row_ids[q] >= rows) {
+            pmf_set_error("%s: row id %d at position %lld outside [0, %lld)", fn, row_ids[q], (long long)q, (long long)rows);
+            return PMF_ERANGE;
+        }
+    return PMF_OK;
+}
+
+// Rows of one round of pmf_gauss_sample_rows: as many as keep the round's device tables -- the draws [rows x n_draws x
+// kpad] of `elem` bytes, the supplied normals of the same shape (`with_z`) and the row ids -- within `budget` bytes; at
+// least one row (a single row over the budget still goes, in a round of its own) and at most n_rows, 0 for no rows.
+static inline int64_t pmf_sample_round_rows(int64_t n_rows, int n_draws, int kpad, size_t elem, bool with_z, int64_t budget) {
+    if (n_rows <= 0) return 0;
+    const int64_t per_row = (int64_t)n_draws * kpad * (int64_t)elem * (with_z ? 2 : 1) + (int64_t)sizeof(int32_t);
+    const int64_t fit = budget / per_row;
+    return fit < 1 ? 1 : (fit < n_rows ? fit : n_rows);
 }
 
 // One buffer carved into typed pieces.  add<T>(n) for every piece, in order; bytes() is what to allocate; piece.at(base)

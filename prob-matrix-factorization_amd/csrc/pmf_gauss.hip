@@ -2923,3 +2923,364 @@ extern "C" int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, doubl
         return pmf_with_dtype(ctx, [&](auto t) { return run_elbo_terms<decltype(t)>(ctx, side, with_data != 0, totals, per_row); });
     });
 }
+
+// ---------------------------------------------------------------------------
+// posterior draws (pmf_gauss_sample_rows, and the tables of pmf_topk_sampled)
+// ---------------------------------------------------------------------------
+// No reference counterpart.  A draw of row r is x = m_r + C_r z with C_r the lower Cholesky factor of V_r and z K standard
+// normals.  C_r is never stored: the elimination the ELBO row kernels run on the Jacobi-scaled matrix A = G V G (G =
+// diag(g), g_j = 1 / sqrt(V_jj)) has, at step k, d_k L[:, k] in the pivot row (A = L D L^T), so column k of chol(A) is that
+// row times 1 / sqrt(d_k), and  x = m + G^-1 chol(A) z  is accumulated column by column.  The normals are a pure function
+// of (seed, side, row id, draw index, k): Philox4x32-10 on the counter (row id, draw index, k / 4, side) under the key
+// (seed low, seed high), then Box-Muller in double on the words (0, 1) and (2, 3), rounded once to the context dtype.
+// A row with a pivot that is not positive (or a NaN scale) gives NaN in all its elements, as PMF_ELBO_LOGDET does.
+
+static const int kSampleDraws = 8;   // draws per pass of the elimination (register kernel) / of the mat-vec (block kernel)
+
+template <typename T>
+struct SampleParams {
+    const int32_t *ids;    // device [n]: the row of request q, or null: request q is row q
+    int64_t n;
+    const T *cov, *factor;
+    const T *z;            // device [n x n_draws x kpad]: the normals in place of the stream, or null
+    T *out;                // [n x n_draws x kpad]
+    int K, kpad, kp, cov_stride;
+    int side, n_draws;
+    uint32_t draw0, key0, key1;
+};
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&w)[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c0 = n0;
+        c1 = (uint32_t)p1;
+        c2 = n2;
+        c3 = (uint32_t)p0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    w[0] = c0;
+    w[1] = c1;
+    w[2] = c2;
+    w[3] = c3;
+}
+
+// z_k of (side, row, draw): words 2h, 2h + 1 of block k / 4 with h = (k / 2) % 2; even k takes the cosine, odd k the sine
+template <typename T>
+__device__ __forceinline__ T sample_normal(const SampleParams<T> &p, uint32_t row, uint32_t draw, int k) {
+    uint32_t w[4];
+    philox4x32_10(row, draw, (uint32_t)k >> 2, (uint32_t)p.side, p.key0, p.key1, w);
+    const bool hi = (k & 2) != 0;
+    const double u0 = ((double)(hi ? w[2] : w[0]) + 0.5) * 0x1p-32, u1 = ((double)(hi ? w[3] : w[1]) + 0.5) * 0x1p-32;
+    const double r = sqrt(-2.0 * log(u0));
+    double sn, cs;
+    sincos(6.283185307179586 * u1, &sn, &cs);
+    return (T)(r * ((k & 1) ? sn : cs));
+}
+
+// elbo_eliminate's schedule (pivot row in register 0, the width dropping by 8) with the draws taken along: at step k the
+// pivot row times 1 / sqrt(d_k) is column k of the factor on lanes j >= k -- lanes j < k hold the rounding residue of
+// d (1 / d) - 1, not zeros, and are masked -- and draw d adds it times z_{d,k}, which lane k holds.
+template <typename T, int N, int DR>
+__device__ __forceinline__ void sample_eliminate(T *B, int k0, int lane, int K, const T *zr, T *acc, bool &ok) {
+    constexpr int STEPS = N > 8 ? 8 : (N > 1 ? N / 2 : 1);
+#pragma unroll 1
+    for (int s = 0; s < STEPS; ++s) {
+        const int k = k0 + s;
+        const T v = B[0];
+        const T d = readlane_dyn(v, k);
+        if (k < K && !(d > (T)0)) ok = false;
+        const T c = lane >= k ? v * ((T)1 / sqrt(d)) : (T)0;
+#pragma unroll
+        for (int dd = 0; dd < DR; ++dd) acc[dd] = fma(c, readlane_dyn(zr[dd], k), acc[dd]);
+        if constexpr (N > 1) {
+            const T u = v * ((T)1 / d);
+#pragma unroll
+            for (int i = 1; i < N; ++i) B[i - 1] = fma(-readlane_dyn(B[i], k), u, B[i]);
+            B[N - 1] = (T)0;
+        }
+    }
+    if constexpr (N > 1) sample_eliminate<T, N - STEPS, DR>(B, k0 + STEPS, lane, K, zr, acc, ok);
+}
+
+// K <= 64: one wavefront per (request, pass of DR draws), the matrix in registers (lane j = column j) as in
+// gauss_elbo_row_reg_kernel; DR draws ride on one elimination, and a request of more draws takes ceil(n_draws / DR)
+// wavefronts, each with an elimination of its own (`passes` per request; wavefront w: request w / passes, pass w % passes).
+// dynamic LDS: 4 waves x (cov_stride + DR x 64) elements
+template <typename T, int KR, int DR>
+__global__ __launch_bounds__(256) void gauss_sample_reg_kernel(SampleParams<T> p, int passes) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + wave;
+    const int64_t idx = w / passes;
+    if (idx >= p.n) return;
+    const int d0 = (int)(w - idx * passes) * DR;
+    const int64_t row = p.ids ? (int64_t)p.ids[idx] : idx;
+    const int K = p.K;
+    T *img = reinterpret_cast<T *>(smem_raw) + (int64_t)wave * (p.cov_stride + DR * 64);
+    T *zs = img + p.cov_stride;   // [DR][64] the pass's normals, staged so that the generator is inlined once
+    const T *V = p.cov + row * p.cov_stride;
+    for (int q = lane * PMF_VEC; q < p.cov_stride; q += 64 * PMF_VEC) store4(img + q, load4(V + q));
+    const int j = lane, jc = j < K ? j : 0;
+    const T mj = j < K ? p.factor[row * p.kpad + j] : (T)0;
+    const int64_t at = idx * p.n_draws * p.kpad;
+#pragma unroll 1
+    for (int dd = 0; dd < DR; ++dd) {
+        const int d = d0 + dd;
+        T z = (T)0;   // (lanes >= K: their columns of the identity padding add nothing)
+        if (j < K && d < p.n_draws)
+            z = p.z ? p.z[at + (int64_t)d * p.kpad + j] : sample_normal<T>(p, (uint32_t)row, p.draw0 + (uint32_t)d, j);
+        zs[dd * 64 + lane] = z;
+    }
+    wave_lds_fence();
+    T zr[DR], acc[DR];
+#pragma unroll
+    for (int dd = 0; dd < DR; ++dd) {
+        zr[dd] = zs[dd * 64 + lane];
+        acc[dd] = (T)0;
+    }
+    // the matrix, Jacobi-scaled to a unit diagonal; rows and columns >= K are the identity
+    T B[KR];
+#pragma unroll
+    for (int i = 0; i < KR; ++i) {
+        const int ic = i < K ? i : 0;
+        const int lo = ic < jc ? ic : jc, hi = ic < jc ? jc : ic;
+        T s = img[hi * (hi + 1) / 2 + lo];
+        if (!(i < K && j < K)) s = (i == j) ? (T)1 : (T)0;
+        B[i] = s;
+    }
+    T diag = (T)1;
+#pragma unroll
+    for (int i = 0; i < KR; ++i) {
+        const T dii = readlane_dyn(B[i], i);
+        if (j == i) diag = dii;
+    }
+    const T g = (T)1 / sqrt(diag);
+#pragma unroll
+    for (int i = 0; i < KR; ++i) B[i] = B[i] * g * readlane_dyn(g, i);
+    bool ok = true;
+    sample_eliminate<T, KR, DR>(B, 0, lane, K, zr, acc, ok);
+    if (j < p.kpad) {
+#pragma unroll
+        for (int dd = 0; dd < DR; ++dd)
+            if (d0 + dd < p.n_draws)
+                p.out[at + (int64_t)(d0 + dd) * p.kpad + j] = j < K ? (ok ? mj + acc[dd] / g : (T)__builtin_nan("")) : (T)0;
+    }
+}
+
+// K > 64: one block per request on the packed lower triangle, in LDS or (`scratch` != null: fp64 at large K) in the block's
+// slice of a global buffer, as gauss_elbo_row_lds_kernel chooses.  After the right-looking elimination A[i, k] (i > k)
+// holds d_k L_ik and the pivots d_k; column k times 1 / sqrt(d_k) makes the triangle chol(A) in place, and the draws are
+// the packed mat-vec  x_i = m_i + (1 / g_i) sum_{k <= i} A[i, k] z_k:  wavefront w takes rows w, w + 4, ..., lane l the
+// columns l, l + 64, ..., then the lanes' sums in group_sum's fixed order.
+// dynamic LDS: [cov_stride unless `scratch`] + g [K] + rs [K] + z [kSampleDraws][K]
+template <typename T>
+__global__ __launch_bounds__(256) void gauss_sample_lds_kernel(SampleParams<T> p, T *scratch) {
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    __shared__ int bad;
+    constexpr int DC = kSampleDraws;
+    const int K = p.K, kp = p.kp;
+    T *lds = reinterpret_cast<T *>(smem_raw);
+    T *A = scratch ? scratch + (int64_t)blockIdx.x * p.cov_stride : lds;   // packed lower triangle
+    T *g = scratch ? lds : lds + p.cov_stride;                             // [K] Jacobi scales
+    T *rs = g + K;                                                         // [K] 1 / sqrt(pivot)
+    T *zs = rs + K;                                                        // [DC][K] the pass's normals
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int64_t idx = blockIdx.x; idx < p.n; idx += gridDim.x) {
+        const int64_t row = p.ids ? (int64_t)p.ids[idx] : idx;
+        const T *V = p.cov + row * p.cov_stride;
+        const T *m = p.factor + row * p.kpad;
+        const int64_t at = idx * p.n_draws * p.kpad;
+        __syncthreads();
+        if (tid == 0) bad = 0;
+        for (int q = tid * PMF_VEC; q < p.cov_stride; q += 256 * PMF_VEC) store4(A + q, load4(V + q));
+        __syncthreads();
+        for (int i = tid; i < K; i += 256) g[i] = (T)1 / sqrt(A[i * (i + 3) / 2]);
+        __syncthreads();
+        for (int e = tid; e < kp; e += 256) {
+            int r, c;
+            tri_rc(e, r, c);
+            A[e] *= g[r] * g[c];
+        }
+        // right-looking elimination on the lower triangle: wavefront w takes rows k + 1 + w, k + 5 + w, ...
+        for (int k = 0; k < K; ++k) {
+            __syncthreads();
+            const T d = A[k * (k + 3) / 2];
+            if (tid == 0) {
+                if (!(d > (T)0)) bad = 1;
+                rs[k] = (T)1 / sqrt(d);
+            }
+            const T pinv = (T)1 / d;
+            for (int i = k + 1 + wave; i < K; i += 4) {
+                const T f = A[i * (i + 1) / 2 + k] * pinv;
+                for (int jj = k + 1 + lane; jj <= i; jj += 64)
+                    A[i * (i + 1) / 2 + jj] = fma(-f, A[jj * (jj + 1) / 2 + k], A[i * (i + 1) / 2 + jj]);
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < kp; e += 256) {
+            int r, c;
+            tri_rc(e, r, c);
+            A[e] *= rs[c];
+        }
+        const bool ok = bad == 0;
+        for (int d0 = 0; d0 < p.n_draws; d0 += DC) {
+            __syncthreads();
+            for (int e = tid; e < DC * K; e += 256) {
+                const int dd = e / K, k = e - dd * K, d = d0 + dd;
+                T z = (T)0;
+                if (d < p.n_draws)
+                    z = p.z ? p.z[at + (int64_t)d * p.kpad + k] : sample_normal<T>(p, (uint32_t)row, p.draw0 + (uint32_t)d, k);
+                zs[e] = z;
+            }
+            __syncthreads();
+            for (int i = wave; i < p.kpad; i += 4) {
+                T s[DC];
+#pragma unroll
+                for (int dd = 0; dd < DC; ++dd) s[dd] = (T)0;
+                if (i < K)
+                    for (int k = lane; k <= i; k += 64) {
+                        const T a = A[i * (i + 1) / 2 + k];
+#pragma unroll
+                        for (int dd = 0; dd < DC; ++dd) s[dd] = fma(a, zs[dd * K + k], s[dd]);
+                    }
+#pragma unroll
+                for (int dd = 0; dd < DC; ++dd) {
+                    const T sum = group_sum<64>(s[dd]);
+                    if (lane == 0 && d0 + dd < p.n_draws)
+                        p.out[at + (int64_t)(d0 + dd) * p.kpad + i] = i < K ? (ok ? m[i] + sum / g[i] : (T)__builtin_nan("")) : (T)0;
+                }
+            }
+        }
+    }
+}
+
+// where the block-per-row kernel keeps its triangle: LDS while triangle and vectors fit the CU's 160 KB
+template <typename T>
+static bool sample_in_lds(const pmf_ctx *ctx) {
+    return (size_t)ctx->cov_stride * sizeof(T) + (size_t)(2 + kSampleDraws) * ctx->K * sizeof(T) + 64 <= (size_t)160 * 1024;
+}
+
+size_t pmf_gauss_sample_tri_bytes(const pmf_ctx *ctx, int64_t n) {
+    if (ctx->K <= 64 || n <= 0) return 0;
+    return pmf_with_dtype(ctx, [&](auto t) -> size_t {
+        using T = decltype(t);
+        return sample_in_lds<T>(ctx) ? 0 : (size_t)std::min<int64_t>(n, 1024) * ctx->cov_stride * sizeof(T);
+    });
+}
+
+template <typename T>
+static int launch_sample(pmf_ctx *ctx, const SampleParams<T> &s, T *tri) {
+    int rc = PMF_OK;
+    if (s.n == 0) return PMF_OK;
+    const int K = ctx->K;
+    PmfProfScope prof(ctx, PMF_KERNEL_GAUSS_SOLVE);
+    if (K <= 64) {
+        const int many = s.n_draws > 1, dr = many ? kSampleDraws : 1, passes = (s.n_draws + dr - 1) / dr;
+        const size_t smem = (size_t)4 * (ctx->cov_stride + dr * 64) * sizeof(T);
+        const int64_t blocks = (s.n * passes + 3) / 4;
+        PMF_REQUIRE(blocks <= (int64_t)INT32_MAX, PMF_ERANGE, "gauss sample: %lld rows x %d draws in one launch", (long long)s.n, s.n_draws);
+        const dim3 grid((unsigned)blocks);
+        pmf_with_pow2<8>(K, [&](auto KR) {
+            auto go = [&](auto kernel) {
+                if (smem > (size_t)48 * 1024 && ctx->sample_lds_bytes[many] != smem)   // fp64 at K = 64; once per context
+                    rc = pmf_allow_dynamic_lds((const void *)kernel, smem);
+                if (rc == PMF_OK) hipLaunchKernelGGL(kernel, grid, dim3(256), smem, ctx->stream, s, passes);
+            };
+            if (many) go(gauss_sample_reg_kernel<T, KR, kSampleDraws>);
+            else go(gauss_sample_reg_kernel<T, KR, 1>);
+        });
+        if (rc) return rc;
+        ctx->sample_lds_bytes[many] = smem;
+    } else {
+        const bool in_lds = sample_in_lds<T>(ctx);
+        PMF_REQUIRE(in_lds || tri, PMF_EINVAL, "gauss sample: no buffer for the packed triangles");
+        const size_t mat = (size_t)ctx->cov_stride * sizeof(T), vecs = (size_t)(2 + kSampleDraws) * K * sizeof(T);
+        const unsigned blocks = (unsigned)std::min<int64_t>(s.n, in_lds ? s.n : 1024);
+        const size_t smem = in_lds ? mat + vecs : vecs;
+        if (ctx->sample_lds_bytes[0] != smem && (rc = pmf_allow_dynamic_lds((const void *)gauss_sample_lds_kernel<T>, smem))) return rc;
+        ctx->sample_lds_bytes[0] = smem;
+        hipLaunchKernelGGL((gauss_sample_lds_kernel<T>), dim3(blocks), dim3(256), smem, ctx->stream, s, in_lds ? (T *)nullptr : tri);
+    }
+    PMF_HIP_CHECK(hipGetLastError());
+    return PMF_OK;
+}
+
+int pmf_gauss_sample_launch(pmf_ctx *ctx, int side, const int32_t *d_ids, int64_t n, int n_draws, int draw0, uint64_t seed,
+                            const void *d_z, void *d_out, void *d_tri) {
+    return pmf_with_dtype(ctx, [&](auto t) {
+        using T = decltype(t);
+        SampleParams<T> s;
+        s.ids = d_ids;
+        s.n = n;
+        s.cov = ctx->arr[side][PMF_ARR_COV].as<const T>();
+        s.factor = ctx->arr[side][PMF_ARR_FACTOR].as<const T>();
+        s.z = static_cast<const T *>(d_z);
+        s.out = static_cast<T *>(d_out);
+        s.K = ctx->K;
+        s.kpad = ctx->kpad;
+        s.kp = ctx->kp;
+        s.cov_stride = ctx->cov_stride;
+        s.side = side;
+        s.n_draws = n_draws;
+        s.draw0 = (uint32_t)draw0;
+        s.key0 = (uint32_t)(seed & 0xFFFFFFFFull);
+        s.key1 = (uint32_t)(seed >> 32);
+        return launch_sample<T>(ctx, s, static_cast<T *>(d_tri));
+    });
+}
+
+// The rounds of pmf_gauss_sample_rows: per round (pmf_sample_round_rows of the staging budget) the ids and, if given, the
+// normals go up through pinned memory, the kernel fills the round's table and the table comes down as FACTOR-shaped rows.
+template <typename T>
+static int run_sample_rows(pmf_ctx *ctx, int side, int64_t n_rows, const int32_t *row_ids, int n_draws, int draw0, uint64_t seed,
+                           const double *z, double *out) {
+    const int K = ctx->K, kpad = ctx->kpad;
+    const int64_t R = pmf_sample_round_rows(n_rows, n_draws, kpad, sizeof(T), z != nullptr, ctx->stage_bytes);
+    const size_t tri_bytes = pmf_gauss_sample_tri_bytes(ctx, R);
+    PmfLayout lay;
+    const auto out_at = lay.add<T>((size_t)R * n_draws * kpad), z_at = lay.add<T>(z ? (size_t)R * n_draws * kpad : 0);
+    const auto ids_at = lay.add<int32_t>((size_t)R);
+    const auto tri_at = lay.add<unsigned char>(tri_bytes);
+    int rc;
+    if ((rc = pmf_ensure_scratch(ctx, lay.bytes()))) return rc;
+    void *base = ctx->d_scratch.as();
+    for (int64_t r0 = 0; r0 < n_rows; r0 += R) {
+        const int64_t nr = std::min(R, n_rows - r0), vecs = nr * n_draws;
+        PMF_HIP_CHECK(hipMemcpyAsync(ids_at.at(base), row_ids + r0, (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        if (z) {   // the conversion of pmf_set_array_rows: rounded to T, zero-padded to Kpad
+            if ((rc = pmf_ensure_pinned(ctx, (size_t)vecs * kpad * sizeof(T)))) return rc;
+            T *pin = ctx->h_pinned.as<T>();
+            for (int64_t v = 0; v < vecs; ++v) {
+                const double *src = z + (r0 * n_draws + v) * K;
+                T *dst = pin + v * kpad;
+                for (int k = 0; k < K; ++k) dst[k] = (T)src[k];
+                for (int k = K; k < kpad; ++k) dst[k] = (T)0;
+            }
+            PMF_HIP_CHECK(hipMemcpyAsync(z_at.at(base), pin, (size_t)vecs * kpad * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        }
+        if ((rc = pmf_gauss_sample_launch(ctx, side, ids_at.at(base), nr, n_draws, draw0, seed, z ? z_at.at(base) : nullptr,
+                                          out_at.at(base), tri_bytes ? tri_at.at(base) : nullptr)))
+            return rc;
+        if ((rc = pmf_fold_in_download(ctx, PMF_ARR_FACTOR, out_at.at(base), out + r0 * n_draws * K, vecs))) return rc;
+    }
+    return PMF_OK;
+}
+
+extern "C" int pmf_gauss_sample_rows(pmf_ctx *ctx, int side, int64_t n_rows, const int32_t *row_ids, int n_draws, int draw0,
+                                     uint64_t seed, const double *z, double *out) {
+    const char *fn = "pmf_gauss_sample_rows";
+    PMF_SIDE_ENTRY("pmf_gauss_sample_rows");
+    int rc;
+    if ((rc = pmf_sample_check(fn, n_rows, row_ids, n_draws, draw0, out, ctx->rows[side]))) return rc;
+    if (n_rows == 0) return PMF_OK;
+    if ((rc = gauss_require_state(ctx, side, false, fn))) return rc;
+    return pmf_no_throw(fn, [&] {
+        return pmf_with_dtype(ctx, [&](auto t) {
+            return run_sample_rows<decltype(t)>(ctx, side, n_rows, row_ids, n_draws, draw0, seed, z, out);
+        });
+    });
+}

@@ -249,6 +249,9 @@ struct pmf_ctx {
     // the candidates' inverse norms -- and the staged query rows of one round (table, coefficients, gather ids).  Grown on
     // demand, in storage of their own: the scans' outputs and score matrix live in d_scratch.
     PmfBuf d_query_call, d_query_rows;
+    // pmf_topk_sampled (pmf_topk.hip): the draw of every row of the candidate side, [rows x kpad] in the context dtype, and
+    // behind it the sample kernel's packed triangles where they do not fit LDS.  Grown on first use, kept for the next call.
+    PmfBuf d_sample_table;
     PmfBuf h_pinned{PmfBuf::PINNED};
 
     // diagnostic switches, read from the environment once when the context is created
@@ -268,6 +271,7 @@ struct pmf_ctx {
     int64_t stage_bytes = 64ll << 20;   // PMF_STAGE_BYTES=n: bytes of one staging round of pmf_set_array / pmf_get_array, the row exchanges, the fold-ins' downloads and pmf_comm_gather_user_rows, at least one row (tests: many rounds on a few rows; 0 / unset: 64 MiB)
     int64_t window_rows = 0;       // PMF_ELBO_ROWS=n caps the rows of one statistics window (PmfRowWindows) of pmf_gauss_elbo_terms and of the zero-mode factor sweep (tests: many windows on a small problem; 0: by scratch size)
     size_t elbo_lds_bytes = 0;     // dynamic LDS size the ELBO row kernel of this context's K and dtype has been allowed (0: not yet asked)
+    size_t sample_lds_bytes[2] = {0, 0};   // the same for the sample kernels: [0] one draw per pass (and the block-per-row kernel), [1] eight
     int task_chunk = 0;            // PMF_TASK_CHUNK=n (power of two in [32, 512]) fixes the task length of the gamma / Gaussian / bias lists (tests: long tasks on small problems; 0: by nnz)
 
     // multi-GPU (pmf_comm.hip): the communicator (shared between contexts of one process, refcounted)
@@ -393,6 +397,15 @@ void pmf_unpack_rows(const pmf_ctx *ctx, int array, const void *src, double *dst
 // `rows` rows of a device array laid out like `array` of the model state -> host float64, in pinned steps (ends with a
 // stream synchronise)
 int pmf_fold_in_download(pmf_ctx *ctx, int array, const void *dev, double *host, int64_t rows);
+
+// Posterior draws of rows of `side` (pmf_gauss.hip; pmf_gauss_sample_rows documents them), queued on the context's stream
+// and timed under PMF_KERNEL_GAUSS_SOLVE: request q is row d_ids[q] (device; null: row q), its draws d = 0 .. n_draws - 1
+// have draw index draw0 + d and go to d_out[(q * n_draws + d) * kpad ..] in the context dtype, pad columns zero.  d_z
+// (device, laid out like d_out; may be null) replaces the stream.  d_tri: pmf_gauss_sample_tri_bytes(ctx, n) bytes of the
+// caller's for the packed triangles that do not fit LDS (0 bytes: null).  FACTOR and COV of `side` are checked by the caller.
+size_t pmf_gauss_sample_tri_bytes(const pmf_ctx *ctx, int64_t n);
+int pmf_gauss_sample_launch(pmf_ctx *ctx, int side, const int32_t *d_ids, int64_t n, int n_draws, int draw0, uint64_t seed,
+                            const void *d_z, void *d_out, void *d_tri);
 
 // multi-GPU (pmf_comm.hip).  With an attached communicator of more than one rank the ITEM half-sweeps
 // run  accumulate -> all-reduce -> finalize  through pmf_comm_half_sweep.

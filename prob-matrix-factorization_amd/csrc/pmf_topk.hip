@@ -1639,6 +1639,13 @@ __global__ __launch_bounds__(256) void query_gather_kernel(const T *table, const
     }
 }
 
+// coef[q] = coef_table[ids[q]]: the coefficients alone, for a round whose rows are sampled (pmf_topk_sampled)
+template <typename T>
+__global__ __launch_bounds__(256) void query_gather_coef_kernel(const T *coef_table, const int32_t *ids, int n, T *coef) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n) coef[q] = coef_table[ids[q]];
+}
+
 // ids[q] = q: the scan's ids of a staged round
 __global__ __launch_bounds__(256) void query_iota_kernel(int32_t *ids, int n) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1685,6 +1692,11 @@ struct QueryStage {
     const double *factor = nullptr, *coef = nullptr;      // vector mode: host [n_query x K] and [n_query] (null: none)
     bool cosine = false;                                  // the coefficient is the staged row's inverse norm
     const int64_t *d_ex_ptr = nullptr;                    // device [n_query + 1]: the rows' exclusion lists, or null
+    // pmf_topk_sampled (ids mode): the staged rows are not the table's but draw `draw` under `seed` of rows `ids` of this side
+    int sample_side = -1;                                 // -1: no sampling
+    uint64_t seed = 0;
+    int draw = 0;
+    void *d_tri = nullptr;                                // the sample kernel's triangles (pmf_gauss_sample_tri_bytes), or null
 };
 
 // rows [row0, row0 + n) of `st` into ctx->d_query_rows; round->fa / ca / ex_ptr are theirs
@@ -1702,11 +1714,20 @@ static int query_stage_rows(pmf_ctx *ctx, const QueryStage &st, int64_t row0, in
     int32_t *d_ids = ids_at.at(base);
     if (st.ids) {
         PMF_HIP_CHECK(hipMemcpyAsync(d_ids, st.ids + row0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
-        const int64_t pieces = n * (int64_t)(row_bytes / 16);
-        hipLaunchKernelGGL((query_gather_kernel<T>), dim3((unsigned)std::min<int64_t>((pieces + 255) / 256, 1 << 20)), dim3(256), 0,
-                           ctx->stream, static_cast<const T *>(st.table), static_cast<const T *>(st.coef_table), d_ids, (int)n, kpad,
-                           d_rows, d_coef);
+        if (st.sample_side >= 0) {   // the sample kernel writes the rows where the gather would
+            if ((rc = pmf_gauss_sample_launch(ctx, st.sample_side, d_ids, n, 1, st.draw, st.seed, nullptr, d_rows, st.d_tri))) return rc;
+            if (st.coef_table) {
+                PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
+                hipLaunchKernelGGL((query_gather_coef_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                                   static_cast<const T *>(st.coef_table), d_ids, (int)n, d_coef);
+            }
+        } else {
+            PmfProfScope prof(ctx, PMF_KERNEL_TOPK);
+            const int64_t pieces = n * (int64_t)(row_bytes / 16);
+            hipLaunchKernelGGL((query_gather_kernel<T>), dim3((unsigned)std::min<int64_t>((pieces + 255) / 256, 1 << 20)), dim3(256), 0,
+                               ctx->stream, static_cast<const T *>(st.table), static_cast<const T *>(st.coef_table), d_ids, (int)n,
+                               kpad, d_rows, d_coef);
+        }
     } else {
         // the caller's float64 rows -> T, zero-padded to Kpad (the conversion of pmf_set_array_rows), through pinned steps
         const int64_t step = std::max<int64_t>(1, ctx->stage_bytes / (int64_t)row_bytes);
@@ -1899,5 +1920,49 @@ extern "C" int pmf_rank_query(pmf_ctx *ctx, int cand_side, int64_t n_query, int 
         PMF_HIP_CHECK(hipSetDevice(ctx->device));
         if (int rc = pmf_with_dtype(ctx, [&](auto t) { return query_begin<decltype(t)>(ctx, &qc); })) return rc;
         return run_rank(ctx, qc.src, n_query, tgt_ptr, tgt_ids, qc.mode, out_rank, out_candidates);
+    });
+}
+
+// pmf_topk_query in ids mode on ONE joint posterior draw: every row of cand_side is sampled into the context's
+// d_sample_table, which becomes the candidates' table, and every round's query rows are sampled into the staged table
+// (QueryStage::sample_side).  Checks, exclusion lists, rounds and scans are pmf_topk_query's.
+extern "C" int pmf_topk_sampled(pmf_ctx *ctx, int cand_side, int64_t n_query, int query_side, const int32_t *query_ids, int score,
+                                const int64_t *ex_ptr, const int32_t *ex_ids, int k, uint64_t seed, int draw, int32_t *out_ids,
+                                double *out_scores) {
+    const char *fn = "pmf_topk_sampled";
+    PMF_REQUIRE(ctx != nullptr, PMF_EINVAL, "%s: null context", fn);
+    PMF_REQUIRE(n_query >= 0, PMF_EINVAL, "%s: negative n_query", fn);
+    if (n_query == 0) return PMF_OK;
+    return pmf_no_throw(fn, [&] {
+        QueryCall qc;
+        PMF_REQUIRE(out_ids && out_scores, PMF_EINVAL, "%s: null out_ids or out_scores", fn);
+        PMF_REQUIRE(query_ids, PMF_EINVAL, "%s: null query_ids", fn);
+        PMF_REQUIRE(score == 0 || score == PMF_PREDICT_BIAS, PMF_EINVAL,
+                    "%s: score must be 0 or PMF_PREDICT_BIAS (got %d): a draw has no scale, and cosine is no model score", fn, score);
+        PMF_REQUIRE(draw >= 0, PMF_EINVAL, "%s: negative draw %d", fn, draw);
+        if (int rc = query_check(fn, ctx, cand_side, n_query, query_side, query_ids, nullptr, nullptr, score, ex_ptr, ex_ids, &qc))
+            return rc;
+        if (int rc = pmf_require_array(ctx, cand_side, PMF_ARR_COV, fn)) return rc;
+        if (int rc = pmf_require_array(ctx, query_side, PMF_ARR_COV, fn)) return rc;
+        PMF_REQUIRE(k >= 1 && k <= 1024 && k <= qc.src.n_cand, PMF_ERANGE, "%s: k=%d outside [1, min(1024, rows of cand_side)]", fn, k);
+        // (every refusal comes before the first write)
+        PMF_HIP_CHECK(hipSetDevice(ctx->device));
+        const int64_t C = qc.src.n_cand;
+        PmfLayout lay;
+        const auto table_at = lay.add<unsigned char>((size_t)C * ctx->kpad * ctx->elem);
+        const auto tri_at = lay.add<unsigned char>(pmf_gauss_sample_tri_bytes(ctx, std::max(C, n_query)));
+        if (int rc = ctx->d_sample_table.reserve(ctx, lay.bytes(), {ctx->stream})) return rc;
+        void *base = ctx->d_sample_table.as();
+        void *tri = tri_at.offset < lay.bytes() ? tri_at.at(base) : nullptr;
+        if (int rc = pmf_gauss_sample_launch(ctx, cand_side, nullptr, C, 1, draw, seed, nullptr, table_at.at(base), tri)) return rc;
+        qc.src.fb = table_at.at(base);
+        qc.stage.sample_side = query_side;
+        qc.stage.seed = seed;
+        qc.stage.draw = draw;
+        qc.stage.d_tri = tri;
+        return pmf_with_dtype(ctx, [&](auto t) {
+            if (int rc = query_begin<decltype(t)>(ctx, &qc)) return rc;
+            return run_topk<decltype(t)>(ctx, qc.src, n_query, k, qc.mode, out_ids, out_scores);
+        });
     });
 }

@@ -105,6 +105,7 @@ SIGNATURES = {
     "pmf_gauss_fold_in_weighted": (C.c_int, [_p, C.c_int, C.c_int64, _i64p, _i32p, _f64p, _f64p, C.c_double, C.c_double,
                                              C.c_double, C.c_int, _f64p, _f64p, _f64p]),
     "pmf_gauss_elbo_terms": (C.c_int, [_p, C.c_int, C.c_int, _f64p, _f64p]),
+    "pmf_gauss_sample_rows": (C.c_int, [_p, C.c_int, C.c_int64, _i32p, C.c_int, C.c_int, C.c_uint64, _f64p, _f64p]),
     "pmf_ctx_set_gauss_zeros": (C.c_int, [_p, C.c_int, C.c_double]),
     "pmf_ctx_get_gauss_zeros": (C.c_int, [_p, C.POINTER(C.c_int), _f64p]),
     "pmf_gauss_gram": (C.c_int, [_p, C.c_int, _f64p]),
@@ -124,6 +125,8 @@ SIGNATURES = {
     "pmf_topk_query": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, _i32p, _f64p, _f64p, C.c_int, _i64p, _i32p, C.c_int, _i32p, _f64p]),
     "pmf_rank_query": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, _i32p, _f64p, _f64p, C.c_int, _i64p, _i32p, _i64p, _i32p, _i64p,
                                  _i64p]),
+    "pmf_topk_sampled": (C.c_int, [_p, C.c_int, C.c_int64, C.c_int, _i32p, C.c_int, _i64p, _i32p, C.c_int, C.c_uint64, C.c_int, _i32p,
+                         _f64p]),
     "pmf_prof_enable": (C.c_int, [_p, C.c_int]),
     "pmf_prof_reset": (C.c_int, [_p]),
     "pmf_prof_get": (C.c_int, [_p, C.c_int, _f64p, _i64p]),

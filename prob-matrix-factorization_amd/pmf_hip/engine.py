@@ -458,6 +458,23 @@ class Context:
                                              ptr(rows, C.c_double) if per_row else None), "pmf_gauss_elbo_terms")
         return (totals, rows) if per_row else totals
 
+    def gauss_sample_rows(self, side, rows, n_draws=1, draw0=0, seed=0, z=None):
+        """Posterior draws x = FACTOR[r] + chol(COV[r]) z of the given rows of `side` (`pmf_gauss_sample_rows`): float64
+        [len(rows), n_draws, K].  Draw d has draw index `draw0` + d of the counter-based stream under `seed` (any integer
+        in [0, 2^64)); the normals are a function of (seed, side, row id, draw index, k) alone.  `z` [len(rows), n_draws,
+        K] replaces the stream.  Rows may repeat.  Biases are not sampled.  The context is only read."""
+        r = as_i32(np.asarray(rows).reshape(-1), "rows")
+        n_draws = int(n_draws)
+        zz = None
+        if z is not None:
+            zz = as_f64(z)
+            if zz.shape != (len(r), n_draws, self.K):
+                raise ValueError(f"z: expected shape {(len(r), n_draws, self.K)}, got {zz.shape}")
+        out = np.empty((len(r), max(n_draws, 0), self.K), dtype=np.float64)
+        check(self._lib.pmf_gauss_sample_rows(self._h, side, len(r), ptr(r, C.c_int32), n_draws, int(draw0), C.c_uint64(int(seed)),
+                                              opt_ptr(zz), ptr(out, C.c_double)), "pmf_gauss_sample_rows")
+        return out
+
     # ---- bias-free Gaussian model with unlisted cells counted as weighted zeros (implicit feedback) ----
     def set_gauss_zeros(self, observed, weight=1.0):
         """`observed=True`: `gauss_factor_sweep`, `gauss_fold_in` and `gauss_elbo_terms(with_data=True)` of this context
@@ -669,6 +686,18 @@ class Context:
         out_scores = np.empty((n, k), dtype=np.float64)
         check(self._lib.pmf_topk_query(self._h, *query, int(score), *ex, int(k), ptr(out_ids, C.c_int32),
                                        ptr(out_scores, C.c_double)), "pmf_topk_query")
+        return out_ids, out_scores
+
+    def topk_sampled(self, cand_side, k, ids, *, query_side=None, score=0, exclude=None, seed=0, draw=0):
+        """`topk_query` in ids mode scored on one joint posterior draw of the Gaussian factors (`pmf_topk_sampled`): every
+        row of `cand_side` and the query rows `ids` of `query_side` are replaced by their draw with index `draw` under
+        `seed` -- row (side, id) by `gauss_sample_rows(side, [id], 1, draw, seed)` to the bit -- and biases stay at their
+        means.  `score`: 0 or PREDICT_BIAS.  Returns (ids int32 [n, k], scores float64 [n, k])."""
+        n, query, ex, keep = self._query_args(cand_side, ids, query_side, None, None, exclude)
+        out_ids = np.empty((n, k), dtype=np.int32)
+        out_scores = np.empty((n, k), dtype=np.float64)
+        check(self._lib.pmf_topk_sampled(self._h, *query[:4], int(score), *ex, int(k), C.c_uint64(int(seed)), int(draw),
+                                         ptr(out_ids, C.c_int32), ptr(out_scores, C.c_double)), "pmf_topk_sampled")
         return out_ids, out_scores
 
     def rank_query(self, cand_side, targets, *, ids=None, query_side=None, factor=None, coef=None, score=0, exclude=None):

@@ -198,6 +198,8 @@ class DeviceModel:
             self._ctx.set_ratings(u, i, x)
         else:                                   # (refused with comm= before this point)
             self._ctx.set_ratings(u, i, x, weights)
+        # the training pairs as given (no copy): `top_k_items(sample_seed=.., exclude_train=True)` builds its lists from them
+        self._train_pairs = (u, i) if self._comm is None else None
         import time
         self._t_last = time.perf_counter()
         for key in ("val_rmse", "val_macro_mae", "seconds"):
@@ -337,11 +339,66 @@ class DeviceModel:
             raise NotImplementedError("after a sharded fit the full-size context holds the factors but no training ratings: "
                                       "exclude_train=True is not available, pass exclude_train=False")
 
-    def top_k_items(self, user_ids, k=10, exclude_train=False):
+    def _sample_ctx(self, what):
+        """The context posterior draws come from; only the Gaussian CAVI classes have one."""
+        raise NotImplementedError(f"{type(self).__name__} keeps no Gaussian posterior covariances: {what} is defined for the "
+                                  "Gaussian CAVI models only")
+
+    def sample_factors(self, side, ids, n_draws=1, seed=0, draw0=0):
+        """Extension (no reference counterpart): draws from the fitted posterior of factor rows, x = m + chol(V) z --
+        float64 [len(ids), n_draws, K] for the rows `ids` of `side` ("user" or "item").  Draw d has draw index `draw0` + d
+        of a counter-based stream: the normals are a function of (seed, side, row id, draw index, k) alone, so a row's
+        draw does not depend on the other rows asked for, on the batch or on the dtype (`pmf_gauss_sample_rows`).
+        Biases are not sampled.  Percentiles of any function of the draws are its credible intervals."""
+        if side not in ("user", "item"):
+            raise ValueError(f"side must be 'user' or 'item', got {side!r}")
+        ctx = self._sample_ctx("sample_factors")
+        return ctx.gauss_sample_rows(USER if side == "user" else ITEM, np.asarray(ids, dtype=int).reshape(-1), int(n_draws),
+                                     int(draw0), int(seed))
+
+    def predict_draws(self, user_ids, item_ids, n_draws, seed=0, global_mean=0.0):
+        """Extension: [n, n_draws] float64 draws of `predict`'s score for the pairs -- theta_u . beta_i under draw d of both
+        rows, plus the mean biases and `global_mean`.  The distinct users and items are sampled once (`sample_factors`)
+        and the dots are formed on the host, so pairs that share a row share its draw."""
+        ctx = self._sample_ctx("predict_draws")
+        u, i = np.asarray(user_ids, dtype=int).reshape(-1), np.asarray(item_ids, dtype=int).reshape(-1)
+        if len(u) != len(i):
+            raise ValueError("user_ids and item_ids must have the same length")
+        uu, ui = np.unique(u, return_inverse=True)
+        ii, iv = np.unique(i, return_inverse=True)
+        theta = self.sample_factors("user", uu, n_draws, seed)
+        beta = self.sample_factors("item", ii, n_draws, seed)
+        out = np.einsum("ndk,ndk->nd", theta[ui], beta[iv]) + global_mean
+        if self._uses_bias == pmf_hip.PREDICT_BIAS:
+            out += (ctx.get_array_rows(USER, pmf_hip.ARR_BIAS, uu)[ui] + ctx.get_array_rows(ITEM, pmf_hip.ARR_BIAS, ii)[iv])[:, None]
+        return out
+
+    def _train_exclusion(self, users):
+        """(row_ptr, item ids): the training items of every entry of `users`, as `topk_query`'s exclusion lists"""
+        if getattr(self, "_train_pairs", None) is None:
+            raise NotImplementedError("exclude_train=True with sample_seed needs the training pairs of a single-process fit")
+        u, i = (np.asarray(a).reshape(-1) for a in self._train_pairs)
+        uq, inv = np.unique(users, return_inverse=True)
+        sel = np.isin(u, uq)
+        ptr, order = pmf_hip.engine.group_rows(np.searchsorted(uq, u[sel]), len(uq))
+        items = i[sel][order]
+        ex_ptr = np.concatenate([[0], np.cumsum(np.diff(ptr)[inv])]).astype(np.int64)
+        ex_ids = np.concatenate([items[ptr[r]:ptr[r + 1]] for r in inv]) if len(inv) else np.zeros(0, dtype=np.int64)
+        return ex_ptr, ex_ids
+
+    def top_k_items(self, user_ids, k=10, exclude_train=False, sample_seed=None, draw=0):
         """Extension (no reference counterpart): the k highest-scoring items per
         user under `predict`'s score, ties to the lower item id.  Returns
         (items [n, k] int32, scores [n, k] float64).  `exclude_train`: the items of the user's training ratings are
-        left out, as a recommender would (the list `evaluate_ranking` measures); -1 / 0.0 where fewer than k remain."""
+        left out, as a recommender would (the list `evaluate_ranking` measures); -1 / 0.0 where fewer than k remain.
+        `sample_seed` (an integer; Gaussian CAVI models): Thompson sampling -- the scores are those of ONE joint posterior
+        draw, index `draw` under that seed, of the users and of every item (`pmf_topk_sampled`; biases at their means), so
+        repeated calls with new `draw`s explore where the posterior is wide.  None: the posterior means."""
+        if sample_seed is not None:
+            ctx = self._sample_ctx("top_k_items with sample_seed")
+            q = np.asarray(user_ids, dtype=int).reshape(-1)
+            return ctx.topk_sampled(ITEM, int(k), q, query_side=USER, score=int(self._uses_bias),
+                                    exclude=self._train_exclusion(q) if exclude_train else None, seed=int(sample_seed), draw=int(draw))
         ctx = self._need_ctx()
         if exclude_train:
             self._need_train_ratings()

@@ -328,6 +328,12 @@ class GaussianHost(DeviceModel):
                                       "(they stay on the ranks' shard contexts)")
         return ctx
 
+    def _sample_ctx(self, what):
+        """Posterior draws read FACTOR and COV of all rows of both sides: a single-process fit of a CAVI class."""
+        if self._comm is not None:
+            raise NotImplementedError(f"{what} with comm=: the user covariances stay sharded over the ranks")
+        return self._cov_ctx(what)
+
     def predict_variance(self, user_ids, item_ids, include_noise=True):
         """Var[theta_u . beta_i] = m_u' V_i m_u + m_i' V_u m_i + tr(V_u V_i) under the fitted q (float64; the biases
         are point values; 0 for ids outside the trained dimensions, which `predict` treats as the point 0), plus
