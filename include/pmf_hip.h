@@ -377,6 +377,7 @@ int pmf_gamma_exact_accumulate(pmf_ctx *ctx, int side, void *stats_dev);
  *   pmf_gamma_exact_sweep  the same, C from the E half of the other side's freshly built table
  *   pmf_gamma_fold_in      B = C of the opposite side's FACTOR for every row (a new row's unlisted cells are zeros), formed
  *                          once per call; the recursion, the long-row kernel and the warm start as before
+ *   pmf_gamma_fold_in_exact  the same, C from the E half of the opposite side's freshly built table
  *   pmf_gamma_elbo_terms   PMF_GAMMA_ELBO_DATA of row r = sum_j x_j lse_j - sum_k E_rk C_k, C from the other side's E table:
  *                          sum over all cells of E_u . E_i = (sum_u E_u) . (sum_i E_i).  LOGFACT as before (lgamma(0 + 1) = 0).
  *                          DATA - LOGFACT from either side still gives the same total.
@@ -412,6 +413,54 @@ int pmf_ctx_get_gamma_zeros(pmf_ctx *ctx, int *mode);
  * PMF_EINVAL, with the missing thing named: null context, bad side, null out, FACTOR (from_q == 0) or SHAPE / RATE
  * (from_q != 0) of `side` not set.  Cost: DESIGN.md section 4.16. */
 int pmf_gamma_column_sums(pmf_ctx *ctx, int side, int from_q, double *out /* [K] */);
+
+/* Exact fold-in: pmf_gamma_fold_in with the update of pmf_gamma_exact_sweep -- coordinate ascent on the bound of
+ * pmf_gamma_elbo_terms for NEW rows of `side`, the opposite side frozen as q = Gamma(SHAPE_o, RATE_o).  No reference
+ * counterpart.  A model fitted with pmf_gamma_exact_sweep serves new and refreshed rows from the objective it was
+ * fitted under: a folded row's bound cannot fall from one pass to the next, except by rounding, and a warm-started
+ * refresh of a fitted row starts at the fit's own fixed point.  The batch, the prior arguments and the outputs are
+ * pmf_gamma_fold_in's.  With L_o = psi(SHAPE_o) - log RATE_o and E_o = SHAPE_o / RATE_o of the opposite side (its
+ * (E log, E) table, as pmf_gamma_exact_sweep builds it: psi in double, rounded once to the context's dtype; FACTOR is
+ * not read), for a row with ratings (o_j, x_j), j = 1 .. n (n may be 0):
+ *     rho^0 = init_prior_rate[r], else hyper_shape / hyper_rate_prior          (hierarchical)
+ *     rho^t = rate_prior for every t                                           (not hierarchical)
+ *     s^0   = init_shape[r], else shape_prior in every element
+ *     r^0   = init_rate[r], else rho^0 in every element
+ *     B     = sum_j E_{o_j}                                                    (formed once per call)
+ *     for t = 1 .. n_iter:
+ *         l_k    = psi(s_k^(t-1)) - log r_k^(t-1)
+ *         phi_jk = exp(l_k + L_{o_j k} - lse_j),   lse_j = log sum_k exp(l_k + L_{o_j k})       (max-subtracted)
+ *         s_k^t  = shape_prior + sum_j x_j phi_jk,    r_k^t = rho^(t-1) + B_k,    theta^t = s^t / r^t
+ *         hierarchical:  h^t = hyper_rate_prior + sum_k theta_k^t,   rho^t = hyper_shape / h^t
+ *     out_factor[r] = theta^n_iter, out_shape[r] = s^n_iter, out_rate[r] = r^n_iter,
+ *     out_prior_rate[r] = rho^n_iter, out_hyper_rate[r] = h^n_iter     (the last two: hierarchical only, else not written)
+ * Under PMF_ZEROS_OBSERVED B of every row is C of the opposite side as pmf_gamma_column_sums(other, from_q = 1) defines
+ * it (a zero adds nothing to a shape sum).  A row without ratings runs the same statements on empty sums.  `init_shape`
+ * and `init_rate` are given together or not at all; with them and `init_prior_rate` the call is a warm start.  One pass
+ * from a context's own SHAPE / RATE / PRIOR_RATE on its own ratings is pmf_gamma_exact_sweep(side).
+ * One kernel launch covers all n_iter passes of a row block: s, r, B, rho and h stay in registers from the first pass to
+ * the last; between passes psi and log of the row's own s and r are evaluated in double and l is rounded once to the
+ * context's dtype; B is summed in the first pass only and nothing is written before the end.  The weights come from a
+ * log-sum-exp, never from a product of exp(E log) tables.  A lane group owns a row; a row with more than
+ * PMF_GAMMA_FOLD_LONG ratings gets a whole block whose groups' partial sums are added in group order.  No atomics: two
+ * calls give the same bits, whatever the row blocks are (PMF_FOLD_IN_ROWS).  Launches are timed as for
+ * pmf_gamma_fold_in, the table and the column sums as PMF_KERNEL_GAMMA_FINAL.
+ * Reads the context's model state only (the table is rebuilt, once per call, into the context-owned storage of
+ * pmf_gamma_exact_sweep: pmf_ctx_device_bytes may grow on the first call and does not grow after it); never a
+ * collective, with or without a communicator.  Not covered: the extended Poisson model -- a context with SCALE arrays is
+ * PMF_EINVAL.
+ * PMF_EINVAL and PMF_ERANGE exactly as for pmf_gamma_fold_in, with SHAPE and RATE of the opposite side (named) in the
+ * place of its FACTOR, which is not needed; one more PMF_EINVAL: one of `init_shape` / `init_rate` without the other.
+ * An argument error writes no output buffer; n_rows = 0 touches nothing.  Cost: DESIGN.md section 4.20. */
+int pmf_gamma_fold_in_exact(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
+                            const double *ratings, double shape_prior, double rate_prior, int hierarchical,
+                            double hyper_shape, double hyper_rate_prior, int n_iter,
+                            const double *init_shape /* n_rows x K, may be NULL */,
+                            const double *init_rate /* n_rows x K, with init_shape or not at all */,
+                            const double *init_prior_rate /* n_rows, may be NULL; hierarchical only */,
+                            double *out_factor /* n_rows x K */, double *out_shape /* n_rows x K, may be NULL */,
+                            double *out_rate /* n_rows x K, may be NULL */, double *out_prior_rate /* n_rows, may be NULL */,
+                            double *out_hyper_rate /* n_rows, may be NULL */);
 
 /* Posterior predictive of the Poisson MF and HPF models for n (user, item) pairs: mean and variance of the rate under
  * q and, with ratings, three log densities of the count.  No reference counterpart beyond PLUGIN (the reference's

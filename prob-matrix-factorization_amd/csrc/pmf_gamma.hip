@@ -401,6 +401,14 @@ struct GammaFoldParams {
     int hierarchical, n_iter, K, kpad;
 };
 
+// pmf_gamma_fold_in_exact (gamma_fold_exact_kernel, with the exact update's code below): the same batch against the
+// opposite side's (E log, E) table; factor_other, init_factor and the floor are not used
+template <typename T>
+struct GammaFoldExactParams : GammaFoldParams<T> {
+    const T *table_other;            // [rows of the other side][2][kpad]: E log (pad elements -inf), then E (pad elements 0)
+    const T *init_shape, *init_rate; // [rows][kpad] (zero pad elements), both or neither: shape_prior / rho in every element
+};
+
 // what a lane keeps of its row between the passes
 template <typename T>
 struct GammaFoldRow {
@@ -855,7 +863,17 @@ struct GammaFoldBatch {
     int n_iter;
     const double *init_factor, *init_prior_rate;
     double *out_factor, *out_shape, *out_rate, *out_prior_rate, *out_hyper_rate;
+    bool exact = false;                  // pmf_gamma_fold_in_exact: `init_factor` holds init_shape
+    const double *init_rate = nullptr;   // [n_rows][K] with init_shape, exact only
 };
+
+// the exact recursion's two steps of the shared host path (defined with its kernel, below the exact half-sweep):
+// the opposite side's freshly built (E log, E) table and, in zero mode, the column sums of its E half
+template <typename T>
+static int gamma_fold_exact_other(pmf_ctx *ctx, int side, const T **table, const T **colsum);
+// one launch of each variant at most, timed as the reference fold-in's
+template <typename T>
+static void launch_gamma_fold_exact(pmf_ctx *ctx, GammaFoldExactParams<T> &p, const int32_t *list, int64_t n_short, int64_t n_long);
 
 // The batch in row blocks of at most PMF_FOLD_IN_BLOCK_NNZ staged ratings (a longer single row still goes), ctx->fold_in_rows
 // rows and kGammaFoldRowBytes per row buffer.  Per block: stage offsets, ids, ratings and start values in the context
@@ -870,15 +888,25 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
     const int64_t max_rows = std::min(by_bytes, ctx->fold_in_rows > 0 ? ctx->fold_in_rows : (int64_t)INT32_MAX);
     const bool hier = a.pr.hierarchical != 0;
     PmfFoldStage<T> st;
-    PmfBuf d_list, d_init, d_init_rate, d_factor, d_shape, d_rate, d_prior_rate, d_hyper_rate;
+    PmfBuf d_list, d_init, d_init_b, d_init_rate, d_factor, d_shape, d_rate, d_prior_rate, d_hyper_rate;
     std::vector<int32_t> list;   // the short rows, then the long rows
-    std::vector<T> init, init_rate;
+    std::vector<T> init, init_b, init_rate;
     int rc;
-    // unlisted cells as zeros: B of every row is the column sum of the other side's FACTOR, formed once per call
-    const T *colsum = nullptr;
-    if (gamma_zeros_observed(ctx) &&
-        (rc = gamma_colsum_scratch<T>(ctx, ctx->arr[1 - side][PMF_ARR_FACTOR].as<const T>(), ctx->rows[1 - side], kpad, nullptr, &colsum)))
+    // unlisted cells as zeros: B of every row is the column sum of the other side's FACTOR (exact: of the E half of its
+    // table, which is built here, once per call), formed once per call
+    const T *colsum = nullptr, *table_other = nullptr;
+    if (a.exact) {
+        if ((rc = gamma_fold_exact_other<T>(ctx, side, &table_other, &colsum))) return rc;
+    } else if (gamma_zeros_observed(ctx) &&
+               (rc = gamma_colsum_scratch<T>(ctx, ctx->arr[1 - side][PMF_ARR_FACTOR].as<const T>(), ctx->rows[1 - side], kpad, nullptr, &colsum))) {
         return rc;
+    }
+    // start values of a row block in the context dtype, pad elements 0
+    const auto stage_rows = [&](const double *src, int64_t r0, int64_t B, std::vector<T> &dst) {
+        dst.assign((size_t)B * kpad, (T)0);
+        for (int64_t r = 0; r < B; ++r)
+            for (int k = 0; k < K; ++k) dst[(size_t)(r * kpad + k)] = (T)src[(r0 + r) * K + k];
+    };
     for (int64_t r0 = 0; r0 < a.n_rows; r0 = st.r1) {
         // (the previous block ended with a stream synchronise: nothing queued still reads the block's buffers)
         if ((rc = st.stage(ctx, a.n_rows, a.row_ptr, a.ratings, r0, max_rows))) return rc;
@@ -893,11 +921,8 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
         if (!std::is_sorted(list.begin(), list.end(), longer)) std::stable_sort(list.begin(), list.end(), longer);
         for (int64_t r = 0; r < B; ++r)
             if (ptr[(size_t)r + 1] - ptr[(size_t)r] > long_row) list.push_back((int32_t)r);
-        if (a.init_factor) {
-            init.assign((size_t)B * kpad, (T)0);
-            for (int64_t r = 0; r < B; ++r)
-                for (int k = 0; k < K; ++k) init[(size_t)(r * kpad + k)] = (T)a.init_factor[(r0 + r) * K + k];
-        }
+        if (a.init_factor) stage_rows(a.init_factor, r0, B, init);
+        if (a.init_rate) stage_rows(a.init_rate, r0, B, init_b);
         if (hier && a.init_prior_rate) {
             init_rate.resize((size_t)B);
             for (int64_t r = 0; r < B; ++r) init_rate[(size_t)r] = (T)a.init_prior_rate[r0 + r];
@@ -908,6 +933,7 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
         if ((rc = d_shape.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
         if ((rc = d_rate.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
         if (a.init_factor && (rc = d_init.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
+        if (a.init_rate && (rc = d_init_b.reserve(ctx, row_bytes, {ctx->stream}))) return rc;
         if (hier) {
             if ((rc = d_prior_rate.reserve(ctx, (size_t)B * sizeof(T), {ctx->stream}))) return rc;
             if ((rc = d_hyper_rate.reserve(ctx, (size_t)B * sizeof(T), {ctx->stream}))) return rc;
@@ -916,14 +942,18 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
         if ((rc = st.upload(a.other_ids))) return rc;
         PMF_HIP_CHECK(hipMemcpy(d_list.as(), list.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice));
         if (a.init_factor) PMF_HIP_CHECK(hipMemcpy(d_init.as(), init.data(), row_bytes, hipMemcpyHostToDevice));
+        if (a.init_rate) PMF_HIP_CHECK(hipMemcpy(d_init_b.as(), init_b.data(), row_bytes, hipMemcpyHostToDevice));
         if (hier && a.init_prior_rate)
             PMF_HIP_CHECK(hipMemcpy(d_init_rate.as(), init_rate.data(), (size_t)B * sizeof(T), hipMemcpyHostToDevice));
-        GammaFoldParams<T> p;
+        GammaFoldExactParams<T> p;   // (the reference recursion's launches take its GammaFoldParams part)
         p.ptr = st.d_ptr.template as<const int64_t>();
         p.other = st.d_other.template as<const int32_t>();
         p.val = st.d_val.template as<const T>();
-        p.factor_other = ctx->arr[1 - side][PMF_ARR_FACTOR].as<const T>();
-        p.init_factor = a.init_factor ? d_init.as<const T>() : nullptr;
+        p.factor_other = a.exact ? nullptr : ctx->arr[1 - side][PMF_ARR_FACTOR].as<const T>();
+        p.init_factor = a.init_factor && !a.exact ? d_init.as<const T>() : nullptr;
+        p.table_other = table_other;
+        p.init_shape = a.init_factor && a.exact ? d_init.as<const T>() : nullptr;
+        p.init_rate = a.init_rate ? d_init_b.as<const T>() : nullptr;
         p.init_prior_rate = hier && a.init_prior_rate ? d_init_rate.as<const T>() : nullptr;
         p.colsum = colsum;
         p.factor = d_factor.as<T>();
@@ -939,20 +969,22 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
         p.n_iter = a.n_iter;
         p.K = K;
         p.kpad = kpad;
-        pmf_with_pow2<1>(lpr, [&](auto L) {
+        if (a.exact) launch_gamma_fold_exact<T>(ctx, p, d_list.as<const int32_t>(), n_short, n_long);
+        else pmf_with_pow2<1>(lpr, [&](auto L) {
             constexpr int G = 256 / L;
+            GammaFoldParams<T> &q = p;
             if (n_short > 0) {
                 PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
-                p.rows = d_list.as<const int32_t>();
-                p.n = n_short;
-                hipLaunchKernelGGL((gamma_fold_kernel<T, L, false>), dim3((unsigned)((n_short + G - 1) / G)), dim3(256), 0, ctx->stream, p);
+                q.rows = d_list.as<const int32_t>();
+                q.n = n_short;
+                hipLaunchKernelGGL((gamma_fold_kernel<T, L, false>), dim3((unsigned)((n_short + G - 1) / G)), dim3(256), 0, ctx->stream, q);
             }
             if (n_long > 0) {
                 PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
-                p.rows = d_list.as<const int32_t>() + n_short;
-                p.n = n_long;
+                q.rows = d_list.as<const int32_t>() + n_short;
+                q.n = n_long;
                 hipLaunchKernelGGL((gamma_fold_kernel<T, L, true>), dim3((unsigned)n_long), dim3(256), (size_t)G * 2 * kpad * sizeof(T),
-                                   ctx->stream, p);
+                                   ctx->stream, q);
             }
         });
         PMF_HIP_CHECK(hipGetLastError());
@@ -966,33 +998,60 @@ static int run_gamma_fold_in(pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
     return PMF_OK;
 }
 
+// What the two fold-in entry points share after PMF_SIDE_ENTRY: the argument checks (`fn` names the caller in every
+// message; `exact`: SHAPE and RATE of the opposite side in place of its FACTOR, init_shape / init_rate together, no
+// SCALE arrays) and the run.
+static int gamma_fold_in_call(const char *fn, pmf_ctx *ctx, int side, const GammaFoldBatch &a) {
+    PMF_REQUIRE(a.n_rows >= 0, PMF_EINVAL, "%s: negative row count", fn);
+    if (a.n_rows == 0) return PMF_OK;
+    PMF_REQUIRE(a.row_ptr && a.out_factor, PMF_EINVAL, "%s: null argument", fn);
+    int rc;
+    if ((rc = pmf_check_offsets(fn, "row_ptr", a.row_ptr, a.n_rows))) return rc;
+    const int64_t nnz = a.row_ptr[a.n_rows];
+    PMF_REQUIRE(nnz == 0 || (a.other_ids && a.ratings), PMF_EINVAL, "%s: null argument", fn);
+    PMF_REQUIRE(a.pr.shape > 0, PMF_EINVAL, "%s: shape_prior must be positive", fn);
+    if (a.pr.hierarchical)
+        PMF_REQUIRE(a.pr.hyper_shape > 0 && a.pr.hyper_rate > 0, PMF_EINVAL, "%s: hyper_shape and hyper_rate_prior must be positive", fn);
+    else
+        PMF_REQUIRE(a.pr.rate > 0, PMF_EINVAL, "%s: rate_prior must be positive", fn);
+    PMF_REQUIRE(a.n_iter >= 1, PMF_EINVAL, "%s: n_iter = %d, must be at least 1", fn, a.n_iter);
+    const int other = 1 - side;
+    if (a.exact) {
+        PMF_REQUIRE((a.init_factor != nullptr) == (a.init_rate != nullptr), PMF_EINVAL,
+                    "%s: init_shape and init_rate are given together or not at all", fn);
+        PMF_REQUIRE(!ctx->arr[0][PMF_ARR_SCALE] && !ctx->arr[1][PMF_ARR_SCALE], PMF_EINVAL,
+                    "%s: the extended Poisson model (a context with SCALE arrays) is not covered", fn);
+        if ((rc = require_gamma_q(ctx, {other}, fn))) return rc;
+    } else if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, fn))) {
+        return rc;
+    }
+    if ((rc = pmf_check_ids(a.other_ids, nnz, ctx->rows[other], fn, "id"))) return rc;
+    return pmf_no_throw(fn, [&] {
+        return pmf_with_dtype(ctx, [&](auto t) { return run_gamma_fold_in<decltype(t)>(ctx, side, a); });
+    });
+}
+
 extern "C" int pmf_gamma_fold_in(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
                                  const double *ratings, double shape_prior, double rate_prior, int hierarchical,
                                  double hyper_shape, double hyper_rate_prior, int n_iter, const double *init_factor,
                                  const double *init_prior_rate, double *out_factor, double *out_shape, double *out_rate,
                                  double *out_prior_rate, double *out_hyper_rate) {
     PMF_SIDE_ENTRY("pmf_gamma_fold_in");
-    PMF_REQUIRE(n_rows >= 0, PMF_EINVAL, "pmf_gamma_fold_in: negative row count");
-    if (n_rows == 0) return PMF_OK;
-    PMF_REQUIRE(row_ptr && out_factor, PMF_EINVAL, "pmf_gamma_fold_in: null argument");
-    int rc;
-    if ((rc = pmf_check_offsets("pmf_gamma_fold_in", "row_ptr", row_ptr, n_rows))) return rc;
-    const int64_t nnz = row_ptr[n_rows];
-    PMF_REQUIRE(nnz == 0 || (other_ids && ratings), PMF_EINVAL, "pmf_gamma_fold_in: null argument");
-    PMF_REQUIRE(shape_prior > 0, PMF_EINVAL, "pmf_gamma_fold_in: shape_prior must be positive");
-    if (hierarchical)
-        PMF_REQUIRE(hyper_shape > 0 && hyper_rate_prior > 0, PMF_EINVAL, "pmf_gamma_fold_in: hyper_shape and hyper_rate_prior must be positive");
-    else
-        PMF_REQUIRE(rate_prior > 0, PMF_EINVAL, "pmf_gamma_fold_in: rate_prior must be positive");
-    PMF_REQUIRE(n_iter >= 1, PMF_EINVAL, "pmf_gamma_fold_in: n_iter = %d, must be at least 1", n_iter);
-    const int other = 1 - side;
-    if ((rc = pmf_require_array(ctx, other, PMF_ARR_FACTOR, "pmf_gamma_fold_in"))) return rc;
-    if ((rc = pmf_check_ids(other_ids, nnz, ctx->rows[other], "pmf_gamma_fold_in", "id"))) return rc;
-    const GammaFoldBatch a = {n_rows, row_ptr, other_ids, ratings, {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior},
-                              n_iter, init_factor, init_prior_rate, out_factor, out_shape, out_rate, out_prior_rate, out_hyper_rate};
-    return pmf_no_throw("pmf_gamma_fold_in", [&] {
-        return pmf_with_dtype(ctx, [&](auto t) { return run_gamma_fold_in<decltype(t)>(ctx, side, a); });
-    });
+    return gamma_fold_in_call("pmf_gamma_fold_in", ctx, side,
+                              {n_rows, row_ptr, other_ids, ratings, {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior},
+                               n_iter, init_factor, init_prior_rate, out_factor, out_shape, out_rate, out_prior_rate, out_hyper_rate});
+}
+
+extern "C" int pmf_gamma_fold_in_exact(pmf_ctx *ctx, int side, int64_t n_rows, const int64_t *row_ptr, const int32_t *other_ids,
+                                       const double *ratings, double shape_prior, double rate_prior, int hierarchical,
+                                       double hyper_shape, double hyper_rate_prior, int n_iter, const double *init_shape,
+                                       const double *init_rate, const double *init_prior_rate, double *out_factor,
+                                       double *out_shape, double *out_rate, double *out_prior_rate, double *out_hyper_rate) {
+    PMF_SIDE_ENTRY("pmf_gamma_fold_in_exact");
+    return gamma_fold_in_call("pmf_gamma_fold_in_exact", ctx, side,
+                              {n_rows, row_ptr, other_ids, ratings, {shape_prior, rate_prior, hierarchical, hyper_shape, hyper_rate_prior},
+                               n_iter, init_shape, init_prior_rate, out_factor, out_shape, out_rate, out_prior_rate, out_hyper_rate,
+                               true, init_rate});
 }
 
 // ---------------------------------------------------------------------------
@@ -1563,6 +1622,247 @@ extern "C" int pmf_gamma_column_sums(pmf_ctx *ctx, int side, int from_q, double 
         PMF_HIP_CHECK(hipMemcpyAsync(out, sum, (size_t)ctx->K * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return PMF_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------
+// exact fold-in (pmf_gamma_fold_in_exact): the n_iter passes of coordinate ascent on the bound for NEW rows
+// ---------------------------------------------------------------------------
+// gamma_fold_kernel's access shape (a lane group owns a row for the whole call, lane c owns elements 4c .. 4c+3, ids and
+// ratings handed out by __shfl, UN gathers in flight, LONG = true: a block per row, group partials added through LDS in
+// group order) around gamma_exact_kernel's inner loop (the other row's (E log, E) pair gathered from one 2 kpad block;
+// per rating a DPP max, one exp per element, a DPP sum, w = x / z; pads are -inf / 0).  What is new lies between the
+// passes: the row's own E log = psi(s) - log r is re-formed in registers from the s and r the pass before left there --
+// psi and log in double (gamma_digamma, the statement of gamma_elbo_row_kernel), rounded once to T -- so s, r, B, rho and
+// h never leave the lanes, the E half is gathered in the first pass only (B is summed there), and nothing is written
+// before the end.  No atomics.
+
+// psi(a) - log(b) in double: the statement of gamma_elbo_row_kernel.  Not inlined: four copies of the shift loop and the
+// two logarithms per pass keep enough masks and constants alive across the rating loop to spill SGPRs.
+__device__ __noinline__ double gamma_fold_exact_elog1(double a, double b) {
+    const double lb = log(b), psi = gamma_digamma(a);
+    return psi - lb;
+}
+
+// e_k = exp(s_k - m) of the lane's four elements.  The double form is not inlined, as gamma_pred_exp_sum's is not: four
+// inlined double exponentials per gathered row in flight cost the fp64 kernels SGPR spills.
+__device__ __forceinline__ Vec4<float> gamma_fold_exact_exp(float s0, float s1, float s2, float s3, float m) {
+    Vec4<float> ex;
+    ex.v[0] = exp(s0 - m); ex.v[1] = exp(s1 - m); ex.v[2] = exp(s2 - m); ex.v[3] = exp(s3 - m);
+    return ex;
+}
+__device__ __noinline__ Vec4<double> gamma_fold_exact_exp(double s0, double s1, double s2, double s3, double m) {
+    Vec4<double> ex;
+    ex.v[0] = exp(s0 - m); ex.v[1] = exp(s1 - m); ex.v[2] = exp(s2 - m); ex.v[3] = exp(s3 - m);
+    return ex;
+}
+
+// l = psi(shape) - log(rate) of the lane's four elements; a pad (and every element of a lane past kpad) is -inf
+template <typename T>
+__device__ __forceinline__ Vec4<T> gamma_fold_exact_elog(const GammaFoldParams<T> &p, int c, bool active, const Vec4<T> &shape,
+                                                         const Vec4<T> &rate) {
+    const int koff = c * PMF_VEC;
+    Vec4<T> l;
+#pragma unroll
+    for (int e = 0; e < PMF_VEC; ++e) {
+        l.v[e] = (T)(-INFINITY);
+        if (active && koff + e < p.K) l.v[e] = (T)gamma_fold_exact_elog1((double)shape.v[e], (double)rate.v[e]);
+    }
+    return l;
+}
+
+// s^0, r^0 and rho^0 of a row (theta and h are set by the first update)
+template <typename T>
+__device__ __forceinline__ GammaFoldRow<T> gamma_fold_exact_start(const GammaFoldExactParams<T> &p, int64_t row, int c, bool active) {
+    const int koff = c * PMF_VEC;
+    GammaFoldRow<T> st;
+    st.hyper = (T)0;
+    st.rho = !p.hierarchical ? p.rate_prior : p.init_prior_rate ? p.init_prior_rate[row] : p.hyper_shape / p.hyper_rate_prior;
+    st.theta = zero4<T>();
+    if (p.init_shape) {   // (staged with zero pad elements)
+        st.shape = active ? load4(p.init_shape + row * p.kpad + koff) : zero4<T>();
+        st.rate = active ? load4(p.init_rate + row * p.kpad + koff) : zero4<T>();
+    } else {
+#pragma unroll
+        for (int e = 0; e < PMF_VEC; ++e) {
+            const bool ok = active && koff + e < p.K;
+            st.shape.v[e] = ok ? p.shape_prior : (T)0;
+            st.rate.v[e] = ok ? st.rho : (T)0;
+        }
+    }
+    return st;
+}
+
+// The ratings [0, n) of one row in batches of LPR, batch `first`, first + step, ...: acc += x_j phi_j with
+// phi_jk = exp(sl_k + L_{o_j k} - lse_j) and, in the call's first pass (`with_b`), bsum += E_{o_j}.  The statements per
+// rating are gamma_exact_kernel's, in its order.  All lanes of the group call it together.
+template <typename T, int LPR>
+__device__ __forceinline__ void gamma_fold_exact_pass(const GammaFoldExactParams<T> &p, const int32_t *col, const T *val, int64_t n,
+                                                      int first, int step, int c, bool active, bool with_b, const Vec4<T> &sl,
+                                                      Vec4<T> &acc, Vec4<T> &bsum) {
+    constexpr int UN = LPR < 4 ? LPR : 4;
+    const int koff = c * PMF_VEC;
+    const int kpad = p.kpad;
+    for (int64_t base = (int64_t)first * LPR; base < n; base += (int64_t)step * LPR) {
+        const int cnt = (int)min((int64_t)LPR, n - base);
+        int my_o = 0;
+        T my_x = (T)0;
+        if (c < cnt) {
+            my_o = col[base + c];
+            my_x = val[base + c];
+        }
+        for (int tt = 0; tt < cnt; tt += UN) {
+            int o[UN];
+            T xv[UN];
+            Vec4<T> bl[UN], be[UN];
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                o[q] = __shfl(my_o, tt + q, LPR);   // (lanes past the batch hold id 0: a valid row, loaded and not used)
+                xv[q] = __shfl(my_x, tt + q, LPR);
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                bl[q] = sl;   // (-inf in every element: what an inactive lane contributes)
+                be[q] = zero4<T>();
+                if (active) {
+                    const T *src = p.table_other + (int64_t)o[q] * 2 * kpad + koff;
+                    bl[q] = load4(src);
+                    if (with_b) be[q] = load4(src + kpad);   // (the same in every lane)
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < UN; ++q) {
+                if (tt + q < cnt) {
+                    T s[PMF_VEC];
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) s[e] = sl.v[e] + bl[q].v[e];
+                    const T m = group_max<LPR>(vmax(vmax(s[0], s[1]), vmax(s[2], s[3])));
+                    const Vec4<T> ex = gamma_fold_exact_exp(s[0], s[1], s[2], s[3], m);   // (a pad is -inf: exp gives 0)
+                    T z = ex.v[0];
+                    z += ex.v[1];
+                    z += ex.v[2];
+                    z += ex.v[3];
+                    z = group_sum<LPR>(z);   // >= 1: the largest element adds exp(0)
+                    const T w = xv[q] / z;
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) {
+                        acc.v[e] += w * ex.v[e];
+                        if (with_b) bsum.v[e] += be[q].v[e];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// `ptr` lives in vector registers from here on (an empty statement the compiler cannot see through)
+template <typename T>
+__device__ __forceinline__ void gamma_fold_hold(T *&ptr) {
+    asm volatile("" : "+v"(ptr));
+}
+
+template <typename T, int LPR, bool LONG>
+__global__ __launch_bounds__(256) void gamma_fold_exact_kernel(GammaFoldExactParams<T> p) {
+    constexpr int G = 256 / LPR;
+    const int c = threadIdx.x % LPR;
+    const int g = threadIdx.x / LPR;
+    const int koff = c * PMF_VEC;
+    const int kpad = p.kpad;
+    const bool active = koff < kpad;
+    if constexpr (!LONG) {
+        const int64_t at = (int64_t)blockIdx.x * G + g;
+        if (at >= p.n) return;
+        const int64_t row = p.rows[at];
+        const int64_t start = p.ptr[row], n = p.ptr[row + 1] - start;
+        const int32_t *col = p.other + start;
+        const T *val = p.val + start;
+        GammaFoldRow<T> st = gamma_fold_exact_start(p, row, c, active);
+        Vec4<T> bsum = (p.colsum && active) ? load4(p.colsum + koff) : zero4<T>();
+        for (int t = 0; t < p.n_iter; ++t) {
+            const Vec4<T> sl = gamma_fold_exact_elog<T>(p, c, active, st.shape, st.rate);
+            Vec4<T> acc = zero4<T>();
+            gamma_fold_exact_pass<T, LPR>(p, col, val, n, 0, 1, c, active, t == 0 && !p.colsum, sl, acc, bsum);
+            gamma_fold_update<T, LPR>(p, c, active, acc, bsum, st);
+        }
+        gamma_fold_store(p, row, c, active, st);
+    } else {
+        // gamma_fold_kernel's block variant: one block per row (the grid is the long list exactly: every thread reaches
+        // every barrier); every group adds the G partials in group order and so holds the same s, r, rho -- and forms
+        // the same E log from them -- bit for bit, without a broadcast.
+        extern __shared__ __align__(16) unsigned char smem_raw[];
+        T *part = reinterpret_cast<T *>(smem_raw);   // [G][kpad] shape partials, then [G][kpad] sum_j E_{o_j} partials (first pass)
+        const int64_t row = p.rows[blockIdx.x];
+        const int64_t start = p.ptr[row], n = p.ptr[row + 1] - start;
+        const int32_t *col = p.other + start;
+        const T *val = p.val + start;
+        GammaFoldRow<T> st = gamma_fold_exact_start(p, row, c, active);
+        Vec4<T> bsum = (p.colsum && active) ? load4(p.colsum + koff) : zero4<T>();
+        // The output pointers are read after the last pass only.  They are the same in every lane, so they would hold
+        // scalar registers through the rating loop, and with the calls of the double kernels inside it some spill:
+        // they wait in vector registers instead.
+        GammaFoldParams<T> out = p;
+        gamma_fold_hold(out.factor), gamma_fold_hold(out.shape), gamma_fold_hold(out.rate);
+        gamma_fold_hold(out.prior_rate), gamma_fold_hold(out.hyper_rate);
+        for (int t = 0; t < p.n_iter; ++t) {
+            const bool with_b = t == 0 && !p.colsum;   // (the same in every thread)
+            const Vec4<T> sl = gamma_fold_exact_elog<T>(p, c, active, st.shape, st.rate);
+            Vec4<T> acc = zero4<T>(), bpart = zero4<T>();
+            gamma_fold_exact_pass<T, LPR>(p, col, val, n, g, G, c, active, with_b, sl, acc, bpart);
+            if (active) {
+                store4(part + g * kpad + koff, acc);
+                if (with_b) store4(part + (G + g) * kpad + koff, bpart);
+            }
+            __syncthreads();
+            acc = zero4<T>();
+            if (active) {
+#pragma unroll 4
+                for (int s = 0; s < G; ++s) {
+                    const Vec4<T> a = load4(part + s * kpad + koff);
+#pragma unroll
+                    for (int e = 0; e < PMF_VEC; ++e) acc.v[e] += a.v[e];
+                    if (with_b) {
+                        const Vec4<T> b = load4(part + (G + s) * kpad + koff);
+#pragma unroll
+                        for (int e = 0; e < PMF_VEC; ++e) bsum.v[e] += b.v[e];
+                    }
+                }
+            }
+            gamma_fold_update<T, LPR>(p, c, active, acc, bsum, st);
+            __syncthreads();
+        }
+        if (g == 0) gamma_fold_store(out, row, c, active, st);
+    }
+}
+
+// the opposite side's table, built once per call into pmf_ctx::d_gamma_tables (at the place gamma_exact_table gives it,
+// so the buffer has the size every exact call reserves), and the zero mode's C from its E half
+template <typename T>
+static int gamma_fold_exact_other(pmf_ctx *ctx, int side, const T **table, const T **colsum) {
+    const int other = 1 - side;
+    int rc;
+    if ((rc = gamma_exact_build_tables<T>(ctx, {other}))) return rc;
+    *table = gamma_exact_table<T>(ctx, other);
+    if (!gamma_zeros_observed(ctx)) return PMF_OK;
+    return gamma_colsum_scratch<T>(ctx, *table + ctx->kpad, ctx->rows[other], 2 * (int64_t)ctx->kpad, nullptr, colsum);
+}
+
+template <typename T>
+static void launch_gamma_fold_exact(pmf_ctx *ctx, GammaFoldExactParams<T> &p, const int32_t *list, int64_t n_short, int64_t n_long) {
+    pmf_with_pow2<1>(pmf_lanes_per_row(p.kpad), [&](auto L) {
+        constexpr int G = 256 / L;
+        if (n_short > 0) {
+            PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_SWEEP);
+            p.rows = list;
+            p.n = n_short;
+            hipLaunchKernelGGL((gamma_fold_exact_kernel<T, L, false>), dim3((unsigned)((n_short + G - 1) / G)), dim3(256), 0, ctx->stream, p);
+        }
+        if (n_long > 0) {
+            PmfProfScope prof(ctx, PMF_KERNEL_GAMMA_FINAL);
+            p.rows = list + n_short;
+            p.n = n_long;
+            hipLaunchKernelGGL((gamma_fold_exact_kernel<T, L, true>), dim3((unsigned)n_long), dim3(256), (size_t)G * 2 * p.kpad * sizeof(T),
+                                ctx->stream, p);
+        }
     });
 }
 

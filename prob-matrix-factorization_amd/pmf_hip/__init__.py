@@ -97,6 +97,8 @@ SIGNATURES = {
     "pmf_ctx_set_gamma_zeros": (C.c_int, [_p, C.c_int]),
     "pmf_ctx_get_gamma_zeros": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "pmf_gamma_column_sums": (C.c_int, [_p, C.c_int, C.c_int, _f64p]),
+    "pmf_gamma_fold_in_exact": (C.c_int, [_p, C.c_int, C.c_int64, _i64p, _i32p, _f64p, C.c_double, C.c_double, C.c_int, C.c_double,
+                                          C.c_double, C.c_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
     "pmf_gamma_predictive": (C.c_int, [_p, C.c_int64, _i32p, _i32p, _f64p, C.c_int, _f64p, _f64p, _f64p, _f64p]),
     "pmf_gauss_factor_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),
     "pmf_gauss_bias_sweep": (C.c_int, [_p, C.c_int, C.c_double, C.c_double]),

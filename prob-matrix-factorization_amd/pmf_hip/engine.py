@@ -313,6 +313,36 @@ class Context:
                                           opt_ptr(shape), opt_ptr(rate), opt_ptr(prior_rate), opt_ptr(hyper_rate)), "pmf_gamma_fold_in")
         return factor, shape, rate, prior_rate, hyper_rate
 
+    def gamma_fold_in_exact(self, side, row_ptr, other_ids, ratings, shape_prior, rate_prior=0.0, hierarchical=False, hyper_shape=0.0,
+                            hyper_rate_prior=0.0, n_iter=10, init_shape=None, init_rate=None, init_prior_rate=None, want_params=True):
+        """`gamma_fold_in` with the update of `gamma_exact_sweep` (`pmf_gamma_fold_in_exact`): `n_iter` passes of coordinate
+        ascent on the bound against the opposite side's q, read from its SHAPE and RATE (FACTOR is not needed).  The same
+        five results.  `init_shape` / `init_rate` [n, K] (both or neither) and `init_prior_rate` [n] warm-start the rows.
+        The context is only read."""
+        rp, o, x = csr_batch("row_ptr must hold n_rows + 1 offsets ending at len(other_ids) == len(ratings)", row_ptr,
+                             other_ids, "other_ids", ratings)
+        n = len(rp) - 1
+        init_s = None if init_shape is None else as_f64(init_shape)
+        init_b = None if init_rate is None else as_f64(init_rate)
+        init_r = None if init_prior_rate is None else as_f64(init_prior_rate)
+        for name, a in (("init_shape", init_s), ("init_rate", init_b)):
+            if a is not None and a.shape != (n, self.K):
+                raise ValueError(f"{name}: expected shape {(n, self.K)}, got {a.shape}")
+        if init_r is not None and init_r.shape != (n,):
+            raise ValueError(f"init_prior_rate: expected shape {(n,)}, got {init_r.shape}")
+        hier = bool(hierarchical)
+        factor = np.zeros((n, self.K), dtype=np.float64)
+        shape = np.zeros((n, self.K), dtype=np.float64) if want_params else None
+        rate = np.zeros((n, self.K), dtype=np.float64) if want_params else None
+        prior_rate = np.zeros(n, dtype=np.float64) if hier else None
+        hyper_rate = np.zeros(n, dtype=np.float64) if hier else None
+        check(self._lib.pmf_gamma_fold_in_exact(self._h, side, n, ptr(rp, C.c_int64), ptr(o, C.c_int32), ptr(x, C.c_double),
+                                                float(shape_prior), float(rate_prior), int(hier), float(hyper_shape),
+                                                float(hyper_rate_prior), int(n_iter), opt_ptr(init_s), opt_ptr(init_b), opt_ptr(init_r),
+                                                ptr(factor, C.c_double), opt_ptr(shape), opt_ptr(rate), opt_ptr(prior_rate),
+                                                opt_ptr(hyper_rate)), "pmf_gamma_fold_in_exact")
+        return factor, shape, rate, prior_rate, hyper_rate
+
     def gamma_elbo_terms(self, side, with_data=False, hierarchical=False, per_row=False):
         """The sums of `side` the Poisson MF / HPF ELBO is assembled from (`pmf_gamma_elbo_terms`; columns
         `pmf_hip.GAMMA_ELBO_*`): the totals [GAMMA_ELBO_TERMS] as float64 and, when asked, the (rows, GAMMA_ELBO_TERMS)

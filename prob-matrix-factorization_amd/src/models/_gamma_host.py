@@ -108,21 +108,28 @@ class GammaModel(DeviceModel):
             self._pull_state()
         return self
 
-    def fold_in_users(self, df, n_iter=10):
+    def fold_in_users(self, df, n_iter=10, update="reference"):
         """Variational parameters of users the fit has not seen, from their ratings of fitted items: `df` has columns
         u, i, rating; `u` holds arbitrary labels.  The item side stays frozen; each user gets `n_iter` row updates
         (poisson_mf_cavi.py:135-167; theta then xi, hpf_cavi.py:126-159) from the prior mean, on the device
         (`pmf_gamma_fold_in`), without a refit.  Rows with an item id the fit has not seen are dropped; a user left
-        without ratings runs the same updates on empty sums.  The row update is the reference's even for a model fitted
-        with `update="exact"`.  After `fit(unobserved="zero")` a new user's unlisted items are zeros too: the rate is the
-        prior rate plus the column sum of the fitted items' factors.  Returns a `GammaFoldIn`, one row per label in sorted
-        order."""
-        return gamma_fold_in(self, USER, df, n_iter, self._priors()[USER])
+        without ratings runs the same updates on empty sums.
+        `update`: "reference" (default, whatever `update` the fit ran) runs the reference's row update against the fitted
+        items' expected factors; "exact" runs coordinate ascent on the bound (`pmf_gamma_fold_in_exact`: the weights of
+        `fit(update="exact")`, formed from the fitted items' shapes and rates and the row's own, which are re-formed
+        between the passes), under which a folded row's bound cannot fall from pass to pass, except by rounding -- the
+        update to serve a model fitted with `update="exact"` with.  Any other value is a ValueError.  "exact" needs a
+        fit that ran at least one iteration, and after a sharded fit (`comm=`) it raises NotImplementedError: the
+        full-size serving context holds the expected factors only, not the shapes and rates.  The record's `update` names
+        the one that ran.
+        After `fit(unobserved="zero")` a new user's unlisted items are zeros too: the rate is the prior rate plus the
+        column sum of the fitted items' factors.  Returns a `GammaFoldIn`, one row per label in sorted order."""
+        return gamma_fold_in(self, USER, df, n_iter, self._priors()[USER], update)
 
-    def fold_in_items(self, df, n_iter=10):
+    def fold_in_items(self, df, n_iter=10, update="reference"):
         """The same for new items (labels in column `i`) against the fitted users (poisson_mf_cavi.py:173-197,
-        hpf_cavi.py:162-193); the reference's row update here too, whatever `update` the fit ran."""
-        return gamma_fold_in(self, ITEM, df, n_iter, self._priors()[ITEM])
+        hpf_cavi.py:162-193); `update` as for `fold_in_users`."""
+        return gamma_fold_in(self, ITEM, df, n_iter, self._priors()[ITEM], update)
 
     def elbo(self, parts=False):
         """The evidence lower bound of the fitted q on the training ratings, for the config's priors (float64):
