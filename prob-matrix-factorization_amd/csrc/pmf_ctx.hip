@@ -8,6 +8,8 @@
 
 #include <algorithm>
 #include <exception>
+#include <map>
+#include <mutex>
 #include <new>
 
 #include "pmf_internal.h"
@@ -91,12 +93,23 @@ int pmf_ensure_partial(pmf_ctx *ctx, size_t bytes) { return ctx->d_partial.reser
 int pmf_ensure_scratch(pmf_ctx *ctx, size_t bytes) { return ctx->d_scratch.reserve(ctx, bytes, {ctx->stream}); }
 int pmf_ensure_pinned(pmf_ctx *ctx, size_t bytes) { return ctx->h_pinned.reserve(nullptr, bytes, {ctx->stream}); }
 
+// The limit is the process's, per device and kernel function, so the grants are kept here and not in a context: two
+// contexts that share a function (the block-per-row kernels serve every K > 64) must not lower each other's.
 int pmf_allow_dynamic_lds(const void *kernel, size_t bytes) {
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> granted;
+    if (bytes <= (size_t)48 * 1024) return PMF_OK;   // what every kernel may use without asking
+    int dev = 0;
+    PMF_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &have = granted[{dev, kernel}];
+    if (bytes <= have) return PMF_OK;
     hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) {
         pmf_set_error("hipFuncSetAttribute(%zu bytes LDS) failed: %s", bytes, hipGetErrorString(e));
         return PMF_EHIP;
     }
+    have = bytes;
     return PMF_OK;
 }
 

@@ -265,6 +265,37 @@ __device__ __forceinline__ double readlane_dyn(double x, int lane) {
     return __builtin_bit_cast(double, q);
 }
 
+// A row's matrix in registers, one wavefront per row: B[i] = row i, lane j = column j.  The row solver, the ELBO row pass
+// and the posterior draws all start from it Jacobi-scaled to a unit diagonal: g_j = 1 / sqrt(B_jj), B_ij *= g_i g_j.
+// Returns lane j's g_j.
+template <typename T, int KR>
+__device__ __forceinline__ T reg_jacobi_scale(T *B, int j) {
+    T diag = (T)1;
+#pragma unroll
+    for (int i = 0; i < KR; ++i) {
+        const T dii = readlane_dyn(B[i], i);
+        if (j == i) diag = dii;
+    }
+    const T g = (T)1 / sqrt(diag);
+#pragma unroll
+    for (int i = 0; i < KR; ++i) B[i] = B[i] * g * readlane_dyn(g, i);
+    return g;
+}
+
+// B from the packed lower triangle `img` in LDS, rows and columns >= K the identity, then scaled; returns g_j
+template <typename T, int KR>
+__device__ __forceinline__ T reg_load_scaled(const T *img, int K, int lane, T *B) {
+    const int j = lane, jc = j < K ? j : 0;
+#pragma unroll
+    for (int i = 0; i < KR; ++i) {
+        const int ic = i < K ? i : 0;
+        const int lo = ic < jc ? ic : jc, hi = ic < jc ? jc : ic;
+        T s = img[hi * (hi + 1) / 2 + lo];
+        if (!(i < K && j < K)) s = (i == j) ? (T)1 : (T)0;
+        B[i] = s;
+    }
+    return reg_jacobi_scale<T, KR>(B, j);
+}
 
 // One wavefront per row, lane j = column j, B[i] = row (i + step) mod KR.
 // Symmetric sweep on the Jacobi-scaled matrix (unit diagonal => pivots in
@@ -288,16 +319,7 @@ __device__ __forceinline__ T solve_from_image(const T *img, T wj, int K, int kpa
         if (i == j) s += (i < K) ? inv_eta2 : (T)1;
         B[i] = s;
     }
-    // Jacobi scaling g_j = 1/sqrt(P_jj)
-    T diag = (T)1;
-#pragma unroll
-    for (int i = 0; i < KR; ++i) {
-        const T dii = readlane_dyn(B[i], i);
-        if (j == i) diag = dii;
-    }
-    const T g = (T)1 / sqrt(diag);
-#pragma unroll
-    for (int i = 0; i < KR; ++i) B[i] = B[i] * g * readlane_dyn(g, i);
+    const T g = reg_jacobi_scale<T, KR>(B, j);   // g_j = 1/sqrt(P_jj)
 
     for (int k = 0; k < KR; ++k) {
         const T v = B[0];
@@ -1876,6 +1898,20 @@ static int run_factor_accumulate(pmf_ctx *ctx, int side, PmfPass pass, void *sta
     return launch_accumulate<T>(ctx, p, tl.n_split, st, fuse, sigma2, eta2, fused);
 }
 
+// Where a block-per-row kernel (row solver, ELBO row pass, posterior draws at K > 64) keeps a row's matrix of `mat` bytes:
+// in LDS while it fits the CU's 160 KB beside the kernel's `vecs` bytes of vectors and its static LDS; else every resident
+// block has a slice of global scratch, and at most `cap` blocks walk the rows.
+struct RowMatrixPlan {
+    size_t mat, vecs;
+    int64_t cap;
+    bool in_lds;
+    RowMatrixPlan(size_t mat, size_t vecs, size_t static_lds, int64_t cap)
+        : mat(mat), vecs(vecs), cap(cap), in_lds(mat + vecs + static_lds <= (size_t)160 * 1024) {}
+    unsigned blocks(int64_t n) const { return (unsigned)std::min<int64_t>(n, in_lds ? n : cap); }
+    size_t smem() const { return in_lds ? mat + vecs : vecs; }   // dynamic LDS
+    size_t scratch_bytes(int64_t n) const { return in_lds ? 0 : (size_t)blocks(n) * mat; }
+};
+
 // the row solver for the context's K and dtype over the rows `sp` names
 template <typename T>
 static int launch_solve(pmf_ctx *ctx, const SolveParams<T> &sp) {
@@ -1899,17 +1935,14 @@ static int launch_solve(pmf_ctx *ctx, const SolveParams<T> &sp) {
         }
     } else {
         const int K = ctx->K;
-        const size_t mat = (size_t)K * (K + 1) * sizeof(T), vecs = (size_t)3 * K * sizeof(T);
-        const bool in_lds = mat + vecs <= (size_t)160 * 1024;
-        const unsigned blocks = (unsigned)std::min<int64_t>(sp.n, in_lds ? sp.n : 2048);
+        const RowMatrixPlan plan((size_t)K * (K + 1) * sizeof(T), (size_t)3 * K * sizeof(T), 0, 2048);
         T *scratch = nullptr;
-        if (!in_lds) {   // one matrix per resident block in global scratch (<= 2048 x 264 KB)
-            if ((rc = pmf_ensure_scratch(ctx, (size_t)blocks * mat))) return rc;
+        if (!plan.in_lds) {   // one matrix per resident block (<= 2048 x 264 KB)
+            if ((rc = pmf_ensure_scratch(ctx, plan.scratch_bytes(sp.n)))) return rc;
             scratch = ctx->d_scratch.as<T>();
         }
-        const size_t smem = in_lds ? mat + vecs : vecs;
-        if ((rc = pmf_allow_dynamic_lds((const void *)gauss_solve_lds_kernel<T>, smem))) return rc;
-        hipLaunchKernelGGL((gauss_solve_lds_kernel<T>), dim3(blocks), dim3(256), smem, ctx->stream, sp, scratch);
+        if ((rc = pmf_allow_dynamic_lds((const void *)gauss_solve_lds_kernel<T>, plan.smem()))) return rc;
+        hipLaunchKernelGGL((gauss_solve_lds_kernel<T>), dim3(plan.blocks(sp.n)), dim3(256), plan.smem(), ctx->stream, sp, scratch);
     }
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
@@ -2608,19 +2641,21 @@ __device__ __forceinline__ double elbo_log_term(double piv, double g) {
     return (piv > 0.0 ? log(piv) : __builtin_nan("")) - 2.0 * log(g);
 }
 
-// Pivots of the symmetric elimination (LDL^T without L) of the matrix held as B[i] = row k0 + i, lane j = column j.
-// The pivot row is always register 0: every update writes row i into register i - 1, as the solver's sweep does; after
-// 8 steps (N / 2 below 16 rows) the live rows are registers 0 .. N - 9 and the same code runs at that width: 2 240 update
-// instructions at 64 rows where a full-width sweep has 4 032 and the triangle 2 016.  Lane k keeps pivot k.
-template <typename T, int N>
-__device__ __forceinline__ void elbo_eliminate(T *B, int k0, int lane, T &piv) {
+// The symmetric elimination (LDL^T without L) of the matrix held as B[i] = row k0 + i, lane j = column j, shared by the
+// ELBO row pass (which keeps the pivots) and the posterior draws (which take the factor's columns along): before the
+// rank-1 update of step k, `step(k, v, d)` sees the pivot row v and the pivot d = v_k.  The pivot row is always register 0:
+// every update writes row i into register i - 1, as the solver's sweep does; after 8 steps (N / 2 below 16 rows) the live
+// rows are registers 0 .. N - 9 and the same code runs at that width: 2 240 update instructions at 64 rows where a
+// full-width sweep has 4 032 and the triangle 2 016.
+template <typename T, int N, typename Step>
+__device__ __forceinline__ void reg_eliminate(T *B, int k0, const Step &step) {
     constexpr int STEPS = N > 8 ? 8 : (N > 1 ? N / 2 : 1);
 #pragma unroll 1
     for (int s = 0; s < STEPS; ++s) {
         const int k = k0 + s;
         const T v = B[0];
         const T d = readlane_dyn(v, k);
-        if (lane == k) piv = d;
+        step(k, v, d);
         if constexpr (N > 1) {
             const T u = v * ((T)1 / d);
 #pragma unroll
@@ -2628,10 +2663,48 @@ __device__ __forceinline__ void elbo_eliminate(T *B, int k0, int lane, T &piv) {
             B[N - 1] = (T)0;
         }
     }
-    if constexpr (N > 1) elbo_eliminate<T, N - STEPS>(B, k0 + STEPS, lane, piv);
+    if constexpr (N > 1) reg_eliminate<T, N - STEPS>(B, k0 + STEPS, step);
 }
 
-// K <= 64: one wavefront per row, the matrix in registers (lane j = column j) as in solve_from_image
+// The same for a block per row (K > 64) on the packed lower triangle A, in LDS or global scratch: g[i] = 1 / sqrt(A_ii),
+// A_ij *= g_i g_j, then the right-looking elimination, wavefront w taking rows k + 1 + w, k + 5 + w, ... of step k.
+// Thread 0 runs `pivot(k, d)` at each step.  Begins with a barrier (A complete) and ends with one (A[i, k] = d_k L_ik).
+template <typename T, typename Pivot>
+__device__ __forceinline__ void block_scale_eliminate(T *A, T *g, int K, int kp, const Pivot &pivot) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    __syncthreads();
+    for (int i = tid; i < K; i += 256) g[i] = (T)1 / sqrt(A[i * (i + 3) / 2]);
+    __syncthreads();
+    for (int e = tid; e < kp; e += 256) {
+        int r, c;
+        tri_rc(e, r, c);
+        A[e] *= g[r] * g[c];
+    }
+    for (int k = 0; k < K; ++k) {
+        __syncthreads();
+        const T d = A[k * (k + 3) / 2];
+        if (tid == 0) pivot(k, d);
+        const T pinv = (T)1 / d;
+        for (int i = k + 1 + wave; i < K; i += 4) {
+            const T f = A[i * (i + 1) / 2 + k] * pinv;
+            for (int jj = k + 1 + lane; jj <= i; jj += 64)
+                A[i * (i + 1) / 2 + jj] = fma(-f, A[jj * (jj + 1) / 2 + k], A[i * (i + 1) / 2 + jj]);
+        }
+    }
+    __syncthreads();
+}
+
+template <typename T>
+__device__ __forceinline__ void elbo_store_terms(const ElboParams<T> &p, int64_t row, T sq, double ld, T ess, bool data) {
+    double *o = p.out + row * PMF_ELBO_TERMS;
+    const T b = p.bias ? p.bias[row] : (T)0;
+    o[PMF_ELBO_SQNORM] = (double)sq;
+    o[PMF_ELBO_LOGDET] = ld;
+    o[PMF_ELBO_BIAS_SQ] = (double)(b * b);
+    o[PMF_ELBO_ESS] = data ? (double)ess : 0.0;
+}
+
+// K <= 64: one wavefront per row, the matrix in registers
 template <typename T, int KR>
 __global__ __launch_bounds__(256) void gauss_elbo_row_reg_kernel(ElboParams<T> p) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -2667,38 +2740,16 @@ __global__ __launch_bounds__(256) void gauss_elbo_row_reg_kernel(ElboParams<T> p
     sq = group_sum<64>(sq);
     if (data) ess += p.csum[idx];
     wave_lds_fence();
-    // the matrix, Jacobi-scaled to a unit diagonal; rows and columns >= K are the identity
-    const int j = lane, jc = j < K ? j : 0;
     T B[KR];
-#pragma unroll
-    for (int i = 0; i < KR; ++i) {
-        const int ic = i < K ? i : 0;
-        const int lo = ic < jc ? ic : jc, hi = ic < jc ? jc : ic;
-        T s = img[hi * (hi + 1) / 2 + lo];
-        if (!(i < K && j < K)) s = (i == j) ? (T)1 : (T)0;
-        B[i] = s;
-    }
-    T diag = (T)1;
-#pragma unroll
-    for (int i = 0; i < KR; ++i) {
-        const T dii = readlane_dyn(B[i], i);
-        if (j == i) diag = dii;
-    }
-    const T g = (T)1 / sqrt(diag);
-#pragma unroll
-    for (int i = 0; i < KR; ++i) B[i] = B[i] * g * readlane_dyn(g, i);
+    const T g = reg_load_scaled<T, KR>(img, K, lane, B);
     T piv = (T)1;
-    elbo_eliminate<T, KR>(B, 0, lane, piv);
+    const auto keep = [&](int k, T, T d) {   // lane k keeps pivot k
+        if (lane == k) piv = d;
+    };
+    reg_eliminate<T, KR>(B, 0, keep);
     double ld = lane < K ? elbo_log_term((double)piv, (double)g) : 0.0;
     ld = group_sum<64>(ld);
-    if (lane == 0) {
-        double *o = p.out + row * PMF_ELBO_TERMS;
-        const T b = p.bias ? p.bias[row] : (T)0;
-        o[PMF_ELBO_SQNORM] = (double)sq;
-        o[PMF_ELBO_LOGDET] = ld;
-        o[PMF_ELBO_BIAS_SQ] = (double)(b * b);
-        o[PMF_ELBO_ESS] = data ? (double)ess : 0.0;
-    }
+    if (lane == 0) elbo_store_terms(p, row, sq, ld, ess, data);
 }
 
 // sum over the 256 threads of a block, the four wavefronts' sums added in order; every thread gets it
@@ -2711,8 +2762,9 @@ __device__ __forceinline__ T elbo_block_sum(T x, T *red) {
     return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
-// K > 64: one block per row, the packed lower triangle in LDS -- or, where it does not fit the CU's 160 KB (`scratch`
-// != null: fp64 at large K), in the block's own slice of a global scratch buffer, as gauss_solve_lds_kernel does.
+// K > 64: one block per row on the packed lower triangle, in LDS or -- `scratch` != null: it does not fit the CU's 160 KB,
+// fp64 at large K -- in the block's own slice of a global scratch buffer (RowMatrixPlan decides)
+// dynamic LDS: [cov_stride unless `scratch`] + ms [kpad] + g [K] + pv [K]
 template <typename T>
 __global__ __launch_bounds__(256) void gauss_elbo_row_lds_kernel(ElboParams<T> p, T *scratch) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -2724,7 +2776,7 @@ __global__ __launch_bounds__(256) void gauss_elbo_row_lds_kernel(ElboParams<T> p
     T *ms = scratch ? lds : lds + p.cov_stride;                            // [kpad] the row's mean
     T *g = ms + p.kpad;                                                    // [K] Jacobi scales
     T *pv = g + K;                                                         // [K] pivots
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     for (int64_t idx = blockIdx.x; idx < p.n; idx += gridDim.x) {
         const int64_t row = p.row0 + idx;
         const T *V = p.cov + row * p.cov_stride;
@@ -2752,38 +2804,11 @@ __global__ __launch_bounds__(256) void gauss_elbo_row_lds_kernel(ElboParams<T> p
         ess = elbo_block_sum(ess, red_t);
         sq = elbo_block_sum(sq, red_t);
         if (data) ess += p.csum[idx];
-        __syncthreads();
-        for (int i = tid; i < K; i += 256) g[i] = (T)1 / sqrt(A[i * (i + 3) / 2]);
-        __syncthreads();
-        for (int e = tid; e < kp; e += 256) {
-            int r, c;
-            tri_rc(e, r, c);
-            A[e] *= g[r] * g[c];
-        }
-        // right-looking elimination on the lower triangle: wavefront w takes rows k + 1 + w, k + 5 + w, ...
-        for (int k = 0; k < K; ++k) {
-            __syncthreads();
-            const T d = A[k * (k + 3) / 2];
-            if (tid == 0) pv[k] = d;
-            const T pinv = (T)1 / d;
-            for (int i = k + 1 + wave; i < K; i += 4) {
-                const T f = A[i * (i + 1) / 2 + k] * pinv;
-                for (int jj = k + 1 + lane; jj <= i; jj += 64)
-                    A[i * (i + 1) / 2 + jj] = fma(-f, A[jj * (jj + 1) / 2 + k], A[i * (i + 1) / 2 + jj]);
-            }
-        }
-        __syncthreads();
+        block_scale_eliminate(A, g, K, kp, [&](int k, T d) { pv[k] = d; });
         double ld = 0.0;
         for (int k = tid; k < K; k += 256) ld += elbo_log_term((double)pv[k], (double)g[k]);
         ld = elbo_block_sum(ld, red_d);
-        if (tid == 0) {
-            double *o = p.out + row * PMF_ELBO_TERMS;
-            const T b = p.bias ? p.bias[row] : (T)0;
-            o[PMF_ELBO_SQNORM] = (double)sq;
-            o[PMF_ELBO_LOGDET] = ld;
-            o[PMF_ELBO_BIAS_SQ] = (double)(b * b);
-            o[PMF_ELBO_ESS] = data ? (double)ess : 0.0;
-        }
+        if (tid == 0) elbo_store_terms(p, row, sq, ld, ess, data);
     }
 }
 
@@ -2795,28 +2820,21 @@ static int launch_elbo_rows(pmf_ctx *ctx, const ElboParams<T> &e) {
     if (K <= 64) {
         const size_t smem = (size_t)4 * (ctx->cov_stride + ctx->kpad) * sizeof(T);
         pmf_with_pow2<8>(K, [&](auto KR) {
-            if (smem > (size_t)48 * 1024 && ctx->elbo_lds_bytes != smem)   // fp64 at K = 64: 67 KB; once per context
-                rc = pmf_allow_dynamic_lds((const void *)gauss_elbo_row_reg_kernel<T, KR>, smem);
+            rc = pmf_allow_dynamic_lds((const void *)gauss_elbo_row_reg_kernel<T, KR>, smem);   // fp64 at K = 64: 67 KB
             if (rc == PMF_OK)
                 hipLaunchKernelGGL((gauss_elbo_row_reg_kernel<T, KR>), dim3((unsigned)((e.n + 3) / 4)), dim3(256), smem,
                                    ctx->stream, e);
         });
         if (rc) return rc;
-        ctx->elbo_lds_bytes = smem;
     } else {
-        const size_t mat = (size_t)ctx->cov_stride * sizeof(T), vecs = (size_t)(ctx->kpad + 2 * K) * sizeof(T);
-        const bool in_lds = mat + vecs + 64 <= (size_t)160 * 1024;
-        const unsigned blocks = (unsigned)std::min<int64_t>(e.n, in_lds ? e.n : 1024);
+        const RowMatrixPlan plan((size_t)ctx->cov_stride * sizeof(T), (size_t)(ctx->kpad + 2 * K) * sizeof(T), 64, 1024);
         T *scratch = nullptr;
-        if (!in_lds) {   // one packed triangle per resident block in global scratch (<= 1024 x 263 KB)
-            if ((rc = pmf_ensure_scratch(ctx, (size_t)blocks * mat))) return rc;
+        if (!plan.in_lds) {   // one packed triangle per resident block (<= 1024 x 263 KB)
+            if ((rc = pmf_ensure_scratch(ctx, plan.scratch_bytes(e.n)))) return rc;
             scratch = ctx->d_scratch.as<T>();
         }
-        const size_t smem = in_lds ? mat + vecs : vecs;
-        // once per context, not once per window (K and the dtype are the context's)
-        if (ctx->elbo_lds_bytes != smem && (rc = pmf_allow_dynamic_lds((const void *)gauss_elbo_row_lds_kernel<T>, smem))) return rc;
-        ctx->elbo_lds_bytes = smem;
-        hipLaunchKernelGGL((gauss_elbo_row_lds_kernel<T>), dim3(blocks), dim3(256), smem, ctx->stream, e, scratch);
+        if ((rc = pmf_allow_dynamic_lds((const void *)gauss_elbo_row_lds_kernel<T>, plan.smem()))) return rc;
+        hipLaunchKernelGGL((gauss_elbo_row_lds_kernel<T>), dim3(plan.blocks(e.n)), dim3(256), plan.smem(), ctx->stream, e, scratch);
     }
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;
@@ -2981,33 +2999,8 @@ __device__ __forceinline__ T sample_normal(const SampleParams<T> &p, uint32_t ro
     return (T)(r * ((k & 1) ? sn : cs));
 }
 
-// elbo_eliminate's schedule (pivot row in register 0, the width dropping by 8) with the draws taken along: at step k the
-// pivot row times 1 / sqrt(d_k) is column k of the factor on lanes j >= k -- lanes j < k hold the rounding residue of
-// d (1 / d) - 1, not zeros, and are masked -- and draw d adds it times z_{d,k}, which lane k holds.
-template <typename T, int N, int DR>
-__device__ __forceinline__ void sample_eliminate(T *B, int k0, int lane, int K, const T *zr, T *acc, bool &ok) {
-    constexpr int STEPS = N > 8 ? 8 : (N > 1 ? N / 2 : 1);
-#pragma unroll 1
-    for (int s = 0; s < STEPS; ++s) {
-        const int k = k0 + s;
-        const T v = B[0];
-        const T d = readlane_dyn(v, k);
-        if (k < K && !(d > (T)0)) ok = false;
-        const T c = lane >= k ? v * ((T)1 / sqrt(d)) : (T)0;
-#pragma unroll
-        for (int dd = 0; dd < DR; ++dd) acc[dd] = fma(c, readlane_dyn(zr[dd], k), acc[dd]);
-        if constexpr (N > 1) {
-            const T u = v * ((T)1 / d);
-#pragma unroll
-            for (int i = 1; i < N; ++i) B[i - 1] = fma(-readlane_dyn(B[i], k), u, B[i]);
-            B[N - 1] = (T)0;
-        }
-    }
-    if constexpr (N > 1) sample_eliminate<T, N - STEPS, DR>(B, k0 + STEPS, lane, K, zr, acc, ok);
-}
-
-// K <= 64: one wavefront per (request, pass of DR draws), the matrix in registers (lane j = column j) as in
-// gauss_elbo_row_reg_kernel; DR draws ride on one elimination, and a request of more draws takes ceil(n_draws / DR)
+// K <= 64: one wavefront per (request, pass of DR draws), the matrix in registers; DR draws ride on one elimination
+// (reg_eliminate), and a request of more draws takes ceil(n_draws / DR)
 // wavefronts, each with an elimination of its own (`passes` per request; wavefront w: request w / passes, pass w % passes).
 // dynamic LDS: 4 waves x (cov_stride + DR x 64) elements
 template <typename T, int KR, int DR>
@@ -3024,7 +3017,7 @@ __global__ __launch_bounds__(256) void gauss_sample_reg_kernel(SampleParams<T> p
     T *zs = img + p.cov_stride;   // [DR][64] the pass's normals, staged so that the generator is inlined once
     const T *V = p.cov + row * p.cov_stride;
     for (int q = lane * PMF_VEC; q < p.cov_stride; q += 64 * PMF_VEC) store4(img + q, load4(V + q));
-    const int j = lane, jc = j < K ? j : 0;
+    const int j = lane;
     const T mj = j < K ? p.factor[row * p.kpad + j] : (T)0;
     const int64_t at = idx * p.n_draws * p.kpad;
 #pragma unroll 1
@@ -3042,27 +3035,18 @@ __global__ __launch_bounds__(256) void gauss_sample_reg_kernel(SampleParams<T> p
         zr[dd] = zs[dd * 64 + lane];
         acc[dd] = (T)0;
     }
-    // the matrix, Jacobi-scaled to a unit diagonal; rows and columns >= K are the identity
     T B[KR];
-#pragma unroll
-    for (int i = 0; i < KR; ++i) {
-        const int ic = i < K ? i : 0;
-        const int lo = ic < jc ? ic : jc, hi = ic < jc ? jc : ic;
-        T s = img[hi * (hi + 1) / 2 + lo];
-        if (!(i < K && j < K)) s = (i == j) ? (T)1 : (T)0;
-        B[i] = s;
-    }
-    T diag = (T)1;
-#pragma unroll
-    for (int i = 0; i < KR; ++i) {
-        const T dii = readlane_dyn(B[i], i);
-        if (j == i) diag = dii;
-    }
-    const T g = (T)1 / sqrt(diag);
-#pragma unroll
-    for (int i = 0; i < KR; ++i) B[i] = B[i] * g * readlane_dyn(g, i);
+    const T g = reg_load_scaled<T, KR>(img, K, lane, B);
     bool ok = true;
-    sample_eliminate<T, KR, DR>(B, 0, lane, K, zr, acc, ok);
+    // at step k the pivot row times 1 / sqrt(d_k) is column k of the factor on lanes j >= k -- lanes j < k hold the rounding
+    // residue of d (1 / d) - 1, not zeros, and are masked -- and draw d adds it times z_{d,k}, which lane k holds
+    const auto column = [&](int k, T v, T d) {
+        if (k < K && !(d > (T)0)) ok = false;
+        const T c = lane >= k ? v * ((T)1 / sqrt(d)) : (T)0;
+#pragma unroll
+        for (int dd = 0; dd < DR; ++dd) acc[dd] = fma(c, readlane_dyn(zr[dd], k), acc[dd]);
+    };
+    reg_eliminate<T, KR>(B, 0, column);
     if (j < p.kpad) {
 #pragma unroll
         for (int dd = 0; dd < DR; ++dd)
@@ -3071,8 +3055,8 @@ __global__ __launch_bounds__(256) void gauss_sample_reg_kernel(SampleParams<T> p
     }
 }
 
-// K > 64: one block per request on the packed lower triangle, in LDS or (`scratch` != null: fp64 at large K) in the block's
-// slice of a global buffer, as gauss_elbo_row_lds_kernel chooses.  After the right-looking elimination A[i, k] (i > k)
+// K > 64: one block per request on the packed lower triangle, in LDS or (`scratch` != null) in the block's slice of a
+// global buffer.  After block_scale_eliminate A[i, k] (i > k)
 // holds d_k L_ik and the pivots d_k; column k times 1 / sqrt(d_k) makes the triangle chol(A) in place, and the draws are
 // the packed mat-vec  x_i = m_i + (1 / g_i) sum_{k <= i} A[i, k] z_k:  wavefront w takes rows w, w + 4, ..., lane l the
 // columns l, l + 64, ..., then the lanes' sums in group_sum's fixed order.
@@ -3097,30 +3081,10 @@ __global__ __launch_bounds__(256) void gauss_sample_lds_kernel(SampleParams<T> p
         __syncthreads();
         if (tid == 0) bad = 0;
         for (int q = tid * PMF_VEC; q < p.cov_stride; q += 256 * PMF_VEC) store4(A + q, load4(V + q));
-        __syncthreads();
-        for (int i = tid; i < K; i += 256) g[i] = (T)1 / sqrt(A[i * (i + 3) / 2]);
-        __syncthreads();
-        for (int e = tid; e < kp; e += 256) {
-            int r, c;
-            tri_rc(e, r, c);
-            A[e] *= g[r] * g[c];
-        }
-        // right-looking elimination on the lower triangle: wavefront w takes rows k + 1 + w, k + 5 + w, ...
-        for (int k = 0; k < K; ++k) {
-            __syncthreads();
-            const T d = A[k * (k + 3) / 2];
-            if (tid == 0) {
-                if (!(d > (T)0)) bad = 1;
-                rs[k] = (T)1 / sqrt(d);
-            }
-            const T pinv = (T)1 / d;
-            for (int i = k + 1 + wave; i < K; i += 4) {
-                const T f = A[i * (i + 1) / 2 + k] * pinv;
-                for (int jj = k + 1 + lane; jj <= i; jj += 64)
-                    A[i * (i + 1) / 2 + jj] = fma(-f, A[jj * (jj + 1) / 2 + k], A[i * (i + 1) / 2 + jj]);
-            }
-        }
-        __syncthreads();
+        block_scale_eliminate(A, g, K, kp, [&](int k, T d) {
+            if (!(d > (T)0)) bad = 1;
+            rs[k] = (T)1 / sqrt(d);
+        });
         for (int e = tid; e < kp; e += 256) {
             int r, c;
             tri_rc(e, r, c);
@@ -3158,18 +3122,15 @@ __global__ __launch_bounds__(256) void gauss_sample_lds_kernel(SampleParams<T> p
     }
 }
 
-// where the block-per-row kernel keeps its triangle: LDS while triangle and vectors fit the CU's 160 KB
+// the block-per-row kernel's placement: the caller of the launch provides the scratch (pmf_gauss_sample_tri_bytes)
 template <typename T>
-static bool sample_in_lds(const pmf_ctx *ctx) {
-    return (size_t)ctx->cov_stride * sizeof(T) + (size_t)(2 + kSampleDraws) * ctx->K * sizeof(T) + 64 <= (size_t)160 * 1024;
+static RowMatrixPlan sample_plan(const pmf_ctx *ctx) {
+    return RowMatrixPlan((size_t)ctx->cov_stride * sizeof(T), (size_t)(2 + kSampleDraws) * ctx->K * sizeof(T), 64, 1024);
 }
 
 size_t pmf_gauss_sample_tri_bytes(const pmf_ctx *ctx, int64_t n) {
     if (ctx->K <= 64 || n <= 0) return 0;
-    return pmf_with_dtype(ctx, [&](auto t) -> size_t {
-        using T = decltype(t);
-        return sample_in_lds<T>(ctx) ? 0 : (size_t)std::min<int64_t>(n, 1024) * ctx->cov_stride * sizeof(T);
-    });
+    return pmf_with_dtype(ctx, [&](auto t) { return sample_plan<decltype(t)>(ctx).scratch_bytes(n); });
 }
 
 template <typename T>
@@ -3186,24 +3147,19 @@ static int launch_sample(pmf_ctx *ctx, const SampleParams<T> &s, T *tri) {
         const dim3 grid((unsigned)blocks);
         pmf_with_pow2<8>(K, [&](auto KR) {
             auto go = [&](auto kernel) {
-                if (smem > (size_t)48 * 1024 && ctx->sample_lds_bytes[many] != smem)   // fp64 at K = 64; once per context
-                    rc = pmf_allow_dynamic_lds((const void *)kernel, smem);
+                rc = pmf_allow_dynamic_lds((const void *)kernel, smem);   // fp64 at K = 64
                 if (rc == PMF_OK) hipLaunchKernelGGL(kernel, grid, dim3(256), smem, ctx->stream, s, passes);
             };
             if (many) go(gauss_sample_reg_kernel<T, KR, kSampleDraws>);
             else go(gauss_sample_reg_kernel<T, KR, 1>);
         });
         if (rc) return rc;
-        ctx->sample_lds_bytes[many] = smem;
     } else {
-        const bool in_lds = sample_in_lds<T>(ctx);
-        PMF_REQUIRE(in_lds || tri, PMF_EINVAL, "gauss sample: no buffer for the packed triangles");
-        const size_t mat = (size_t)ctx->cov_stride * sizeof(T), vecs = (size_t)(2 + kSampleDraws) * K * sizeof(T);
-        const unsigned blocks = (unsigned)std::min<int64_t>(s.n, in_lds ? s.n : 1024);
-        const size_t smem = in_lds ? mat + vecs : vecs;
-        if (ctx->sample_lds_bytes[0] != smem && (rc = pmf_allow_dynamic_lds((const void *)gauss_sample_lds_kernel<T>, smem))) return rc;
-        ctx->sample_lds_bytes[0] = smem;
-        hipLaunchKernelGGL((gauss_sample_lds_kernel<T>), dim3(blocks), dim3(256), smem, ctx->stream, s, in_lds ? (T *)nullptr : tri);
+        const RowMatrixPlan plan = sample_plan<T>(ctx);
+        PMF_REQUIRE(plan.in_lds || tri, PMF_EINVAL, "gauss sample: no buffer for the packed triangles");
+        if ((rc = pmf_allow_dynamic_lds((const void *)gauss_sample_lds_kernel<T>, plan.smem()))) return rc;
+        hipLaunchKernelGGL((gauss_sample_lds_kernel<T>), dim3(plan.blocks(s.n)), dim3(256), plan.smem(), ctx->stream, s,
+                           plan.in_lds ? (T *)nullptr : tri);
     }
     PMF_HIP_CHECK(hipGetLastError());
     return PMF_OK;

@@ -270,8 +270,6 @@ struct pmf_ctx {
     int64_t topk_query_rows = 0;   // PMF_TOPK_QUERY_ROWS=n caps the query rows of one round of pmf_topk_items*, pmf_rank_items and the two query calls, rounded down to a multiple of 32 and at least 32 (tests: many rounds on a small batch; 0: 1 << 20 rows, or 512 MB of scores on the two-phase path)
     int64_t stage_bytes = 64ll << 20;   // PMF_STAGE_BYTES=n: bytes of one staging round of pmf_set_array / pmf_get_array, the row exchanges, the fold-ins' downloads and pmf_comm_gather_user_rows, at least one row (tests: many rounds on a few rows; 0 / unset: 64 MiB)
     int64_t window_rows = 0;       // PMF_ELBO_ROWS=n caps the rows of one statistics window (PmfRowWindows) of pmf_gauss_elbo_terms and of the zero-mode factor sweep (tests: many windows on a small problem; 0: by scratch size)
-    size_t elbo_lds_bytes = 0;     // dynamic LDS size the ELBO row kernel of this context's K and dtype has been allowed (0: not yet asked)
-    size_t sample_lds_bytes[2] = {0, 0};   // the same for the sample kernels: [0] one draw per pass (and the block-per-row kernel), [1] eight
     int task_chunk = 0;            // PMF_TASK_CHUNK=n (power of two in [32, 512]) fixes the task length of the gamma / Gaussian / bias lists (tests: long tasks on small problems; 0: by nnz)
 
     // multi-GPU (pmf_comm.hip): the communicator (shared between contexts of one process, refcounted)
@@ -375,7 +373,8 @@ PmfTaskView pmf_task_view(const pmf_ctx *ctx, int side, const PmfTaskList &tl, b
 int pmf_ensure_partial(pmf_ctx *ctx, size_t bytes);
 int pmf_ensure_scratch(pmf_ctx *ctx, size_t bytes);
 int pmf_ensure_pinned(pmf_ctx *ctx, size_t bytes);
-// allow `kernel` `bytes` of dynamic LDS (past the default limit); PMF_EHIP with the runtime's message if it refuses
+// allow `kernel` `bytes` of dynamic LDS on the current device: asks the runtime only for more than the default 48 KB and
+// more than the function has been granted before (grants never shrink); PMF_EHIP with the runtime's message if it refuses
 int pmf_allow_dynamic_lds(const void *kernel, size_t bytes);
 size_t pmf_array_elems(const pmf_ctx *ctx, int side, int array);  // device elements
 int pmf_require_array(pmf_ctx *ctx, int side, int array, const char *what);

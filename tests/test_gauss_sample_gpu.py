@@ -271,3 +271,41 @@ def test_the_call_only_reads_the_context():
     ctx.gauss_sample_rows(ITEM, np.arange(7), 2, seed=1)
     for b, a in zip(before, [ctx.get_array(s, a) for s in (USER, ITEM) for a in (ARR_FACTOR, ARR_COV)]):
         np.testing.assert_array_equal(a, b)
+
+
+def _swept_context(K, dtype):
+    """64 x 64 rows, random means, identity covariances, then one user and one item sweep on 300 ratings"""
+    import pmf_hip
+    from pmf_hip import ARR_FACTOR, ITEM, USER
+    rng = np.random.default_rng(K)
+    ctx = pmf_hip.Context(64, 64, K, dtype=dtype)
+    cells = rng.choice(64 * 64, 300, replace=False)
+    ctx.set_ratings((cells // 64).astype(np.int32), (cells % 64).astype(np.int32), rng.standard_normal(300))
+    for side in (USER, ITEM):
+        ctx.set_array(side, ARR_FACTOR, 0.3 * rng.standard_normal((64, K)))
+        ctx.set_cov_identity(side, 0.5)
+    for side in (USER, ITEM):
+        ctx.gauss_factor_sweep(side, 0.4, 0.7)
+    return ctx
+
+
+def _row_results(ctx):
+    from pmf_hip import USER
+    _, per_row = ctx.gauss_elbo_terms(USER, with_data=False, per_row=True)
+    return per_row, ctx.gauss_sample_rows(USER, np.arange(3, 64, 8), 2, seed=9)
+
+
+@pytest.mark.parametrize("dtype,K_a,K_b", [("f32", 200, 72), ("f64", 130, 66)])
+def test_two_contexts_share_the_block_per_row_kernels(dtype, K_a, K_b):
+    """A (large K, more dynamic LDS than the default) and B (small K) are alive together on one device and launch the same
+    block-per-row ELBO and sample functions in the order A, B, A: A's second results are its first bit for bit, and B's are
+    those of a context like it that ran alone -- the LDS size a function may use belongs to the process, not to a context."""
+    with _swept_context(K_b, dtype) as alone:
+        want_b = _row_results(alone)
+    with _swept_context(K_a, dtype) as a, _swept_context(K_b, dtype) as b:
+        first_a = _row_results(a)
+        got_b = _row_results(b)
+        again_a = _row_results(a)
+    for got, want in zip(got_b + again_a, want_b + first_a):
+        assert np.isfinite(got).all()
+        np.testing.assert_array_equal(got, want)

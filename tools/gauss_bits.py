@@ -1,10 +1,12 @@
 """SHA-256 digests of what the Gaussian host paths compute, for comparing two builds of the library bit by bit: the
-factor sweeps, `gauss_elbo_terms(with_data=True, per_row=True)`, `gauss_fold_in` and the accumulate / finalize pair, in
-the default mode and (bias-free cases) with unlisted cells as weighted zeros.  Only the public `Context` API is used, so
+factor sweeps, `gauss_elbo_terms(with_data=True, per_row=True)`, `gauss_fold_in`, `gauss_sample_rows` (1 and 9 draws of
+the stream, 2 draws of given normals; 16 user rows, one of them twice) and the accumulate / finalize pair, in the
+default mode and (bias-free cases) with unlisted cells as weighted zeros.  Only the public `Context` API is used, so
 the script runs unchanged on any build of the same ABI; `PMF_HIP_LIBRARY` selects the build.
 
 Problem: `tests/helpers.skewed_problem` at 600 x 120 x 12000 (split rows, empty rows), a fixed drawn state.  Cases: K in
-(20, 64, 100) x (f32, f64) x (without, with bias), each once with PMF_ELBO_ROWS / PMF_FOLD_IN_ROWS unset and once with
+(20, 64, 100) x (f32, f64) x (without, with bias), and without bias K = 150 in f32 (the block-per-row solver with its
+matrix in LDS) and K = 200 in f64 (solver, ELBO row pass and draws with the matrix in global scratch), each once with PMF_ELBO_ROWS / PMF_FOLD_IN_ROWS unset and once with
 both set to 17 (many windows and blocks).  One digest per step; two builds agree when the two files are equal.
 
     python tools/gauss_bits.py out.json
@@ -13,6 +15,7 @@ import hashlib
 import json
 import os
 import sys
+import time
 
 import numpy as np
 import torch  # noqa: F401  (before the engine: pmf_hip.load() explains)
@@ -26,6 +29,7 @@ from pmf_hip import ARR_BIAS, ARR_COV, ARR_FACTOR, ITEM, USER  # noqa: E402
 U, I, N = 600, 120, 12000
 SIGMA2, ETA2, ETA_B2, W0 = 0.4, 0.7, 1.3, 0.25
 FOLD_ROWS = 40
+SAMPLE_ROWS = np.r_[np.arange(0, U, U // 15)[:15], 40].astype(np.int32)   # row 40 twice
 
 
 def sha(*arrays):
@@ -51,6 +55,10 @@ def steps(ctx, out, tag, batch, bias):
     for side, name in ((USER, "user"), (ITEM, "item")):
         out[f"{tag}elbo_{name}"] = sha(*ctx.gauss_elbo_terms(side, with_data=True, per_row=True))
     out[f"{tag}fold_in"] = sha(*ctx.gauss_fold_in(USER, *batch, SIGMA2, ETA2, ETA_B2, n_iter=2 if bias else 1))
+    for n_draws in (1, 9):
+        out[f"{tag}sample_{n_draws}"] = sha(ctx.gauss_sample_rows(USER, SAMPLE_ROWS, n_draws, draw0=3, seed=2 ** 40 + 5))
+    z = np.random.default_rng(5).standard_normal((len(SAMPLE_ROWS), 2, ctx.K))
+    out[f"{tag}sample_z"] = sha(ctx.gauss_sample_rows(USER, SAMPLE_ROWS, 2, z=z))
 
 
 def case(K, dtype, bias, u, i, r):
@@ -87,12 +95,12 @@ def main(path):
             os.environ.pop(name, None)
             if rows:
                 os.environ[name] = rows
-        for K in (20, 64, 100):
-            for dtype in ("f32", "f64"):
-                for bias in (False, True):
-                    key = f"rows={rows or 'unset'} K={K} {dtype} {'bias' if bias else 'plain'}"
-                    result[key] = case(K, dtype, bias, u, i, r)
-                    print(key, len(result[key]), "digests", flush=True)
+        cases = [(K, dtype, bias) for K in (20, 64, 100) for dtype in ("f32", "f64") for bias in (False, True)]
+        for K, dtype, bias in cases + [(150, "f32", False), (200, "f64", False)]:
+            key = f"rows={rows or 'unset'} K={K} {dtype} {'bias' if bias else 'plain'}"
+            t0 = time.perf_counter()
+            result[key] = case(K, dtype, bias, u, i, r)
+            print(key, len(result[key]), "digests", f"{time.perf_counter() - t0:.1f} s", flush=True)
     with open(path, "w") as f:
         json.dump(result, f, indent=1, sort_keys=True)
 
