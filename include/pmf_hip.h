@@ -170,8 +170,15 @@ int pmf_ctx_set_ratings_weighted(pmf_ctx *ctx, int64_t nnz, const int32_t *user_
 /* *has = 1 while the context's ratings came with weights */
 int pmf_ctx_has_rating_weights(pmf_ctx *ctx, int *has);
 /* C_r of every row of `side` as the kernels read it (the row's weights summed in double, rounded once to the context
- * dtype); the rating counts when the context holds no weights.  PMF_EINVAL: ratings have not been set. */
+ * dtype); the rating counts when the context holds no weights.  After pmf_gauss_logit_refresh(side) they are the sums
+ * that call re-formed, read back from the device.  PMF_EINVAL: ratings have not been set. */
 int pmf_ctx_rating_weight_sums(pmf_ctx *ctx, int side, double *out /* rows */);
+/* The ratings as `side` holds them (CSR when side = user, CSC when side = item), read back from the device after the
+ * work queued on the context's stream: row_ptr [rows + 1], other_ids [nnz] (ids on the opposite side, every row in
+ * ascending original position), ratings [nnz] and weights [nnz] as float64 of the stored context-dtype values.  Every
+ * output may be NULL.  After pmf_gauss_logit_refresh(side) the ratings and weights are the refreshed ones.  PMF_EINVAL:
+ * ratings have not been set; `weights` asked of a context that holds none. */
+int pmf_ctx_side_ratings(pmf_ctx *ctx, int side, int64_t *row_ptr, int32_t *other_ids, double *ratings, double *weights);
 
 /* Host float64 -> device (and back).  `host` holds rows x K (FACTOR, SHAPE,
  * RATE), rows (PRIOR_RATE, HYPER_RATE, BIAS) or rows x K x K (COV) doubles,
@@ -611,6 +618,26 @@ int pmf_gauss_fold_in_weighted(pmf_ctx *ctx, int side, int64_t n_rows, const int
 #define PMF_ELBO_TERMS 4
 int pmf_gauss_elbo_terms(pmf_ctx *ctx, int side, int with_data, double *totals /* [PMF_ELBO_TERMS] */,
                          double *per_row /* rows x PMF_ELBO_TERMS, may be NULL */);
+
+/* Logistic matrix factorisation on the Gaussian path.  No reference counterpart.  Ratings
+ * x_j in {0, 1}, p(x_j = 1) = sigmoid(theta_u . beta_i), bias-free, q Gaussian per row as the Gaussian CAVI model holds
+ * it.  Under the Jaakkola-Jordan bound with one parameter xi_j per rating the likelihood is Gaussian: rating j adds
+ * c_j = 2 lambda(xi_j) times the outer product and x_j - 1/2 times the mean to its row's statistics, lambda(xi) =
+ * tanh(xi / 2) / (4 xi), which is pmf_ctx_set_ratings_weighted's model with sigma2 = 1, weight c_j and stored rating
+ * y_j = (x_j - 1/2) / c_j.  The label stays readable as x_j = [y_j > 0].
+ * The call sets every xi_j of `side`'s stream to its optimum under the current q,
+ *     xi_j^2 = E[(theta_r . beta_o)^2] = < COV[r] + m_r m_r^T, COV_other[o_j] + m_o m_o^T >     (summed in the context dtype),
+ * and overwrites that stream's weights with c_j and its ratings with y_j (everything from xi on in double, rounded once),
+ * re-forms the side's weight sums C_r (in double in the row's rating order, rounded once), and returns in *data_term
+ * (may be NULL: nothing is read back and the call does not wait) the data term of the bound at these xi,
+ *     D = sum_j [ log sigmoid(xi_j) - xi_j / 2 + (x_j - 1/2) m_r . m_o ],
+ * summed in double in a fixed order: two calls on the same state give the same bits.  The other side's stream is not
+ * touched: refresh a side before its pmf_gauss_factor_sweep(side, 1.0, eta2).  The index, work lists and hot-row flags
+ * stay valid; the work is timed under PMF_KERNEL_PREDICT_VAR.
+ * PMF_EINVAL (nothing is written): null context, bad side, no ratings, a context whose ratings were not loaded through
+ * pmf_ctx_set_ratings_weighted, BIAS arrays, a missing FACTOR / COV of either side (named), a communicator,
+ * PMF_ZEROS_OBSERVED. */
+int pmf_gauss_logit_refresh(pmf_ctx *ctx, int side, double *data_term /* may be NULL */);
 
 /* Posterior draws of factor rows.  No reference counterpart.  A draw of row r of `side` is
  *     x = m_r + C_r z,     C_r the lower Cholesky factor of V_r = COV[r] (C_r C_r' = V_r),  m_r = FACTOR[r],

@@ -706,6 +706,19 @@ extern "C" int pmf_ctx_rating_weight_sums(pmf_ctx *ctx, int side, double *out) {
     PMF_REQUIRE(out != nullptr, PMF_EINVAL, "pmf_ctx_rating_weight_sums: null argument");
     const PmfSideIndex &ix = ctx->index[side];
     PMF_REQUIRE(ix.d_ptr, PMF_EINVAL, "pmf_ctx_rating_weight_sums: ratings have not been set");
+    if (ctx->weighted && ix.wsum_refreshed) {   // pmf_gauss_logit_refresh re-formed the sums on the device: h_wsum is stale
+        const int64_t rows = ctx->rows[side];
+        PMF_HIP_CHECK(hipSetDevice(ctx->device));
+        PMF_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return pmf_no_throw("pmf_ctx_rating_weight_sums", [&] {
+            return pmf_with_dtype(ctx, [&](auto t) -> int {
+                std::vector<decltype(t)> sums((size_t)rows);
+                if (rows) PMF_HIP_CHECK(hipMemcpy(sums.data(), ix.d_wsum.as(), (size_t)rows * sizeof(t), hipMemcpyDeviceToHost));
+                for (int64_t r = 0; r < rows; ++r) out[r] = (double)sums[(size_t)r];
+                return PMF_OK;
+            });
+        });
+    }
     // C_r as the kernels read it: the double sum rounded once to the context dtype; the counts without weights
     for (int64_t r = 0; r < ctx->rows[side]; ++r) {
         const double c = ctx->weighted ? ix.h_wsum[(size_t)r] : (double)(ix.h_ptr[(size_t)r + 1] - ix.h_ptr[(size_t)r]);

@@ -160,6 +160,9 @@ struct PmfSideIndex {
     PmfBuf d_wgt;                // [nnz] context dtype
     PmfBuf d_wsum;               // [rows] context dtype
     std::vector<double> h_wsum;  // [rows] C_r in double (pmf_ctx_rating_weight_sums); empty without weights
+    // pmf_gauss_logit_refresh has rewritten d_wgt / d_wsum of this side: h_wsum is stale, pmf_ctx_rating_weight_sums
+    // reads d_wsum back instead.  Goes with the ratings.
+    bool wsum_refreshed = false;
     std::vector<int64_t> h_ptr;  // host copy of ptr (task building)
     PmfBuf d_nonempty;           // int32_t [n_nonempty]: rows with at least one rating (Gaussian solve list)
     int64_t n_nonempty = 0;

@@ -79,6 +79,8 @@ SIGNATURES = {
     "pmf_ctx_set_ratings_weighted": (C.c_int, [_p, C.c_int64, _i32p, _i32p, _f64p, _f64p]),
     "pmf_ctx_has_rating_weights": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "pmf_ctx_rating_weight_sums": (C.c_int, [_p, C.c_int, _f64p]),
+    "pmf_ctx_side_ratings": (C.c_int, [_p, C.c_int, _i64p, _i32p, _f64p, _f64p]),
+    "pmf_gauss_logit_refresh": (C.c_int, [_p, C.c_int, _f64p]),
     "pmf_set_array": (C.c_int, [_p, C.c_int, C.c_int, _f64p]),
     "pmf_get_array": (C.c_int, [_p, C.c_int, C.c_int, _f64p]),
     "pmf_get_array_rows": (C.c_int, [_p, C.c_int, C.c_int, C.c_int64, _i64p, _f64p]),

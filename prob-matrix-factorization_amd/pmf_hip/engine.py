@@ -233,6 +233,18 @@ class Context:
         check(self._lib.pmf_ctx_rating_weight_sums(self._h, side, ptr(out, C.c_double)), "pmf_ctx_rating_weight_sums")
         return out
 
+    def side_ratings(self, side, weights=True):
+        """The ratings as `side` holds them, read back from the device (`pmf_ctx_side_ratings`): (row_ptr int64
+        [rows + 1], other_ids int32 [nnz], ratings float64 [nnz], weights float64 [nnz] or None without `weights`) --
+        after `gauss_logit_refresh(side)` the refreshed values."""
+        rp = np.zeros(self.rows(side) + 1, dtype=np.int64)
+        other = np.zeros(self.nnz, dtype=np.int32)
+        x = np.zeros(self.nnz, dtype=np.float64)
+        w = np.zeros(self.nnz, dtype=np.float64) if weights else None
+        check(self._lib.pmf_ctx_side_ratings(self._h, side, ptr(rp, C.c_int64), ptr(other, C.c_int32), ptr(x, C.c_double),
+                                             opt_ptr(w)), "pmf_ctx_side_ratings")
+        return rp, other, x, w
+
     def _host_shape(self, side, array):
         r = self.rows(side)
         if array in (0, 1, 2):
@@ -487,6 +499,16 @@ class Context:
         check(self._lib.pmf_gauss_elbo_terms(self._h, side, int(bool(with_data)), ptr(totals, C.c_double),
                                              ptr(rows, C.c_double) if per_row else None), "pmf_gauss_elbo_terms")
         return (totals, rows) if per_row else totals
+
+    def gauss_logit_refresh(self, side, want_data_term=True):
+        """Logistic model on the Gaussian path (`pmf_gauss_logit_refresh`): every Jaakkola-Jordan parameter of `side`'s
+        stream to its optimum under the current FACTOR / COV, the stream's weights and ratings rewritten to c_j = 2
+        lambda(xi_j) and (x_j - 1/2) / c_j, so that `gauss_factor_sweep(side, 1.0, eta2)` is the logistic factor update.
+        Returns the data term of the bound (float), or None without `want_data_term` (the call then does not wait)."""
+        d = np.zeros(1, dtype=np.float64)
+        check(self._lib.pmf_gauss_logit_refresh(self._h, side, ptr(d, C.c_double) if want_data_term else None),
+              "pmf_gauss_logit_refresh")
+        return float(d[0]) if want_data_term else None
 
     def gauss_sample_rows(self, side, rows, n_draws=1, draw0=0, seed=0, z=None):
         """Posterior draws x = FACTOR[r] + chol(COV[r]) z of the given rows of `side` (`pmf_gauss_sample_rows`): float64
