@@ -17,7 +17,8 @@ Two forms of every half-sweep are provided:
                    does).  This is the "port" timed as `cpu_baseline`.
   * `*_segsum`  -- the same update as a segmented sum over the CSR-ordered
                    ratings (vectorised), used to check mid-size problems in
-                   seconds.
+                   seconds (the Gaussian one needs scipy.sparse, as the
+                   tests' other references need scipy).
 
 State is a plain dict of float64 arrays; index structure is a CSR-like
 `(ptr, pos)` pair per side where `pos` lists rating positions in their
@@ -166,6 +167,16 @@ def _segment_sum(values, ptr):
     return out
 
 
+def _segment_sum_of_rows(table, ids, ptr):
+    """`_segment_sum(table[ids], ptr)` without materialising the gathered (nnz, C) array (2 GB for the covariance
+    rows of a 272k-rating problem at K = 30): the CSR incidence matrix of the segments times the table.  scipy's
+    CSR product adds a row's terms one after the other, in their order; the factors are exact ones."""
+    from scipy.sparse import csr_matrix
+    n_rows = ptr.size - 1
+    A = csr_matrix((np.ones(len(ids)), ids, ptr), shape=(n_rows, table.shape[0]))
+    return np.asarray(A @ table)
+
+
 def gamma_half_sweep_segsum(E_self, E_other, ptr, pos, other_ids, x, shape_prior, rate_prior):
     """Vectorised form of `gamma_half_sweep_rows` (same update, reduceat
     summation order)."""
@@ -290,10 +301,10 @@ def gauss_factor_sweep_segsum(m_self, V_self, m_other, V_other, ptr, pos, other_
     o = other_ids[pos]
     row_of = np.repeat(np.arange(n_rows), np.diff(ptr))
     mo = m_other[o]
-    # sum_j m m^T per segment without materialising (nnz, K, K): loop over k
-    S = _segment_sum(V_other[o].reshape(len(o), K * K), ptr).reshape(n_rows, K, K)
-    for k in range(K):
-        S[:, k, :] += _segment_sum(mo * mo[:, k:k + 1], ptr)
+    # sum_j V_j and sum_j m_j m_j^T per segment without materialising (nnz, K, K)
+    S = _segment_sum_of_rows(V_other.reshape(-1, K * K), o, ptr)
+    S += _segment_sum_of_rows(np.einsum("nk,nl->nkl", m_other, m_other).reshape(-1, K * K), o, ptr)
+    S = S.reshape(n_rows, K, K)
     resid = x[pos] - bias_self[row_of] - bias_other[o]
     w = _segment_sum(mo * resid[:, None], ptr)
     nonempty = np.diff(ptr) > 0

@@ -15,7 +15,11 @@ fixtures (inputs + expected outputs, no code) that pin
   * `metrics.rmse / mae / macro_mae` on fixed vectors,
   * `HPF_PyTorch.loss` value + gradients on a fixed batch.
 
-Usage:  python tests/golden/make_golden.py            (rewrites tests/golden/*.npz)
+Usage:  python tests/golden/make_golden.py            (rewrites the small-problem fixtures)
+        python tests/golden/make_golden.py config5    (config5_poisson.npz only)
+        python tests/golden/make_golden.py op_gauss_stop op_gauss_sharp op_gauss_long op_hpf op_poisson
+                                                      (the published operating points, op_*.npz: any subset, each
+                                                       word writes its own file and no other)
 """
 import contextlib
 import io
@@ -393,8 +397,159 @@ def gen_config5():
             "E_theta_rows_it20": early.E_theta[users]}
 
 
+# ---- the reference's published operating points --------------------------------------------------
+# One configuration per model (model_comparison_params.txt / best_hyperparams.txt:3-5), on the recipe-shaped stand-in:
+# trained on the TRAIN frame, monitored on a validation frame, scored on the test frame.  Each fixture is one
+# reference run; the per-iteration validation values are captured at full precision by shadowing the instance's
+# `evaluate_rmse` / `evaluate_macro_mae` with a recording wrapper before `fit` (data only: what the reference computed).
+OP_CFG = {
+    "gauss_bias": dict(n_factors=30, sigma2=0.3, eta_theta2=0.5, eta_beta2=0.5, eta_bias2=1.0, max_iter=100, tol=1e-3,
+                       random_state=42),
+    "hpf": dict(n_factors=20, a=0.3, a_prime=5.0, b_prime=5.0, c=0.3, c_prime=5.0, d_prime=5.0, max_iter=100, tol=None,
+                random_state=42),
+    "poisson": dict(n_factors=40, a0=0.1, b0=0.5, max_iter=150, tol=None, random_state=42),
+}
+# word -> (file stem, kind, config overrides, frames of val_df, carries a final state, iterations of the cheaper
+# second state the CPU oracle is held to)
+OP_CASES = {
+    "op_gauss_stop": ("op_gauss_bias_k30_stop", "gauss_bias", {}, ("validation", "test"), True, None),
+    "op_gauss_sharp": ("op_gauss_bias_k30_stop_sharp", "gauss_bias", {}, ("validation",), False, None),
+    "op_gauss_long": ("op_gauss_bias_k30_long", "gauss_bias", {"tol": 0.0}, ("validation",), True, None),
+    "op_hpf": ("op_hpf_k20", "hpf", {}, ("validation",), True, 20),
+    "op_poisson": ("op_poisson_k40", "poisson", {}, ("validation",), True, 20),
+}
+OP_ROWS = {"gauss_bias": (("m_theta", "m_user_bias"), ("m_beta", "m_item_bias")),
+           "hpf": (("E_theta", "E_xi"), ("E_beta", "E_eta")),
+           "poisson": (("E_theta",), ("E_beta",))}
+
+
+def record_validation(model, also=None):
+    """Shadow the two evaluation methods of THIS instance: every value `fit` computes is kept at full precision.
+    Returns the list the (rmse, macro_mae) pairs of the iterations go to (HPF evaluates the RMSE twice per
+    iteration, hpf_cavi.py:197-198: a pair takes the last RMSE before its MacroMAE).  `also`: a second frame that is
+    scored with the same arguments right after the monitored one; its two values are appended to the pair."""
+    pairs, last = [], []
+    rmse_fn, mae_fn = model.evaluate_rmse, model.evaluate_macro_mae
+
+    def rec_rmse(*a, **k):
+        last[:] = [rmse_fn(*a, **k)]
+        return last[0]
+
+    def rec_mae(df, *a, **k):
+        v = mae_fn(df, *a, **k)
+        pairs.append((last[0], v) + (() if also is None else (rmse_fn(also, *a, **k), mae_fn(also, *a, **k))))
+        return v
+    model.evaluate_rmse, model.evaluate_macro_mae = rec_rmse, rec_mae
+    return pairs
+
+
+def op_frames(kind, val_parts):
+    here = os.path.dirname(OUT)
+    sys.path.append(here)                                                        # tests/helpers.py
+    sys.path.append(os.path.join(os.path.dirname(here), "prob-matrix-factorization_amd"))   # pmf_hip.synth only: appended, so `src` stays the reference's
+    from helpers import recipe_standin
+    named = dict(zip(("train", "validation", "test"), recipe_standin()))
+    val_raw = pd.concat([named[p] for p in val_parts], ignore_index=True)
+    train, val, gm = preprocess(kind, named["train"], val_raw)
+    _, test, _ = preprocess(kind, named["train"], named["test"])
+    return train, val, test, gm, {p: len(named[p]) for p in named}
+
+
+def op_state(kind, m, users, items, tag=""):
+    out = {}
+    for ids, names in zip((users, items), OP_ROWS[kind]):
+        for name in names:
+            out[f"{name}_rows{tag}"] = np.asarray(getattr(m, name))[ids]
+    return out
+
+
+def gen_operating_point(word):
+    stem, kind, override, val_parts, final_state, early_iters = OP_CASES[word]
+    cfg = dict(OP_CFG[kind], **override)
+    train, val, test, gm, n_rows = op_frames(kind, val_parts)
+    is_gauss = kind == "gauss_bias"
+    fit_kw = dict(val_df=val, global_mean=gm) if is_gauss else dict(val_df=val)
+    # val_df of several frames: the first frame alone is scored too, which ties this run to the runs monitored on it
+    first = val.iloc[:n_rows[val_parts[0]]] if len(val_parts) > 1 else None
+
+    def run(max_iter):
+        m = make(kind, dict(cfg, max_iter=max_iter, verbose=True))
+        pairs = record_validation(m, also=first)
+        _, log = quiet(m.fit, train, **fit_kw)
+        return m, np.array(pairs, dtype=np.float64).reshape(len(pairs), -1), log
+    m, traj, log = run(cfg["max_iter"])
+    assert len(VAL_RE.findall(log)) == len(traj)             # one recorded pair per monitored iteration
+    out = {"cfg": np.array(json.dumps(cfg)), "kind": np.array(kind), "val_frames": np.array("+".join(val_parts)),
+           "n_train_rows": np.int64(len(train)), "n_val_rows": np.int64(len(val)), "n_test_rows": np.int64(len(test)),
+           "global_mean": np.float64(gm), "val_rmse": traj[:, 0], "val_macro_mae": traj[:, 1],
+           "iterations": np.int64(len(traj)), "stopped_early": np.bool_("Early stopping" in log)}
+    assert n_rows["train"] == len(train) and sum(n_rows[p] for p in val_parts) == len(val)
+    if first is not None:
+        out[f"{val_parts[0]}_rmse"], out[f"{val_parts[0]}_macro_mae"] = traj[:, 2], traj[:, 3]
+    if not final_state:
+        return stem, out
+    rng = np.random.default_rng(1)
+    users = rng.choice(m.n_users, 300, replace=False)
+    items = rng.choice(m.n_items, 300, replace=False)
+    out["users"], out["items"] = users, items
+    out.update(op_state(kind, m, users, items))
+    for names in OP_ROWS[kind]:
+        for name in names:
+            out[f"{name}_sum"] = np.float64(np.asarray(getattr(m, name)).sum())
+    tu, ti = test["u"].to_numpy(), test["i"].to_numpy()
+    A, B = getattr(m, OP_ROWS[kind][0][0]), getattr(m, OP_ROWS[kind][1][0])
+    scores = A[users] @ B.T
+    if is_gauss:     # the test frame is centred like the validation frame; targets and predictions on the rating scale
+        out["test_pred"] = m.predict(tu, ti, gm)
+        out["test_rmse"] = np.float64(ref_metrics.rmse(test["rating"].to_numpy(dtype=float) + gm, out["test_pred"]))
+        scores = scores + m.m_user_bias[users][:, None] + m.m_item_bias[None, :]       # predict's score without global_mean
+    else:
+        out["test_pred"] = m.predict(tu, ti)
+        out["test_rmse"] = np.float64(ref_metrics.rmse(test["rating"].to_numpy(dtype=float), out["test_pred"]))
+    top = np.argsort(-scores, axis=1, kind="stable")[:, :11]
+    out["top11"], out["top11_scores"] = top.astype(np.int32), np.take_along_axis(scores, top, axis=1)
+    # the items outside a user's top 10 whose score lies within 1e-4 (relative) of the 10th: what the fp32 ranking
+    # bar (tests/test_parity_bar_gpu.py:_topk_agree) does not count as a difference
+    kth = out["top11_scores"][:, 9:10]
+    near = np.abs(scores - kth) <= 1e-4 * np.abs(kth)
+    near[np.arange(len(users))[:, None], top[:, :10]] = False
+    out["near10_ptr"] = np.concatenate([[0], np.cumsum(near.sum(axis=1))]).astype(np.int64)
+    out["near10_items"] = np.nonzero(near)[1].astype(np.int32)
+    if early_iters:       # a cheaper pin for the CPU oracle test: a run of its own, the same trajectory prefix bit for bit
+        early, traj_e, _ = run(early_iters)
+        assert np.array_equal(traj_e, traj[:early_iters])
+        out["early_iterations"] = np.int64(early_iters)
+        out.update(op_state(kind, early, users, items, tag=f"_it{early_iters}"))
+        out[f"test_pred_it{early_iters}"] = early.predict(tu, ti)
+    return stem, out
+
+
+def check_shared_prefixes():
+    """The three Gaussian fixtures are separate reference runs of the same training problem, so their validation-frame
+    trajectories share a prefix, which must agree bit for bit: that checks the recorder.  (The stop fixture monitors
+    validation + test; it carries the validation frame's values of the same iterations beside them.)"""
+    words = ("op_gauss_stop", "op_gauss_sharp", "op_gauss_long")
+    paths = [os.path.join(OUT, OP_CASES[w][0] + ".npz") for w in words]
+    have = [np.load(p) for p in paths if os.path.exists(p)]
+    traj = [np.stack([d["validation_rmse"], d["validation_macro_mae"]] if "validation_rmse" in d
+                     else [d["val_rmse"], d["val_macro_mae"]]) for d in have]
+    for a in traj[1:]:
+        n = min(a.shape[1], traj[0].shape[1])
+        assert n > 0 and np.array_equal(a[:, :n], traj[0][:, :n]), "the Gaussian fixtures' shared prefix differs"
+    print("validation-frame trajectory prefix of", len(have), "Gaussian fixtures: bit-equal")
+
+
 def main():
     only = sys.argv[1:]
+    if any(w in OP_CASES for w in only):
+        for word in only:
+            stem, out = gen_operating_point(word)
+            path = os.path.join(OUT, stem + ".npz")
+            np.savez_compressed(path, **out)
+            print("wrote", path, os.path.getsize(path) // 1024, "KiB", "iterations", int(out["iterations"]),
+                  "stopped_early", bool(out["stopped_early"]))
+        check_shared_prefixes()
+        return
     if "config5" in only:
         path = os.path.join(OUT, "config5_poisson.npz")
         np.savez_compressed(path, **gen_config5())

@@ -72,6 +72,9 @@ def midsize():
 
 @pytest.mark.parametrize("kind", ["hpf", "poisson", "gauss_bias"])
 def test_fp32_vs_fp64_after_100_iterations_k64(kind, midsize):
+    """fp32 against the device's own fp64 mode: an error that both modes share passes here.  The long runs that are
+    pinned to the reference itself (its published configurations, every iteration of the validation trajectory) live in
+    tests/test_operating_points_gpu.py."""
     train, val = midsize
     fits = {}
     for dtype in ("f64", "f32"):
